@@ -29,7 +29,8 @@ fresh child processes (before anything touches the GPU: the parent never imports
     --mode predict     GP.predict at M query points for the S posteriors of the configuration
                        (gaussian_process.py:1741-1764): point-samples/s
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  With `--dump-outputs DIR` it also writes what the last timed step returned as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 """
 
 import argparse
@@ -382,6 +383,28 @@ def both_splits(args, world, dist, dev, S_arg, evaluate, sync, grad):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """Write what the timed path returned in its last step as ``dirname/<name>.npy`` (float64, or float32 if that is
+    what the caller got), so that two builds can be compared output for output.  Above DUMP_BUDGET_BYTES in all, the
+    same fixed, seeded sample of leading-axis rows is kept of every array (the arrays share their leading axis: the
+    samples of nll_batch, the query points of predict).  Returns the names written."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items() if v is not None}
+    arrays = {k: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_BUDGET_BYTES:
+        n = min(v.shape[0] for v in arrays.values())
+        keep = max(1, int(n * DUMP_BUDGET_BYTES // total))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), np.ascontiguousarray(v))
+    return sorted(arrays)
+
+
 def per_r(S, world):
     from gpyreg_amd import sharding as _sh
 
@@ -585,6 +608,11 @@ def run(args):
             dist.destroy_process_group()
         return
 
+    dumped = None
+    if args.dump_outputs:  # the last timed step's results (every rank holds every sample's; rank 0 writes them)
+        names = ("mu", "s2") if mode == "predict" else ("nlz", "dnlz")
+        dumped = dump_outputs(args.dump_outputs, dict(zip(names, (r0, r1))))
+
     N, D = cfg["N"], cfg["D"]
     peak = FP64_MFMA_PEAK_TFLOPS if dtype == "f64" else FP32_MFMA_PEAK_TFLOPS
     tf, cyc, ghz = ctx.mfma_peak(_lib.F64 if dtype == "f64" else _lib.F32)
@@ -603,6 +631,8 @@ def run(args):
         "dtype": dtype,
         "data": "synthetic",
     }
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     config = {
         "global_samples": S_global,
         "samples_per_gpu": per_rank[0] if len(set(per_rank)) == 1 else per_rank,
@@ -757,7 +787,14 @@ def main():
                     help="launcher / exchange rehearsal without device work (no GPU needed, gloo); reports no throughput")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend (nccl = RCCL; gloo only to rehearse ranks on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (fit/nll: nlz, dnlz; predict: mu, s2) "
+                         "as DIR/<name>.npy, at most 64 MB in all (a fixed, seeded sample of rows beyond that)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the real timed path, not --dry-run")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # no launcher around us: start the ranks ourselves, before this process touches the GPU

@@ -8,6 +8,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -241,3 +242,51 @@ def test_the_alone_figure_of_a_batch_that_runs_as_two_sample_groups():
     assert abs(alone["flops_per_launch"] - 2.0 * roof["flops_per_launch"]) < 1e-6 * alone["flops_per_launch"]
     assert alone["frac"] >= roof["frac"] - 0.02, (alone["frac"], roof["frac"])
     assert 0.5 < alone["frac"] < 1.0
+
+
+def test_steps_below_one_are_refused():
+    r, line = _bench("--gpus", "1", "--dry-run", "--steps", "0", "--warmup", "0", timeout=120)
+    assert r.returncode != 0 and line is None and "--steps" in r.stderr
+
+
+def test_dump_outputs_keeps_a_seeded_sample_within_the_budget(tmp_path, monkeypatch):
+    """`--dump-outputs` writes the arrays the timed path returned; above the budget the SAME seeded rows of every array
+    are kept, so two runs (two builds) write comparable files."""
+    import bench
+
+    rng = np.random.default_rng(5)
+    mu, s2, nlz = rng.standard_normal((1000, 4)), rng.random((1000, 4)), rng.standard_normal(7).astype(np.float32)
+    assert bench.dump_outputs(str(tmp_path / "small"), {"nlz": nlz, "dnlz": None}) == ["nlz"]
+    got = np.load(tmp_path / "small" / "nlz.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, nlz)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 16000)
+    for d in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / d), {"mu": mu, "s2": s2}) == ["mu", "s2"]
+    a_mu, a_s2 = np.load(tmp_path / "a" / "mu.npy"), np.load(tmp_path / "a" / "s2.npy")
+    assert a_mu.nbytes + a_s2.nbytes <= 16000 and a_mu.shape[0] == a_s2.shape[0] > 0 and a_mu.dtype == np.float64
+    rows = [int(np.flatnonzero((mu == r).all(1))[0]) for r in a_mu]
+    assert rows == sorted(set(rows)) and np.array_equal(a_s2, s2[rows])
+    assert np.array_equal(a_mu, np.load(tmp_path / "b" / "mu.npy"))
+    r, line = _bench("--gpus", "1", "--dry-run", "--dump-outputs", str(tmp_path / "c"), timeout=120)
+    assert r.returncode != 0 and line is None and not (tmp_path / "c").exists()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """nll_batch's (nlZ, dnlZ) and predict's (mu, s2) of the last timed step, as the JSON line quotes them; the seeded
+    inputs make a second run write the same values."""
+    fit = ("--config", "2", "--samples", "3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
+    outs = []
+    for d in ("a", "b"):
+        r, line = _bench("--gpus", "1", *fit, "--dump-outputs", str(tmp_path / d))
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert line["steps"] == 2 and line["dumped_outputs"]["arrays"] == ["dnlz", "nlz"]
+        nlz, dnlz = np.load(tmp_path / d / "nlz.npy"), np.load(tmp_path / d / "dnlz.npy")
+        assert nlz.shape == (3,) and dnlz.shape == (3, 8) and nlz.dtype == dnlz.dtype == np.float64
+        assert nlz[0] == line["nlz_sample0"] and np.isfinite(dnlz).all()
+        outs.append((nlz, dnlz))
+    assert np.allclose(outs[0][0], outs[1][0], rtol=1e-12) and np.allclose(outs[0][1], outs[1][1], rtol=1e-10)
+    r, line = _bench("--gpus", "1", "--mode", "predict", "--points", "300", *fit, "--dump-outputs", str(tmp_path / "p"))
+    assert r.returncode == 0, r.stderr[-3000:]
+    mu, s2 = np.load(tmp_path / "p" / "mu.npy"), np.load(tmp_path / "p" / "s2.npy")
+    assert mu.shape == s2.shape == (300, 3) and mu[0, 0] == line["mu_sample0_first"] and (s2 > 0).all()
