@@ -66,6 +66,7 @@ SIGNATURES = {
     "gpc_post_fetch": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "gpc_post_free": (C.c_int, [_vp]),
     "gpc_predict": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
+    "gpc_predict_grad": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "gpc_post_append": (C.c_int, [_vp, _dp, _dp, C.c_double, _ip]),
     "gpc_post_recompute": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_post_append_K": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_double, _ip]),
@@ -439,6 +440,20 @@ class PostHandle:
         rc = self.ctx._lib.gpc_predict(self._h, _ptr(xs), M, _ptr(fmu), _ptr(fs2))
         self.ctx._check(rc, "gpc_predict")
         return fmu, fs2
+
+    @_serial
+    def predict_grad(self, x_star):
+        """gpc_predict_grad: fmu, fs2 (M, S) as predict, and their gradients with respect to x_star, dfmu and dfs2
+        (M, D, S).  x_star has the D columns of the training inputs."""
+        xs = _f64(x_star)
+        M, D = xs.shape
+        fmu = np.empty((M, self.S))
+        fs2 = np.empty((M, self.S))
+        dfmu = np.empty((M, D, self.S))
+        dfs2 = np.empty((M, D, self.S))
+        rc = self.ctx._lib.gpc_predict_grad(self._h, _ptr(xs), M, _ptr(fmu), _ptr(fs2), _ptr(dfmu), _ptr(dfs2))
+        self.ctx._check(rc, "gpc_predict_grad")
+        return fmu, fs2, dfmu, dfs2
 
     @_serial
     def predict_K(self, Ks, Kss=None, want_var=True):

@@ -836,6 +836,142 @@ __global__ __launch_bounds__(256) void colpart_reduce_kernel(const double* __res
 }
 
 // ---------------------------------------------------------------------------------
+// predict_grad: gradients of the predictive mean and variance with respect to the query inputs.  With xs the scaled
+// inputs (scale_x_kernel), c_l = mul_l / dv_l and F the radial factor of the pair functor (dK/dlog ell_l = F d_l),
+// dK_ij / dx*_jl = F_ij (xs_il - xs*_jl) c_l, so
+//   dmu_jl = c_l      sum_i P_ij (xs_il - xs*_jl),   P_ij = F_ij alpha_i
+//   ds2_jl = -2 c_l   sum_i R_ij (xs_il - xs*_jl),   R_ij = F_ij Q_ij,  Q = (K + Sigma)^-1 K* = qs * Qstored
+// (qs = 1/sl for L_chol samples, Qstored = W^T V; qs = -1 otherwise, Qstored = G = A K*).  This kernel forms one
+// 64 x 64 tile of sample b and writes its column sums over the 64 tile rows:
+//   part[b][ti][l][j] (l < D: the P sums; D <= l < 2D: the R sums of dimension l - D).
+// F is recomputed from r2 rather than read back from K*: K* gives F for the squared exponential only, and
+// recomputing it is one pair evaluation per pair, the same VALU work cross_tile_kernel already does.  The
+// differences xs_il - xs*_jl are taken before the products (not sum P xs - xs* sum P): no cancellation when the
+// inputs lie far from the origin.  A pair with r2 = 0 contributes 0 (the limit for SE, Matern 3/5 and RQ; for
+// Matern 1, where F = 1/t is infinite, the convention).
+// The contraction (P | R)^T (Xs - xs*) is 64 x 64 by 64 x D per tile and runs on the fp64 VALU through LDS, not on
+// v_mfma_f64_16x16x4: with D ~ 10 it is ~2 D FMAs per pair against the ~25-40 VALU instructions of the pair
+// evaluation (exp, sqrt, the Matern / RQ polynomial) that dominate the tile, and a per-column difference xs - xs*
+// is not an operand layout an MFMA B fragment takes without a second staging pass.
+// grid = (mpad/64, npad/64, batch), 256 threads, 41 KB of LDS (three blocks per CU).
+// ---------------------------------------------------------------------------------
+constexpr int GCH = 16;  // dimensions of Xs staged per contraction pass (4 per wave)
+
+__device__ __forceinline__ void grad_contract(const double (*wt)[CT], double (*xg)[GCH + 1],
+                                              const double* __restrict__ Xs, const double* __restrict__ Xss, int D,
+                                              int i0, int j0, int jlim, int t, double* __restrict__ out,
+                                              size_t lstride) {
+  const int lane = t & 63, w = t >> 6;
+  const int j = j0 + lane;
+  for (int h0 = 0; h0 < D; h0 += GCH) {
+    const int dc = min(GCH, D - h0);
+    __syncthreads();  // the weights are written / the previous pass has read xg
+    for (int e = t; e < CT * GCH; e += 256) {
+      const int r = e / GCH, h = e % GCH;
+      xg[r][h] = h < dc ? Xs[(size_t)(i0 + r) * D + h0 + h] : 0.0;
+    }
+    __syncthreads();
+    double xq[4], acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int h = w + 4 * q;
+      xq[q] = (h < dc && j < jlim) ? Xss[(size_t)j * D + h0 + h] : 0.0;
+    }
+    for (int i = 0; i < CT; ++i) {
+      const double p = wt[i][lane];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = fma(p, xg[i][w + 4 * q] - xq[q], acc[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int h = w + 4 * q;
+      if (h < dc) out[(size_t)(h0 + h) * lstride + j] = acc[q];
+    }
+  }
+}
+
+template <typename T, int KIND, int DEG>
+__global__ __launch_bounds__(256) void cross_grad_tile_kernel(CovDesc cd, const double* __restrict__ Xs_all,
+                                                              const double* __restrict__ Xss_all,
+                                                              const double* __restrict__ sp_all,
+                                                              const double* __restrict__ alpha_all, int astride,
+                                                              const T* __restrict__ Q_all, long long sQ, int lch, int n,
+                                                              int npad, int m, int mpad, double* __restrict__ part_all) {
+  // [xi | xj] while the distances form, then [weights | xg]
+  __shared__ double shm[CT * CT + CT * (GCH + 1)];
+  static_assert(2 * CT * (DCH + 1) <= CT * CT + CT * (GCH + 1), "LDS overlay");
+  double(*xi)[DCH + 1] = reinterpret_cast<double(*)[DCH + 1]>(shm);
+  double(*xj)[DCH + 1] = reinterpret_cast<double(*)[DCH + 1]>(shm + CT * (DCH + 1));
+  double(*wt)[CT] = reinterpret_cast<double(*)[CT]>(shm);
+  double(*xg)[GCH + 1] = reinterpret_cast<double(*)[GCH + 1]>(shm + CT * CT);
+  const int t = threadIdx.x, tx = t & 15, ty = t >> 4, b = blockIdx.z;
+  const int D = cd.D;
+  const int i0 = blockIdx.y * CT, j0 = blockIdx.x * CT;
+  const double* Xs = Xs_all + (size_t)b * npad * D;
+  const double* Xss = Xss_all + (size_t)b * mpad * D;
+  const double* sp = sp_all + (size_t)b * SP_STRIDE;
+  const double* alpha = alpha_all + (size_t)b * astride;
+  const T* Q = Q_all + (size_t)b * sQ;
+  double r2[4][4];
+  tile_r2_ab(r2, xi, xj, Xs, Xss, D, i0, j0, t, tx, ty);
+  const double sf2 = sp[SP_SF2], rqa = sp[SP_RQA];
+  const double qs = lch ? 1.0 / sp[SP_SL] : -1.0;
+  ExpC ex;
+  ex.load();
+  double pw[4][4], rw[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) {
+    const int i = i0 + ty + 16 * a;
+    const double al = i < n ? alpha[i] : 0.0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int j = j0 + tx + 16 * c;
+      double f = 0.0, q = 0.0;
+      if (i < n && j < m && r2[a][c] > 0.0) {
+        f = pair_eval_t<KIND, DEG>(r2[a][c], sf2, rqa, ex).F;
+        q = (double)Q[(size_t)i * mpad + j] * qs;
+      }
+      pw[a][c] = f * al;
+      rw[a][c] = f * q;
+    }
+  }
+  const size_t nt = npad / CT, tile = (size_t)b * nt + blockIdx.y;
+  double* outP = part_all + tile * 2 * D * mpad;
+  double* outR = outP + (size_t)D * mpad;
+  __syncthreads();  // xi / xj are read: the weights overlay them
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) wt[ty + 16 * a][tx + 16 * c] = pw[a][c];
+  grad_contract(wt, xg, Xs, Xss, D, i0, j0, m, t, outP, mpad);
+  __syncthreads();
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) wt[ty + 16 * a][tx + 16 * c] = rw[a][c];
+  grad_contract(wt, xg, Xs, Xss, D, i0, j0, m, t, outR, mpad);
+}
+
+// dmu[b][j][l] = c_l sum_t part[b][t][l][j],  ds2[b][j][l] = -2 c_l sum_t part[b][t][D + l][j]; tiles t ascending.
+// grid = (mpad/256, batch)
+__global__ __launch_bounds__(256) void grad_reduce_kernel(const double* __restrict__ part, int nt, int D, int mpad,
+                                                          const double* __restrict__ mul, const double* __restrict__ dv,
+                                                          double* __restrict__ dmu, double* __restrict__ ds2) {
+  const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= mpad) return;
+  for (int l = 0; l < 2 * D; ++l) {
+    double s = 0.0;
+    for (int k = 0; k < nt; ++k) s += part[(((size_t)b * nt + k) * 2 * D + l) * mpad + j];
+    const int h = l < D ? l : l - D;
+    const double c = mul[(size_t)b * D + h] / dv[(size_t)b * D + h];
+    if (l < D)
+      dmu[((size_t)b * mpad + j) * D + h] = c * s;
+    else
+      ds2[((size_t)b * mpad + j) * D + h] = -2.0 * c * s;
+  }
+}
+
+// ---------------------------------------------------------------------------------
 // Cross covariance Ks[b] (npad x mpad, row-major, zero padding) = K(Xs, Xss).
 // One thread per entry; both operands are small and L2 resident.
 // grid = (mpad/64, npad/4, batch), block = (64, 4)

@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 
 #include "blas1.h"
@@ -502,6 +503,7 @@ struct gpc_ctx {
   DevBuf parts, gout, diagq;     // trace pass
   DevBuf dmb, dsn2b, mg, ng;     // mean / noise gradient inputs and outputs
   DevBuf ks, vb, kss, xss, pout; // predict / predict_full / quad
+  DevBuf qb, gpart, gres;        // predict_grad: Q = W^T V, per-tile partials, the gradients
   DevBuf dbg1, dbg2, dbg3;       // debug hooks / fetch staging
   PinBuf pin;                    // pinned staging for host<->device transfers (see PinBuf)
   // Launch graphs of the device pipeline for small problems (npad <= graph_max_npad, one sample
@@ -2363,11 +2365,14 @@ int post_impl(gpc_ctx* c, Batch& b, gpc_post* po, double* sn2_mult, int* L_chol,
 //   quad[j*S+s] = |W_s R_s[:, j]|^2          (L_chol;  the caller divides by sl)
 //               = R_s[:, j] . (L_s R_s[:, j]) (low noise, L = -inv)
 //   full[s]     = Kss_s - (W R)^T (W R) / sl   or   Kss_s + R^T (L R)     (mode_full)
+//   dlin / dquad [(j*D + l)*S + s] = d lin / dx*_jl and d(kss - k*^T (K + Sigma)^-1 k*) / dx*_jl  (mode 0 with
+//                 want_quad only; covfun.h: cross_grad_tile_kernel): V is written (no EPI = 1 product), Q = W^T V
+//                 is one more product of the same size (L_chol; the other samples use G = L R as it is)
 // mode: 0 = cross covariance of xa (M x D) with the training inputs; 1 = quadrature
 // vectors z for Gaussian measures N(xa[j], diag(xb[j]^2)) (gaussian_process.py:1908-1921).
 template <typename T>
 int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int M, bool want_quad,
-                 double* lin, double* quad, double* full) {
+                 double* lin, double* quad, double* full, double* dlin = nullptr, double* dquad = nullptr) {
   gpc_ctx* c = po->ctx;
   const int S = po->S, N = po->N, D = po->D, npad = po->npad;
   const int mpad = pad_tile(M);
@@ -2375,19 +2380,30 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
   const long long sM = (long long)npad * npad;
   const long long sKs = (long long)npad * mpad;
   const long long sKss = (long long)mpad * mpad;
-  const size_t per = (2ull * npad * mpad + (full ? (size_t)mpad * mpad : 0)) * sizeof(T);
+  const bool grad = dlin != nullptr;
+  const int gnt = npad / CT;  // tile rows of the gradient pass
+  // gradient scratch per sample: Q (as V), the per-tile partials and the results
+  const size_t gpart_per = grad ? (size_t)gnt * 2 * D * mpad * 8 : 0, gres_per = grad ? 2ull * mpad * D * 8 : 0;
+  const size_t per = (2ull * npad * mpad + (full ? (size_t)mpad * mpad : 0) + (grad ? (size_t)npad * mpad : 0)) * sizeof(T) +
+                     gpart_per + gres_per;
+  const size_t held = c->ks.bytes + c->vb.bytes + c->kss.bytes + (grad ? c->qb.bytes + c->gpart.bytes + c->gres.bytes : 0);
   int chunk = S;
-  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > c->ks.bytes + c->vb.bytes + c->kss.bytes ||
+  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > held ||
       (size_t)S * sKs * sizeof(T) > std::min(c->ks.bytes, c->vb.bytes) ||
-      (full && (size_t)S * sKss * sizeof(T) > c->kss.bytes)) {
+      (full && (size_t)S * sKss * sizeof(T) > c->kss.bytes) ||
+      (grad && ((size_t)S * sKs * sizeof(T) > c->qb.bytes || (size_t)S * gpart_per > c->gpart.bytes))) {
     c->pool_drain();
-    size_t budget = (size_t)((free_device_bytes() +
-                              (getenv("GPC_MEM_BUDGET_MB") ? 0 : c->ks.bytes + c->vb.bytes + c->kss.bytes)) * 0.8);
+    size_t budget = (size_t)((free_device_bytes() + (getenv("GPC_MEM_BUDGET_MB") ? 0 : held)) * 0.8);
     chunk = (int)std::max<size_t>(1, std::min<size_t>(S, budget / per));
   }
   HIPCHK(c, c->ks.ensure((size_t)chunk * sKs * sizeof(T)));
   HIPCHK(c, c->vb.ensure((size_t)chunk * sKs * sizeof(T)));
   if (full) HIPCHK(c, c->kss.ensure((size_t)chunk * sKss * sizeof(T)));
+  if (grad) {
+    HIPCHK(c, c->qb.ensure((size_t)chunk * sKs * sizeof(T)));
+    HIPCHK(c, c->gpart.ensure((size_t)chunk * gpart_per));
+    HIPCHK(c, c->gres.ensure((size_t)chunk * gres_per));
+  }
   HIPCHK(c, c->xss.ensure(((size_t)chunk * mpad * D + 2 * (size_t)M * D) * 8));
   HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
   HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
@@ -2418,6 +2434,17 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
   double* hfull = nullptr;
   if (full && (size_t)M * M * 8 >= PinBuf::kMin && (size_t)M * M * 8 <= PinBuf::kMax)
     hfull = static_cast<double*>(c->pin.alloc((size_t)M * M * 8));
+  // landing block of the gradients [dmu | ds2] of a chunk: pinned when it fits, else uninitialised pageable memory
+  std::unique_ptr<double[]> hgrad_v;
+  double* hgrad = nullptr;
+  if (grad) {
+    const size_t gbytes = gres_per * (size_t)chunk;
+    if (gbytes <= PinBuf::kMax) hgrad = static_cast<double*>(c->pin.alloc(gbytes));
+    if (!hgrad) {
+      hgrad_v.reset(new double[gbytes / 8]);
+      hgrad = hgrad_v.get();
+    }
+  }
 
   // all samples in one chunk (the usual case): the posterior's constants are resident, see gpc_post
   const bool resident = chunk == S && mode != 2;
@@ -2530,7 +2557,7 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
       // Decided by the problem size only, never by the number of samples: the two forms add in different orders, and a
       // sample of a batch must carry the bits of its single evaluation)
       const long long tiles128 = (long long)(npad / TILE) * (mpad / TILE);
-      if (lch && !full && tiles128 >= 64) {
+      if (lch && !full && !grad && tiles128 >= 64) {
         // the variance needs the column sums of squares of V only: the product's epilogue forms them per tile row and V
         // is never written (gemm.h: EPI = 1); a small reduction over the tile rows follows
         const int tm = npad / TILE;
@@ -2551,6 +2578,25 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
       const T* left = lch ? (const T*)(V + (size_t)a * sKs) : (const T*)(Ks + (size_t)a * sKs);
       hipLaunchKernelGGL((colsum_prod_kernel<T>), dim3(mpad / 64, len), dim3(256), 0, st, left, sKs,
                          (const T*)(V + (size_t)a * sKs), sKs, mpad, npad, mpad, d_v + (size_t)a * mpad);
+      if (grad) {
+        // Q = W^T V (L_chol: the upper triangular A operand W^T, k from the tile row's diagonal block on) | G as it is
+        const T* Qs = V + (size_t)a * sKs;
+        if (lch) {
+          GemmArgs q = g;
+          q.A = po->W.as<T>() + (size_t)(s0 + a) * sM;
+          q.B = V + (size_t)a * sKs;
+          q.C = c->qb.as<T>() + (size_t)a * sKs;
+          q.klo = KLO_ROW;
+          q.khi = KHI_FULL;
+          HIPCHK(c, launch_gemm<T>(st, q, true, true, len));
+          Qs = c->qb.as<T>() + (size_t)a * sKs;
+        }
+        GPC_COV_DISPATCH(cross_grad_tile_kernel, T, po->cd, dim3(mpad / CT, npad / CT, len), dim3(256), 0, st, po->cd,
+                         xsb + (size_t)a * npad * D, (const double*)(c->xss.as<double>() + (size_t)a * mpad * D),
+                         spb + (size_t)a * SP_STRIDE, (const double*)(po->alpha.as<double>() + (size_t)(s0 + a) * npad),
+                         npad, Qs, sKs, lch ? 1 : 0, N, npad, M, mpad,
+                         c->gpart.as<double>() + (size_t)a * gnt * 2 * D * mpad);
+      }
       if (full) {
         // Kss -= V^T V / sl  (per sample: alpha differs)   |   Kss += R^T G
         for (int i = a; i < e; ++i) {
@@ -2572,9 +2618,16 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
       }
       a = e;
     }
+    if (grad) {
+      double* d_dmu = c->gres.as<double>();
+      double* d_ds2 = d_dmu + (size_t)chunk * mpad * D;
+      hipLaunchKernelGGL(grad_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
+                         (const double*)c->gpart.as<double>(), gnt, D, mpad, mulb, divb, d_dmu, d_ds2);
+      HIPCHK(c, hipMemcpyAsync(hgrad, d_dmu, 2 * (size_t)chunk * mpad * D * 8, hipMemcpyDeviceToHost, st));
+    }
     HIPCHK(c, hipGetLastError());
     const size_t out_bytes = (want_quad ? 2 : 1) * (size_t)chunk * mpad * 8;
-    const bool poll = !timing_on && !full && c->small_poll && c->land_blk && cnt == chunk && out_bytes <= PinBuf::kGather / 8;
+    const bool poll = !timing_on && !full && !grad && c->small_poll && c->land_blk && cnt == chunk && out_bytes <= PinBuf::kGather / 8;
     if (poll) {  // the results through the gathered download launch, which carries the completion word
       HIPCHK(c, c->pin.gather(hmu, d_mu, want_quad ? out_bytes : (size_t)cnt * mpad * 8, st));
     } else if (want_quad && cnt == chunk)  // d_v = d_mu + chunk * mpad: one contiguous block
@@ -2638,13 +2691,29 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
         if (want_quad) quad[(size_t)j * S + s] = hv[(size_t)i * mpad + j];
       }
     }
+    if (grad) {  // [(j*D + l)*S + s]: the samples of the chunk side by side, the output written in order
+      const double* gm = hgrad;
+      const double* gv = hgrad + (size_t)chunk * mpad * D;
+      const size_t ss = (size_t)mpad * D;
+      for (size_t jl = 0; jl < (size_t)M * D; ++jl) {
+        double* om = dlin + jl * S + s0;
+        double* ov = dquad + jl * S + s0;
+        for (int i = 0; i < cnt; ++i) {
+          om[i] = gm[i * ss + jl];
+          ov[i] = gv[i * ss + jl];
+        }
+      }
+    }
   }
   return 0;
 }
 
 template <typename T>
-int predict_impl(gpc_post* po, const double* xstar, int M, double* fmu, double* fs2) {
-  int rc = rhs_products<T>(po, 0, xstar, nullptr, M, true, fmu, fs2, nullptr);
+int predict_impl(gpc_post* po, const double* xstar, int M, double* fmu, double* fs2, double* dfmu = nullptr,
+                 double* dfs2 = nullptr) {
+  // (with dfmu: the gradients come back complete -- kss is constant for stationary kernels, and the 1/sl of the
+  // L_chol samples is applied to Q on the device)
+  int rc = rhs_products<T>(po, 0, xstar, nullptr, M, true, fmu, fs2, nullptr, dfmu, dfs2);
   if (rc) return rc;
   const int S = po->S;
   for (int s = 0; s < S; ++s) {
@@ -3064,7 +3133,7 @@ void gpc_destroy(gpc_ctx* c) {
   DevBuf* bufs[] = {&c->dX,   &c->dY,  &c->mA,    &c->mW,  &c->mT,   &c->xs,   &c->spb,  &c->mulb, &c->divb,
                     &c->dvec, &c->rvec,  &c->zvec, &c->avec, &c->scal, &c->parts, &c->gout, &c->diagq,
                     &c->dmb,  &c->dsn2b, &c->mg,  &c->ng,   &c->ks,   &c->vb,   &c->xss,  &c->pout, &c->kss,
-                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->tile_ctr, &c->rsv_tbl};
+                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->tile_ctr, &c->rsv_tbl};
   for (auto& g : c->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (DevBuf* b : bufs) b->release();
@@ -3483,6 +3552,20 @@ int gpc_predict(gpc_post* po, const double* xstar, int M, double* fmu, double* f
   HIPCHK(c, hipSetDevice(c->device));
   return po->dtype == GPC_F64 ? predict_impl<double>(po, xstar, M, fmu, fs2)
                               : predict_impl<float>(po, xstar, M, fmu, fs2);
+}
+
+int gpc_predict_grad(gpc_post* po, const double* xstar, int M, double* fmu, double* fs2, double* dfmu, double* dfs2) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!xstar || !fmu || !fs2 || !dfmu || !dfs2 || M <= 0) FAIL(c, "gpc_predict_grad: bad arguments");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_predict_grad: this posterior was built from caller-provided K; a caller-provided kernel has no "
+            "derivative with respect to x*");
+  for (int s = 0; s < po->S; ++s)
+    if (po->info[s] != 0) FAIL(c, "gpc_predict_grad: posterior contains a failed factorization");
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? predict_impl<double>(po, xstar, M, fmu, fs2, dfmu, dfs2)
+                              : predict_impl<float>(po, xstar, M, fmu, fs2, dfmu, dfs2);
 }
 
 int gpc_predict_full(gpc_post* po, const double* xstar, int M, double* fmu, double* cov) {

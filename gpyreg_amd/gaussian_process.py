@@ -131,6 +131,33 @@ def _mix_samples(means, variances):
     return centre, total, between
 
 
+def _mix_sample_grads(means, dmeans, dvariances):
+    """Gradients of ``_mix_samples``' mixture moments.  means (M, S); dmeans, dvariances (M, D, S), the per-sample
+    gradients with respect to the D inputs of each row: (dmean (M, D), dvariance (M, D)).  The spread term is
+    d/dx sum_s (mu_s - mu)^2 / (S - 1) = 2 sum_s (mu_s - mu) dmu_s / (S - 1) (sum_s (mu_s - mu) = 0)."""
+    S = means.shape[1]
+    if S == 1:
+        return dmeans[:, :, 0], dvariances[:, :, 0]
+    centre = np.sum(means, 1, keepdims=True) / S
+    dmu = np.sum(dmeans, 2) / S
+    ds2 = np.sum(dvariances, 2) / S + 2 * np.einsum("ms,mds->md", means - centre, dmeans) / (S - 1)
+    return dmu, ds2
+
+
+def _mean_grad_x(mean, hyp, X):
+    """d m(x) / dx (M, D) of a stock mean function under the mean hyperparameters ``hyp``; exact types only (a
+    subclass may compute anything): other mean objects raise NotImplementedError."""
+    from .mean_functions import ConstantMean, NegativeQuadratic, ZeroMean
+
+    if type(mean) in (ZeroMean, ConstantMean):
+        return np.zeros(X.shape)
+    if type(mean) is NegativeQuadratic:
+        D = X.shape[1]
+        return -(X - hyp[1:1 + D]) / np.exp(2 * hyp[1 + D:1 + 2 * D])
+    raise NotImplementedError(f"predict_grad: the mean function {mean!r} is user-defined; its gradient with "
+                              "respect to x_star is unknown")
+
+
 # GP.fit's options with the reference's defaults (gaussian_process.py:991-1006; "burn": thin * n_samples when unset)
 _FIT_DEFAULTS = {"opts_N": 3, "init_N": 2**10, "init_method": "sobol", "thin": 5, "df_base": 7, "widths": None,
                  "tol_opt": 1e-5, "tol_opt_mcmc": 1e-3, "sampler": "slicesample", "n_samples": 10, "burn": None,
@@ -1210,6 +1237,86 @@ class GP:
         if return_lpd:
             return mu, s2, lpd
         return mu, s2
+
+    @_on_device
+    def predict_grad(self, x_star, y_star=None, s2_star=None, add_noise: bool = False,
+                     separate_samples: bool = False):
+        """``predict``'s mean and variance at ``x_star`` and their gradients with respect to ``x_star``:
+        (mu, s2, dmu, ds2).  mu and s2 are what ``predict`` returns for the same arguments (within rounding: the
+        device sums the variance in another order); dmu and ds2 are (M, D), or (M, D, S) with ``separate_samples``,
+        entry [j, l] the derivative with respect to x_star[j, l].  The covariance part runs on the device
+        (gpc_predict_grad), the mean function's part on the host.  Where the clamp s2 = max(s2, 0) is active the
+        variance gradient is 0; the noise does not depend on x_star, so ``add_noise`` leaves it unchanged.  Built-in
+        (stationary) covariance functions and the stock mean and noise functions only: other objects raise
+        NotImplementedError."""
+        from .noise_functions import GaussianNoise
+
+        x_star, y_star, s2_star = self._convert_shapes(x_star, y_star, s2_star)
+        if not self._builtin:
+            raise NotImplementedError(f"predict_grad: the covariance function {self.covariance!r} is user-defined; it "
+                                      "has no derivative with respect to x_star")
+        if add_noise and type(self.noise) is not GaussianNoise:
+            raise NotImplementedError(f"predict_grad: the noise function {self.noise!r} is user-defined; add_noise "
+                                      "needs noise that does not depend on x_star")
+        s_N = self.posteriors.size
+        N_star, D = x_star.shape
+        cov_N, noise_N, mean_N = self._counts()
+        hyps = [self.posteriors[s].hyp for s in range(s_N)]
+        dm = np.stack([_mean_grad_x(self.mean, h[cov_N + noise_N:cov_N + noise_N + mean_N], x_star) for h in hyps],
+                      axis=2)
+
+        mu = np.zeros((N_star, s_N))
+        s2 = np.zeros((N_star, s_N))
+        dmu, ds2 = dm, np.zeros((N_star, D, s_N))
+        if self.y is not None:
+            self._restore()
+            if self._post_handle is None and self._post_range is None:
+                raise ValueError("posteriors have been cleaned; call update() first")
+            self._ctx()
+            local_posts, _ = self._local_posteriors()
+            if not local_posts:
+                fmu = fs2 = np.zeros((N_star, 0))
+                dfmu = dfs2 = np.zeros((N_star, D, 0))
+            else:
+                fmu, fs2, dfmu, dfs2 = self._post_handle.predict_grad(x_star)
+            if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
+                k = fmu.shape[1]
+                rows = np.concatenate([fmu, fs2, dfmu.reshape(N_star * D, k), dfs2.reshape(N_star * D, k)], axis=0)
+                rows = self._gather_samples(rows, x_star)
+                nd = N_star * D
+                fmu, fs2 = rows[:N_star], rows[N_star:2 * N_star]
+                dfmu = rows[2 * N_star:2 * N_star + nd].reshape(N_star, D, -1)
+                dfs2 = rows[2 * N_star + nd:].reshape(N_star, D, -1)
+            dmu = dm + dfmu
+            ds2 = dfs2
+        y_s2 = np.zeros((N_star, s_N)) if add_noise else None
+        for s in range(s_N):
+            hyp = hyps[s]
+            m_star = np.reshape(
+                self.mean.compute(hyp[cov_N + noise_N:cov_N + noise_N + mean_N], x_star), (-1,))
+            if self.y is not None:
+                mu[:, s] = m_star + fmu[:, s]
+                s2[:, s] = fs2[:, s]
+            else:  # no data: the prior, whose variance is constant for stationary kernels
+                mu[:, s] = m_star
+                s2[:, s] = self.covariance.compute(hyp[0:cov_N], x_star, compute_diag=True)[:, 0]
+            s2[:, s] = np.maximum(s2[:, s], 0)
+            if add_noise:
+                sn2_mult = self.posteriors[s].sn2_mult
+                if sn2_mult is None:
+                    sn2_mult = 1
+                sn2_star = self.noise.compute(hyp[cov_N:cov_N + noise_N], x_star, y_star, s2_star)
+                y_s2[:, s:s + 1] = s2[:, s:s + 1] + sn2_star * sn2_mult
+
+        # the clamp of predict, s2 = max(s2, 0): no variance gradient where it holds s2 at 0 (s2 <= 0 before it; at
+        # s2 = 0 exactly the one-sided derivatives differ, and 0 is the one that keeps the floor)
+        ds2 = np.where((s2 <= 0)[:, None, :], 0.0, ds2)
+        if add_noise:
+            s2 = y_s2
+        if not separate_samples:
+            dmu, ds2 = _mix_sample_grads(mu, dmu, ds2)
+            mu, s2, _ = _mix_samples(mu, s2)
+        return mu, s2, dmu, ds2
 
     @_on_device
     def predict_full(self, x_star, y_star=None, s2_star=None, add_noise: bool = False):

@@ -144,6 +144,20 @@ int gpc_post_free(gpc_post* post);
  *   fs2[j*S + s]  = kss - colsum(V*V)   or   kss + colsum(Ks * (L Ks))   (unclamped) */
 int gpc_predict(gpc_post* post, const double* xstar, int M, double* fmu, double* fs2);
 
+/* ---- GP.predict_grad: gradients of the predictive mean and variance with respect to x* -------------
+ * fmu, fs2 as gpc_predict; for every sample s, query point j and input dimension l (D of gpc_set_data):
+ *   dfmu[(j*D + l)*S + s] = d fmu_js / d x*_jl = -c_l sum_i alpha_i F_ij (xs*_jl - xs_il)
+ *   dfs2[(j*D + l)*S + s] = d fs2_js / d x*_jl = -2 sum_i Q_ij dk_ij / dx*_jl
+ *                         =  2 c_l sum_i Q_ij F_ij (xs*_jl - xs_il)
+ * with xs = x mul / dv the scaled inputs of the kernel family, c_l = mul_l / dv_l, F the radial factor of
+ * the covariance (dK / dlog ell_l = F d_l), and Q = (K + Sigma)^-1 K* under the posterior's own scaling:
+ * W^T (W K*) / sl for L_chol samples, -(A K*) otherwise.  kss is constant (stationary kernels): it adds
+ * nothing.  A pair with x* equal to a training point contributes 0 (Matern nu = 1: by convention).  The
+ * mean function's gradient, the clamp of fs2 at 0 and the mixture over samples are the caller's.
+ * Posteriors from caller-provided K fail with a message, as in gpc_predict.                             */
+int gpc_predict_grad(gpc_post* post, const double* xstar, int M, double* fmu, double* fs2, double* dfmu,
+                     double* dfs2);
+
 /* ---- rank-one append of ONE training point to resident posteriors (GP.update fast path,
  *      gaussian_process.py:750-844; scalar noise) ------------------------------------------------
  * Call gpc_set_data with the extended X (N+1 rows; the new point last) and y first.
