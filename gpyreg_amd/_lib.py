@@ -72,6 +72,7 @@ SIGNATURES = {
     "gpc_post_append_K": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_double, _ip]),
     "gpc_post_recompute_K": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_predict_full": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
+    "gpc_draw": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_ulonglong, C.c_int, _dp, _dp, _dp]),
     "gpc_quad": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpc_last_timing": (C.c_int, [_vp, _dp, _dp]),
     "gpc_last_lauum_timing": (C.c_int, [_vp, _dp, _dp]),
@@ -85,6 +86,7 @@ SIGNATURES = {
     ),
     "gpc_debug_leaf": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _ip]),
     "gpc_debug_factor": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "gpc_debug_normals": (C.c_int, [_vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "gpc_debug_workspace_hash": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
 }
 # declared under GPC_EXPERIMENTS in include/gpcore.h: present in the experiments build only (lib/libgpcore_exp.so, which
@@ -414,6 +416,14 @@ class Context:
         self._check(rc, "gpc_debug_factor")
         return L, W, Ainv, logdet.value, info.value
 
+    @_serial
+    def debug_normals(self, seed, stream, s, r, j0, count):
+        """gpc_debug_normals: the device's z of rows j0 .. j0 + count - 1 of (seed, stream, sample s, draw r)."""
+        out = np.empty(count)
+        rc = self._lib.gpc_debug_normals(self._h, int(seed), stream, s, r, j0, count, _ptr(out))
+        self._check(rc, "gpc_debug_normals")
+        return out
+
 
 class PostHandle:
     """Device-resident posteriors of one hyperparameter batch (gpc_post)."""
@@ -529,6 +539,22 @@ class PostHandle:
         rc = self.ctx._lib.gpc_predict_full(self._h, _ptr(xs), M, _ptr(fmu), _ptr(cov))
         self.ctx._check(rc, "gpc_predict_full")
         return fmu, cov
+
+    @_serial
+    def draw(self, x_star, n_draws, seed, s_offset=0, noise_sd=None):
+        """gpc_draw: f (M, n_draws, S) = fmu + L z (+ noise_sd z'), without the mean function, and the jitter tau (S,)
+        each sample needed.  s_offset is the global index of this posterior's first sample (the random stream's key);
+        noise_sd (M, S) or None.  A sample that cannot be factored raises numpy.linalg.LinAlgError."""
+        xs = _f64(x_star)
+        M = xs.shape[0]
+        f = np.empty((M, n_draws, self.S))
+        tau = np.empty(self.S)
+        nsd = None if noise_sd is None else _f64(noise_sd)
+        rc = self.ctx._lib.gpc_draw(self._h, _ptr(xs), M, n_draws, int(seed), s_offset, _ptr(nsd), _ptr(f), _ptr(tau))
+        if rc == -3:
+            raise np.linalg.LinAlgError(self.ctx._lib.gpc_last_error(self.ctx._h).decode())
+        self.ctx._check(rc, "gpc_draw")
+        return f, tau
 
     @_serial
     def quad(self, mu, sigma, compute_var):

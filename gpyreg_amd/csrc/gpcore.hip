@@ -22,6 +22,7 @@
 #include "blas1.h"
 #include "common.h"
 #include "covfun.h"
+#include "draw.h"
 #include "gemm.h"
 #include "leaf.h"
 #include "plan.h"
@@ -504,6 +505,7 @@ struct gpc_ctx {
   DevBuf dmb, dsn2b, mg, ng;     // mean / noise gradient inputs and outputs
   DevBuf ks, vb, kss, xss, pout; // predict / predict_full / quad
   DevBuf qb, gpart, gres;        // predict_grad: Q = W^T V, per-tile partials, the gradients
+  DevBuf zb, fb, dout, daux;     // draw: Z, F = L Z, the draws, [logdet | info | noise sd] (the factor: mA mW mT)
   DevBuf dbg1, dbg2, dbg3;       // debug hooks / fetch staging
   PinBuf pin;                    // pinned staging for host<->device transfers (see PinBuf)
   // Launch graphs of the device pipeline for small problems (npad <= graph_max_npad, one sample
@@ -2359,6 +2361,120 @@ int post_impl(gpc_ctx* c, Batch& b, gpc_post* po, double* sn2_mult, int* L_chol,
   return 0;
 }
 
+// A gpc_draw request (rhs_products with mode_full): the covariances C_s stay resident and are factored and
+// multiplied on the device instead of being downloaded.
+struct DrawReq {
+  unsigned long long seed;
+  int R;
+  int s_offset;       // global index of the posterior's first sample (the random stream is keyed on it)
+  const double* nsd;  // M x S noise standard deviations, or null
+  double* f;          // M x R x S
+  double* tau;        // S
+};
+
+// One chunk of draws: C_s (in c->kss, chunk layout) -> A = C_s + tau_s I -> L (batched Factor, stable retries with
+// jitter for the samples that failed; the diagonal tiles cleaned above the diagonal) -> Z (normals_kernel) -> F = L Z (gemm.h: lower A operand, KHI_ROW skips the
+// zero upper tiles) -> fmu + F (+ noise) into c->dout, copied to hout.  Every step is per sample with a reduction order
+// fixed by the shape (the leaf and the product library do not depend on the batch), so a sample's draws carry the same
+// bits in any batch or chunk.  Returns -3 with a message when a sample cannot be factored with the largest jitter.
+template <typename T>
+int draw_chunk(gpc_post* po, const DrawReq& d, int s0, int cnt, int M, const double* d_mu, double* hout) {
+  gpc_ctx* c = po->ctx;
+  hipStream_t st = c->st;
+  const int mpad = pad_tile(M), R = d.R, rpad = pad_tile(R);
+  const long long sKss = (long long)mpad * mpad, sZ = (long long)mpad * rpad;
+  T* C = c->kss.as<T>();
+  T* A = c->mA.as<T>();
+  double* d_nsd = d.nsd ? c->daux.as<double>() : nullptr;
+  double* logdet = c->daux.as<double>() + (size_t)M * po->S;
+  int* info = reinterpret_cast<int*>(logdet + cnt);
+  const dim3 blk(64, 4);
+  auto factor = [&](int i0, int n, double tau, bool stable) -> int {
+    HIPCHK(c, hipMemsetAsync(logdet + i0, 0, (size_t)n * 8, st));
+    HIPCHK(c, hipMemsetAsync(info + i0, 0, (size_t)n * sizeof(int), st));
+    hipLaunchKernelGGL((jitter_load_kernel<T>), dim3(mpad / 64, mpad / 4, n), blk, 0, st, (const T*)(C + i0 * sKss),
+                       A + i0 * sKss, sKss, mpad, M, tau);
+    Factor<T> F;
+    F.st = st;
+    F.batch = n;
+    F.npad = mpad;
+    F.nvalid = M;
+    F.A = A + i0 * sKss;
+    F.W = c->mW.as<T>() + i0 * sKss;
+    F.Tm = c->mT.as<T>() + i0 * sKss;
+    F.sA = F.sW = F.sT = sKss;
+    F.logdet = logdet + i0;
+    F.info = info + i0;
+    F.stable = stable;
+    F.potrf_inv(0, mpad, false, true);
+    HIPCHK(c, F.err);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  };
+  int rc = factor(0, cnt, 0.0, false);
+  if (rc) return rc;
+  std::vector<int> hinfo(cnt);
+  HIPCHK(c, hipMemcpyAsync(hinfo.data(), info, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  for (int i = 0; i < cnt; ++i) {
+    double tau = 0.0;
+    if (hinfo[i] & LEAF_TIMEOUT) FAIL(c, "gpc_draw: internal error: a leaf of the factorization timed out");
+    if (hinfo[i] != 0) {
+      // jitter ladder: tau = t mean(diag C_s), t = 1e-12 .. 1e-6, stable mode, this sample alone
+      std::vector<T> dg(M);
+      HIPCHK(c, hipMemcpy2DAsync(dg.data(), sizeof(T), C + i * sKss, (size_t)(mpad + 1) * sizeof(T), sizeof(T), M,
+                                 hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipStreamSynchronize(st));
+      double mean = 0.0;
+      for (int j = 0; j < M; ++j) mean += (double)dg[j];
+      mean /= M;
+      bool ok = false;
+      for (int e = -12; e <= -6 && !ok; ++e) {
+        tau = std::pow(10.0, (double)e) * mean;
+        rc = factor(i, 1, tau, true);
+        if (rc) return rc;
+        int inf = 0;
+        HIPCHK(c, hipMemcpyAsync(&inf, info + i, sizeof(int), hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (inf & LEAF_TIMEOUT) FAIL(c, "gpc_draw: internal error: a leaf of the factorization timed out");
+        ok = inf == 0 && tau > 0;
+      }
+      if (!ok) {
+        c->err = "gpc_draw: the posterior covariance of sample " + std::to_string(d.s_offset + s0 + i) +
+                 " is not positive definite, even with a jitter of 1e-6 mean(diag C)";
+        return -3;
+      }
+    }
+    d.tau[s0 + i] = tau;
+  }
+  hipLaunchKernelGGL((diag_tile_upper_zero_kernel<T>), dim3(mpad / TILE, cnt), dim3(256), 0, st, A, sKss, mpad);
+  const long long s_base = (long long)d.s_offset + s0;
+  hipLaunchKernelGGL((normals_kernel<T>), dim3(rpad / 64, mpad / 16, cnt), blk, 0, st, d.seed, 0, s_base, M, R, mpad,
+                     rpad, c->zb.as<T>(), sZ);
+  GemmArgs g;
+  g.A = A;
+  g.B = c->zb.as<T>();
+  g.C = c->fb.as<T>();
+  g.sA = sKss;
+  g.sB = g.sC = sZ;
+  g.lda = mpad;
+  g.ldb = g.ldc = rpad;
+  g.M = mpad;
+  g.N = rpad;
+  g.K = mpad;
+  g.alpha = 1.0;
+  g.beta = 0;
+  g.klo = KLO_ZERO;
+  g.khi = KHI_ROW;  // L lower triangular: tile row ti needs k < (ti + 1) 128 only
+  g.lower_only = 0;
+  HIPCHK(c, launch_gemm<T>(st, g, false, true, cnt));
+  hipLaunchKernelGGL((draw_assemble_kernel<T>), dim3((R + 63) / 64, mpad / 16, cnt), blk, 0, st, (const T*)c->fb.as<T>(),
+                     sZ, rpad, d_mu, mpad, M, R, (const double*)d_nsd, po->S, s0, d.seed, s_base, c->dout.as<double>());
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(hout, c->dout.p, (size_t)cnt * M * R * 8, hipMemcpyDeviceToHost, st));
+  return 0;
+}
+
 // Shared by predict / predict_full / quad: for every posterior sample s build a right-hand
 // side matrix R_s (npad x mpad: cross covariances, or quadrature kernel means), then
 //   lin[j*S+s]  = R_s[:, j] . alpha_s
@@ -2368,11 +2484,13 @@ int post_impl(gpc_ctx* c, Batch& b, gpc_post* po, double* sn2_mult, int* L_chol,
 //   dlin / dquad [(j*D + l)*S + s] = d lin / dx*_jl and d(kss - k*^T (K + Sigma)^-1 k*) / dx*_jl  (mode 0 with
 //                 want_quad only; covfun.h: cross_grad_tile_kernel): V is written (no EPI = 1 product), Q = W^T V
 //                 is one more product of the same size (L_chol; the other samples use G = L R as it is)
+//   draw        with `full`: C_s is factored and multiplied on the device (draw_chunk), not downloaded
 // mode: 0 = cross covariance of xa (M x D) with the training inputs; 1 = quadrature
 // vectors z for Gaussian measures N(xa[j], diag(xb[j]^2)) (gaussian_process.py:1908-1921).
 template <typename T>
 int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int M, bool want_quad,
-                 double* lin, double* quad, double* full, double* dlin = nullptr, double* dquad = nullptr) {
+                 double* lin, double* quad, double* full, double* dlin = nullptr, double* dquad = nullptr,
+                 const DrawReq* draw = nullptr) {
   gpc_ctx* c = po->ctx;
   const int S = po->S, N = po->N, D = po->D, npad = po->npad;
   const int mpad = pad_tile(M);
@@ -2384,21 +2502,41 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
   const int gnt = npad / CT;  // tile rows of the gradient pass
   // gradient scratch per sample: Q (as V), the per-tile partials and the results
   const size_t gpart_per = grad ? (size_t)gnt * 2 * D * mpad * 8 : 0, gres_per = grad ? 2ull * mpad * D * 8 : 0;
+  // draw scratch per sample: the factor's three slabs (mA mW mT), Z and F (mpad x rpad), the draws
+  const int rpad = draw ? pad_tile(draw->R) : 0;
+  const size_t sZ = (size_t)mpad * rpad;
+  const size_t draw_per = draw ? (3 * (size_t)sKss + 2 * sZ) * sizeof(T) + (size_t)M * draw->R * 8 : 0;
   const size_t per = (2ull * npad * mpad + (full ? (size_t)mpad * mpad : 0) + (grad ? (size_t)npad * mpad : 0)) * sizeof(T) +
-                     gpart_per + gres_per;
-  const size_t held = c->ks.bytes + c->vb.bytes + c->kss.bytes + (grad ? c->qb.bytes + c->gpart.bytes + c->gres.bytes : 0);
+                     gpart_per + gres_per + draw_per;
+  const size_t held = c->ks.bytes + c->vb.bytes + c->kss.bytes + (grad ? c->qb.bytes + c->gpart.bytes + c->gres.bytes : 0) +
+                      (draw ? c->mA.bytes + c->mW.bytes + c->mT.bytes + c->zb.bytes + c->fb.bytes + c->dout.bytes : 0);
   int chunk = S;
   if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > held ||
       (size_t)S * sKs * sizeof(T) > std::min(c->ks.bytes, c->vb.bytes) ||
       (full && (size_t)S * sKss * sizeof(T) > c->kss.bytes) ||
-      (grad && ((size_t)S * sKs * sizeof(T) > c->qb.bytes || (size_t)S * gpart_per > c->gpart.bytes))) {
+      (grad && ((size_t)S * sKs * sizeof(T) > c->qb.bytes || (size_t)S * gpart_per > c->gpart.bytes)) ||
+      (draw && ((size_t)S * sKss * sizeof(T) > std::min({c->mA.bytes, c->mW.bytes, c->mT.bytes}) ||
+                (size_t)S * sZ * sizeof(T) > std::min(c->zb.bytes, c->fb.bytes) ||
+                (size_t)S * M * draw->R * 8 > c->dout.bytes))) {
     c->pool_drain();
     size_t budget = (size_t)((free_device_bytes() + (getenv("GPC_MEM_BUDGET_MB") ? 0 : held)) * 0.8);
+    if (draw && budget < per)
+      FAIL(c, "gpc_draw: the scratch of one sample (" + std::to_string(per >> 20) + " MB) exceeds the device memory "
+              "budget (" + std::to_string(budget >> 20) + " MB)");
     chunk = (int)std::max<size_t>(1, std::min<size_t>(S, budget / per));
   }
   HIPCHK(c, c->ks.ensure((size_t)chunk * sKs * sizeof(T)));
   HIPCHK(c, c->vb.ensure((size_t)chunk * sKs * sizeof(T)));
   if (full) HIPCHK(c, c->kss.ensure((size_t)chunk * sKss * sizeof(T)));
+  if (draw) {
+    HIPCHK(c, c->mA.ensure((size_t)chunk * sKss * sizeof(T)));
+    HIPCHK(c, c->mW.ensure((size_t)chunk * sKss * sizeof(T)));
+    HIPCHK(c, c->mT.ensure((size_t)chunk * sKss * sizeof(T)));
+    HIPCHK(c, c->zb.ensure((size_t)chunk * sZ * sizeof(T)));
+    HIPCHK(c, c->fb.ensure((size_t)chunk * sZ * sizeof(T)));
+    HIPCHK(c, c->dout.ensure((size_t)chunk * M * draw->R * 8));
+    HIPCHK(c, c->daux.ensure(((size_t)M * S + 2 * (size_t)chunk) * 8));
+  }
   if (grad) {
     HIPCHK(c, c->qb.ensure((size_t)chunk * sKs * sizeof(T)));
     HIPCHK(c, c->gpart.ensure((size_t)chunk * gpart_per));
@@ -2432,8 +2570,20 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
   }
   double* hv = hmu + (size_t)chunk * mpad;
   double* hfull = nullptr;
-  if (full && (size_t)M * M * 8 >= PinBuf::kMin && (size_t)M * M * 8 <= PinBuf::kMax)
+  if (full && !draw && (size_t)M * M * 8 >= PinBuf::kMin && (size_t)M * M * 8 <= PinBuf::kMax)
     hfull = static_cast<double*>(c->pin.alloc((size_t)M * M * 8));
+  // landing block of a chunk's draws (M x R per sample): pinned when it fits, else uninitialised pageable memory
+  std::unique_ptr<double[]> hdraw_v;
+  double* hdraw = nullptr;
+  if (draw) {
+    const size_t dbytes = (size_t)chunk * M * draw->R * 8;
+    if (dbytes <= PinBuf::kMax) hdraw = static_cast<double*>(c->pin.alloc(dbytes));
+    if (!hdraw) {
+      hdraw_v.reset(new double[dbytes / 8]);
+      hdraw = hdraw_v.get();
+    }
+    if (draw->nsd) HIPCHK(c, hipMemcpyAsync(c->daux.p, draw->nsd, (size_t)M * S * 8, hipMemcpyHostToDevice, st));
+  }
   // landing block of the gradients [dmu | ds2] of a chunk: pinned when it fits, else uninitialised pageable memory
   std::unique_ptr<double[]> hgrad_v;
   double* hgrad = nullptr;
@@ -2636,7 +2786,10 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
       HIPCHK(c, hipMemcpyAsync(hmu, d_mu, (size_t)cnt * mpad * 8, hipMemcpyDeviceToHost, st));
       if (want_quad) HIPCHK(c, hipMemcpyAsync(hv, d_v, (size_t)cnt * mpad * 8, hipMemcpyDeviceToHost, st));
     }
-    if (full) {
+    if (draw) {
+      const int rc = draw_chunk<T>(po, *draw, s0, cnt, M, d_mu, hdraw);
+      if (rc) return rc;
+    } else if (full) {
       HIPCHK(c, c->dbg3.ensure((size_t)M * M * 8));
       for (int i = 0; i < cnt; ++i) {
         dim3 gn((M + 63) / 64, (M + 3) / 4), blk(64, 4);
@@ -2689,6 +2842,13 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
       for (int j = 0; j < M; ++j) {
         lin[(size_t)j * S + s] = hmu[(size_t)i * mpad + j];
         if (want_quad) quad[(size_t)j * S + s] = hv[(size_t)i * mpad + j];
+      }
+    }
+    if (draw) {  // f[(j*R + r)*S + s]
+      const int R = draw->R;
+      for (size_t jr = 0; jr < (size_t)M * R; ++jr) {
+        double* o = draw->f + jr * S + s0;
+        for (int i = 0; i < cnt; ++i) o[i] = hdraw[(size_t)i * M * R + jr];
       }
     }
     if (grad) {  // [(j*D + l)*S + s]: the samples of the chunk side by side, the output written in order
@@ -3133,7 +3293,7 @@ void gpc_destroy(gpc_ctx* c) {
   DevBuf* bufs[] = {&c->dX,   &c->dY,  &c->mA,    &c->mW,  &c->mT,   &c->xs,   &c->spb,  &c->mulb, &c->divb,
                     &c->dvec, &c->rvec,  &c->zvec, &c->avec, &c->scal, &c->parts, &c->gout, &c->diagq,
                     &c->dmb,  &c->dsn2b, &c->mg,  &c->ng,   &c->ks,   &c->vb,   &c->xss,  &c->pout, &c->kss,
-                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->tile_ctr, &c->rsv_tbl};
+                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
   for (auto& g : c->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (DevBuf* b : bufs) b->release();
@@ -3566,6 +3726,37 @@ int gpc_predict_grad(gpc_post* po, const double* xstar, int M, double* fmu, doub
   HIPCHK(c, hipSetDevice(c->device));
   return po->dtype == GPC_F64 ? predict_impl<double>(po, xstar, M, fmu, fs2, dfmu, dfs2)
                               : predict_impl<float>(po, xstar, M, fmu, fs2, dfmu, dfs2);
+}
+
+int gpc_draw(gpc_post* po, const double* xstar, int M, int R, unsigned long long seed, int s_offset,
+             const double* noise_sd, double* f, double* tau) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!xstar || !f || !tau || M <= 0 || R <= 0 || s_offset < 0) FAIL(c, "gpc_draw: bad arguments");
+  if (po->cd.kind < 0) FAIL(c, "gpc_draw: this posterior was built from caller-provided K; there is no K** to draw from");
+  for (int s = 0; s < po->S; ++s)
+    if (po->info[s] != 0) FAIL(c, "gpc_draw: posterior contains a failed factorization");
+  HIPCHK(c, hipSetDevice(c->device));
+  DrawReq req{seed, R, s_offset, noise_sd, f, tau};
+  std::vector<double> fmu((size_t)M * po->S);
+  // (`full` only marks the covariance build: draw_chunk consumes C_s on the device, nothing M x M is written)
+  return po->dtype == GPC_F64
+             ? rhs_products<double>(po, 0, xstar, nullptr, M, false, fmu.data(), nullptr, f, nullptr, nullptr, &req)
+             : rhs_products<float>(po, 0, xstar, nullptr, M, false, fmu.data(), nullptr, f, nullptr, nullptr, &req);
+}
+
+int gpc_debug_normals(gpc_ctx* c, unsigned long long seed, int stream, int s, int r, int j0, int count, double* out) {
+  if (!c) return -2;
+  if (!out || count <= 0 || s < 0 || r < 0 || j0 < 0 || (stream != 0 && stream != 1))
+    FAIL(c, "gpc_debug_normals: bad arguments");
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, c->dbg1.ensure((size_t)count * 8));
+  hipLaunchKernelGGL(debug_normals_kernel, dim3((count + 255) / 256), dim3(256), 0, c->st, seed, stream, (long long)s, r,
+                     (long long)j0, count, c->dbg1.as<double>());
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, c->dbg1.p, (size_t)count * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  return 0;
 }
 
 int gpc_predict_full(gpc_post* po, const double* xstar, int M, double* fmu, double* cov) {

@@ -1388,6 +1388,101 @@ class GP:
         mult = getattr(post, "sn2_mult", None)
         return f_star + np.sqrt(sn2 * (1 if mult is None else mult)) * np.random.standard_normal(size=f_mu.shape)
 
+    def draw_functions(self, x_star, n_draws: int = 1, add_noise: bool = False, seed: int = 0, y_star=None,
+                       s2_star=None, return_jitter: bool = False):
+        """``n_draws`` joint draws of the latent function at ``x_star`` from the posterior of EACH hyperparameter
+        sample: f (M, n_draws, S), with ``f[:, r, s] = m_s(x*) + fmu_s + chol(C_s + tau_s I) z_{s,r}`` -- fmu_s and C_s
+        are ``predict_full``'s mean part and covariance, z the seeded stream of ``_philox`` (a value depends on seed,
+        sample, draw and row only).  C_s is factored without jitter first; a sample that fails is retried with
+        tau_s = t mean(diag C_s), t = 1e-12 ... 1e-6 (``LinAlgError`` naming the sample if none succeeds).  With
+        ``add_noise`` each value gets sqrt(sn2* sn2_mult_s) z' from noise stream 1.  ``return_jitter``: (f, tau),
+        tau (S,) the absolute jitter of every sample.  With data the factorization and the product run on the device
+        (gpc_draw; fp32 posteriors in fp32); a GP without data draws from the prior N(m, K**), K** from the covariance
+        object and the factorization and product in NumPy.  Built-in
+        covariance functions only.  Under sharding each rank draws its samples and the results are gathered:
+        the same values as one process.  ``random_function`` is unchanged."""
+        from . import _philox
+
+        if not self._builtin:
+            raise NotImplementedError(f"draw_functions: the covariance function {self.covariance!r} is user-defined; "
+                                      "draws run on the built-in covariance functions only")
+        if isinstance(n_draws, bool) or int(n_draws) != n_draws or n_draws < 1:
+            raise ValueError(f"n_draws must be a positive integer, got {n_draws!r}")
+        n_draws = int(n_draws)
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2**64:
+            raise ValueError(f"seed must be an integer in [0, 2**64), got {seed!r}")
+        seed = int(seed)
+        x_star, y_star, s2_star = self._convert_shapes(x_star, y_star, s2_star)
+        s_N = self.posteriors.size
+        M = x_star.shape[0]
+        cov_N, noise_N, mean_N = self._counts()
+        hyps = [self.posteriors[s].hyp for s in range(s_N)]
+        nsd = None
+        if add_noise:
+            nsd = np.empty((M, s_N))
+            for s in range(s_N):
+                mult = self.posteriors[s].sn2_mult
+                sn2 = np.asarray(self.noise.compute(hyps[s][cov_N:cov_N + noise_N], x_star, y_star, s2_star), float)
+                sn2 = np.broadcast_to(sn2.reshape(-1) if sn2.size == M else sn2.reshape(-1)[:1], (M,))
+                nsd[:, s] = np.sqrt(sn2 * (1 if mult is None else mult))
+
+        if self.y is not None:
+            f, tau = self._draw_on_device(x_star, n_draws, seed, nsd)
+        else:  # no data: the prior N(m, K**), on the host
+            f = np.empty((M, n_draws, s_N))
+            tau = np.zeros(s_N)
+            for s in range(s_N):
+                K = self.covariance.compute(hyps[s][0:cov_N], x_star)
+                L, tau[s] = self._jittered_cholesky(K, s)
+                z = _philox.normals_block(seed, 0, M, n_draws, [s])[:, :, 0]
+                f[:, :, s] = L @ z
+                if add_noise:
+                    f[:, :, s] += nsd[:, s:s + 1] * _philox.normals_block(seed, 1, M, n_draws, [s])[:, :, 0]
+        for s in range(s_N):
+            m_star = np.reshape(self.mean.compute(hyps[s][cov_N + noise_N:cov_N + noise_N + mean_N], x_star), (-1,))
+            f[:, :, s] += m_star[:, None]
+        return (f, tau) if return_jitter else f
+
+    @_on_device
+    def _draw_on_device(self, x_star, n_draws, seed, nsd):
+        """draw_functions' posterior part: (f (M, n_draws, S) without the mean function, tau (S,)), gathered over the
+        ranks when sharded (each rank draws its block of samples under their global indices)."""
+        M = x_star.shape[0]
+        self._restore()
+        if self._post_handle is None and self._post_range is None:
+            raise ValueError("posteriors have been cleaned; call update() first")
+        self._ctx()
+        local_posts, lo = self._local_posteriors()
+        if not local_posts:
+            f, tau = np.zeros((M, n_draws, 0)), np.zeros(0)
+        else:
+            k = len(local_posts)
+            f, tau = self._post_handle.draw(x_star, n_draws, seed, lo, None if nsd is None else nsd[:, lo:lo + k])
+        if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
+            k = f.shape[2]
+            rows = np.concatenate([f.reshape(M * n_draws, k), tau.reshape(1, k)], axis=0)
+            rows = self._gather_samples(rows, x_star, n_draws, seed, nsd is not None)
+            f, tau = rows[:M * n_draws].reshape(M, n_draws, -1), rows[M * n_draws].copy()
+        return f, tau
+
+    @staticmethod
+    def _jittered_cholesky(C, s):
+        """(L, tau): the lower Cholesky factor of C + tau I, tau = 0 when C itself factors, else the first of
+        t mean(diag C), t = 1e-12, 1e-11, ..., 1e-6 that does (``draw_functions``' ladder; LinAlgError names sample s)."""
+        try:
+            return np.linalg.cholesky(C), 0.0
+        except np.linalg.LinAlgError:
+            pass
+        mean = np.sum(np.diag(C)) / C.shape[0]
+        for e in range(-12, -5):
+            tau = 10.0**e * mean
+            try:
+                return np.linalg.cholesky(C + tau * np.eye(C.shape[0])), tau
+            except np.linalg.LinAlgError:
+                pass
+        raise np.linalg.LinAlgError(f"draw_functions: the prior covariance of sample {s} is not positive definite, "
+                                    "even with a jitter of 1e-6 mean(diag C)")
+
     @staticmethod
     def _robust_factor(C):
         """T with T^T T = C for a covariance matrix that may have lost definiteness to rounding (reference

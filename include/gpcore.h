@@ -158,6 +158,30 @@ int gpc_predict(gpc_post* post, const double* xstar, int M, double* fmu, double*
 int gpc_predict_grad(gpc_post* post, const double* xstar, int M, double* fmu, double* fs2, double* dfmu,
                      double* dfs2);
 
+/* ---- GP.draw_functions: joint posterior draws, n_draws per sample (extends gaussian_process.py:2241-2329) ----
+ * For every sample s of the posterior (global index s_offset + s), draw r < R and query point j < M:
+ *   f[(j*R + r)*S + s] = fmu_js + (L_s z_{s,r})_j  (+ noise_sd[j*S + s] z'_{s,r,j})
+ * with fmu as gpc_predict, C_s = K** - V^T V the covariance of gpc_predict_full, L_s the lower Cholesky factor
+ * of C_s + tau_s I.  C_s is factored first without jitter; a sample that fails is retried alone in stable mode
+ * with tau_s = t mean(diag C_s), t = 1e-12, 1e-11, ..., 1e-6, the first success kept; tau[s] receives the
+ * absolute jitter (0 when none was needed).  If every level fails the call returns -3 and gpc_last_error
+ * names the global sample index.  noise_sd (M x S, may be NULL) is the caller's sqrt(sn2* sn2_mult).  The
+ * mean function is the caller's.  fp32 posteriors factor and multiply in fp32.  A sample's draws are the
+ * same bits whatever the batch of samples, the chunking (GPC_MEM_BUDGET_MB) or R beyond r.  Returns -2
+ * with a message when one sample's scratch (three M x M slabs of the factorization, Z and L Z) does not
+ * fit the memory budget.
+ * Random stream: Philox4x64-10 with key (seed, stream), stream 0 for z, 1 for z'.  The 64-bit word of row j
+ * is lane j % 4 of the block at counter (j / 4 + 1, r, s_global, 0) -- the first block numpy's
+ * Philox(key=[seed, stream], counter=[j / 4, r, s_global, 0]).random_raw(4) returns.  Rows (2t, 2t+1):
+ *   u1 = ((w[2t] >> 11) + 1) 2^-53,  u2 = (w[2t+1] >> 11) 2^-53,
+ *   z[2t] = sqrt(-2 ln u1) cos(2 pi u2),  z[2t+1] = sqrt(-2 ln u1) sin(2 pi u2)
+ * (odd M: the last row's partner is computed and unused).  gpyreg_amd/_philox.py restates it.           */
+int gpc_draw(gpc_post* post, const double* xstar, int M, int R, unsigned long long seed, int s_offset,
+             const double* noise_sd, double* f, double* tau);
+/* out[i] = z of row j0 + i, i < count, of (seed, stream, sample s, draw r), computed on the device (tests). */
+int gpc_debug_normals(gpc_ctx* ctx, unsigned long long seed, int stream, int s, int r, int j0, int count,
+                      double* out);
+
 /* ---- rank-one append of ONE training point to resident posteriors (GP.update fast path,
  *      gaussian_process.py:750-844; scalar noise) ------------------------------------------------
  * Call gpc_set_data with the extended X (N+1 rows; the new point last) and y first.
