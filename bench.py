@@ -31,6 +31,14 @@ fresh child processes (before anything touches the GPU: the parent never imports
 
 Rank 0 prints ONE JSON line.  With `--dump-outputs DIR` it also writes what the last timed step returned as
 DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
+
+A plain run sets up, warms up, times the steps, dumps (if asked) and prints the line: the headline and what the timed
+steps' own hipEvents give (`roofline` from the factorization section, the wall clock and the W^T W launch as it ran).
+`--full` adds the measurements that take runs of their own, after the timed region:
+    cpu_baseline       the CPU oracle on sample 0, with its live parity check (one rank; not with --no-cpu-baseline)
+    roofline.alone     the dominant launch timed alone in three extra steps (rank 0, fit mode)
+    roofline.measured_mfma_ceiling   the issue-rate ceiling of a bare MFMA loop (gpc_mfma_peak)
+    config.weak|strong, config.expected_from_1gpu   the other split and the rank-local yardstick (multi-rank runs)
 """
 
 import argparse
@@ -441,7 +449,7 @@ def dry_run(args, world, rank):
     per_rank = [_sh.shard_bounds(S_global, r, world)[1] - _sh.shard_bounds(S_global, r, world)[0] for r in range(world)]
     splits = {}
     calls_per_step = _sh.stats()["calls"] / (args.warmup + args.steps)
-    if dist.is_initialized():
+    if dist.is_initialized() and args.full:
         import torch
 
         def evaluate(h, shard):  # the same stand-in rows, sharded through the exchange or rank-local
@@ -567,9 +575,9 @@ def run(args):
     else:
         exch_max = exch["seconds"]
 
-    # both splits and the single-GPU yardstick in the same job (multi-rank runs; after the timed region)
+    # both splits and the single-GPU yardstick in the same job (multi-rank --full runs; after the timed region)
     splits = {}
-    if dist is not None and world > 1 and mode != "predict":
+    if args.full and dist is not None and world > 1 and mode != "predict":
         def evaluate(h, shard):
             prev = gp.shard
             gp.shard = shard
@@ -582,9 +590,9 @@ def run(args):
 
     # The dominant single kernel, timed ALONE as well: three extra UNTIMED steps with one sample group and the two
     # triangular mat-vecs after the launch instead of under it (they cost it ~3 %), so that its hipEvent
-    # time is the kernel's own duration; the first of the three is dropped.
+    # time is the kernel's own duration; the first of the three is dropped.  (--full)
     lau_alone, lau_alone_fl = [], 0.0
-    if rank == 0 and grad and S_local > 0:
+    if args.full and rank == 0 and grad and S_local > 0:
         prev = {k: ctx.get_option(k) for k in ("groups", "solves_beside_lauum")}
         ctx.set_option("groups", 1)
         ctx.set_option("solves_beside_lauum", 0)
@@ -615,7 +623,10 @@ def run(args):
 
     N, D = cfg["N"], cfg["D"]
     peak = FP64_MFMA_PEAK_TFLOPS if dtype == "f64" else FP32_MFMA_PEAK_TFLOPS
-    tf, cyc, ghz = ctx.mfma_peak(_lib.F64 if dtype == "f64" else _lib.F32)
+    ceiling = None  # the issue-rate ceiling of a bare MFMA loop, launches of its own (--full)
+    if args.full:
+        tf, cyc, ghz = ctx.mfma_peak(_lib.F64 if dtype == "f64" else _lib.F32)
+        ceiling = {"tflops": tf, "cycles_per_mfma_per_simd": cyc, "clock_ghz": ghz}
     wall = dt / args.steps
     fac = float(np.mean(fac_ms)) * 1e-3
     workload = (f"cfg{args.config}: N={N} D={D} {cfg['kernel']}{cfg['degree'] or ''} ARD, ConstantMean, "
@@ -680,10 +691,10 @@ def run(args):
             # the whole call by the wall clock (cross-kernel build, mat-vec, product, column sums, transfers, host)
             "frac_wall": flops_all / wall / 1e12 / peak,
             "hbm_bytes_algorithmic": float(S_local) * N * N * (8 if dtype == "f64" else 4) / 2,
-            "measured_mfma_ceiling": {"tflops": tf, "cycles_per_mfma_per_simd": cyc, "clock_ghz": ghz},
+            "measured_mfma_ceiling": ceiling,
         }
         out["mu_sample0_first"] = float(mu[0, 0])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_predict(args.config, xs, mu[:, 0], s2[:, 0])
             out["vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
             if dtype == "f64":
@@ -708,7 +719,7 @@ def run(args):
             "bound": "mfma",
             "unit": "TFLOP/s",
             "peak": peak,
-            "measured_mfma_ceiling": {"tflops": tf, "cycles_per_mfma_per_simd": cyc, "clock_ghz": ghz},
+            "measured_mfma_ceiling": ceiling,
             # the whole pipeline of one step on this rank: S N^3 algorithmic flops
             "flops_per_step": flops_step,
             "factor_section_ms": fac * 1e3,
@@ -754,7 +765,7 @@ def run(args):
             })
         out["roofline"] = roof
         out["nlz_sample0"] = float(nlz[0])
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.config, float(nlz[0]), dnlz[0] if grad else None, grad)
             out["vs_cpu"] = out["value"] / out["cpu_baseline"]["value"]
             if grad and args.config in (2, 3) and dtype == "f64":  # north_star bar, checked live
@@ -781,7 +792,10 @@ def main():
                          "config, per GPU with --scaling weak")
     ap.add_argument("--points", type=int, default=1000, help="--mode predict: query points M")
     ap.add_argument("--dtype", default=None, choices=["f64", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure what takes runs of its own: the CPU baseline, the dominant "
+                         "launch alone, the MFMA ceiling, the other split of a multi-rank run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--nll-only", action="store_true", help="same as --mode nll")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / exchange rehearsal without device work (no GPU needed, gloo); reports no throughput")

@@ -24,7 +24,7 @@ def _bench(*argv, env=None, timeout=600):
 
 
 def test_gpus_2_without_a_launcher_starts_two_ranks():
-    r, line = _bench("--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1")
+    r, line = _bench("--gpus", "2", "--dry-run", "--steps", "2", "--warmup", "1", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     assert line["n_gpus"] == 2 and line["config"]["process_group_ranks"] == 2
     assert line["config"]["launcher"] == "self"
@@ -37,7 +37,7 @@ def test_gpus_2_without_a_launcher_starts_two_ranks():
 
 
 def _check_both_splits(line, world, S, headline):
-    """The record of a multi-rank run carries the OTHER split and the single-GPU yardstick."""
+    """The record of a multi-rank --full run carries the OTHER split and the single-GPU yardstick."""
     cfg = line["config"]
     other = "weak" if headline == "strong" else "strong"
     assert other in cfg and headline not in cfg
@@ -55,9 +55,10 @@ def test_config_split_at_eight_ranks_and_weak_scaling():
     r, line = _bench("--gpus", "8", "--dry-run", "--steps", "1", "--warmup", "0")
     assert r.returncode == 0, r.stderr[-2000:]
     assert line["n_gpus"] == 8 and line["config"]["global_samples"] == 16 and line["config"]["samples_per_gpu"] == 2
+    assert not {"weak", "strong", "expected_from_1gpu"} & set(line["config"])  # a plain run times the headline split only
     r, line = _bench("--gpus", "8", "--dry-run", "--steps", "1", "--warmup", "0", "--config", "5")
     assert line["config"]["global_samples"] == 64 and line["config"]["samples_per_gpu"] == 8
-    r, line = _bench("--gpus", "4", "--dry-run", "--steps", "1", "--warmup", "0", "--scaling", "weak")
+    r, line = _bench("--gpus", "4", "--dry-run", "--steps", "1", "--warmup", "0", "--scaling", "weak", "--full")
     assert r.returncode == 0, r.stderr[-2000:]
     assert line["n_gpus"] == 4 and line["config"]["global_samples"] == 64 and line["config"]["samples_per_gpu"] == 16
     assert line["scaling"] == "weak"
@@ -94,7 +95,7 @@ def test_under_a_launcher_the_environment_is_used():
 @pytest.mark.gpu
 def test_two_self_launched_ranks_on_one_gpu_run_the_timed_path():
     r, line = _bench("--gpus", "2", "--backend", "gloo", "--config", "2", "--samples", "4", "--steps", "2", "--warmup", "1",
-                     "--no-cpu-baseline")
+                     "--full", "--no-cpu-baseline")
     assert r.returncode == 0, r.stderr[-3000:]
     assert line["n_gpus"] == 2 and line["config"]["samples_per_gpu"] == 2 and line["config"]["global_samples"] == 4
     assert line["value"] > 0 and line["config"]["exchanges_per_step"] == 1.0
@@ -107,7 +108,8 @@ def test_two_self_launched_ranks_on_one_gpu_run_the_timed_path():
 
 @pytest.mark.gpu
 def test_predict_mode_reports_a_roofline_and_matches_the_oracle():
-    r, line = _bench("--mode", "predict", "--config", "2", "--samples", "3", "--points", "300", "--steps", "2", "--warmup", "1")
+    r, line = _bench("--mode", "predict", "--config", "2", "--samples", "3", "--points", "300", "--steps", "2", "--warmup", "1",
+                     "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     assert line["unit"] == "point-samples/s" and line["value"] > 0
     assert line["roofline"]["launch_ms"] > 0 and 0 < line["roofline"]["frac"] < 1
@@ -207,7 +209,7 @@ def test_the_bench_line_carries_every_field_of_the_contract():
     ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload, `roofline` with bound,
     achieved, peak, unit, frac and traffic, `cpu_baseline` with value, unit, cores, kind and sample) -- on cfg2, whose CPU
     leg takes seconds."""
-    r, line = _bench("--config", "2", "--steps", "5", "--warmup", "2")
+    r, line = _bench("--config", "2", "--steps", "5", "--warmup", "2", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     assert len([ln for ln in r.stdout.splitlines() if ln.strip()]) == 1  # ONE line on stdout
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
@@ -235,13 +237,30 @@ def test_the_alone_figure_of_a_batch_that_runs_as_two_sample_groups():
     flops of the launch it timed (all S samples), not with the timed loop's per-group flops -- round 5 read 0.45 for a
     launch that ran at 0.90.  cfg5's size, N = 8192, with 16 samples (S (N_pad/4096)^3 = 128: two groups
     of 8; beyond N_pad = 4096 the one-group pipeline is issued eagerly, so its launch carries events)."""
-    r, line = _bench("--config", "5", "--samples", "16", "--steps", "2", "--warmup", "1", "--no-cpu-baseline")
+    r, line = _bench("--config", "5", "--samples", "16", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline")
     assert r.returncode == 0, r.stderr[-3000:]
     roof = line["roofline"]
     alone = roof["alone"]
     assert abs(alone["flops_per_launch"] - 2.0 * roof["flops_per_launch"]) < 1e-6 * alone["flops_per_launch"]
     assert alone["frac"] >= roof["frac"] - 0.02, (alone["frac"], roof["frac"])
     assert 0.5 < alone["frac"] < 1.0
+
+
+@pytest.mark.gpu
+def test_a_plain_run_measures_the_timed_steps_only():
+    """Without --full the line carries the headline and the roofline of the timed steps (here with the dominant launch as it
+    ran, as in the test above), and nothing that needs a run of its own: no CPU leg, no alone steps, no MFMA-ceiling loop."""
+    r, line = _bench("--config", "5", "--samples", "16", "--steps", "2", "--warmup", "1")
+    assert r.returncode == 0, r.stderr[-3000:]
+    assert len([ln for ln in r.stdout.splitlines() if ln.strip()]) == 1  # ONE line on stdout
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "roofline"):
+        assert k in line, k
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["dtype"] == "f64" and line["unit"] == "fit-evals/s"
+    assert abs(line["value"] - 16 / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    roof = line["roofline"]
+    assert roof["launch_ms"] > 0 and 0 < roof["frac"] < 1 and roof["frac_wall"] > 0
+    assert "alone" not in roof and roof["measured_mfma_ceiling"] is None
+    assert "cpu_baseline" not in line and "vs_cpu" not in line
 
 
 def test_steps_below_one_are_refused():

@@ -1,6 +1,6 @@
 """The per-kernel table of DESIGN.md section 5, generated from the committed rocprofv3 summaries so that it cannot go stale
 (VERDICT r4 item 7).  usage: python tools/design_kernel_table.py <tag> [--write]
-reads  profiles/<tag>_kernel_stats_bench_cfg3_groups1.csv   (bench.py --steps 3 --warmup 1, one sample group: 1 warm-up + 3 timed + 3
+reads  profiles/<tag>_kernel_stats_bench_cfg3_groups1.csv   (bench.py --full --steps 3 --warmup 1, one sample group: 1 warm-up + 3 timed + 3
                                                              untimed 'alone' steps = 7 steps of cfg3: N = 4096, D = 10, 16 samples)
        profiles/<tag>_pmc_summary.txt                       (MFMA utilisation per GEMM class, if present)
        profiles/<tag>_cfg4_kernel_stats.csv                 (cfg4, fp32, if present)

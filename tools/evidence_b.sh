@@ -5,7 +5,7 @@ TAG=${1:?usage: evidence_b.sh <run-tag> <profiles-tag>}; PTAG=${2:?profiles tag}
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out/$TAG
 rm -rf "$O"; mkdir -p "$O/profiles"; cd $R
 python3 tools/source_hash.py > $O/source.sha256
-b() { out=$1; shift; timeout -k 10 500 python bench.py "$@" > $O/profiles/${PTAG}_$out.json 2>> $O/bench.err; echo "$out exit=$?"; python3 -c "import json; d=json.load(open('$O/profiles/${PTAG}_$out.json')); print('   ', d['metric'], d['value'], d['ms_per_step'], d['roofline'].get('frac'), d['roofline'].get('frac_wall'))"; }
+b() { out=$1; shift; timeout -k 10 500 python bench.py --full "$@" > $O/profiles/${PTAG}_$out.json 2>> $O/bench.err; echo "$out exit=$?"; python3 -c "import json; d=json.load(open('$O/profiles/${PTAG}_$out.json')); print('   ', d['metric'], d['value'], d['ms_per_step'], d['roofline'].get('frac'), d['roofline'].get('frac_wall'))"; }
 b bench_cfg3_nll --mode nll --steps 20 --warmup 5
 b bench_cfg2 --config 2 --steps 50 --warmup 10
 b bench_cfg5 --config 5 --steps 3 --warmup 1

@@ -12,7 +12,7 @@ min_us = float(sys.argv[2]) if len(sys.argv) > 2 else 50.0
 f = glob.glob(f"{d}/*/*_kernel_trace.csv")[0]
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
 starts = [i for i, r in enumerate(rows) if "build_kernel" in r["Kernel_Name"] or "small_front_kernel" in r["Kernel_Name"]]
-# bench.py --steps 2 --warmup 2: the 4th evaluation is the last timed one (the untimed 'alone' steps follow)
+# bench.py --steps 2 --warmup 2: the 4th evaluation is the last timed one (with --full, the untimed 'alone' steps follow)
 b = starts[3]
 e = starts[4] if len(starts) > 4 else len(rows)
 seg = rows[b:e]

@@ -2,13 +2,13 @@
 # bash tools/prof_cfg4.sh <tag>: cfg4 (N=16384 D=20 RQ fp32, S=1) evidence: bench line, rocprofv3 kernel stats,
 # and FETCH_SIZE / WRITE_SIZE / GRBM passes for the HBM-bound kernel-build regime (BASELINE.json configs[3])
 R=${GRAFT_REPO_ROOT:-$(pwd)}; TAG=${1:-cfg4}; O=$R/gpurun_out/$TAG; rm -rf $O; mkdir -p $O; python3 $R/tools/source_hash.py > $O/source.sha256
-cd $R && timeout -k 10 300 python3 bench.py --config 4 --steps 5 --warmup 2 > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "bench exit=$?"
+cd $R && timeout -k 10 300 python3 bench.py --full --config 4 --steps 5 --warmup 2 > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "bench exit=$?"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --config 4 --steps 3 --warmup 1 --no-cpu-baseline > $O/prof.log 2>&1; echo "stats exit=$?"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -- python3 $R/bench.py --full --config 4 --steps 3 --warmup 1 --no-cpu-baseline > $O/prof.log 2>&1; echo "stats exit=$?"
 cp $(find $O/prof -name "*kernel_stats.csv" | head -1) $O/kernel_stats_cfg4.csv
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE TCC_HIT_sum --kernel-trace --output-format csv -d $O/pmc_f -- python3 $R/bench.py --config 4 --steps 1 --warmup 1 --no-cpu-baseline > $O/pmc_f.log 2>&1; echo "pmc fetch exit=$?"
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE TCC_MISS_sum GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_w -- python3 $R/bench.py --config 4 --steps 1 --warmup 1 --no-cpu-baseline > $O/pmc_w.log 2>&1; echo "pmc write exit=$?"
-timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $O/pmc_s -- python3 $R/bench.py --config 4 --steps 1 --warmup 1 --no-cpu-baseline > $O/pmc_s.log 2>&1; echo "pmc sq exit=$?"
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE TCC_HIT_sum --kernel-trace --output-format csv -d $O/pmc_f -- python3 $R/bench.py --full --config 4 --steps 1 --warmup 1 --no-cpu-baseline > $O/pmc_f.log 2>&1; echo "pmc fetch exit=$?"
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE TCC_MISS_sum GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/pmc_w -- python3 $R/bench.py --full --config 4 --steps 1 --warmup 1 --no-cpu-baseline > $O/pmc_w.log 2>&1; echo "pmc write exit=$?"
+timeout -k 10 300 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY --kernel-trace --output-format csv -d $O/pmc_s -- python3 $R/bench.py --full --config 4 --steps 1 --warmup 1 --no-cpu-baseline > $O/pmc_s.log 2>&1; echo "pmc sq exit=$?"
 python3 - <<PY
 import csv,glob,collections,json
 O="$O"
