@@ -74,6 +74,7 @@ SIGNATURES = {
     "gpc_predict_full": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "gpc_draw": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_ulonglong, C.c_int, _dp, _dp, _dp]),
     "gpc_quad": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp]),
+    "gpc_quad_grad": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpc_last_timing": (C.c_int, [_vp, _dp, _dp]),
     "gpc_last_lauum_timing": (C.c_int, [_vp, _dp, _dp]),
     "gpc_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
@@ -565,6 +566,23 @@ class PostHandle:
         rc = self.ctx._lib.gpc_quad(self._h, _ptr(mu), _ptr(sigma), M, 1 if compute_var else 0, _ptr(za), _ptr(zkz))
         self.ctx._check(rc, "gpc_quad")
         return za, zkz
+
+    @_serial
+    def quad_grad(self, mu, sigma, compute_var):
+        """gpc_quad_grad: za, zkz (M, S) as quad, and the gradients of each with respect to mu and sigma (M, D, S):
+        (za, zkz, dza_dmu, dza_dsigma, dzkz_dmu, dzkz_dsigma); the zkz entries are None without compute_var."""
+        mu, sigma = _f64(mu), _f64(sigma)
+        if mu.ndim != 2 or sigma.shape != mu.shape:
+            raise ValueError(f"quad_grad: mu and sigma must both be (M, D), got {mu.shape} and {sigma.shape}")
+        M, D = mu.shape
+        za = np.empty((M, self.S))
+        dza = np.empty((M, D, self.S)), np.empty((M, D, self.S))
+        zkz = np.empty((M, self.S)) if compute_var else None
+        dzkz = (np.empty((M, D, self.S)), np.empty((M, D, self.S))) if compute_var else (None, None)
+        rc = self.ctx._lib.gpc_quad_grad(self._h, _ptr(mu), _ptr(sigma), M, 1 if compute_var else 0, _ptr(za),
+                                         _ptr(zkz), _ptr(dza[0]), _ptr(dza[1]), _ptr(dzkz[0]), _ptr(dzkz[1]))
+        self.ctx._check(rc, "gpc_quad_grad")
+        return za, zkz, dza[0], dza[1], dzkz[0], dzkz[1]
 
     @_serial
     def free(self):

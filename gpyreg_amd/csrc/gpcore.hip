@@ -26,6 +26,7 @@
 #include "gemm.h"
 #include "leaf.h"
 #include "plan.h"
+#include "quad.h"
 #ifdef GPC_EXPERIMENTS
 // Schedules that were built, measured and rejected -- the tile-level dataflow graph, independent
 // per-sample pipelines, rectangular / eight-wave tiles, right-looking panels -- are compiled only into the experiments
@@ -504,7 +505,8 @@ struct gpc_ctx {
   DevBuf parts, gout, diagq;     // trace pass
   DevBuf dmb, dsn2b, mg, ng;     // mean / noise gradient inputs and outputs
   DevBuf ks, vb, kss, xss, pout; // predict / predict_full / quad
-  DevBuf qb, gpart, gres;        // predict_grad: Q = W^T V, per-tile partials, the gradients
+  DevBuf qb, gpart, gres;        // predict_grad / quad_grad: Q = W^T V, per-tile partials, the gradients
+  DevBuf qcon;                   // quad_grad: the measures' constants (quad.h: quad_grad_prep_kernel)
   DevBuf zb, fb, dout, daux;     // draw: Z, F = L Z, the draws, [logdet | info | noise sd] (the factor: mA mW mT)
   DevBuf dbg1, dbg2, dbg3;       // debug hooks / fetch staging
   PinBuf pin;                    // pinned staging for host<->device transfers (see PinBuf)
@@ -2485,12 +2487,19 @@ int draw_chunk(gpc_post* po, const DrawReq& d, int s0, int cnt, int M, const dou
 //                 want_quad only; covfun.h: cross_grad_tile_kernel): V is written (no EPI = 1 product), Q = W^T V
 //                 is one more product of the same size (L_chol; the other samples use G = L R as it is)
 //   draw        with `full`: C_s is factored and multiplied on the device (draw_chunk), not downloaded
+//   qg          (mode 1 only; quad.h) d lin / d xa, d lin / d xb and, with want_quad, d quad / d xa, d quad / d xb, the
+//                 last two under quad's convention (scaled by 1/sl or negated) and complete, [(j*D + l)*S + s].  Without
+//                 want_quad there is no product at all; with it V is written as for dlin and Q = W^T V is formed
 // mode: 0 = cross covariance of xa (M x D) with the training inputs; 1 = quadrature
 // vectors z for Gaussian measures N(xa[j], diag(xb[j]^2)) (gaussian_process.py:1908-1921).
+struct QuadGradOut {
+  double* p[4];  // dza_dmu, dza_dsigma, dzkz_dmu, dzkz_dsigma
+};
+
 template <typename T>
 int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int M, bool want_quad,
                  double* lin, double* quad, double* full, double* dlin = nullptr, double* dquad = nullptr,
-                 const DrawReq* draw = nullptr) {
+                 const DrawReq* draw = nullptr, const QuadGradOut* qg = nullptr) {
   gpc_ctx* c = po->ctx;
   const int S = po->S, N = po->N, D = po->D, npad = po->npad;
   const int mpad = pad_tile(M);
@@ -2498,23 +2507,30 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
   const long long sM = (long long)npad * npad;
   const long long sKs = (long long)npad * mpad;
   const long long sKss = (long long)mpad * mpad;
-  const bool grad = dlin != nullptr;
+  const bool grad = dlin != nullptr || qg != nullptr;
   const int gnt = npad / CT;  // tile rows of the gradient pass
-  // gradient scratch per sample: Q (as V), the per-tile partials and the results
-  const size_t gpart_per = grad ? (size_t)gnt * 2 * D * mpad * 8 : 0, gres_per = grad ? 2ull * mpad * D * 8 : 0;
+  // result planes of the gradient pass: [dmu | ds2] (mode 0), [dza_dmu | dza_dsigma (| dzkz_dmu | dzkz_dsigma)] (qg)
+  const int gpl = qg && want_quad ? 4 : 2;
+  // gradient scratch per sample: Q (as V; not without a product), the per-tile partials, the results and (qg) the
+  // measures' constants
+  const bool gq = grad && (!qg || want_quad);
+  const size_t gpart_per = grad ? (size_t)gnt * gpl * D * mpad * 8 : 0, gres_per = grad ? (size_t)gpl * mpad * D * 8 : 0;
+  const size_t qcon_per = qg ? (size_t)(D + 1) * mpad * 8 : 0;
   // draw scratch per sample: the factor's three slabs (mA mW mT), Z and F (mpad x rpad), the draws
   const int rpad = draw ? pad_tile(draw->R) : 0;
   const size_t sZ = (size_t)mpad * rpad;
   const size_t draw_per = draw ? (3 * (size_t)sKss + 2 * sZ) * sizeof(T) + (size_t)M * draw->R * 8 : 0;
-  const size_t per = (2ull * npad * mpad + (full ? (size_t)mpad * mpad : 0) + (grad ? (size_t)npad * mpad : 0)) * sizeof(T) +
-                     gpart_per + gres_per + draw_per;
+  const size_t per = (2ull * npad * mpad + (full ? (size_t)mpad * mpad : 0) + (gq ? (size_t)npad * mpad : 0)) * sizeof(T) +
+                     gpart_per + gres_per + qcon_per + draw_per;
   const size_t held = c->ks.bytes + c->vb.bytes + c->kss.bytes + (grad ? c->qb.bytes + c->gpart.bytes + c->gres.bytes : 0) +
+                      (qg ? c->qcon.bytes : 0) +
                       (draw ? c->mA.bytes + c->mW.bytes + c->mT.bytes + c->zb.bytes + c->fb.bytes + c->dout.bytes : 0);
   int chunk = S;
   if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > held ||
       (size_t)S * sKs * sizeof(T) > std::min(c->ks.bytes, c->vb.bytes) ||
       (full && (size_t)S * sKss * sizeof(T) > c->kss.bytes) ||
-      (grad && ((size_t)S * sKs * sizeof(T) > c->qb.bytes || (size_t)S * gpart_per > c->gpart.bytes)) ||
+      (grad && ((gq && (size_t)S * sKs * sizeof(T) > c->qb.bytes) || (size_t)S * gpart_per > c->gpart.bytes)) ||
+      (qg && (size_t)(S + 1) * qcon_per > c->qcon.bytes) ||
       (draw && ((size_t)S * sKss * sizeof(T) > std::min({c->mA.bytes, c->mW.bytes, c->mT.bytes}) ||
                 (size_t)S * sZ * sizeof(T) > std::min(c->zb.bytes, c->fb.bytes) ||
                 (size_t)S * M * draw->R * 8 > c->dout.bytes))) {
@@ -2538,10 +2554,14 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
     HIPCHK(c, c->daux.ensure(((size_t)M * S + 2 * (size_t)chunk) * 8));
   }
   if (grad) {
-    HIPCHK(c, c->qb.ensure((size_t)chunk * sKs * sizeof(T)));
+    if (gq) HIPCHK(c, c->qb.ensure((size_t)chunk * sKs * sizeof(T)));
     HIPCHK(c, c->gpart.ensure((size_t)chunk * gpart_per));
     HIPCHK(c, c->gres.ensure((size_t)chunk * gres_per));
   }
+  // (qg) [mu_jl transposed: D x mpad | per sample: 1/tau_jl, D x mpad, and ln nf_j, mpad]
+  if (qg) HIPCHK(c, c->qcon.ensure((size_t)(chunk + 1) * qcon_per));
+  double* d_mut = qg ? c->qcon.as<double>() : nullptr;
+  double* d_qcon = qg ? d_mut + (size_t)D * mpad : nullptr;
   HIPCHK(c, c->xss.ensure(((size_t)chunk * mpad * D + 2 * (size_t)M * D) * 8));
   HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
   HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
@@ -2584,7 +2604,7 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
     }
     if (draw->nsd) HIPCHK(c, hipMemcpyAsync(c->daux.p, draw->nsd, (size_t)M * S * 8, hipMemcpyHostToDevice, st));
   }
-  // landing block of the gradients [dmu | ds2] of a chunk: pinned when it fits, else uninitialised pageable memory
+  // landing block of the gradient planes of a chunk: pinned when it fits, else uninitialised pageable memory
   std::unique_ptr<double[]> hgrad_v;
   double* hgrad = nullptr;
   if (grad) {
@@ -2666,6 +2686,9 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
       hipLaunchKernelGGL((quad_z_kernel<T>), dim3(mpad / 64, npad / 4, cnt), dim3(64, 4), 0, st,
                          c->dX.as<double>(), (const double*)d_xa, (const double*)d_xb, mulb, divb, spb, N, npad, M, mpad,
                          D, Ks, sKs);
+      if (qg)
+        hipLaunchKernelGGL(quad_grad_prep_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
+                           (const double*)d_xa, (const double*)d_xb, divb, spb, M, mpad, D, d_mut, d_qcon);
     }
     double* d_mu = c->pout.as<double>();
     double* d_v = d_mu + (size_t)chunk * mpad;
@@ -2741,11 +2764,20 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
           HIPCHK(c, launch_gemm<T>(st, q, true, true, len));
           Qs = c->qb.as<T>() + (size_t)a * sKs;
         }
-        GPC_COV_DISPATCH(cross_grad_tile_kernel, T, po->cd, dim3(mpad / CT, npad / CT, len), dim3(256), 0, st, po->cd,
-                         xsb + (size_t)a * npad * D, (const double*)(c->xss.as<double>() + (size_t)a * mpad * D),
-                         spb + (size_t)a * SP_STRIDE, (const double*)(po->alpha.as<double>() + (size_t)(s0 + a) * npad),
-                         npad, Qs, sKs, lch ? 1 : 0, N, npad, M, mpad,
-                         c->gpart.as<double>() + (size_t)a * gnt * 2 * D * mpad);
+        if (mode == 1 && e == cnt && timing_on) HIPCHK(c, hipEventRecord(c->ev[2], st));  // (quad_grad: with Q)
+        if (mode == 1)
+          hipLaunchKernelGGL((quad_grad_tile_kernel<T, true>), dim3(mpad / CT, npad / CT, len), dim3(256), 0, st,
+                             (const double*)c->dX.as<double>(), D, (const double*)d_mut,
+                             (const double*)(d_qcon + (size_t)a * (D + 1) * mpad),
+                             (const double*)(po->alpha.as<double>() + (size_t)(s0 + a) * npad), npad, Qs, sKs,
+                             spb + (size_t)a * SP_STRIDE, lch ? 1 : 0, N, M, mpad,
+                             c->gpart.as<double>() + (size_t)a * gnt * gpl * D * mpad);
+        else
+          GPC_COV_DISPATCH(cross_grad_tile_kernel, T, po->cd, dim3(mpad / CT, npad / CT, len), dim3(256), 0, st, po->cd,
+                           xsb + (size_t)a * npad * D, (const double*)(c->xss.as<double>() + (size_t)a * mpad * D),
+                           spb + (size_t)a * SP_STRIDE, (const double*)(po->alpha.as<double>() + (size_t)(s0 + a) * npad),
+                           npad, Qs, sKs, lch ? 1 : 0, N, npad, M, mpad,
+                           c->gpart.as<double>() + (size_t)a * gnt * 2 * D * mpad);
       }
       if (full) {
         // Kss -= V^T V / sl  (per sample: alpha differs)   |   Kss += R^T G
@@ -2768,12 +2800,22 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
       }
       a = e;
     }
+    if (qg && !want_quad)  // no product: the alpha weights only, the whole chunk in one launch
+      hipLaunchKernelGGL((quad_grad_tile_kernel<T, false>), dim3(mpad / CT, npad / CT, cnt), dim3(256), 0, st,
+                         (const double*)c->dX.as<double>(), D, (const double*)d_mut, (const double*)d_qcon,
+                         (const double*)(po->alpha.as<double>() + (size_t)s0 * npad), npad, (const T*)nullptr, 0LL, spb,
+                         0, N, M, mpad, c->gpart.as<double>());
     if (grad) {
       double* d_dmu = c->gres.as<double>();
       double* d_ds2 = d_dmu + (size_t)chunk * mpad * D;
-      hipLaunchKernelGGL(grad_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
-                         (const double*)c->gpart.as<double>(), gnt, D, mpad, mulb, divb, d_dmu, d_ds2);
-      HIPCHK(c, hipMemcpyAsync(hgrad, d_dmu, 2 * (size_t)chunk * mpad * D * 8, hipMemcpyDeviceToHost, st));
+      if (qg)
+        hipLaunchKernelGGL(quad_grad_reduce_kernel, dim3((mpad + 255) / 256, gpl * D, cnt), dim3(256), 0, st,
+                           (const double*)c->gpart.as<double>(), gnt, D, gpl, M, mpad, (const double*)d_xb,
+                           (const double*)d_qcon, d_dmu, (size_t)chunk * mpad * D);
+      else
+        hipLaunchKernelGGL(grad_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
+                           (const double*)c->gpart.as<double>(), gnt, D, mpad, mulb, divb, d_dmu, d_ds2);
+      HIPCHK(c, hipMemcpyAsync(hgrad, d_dmu, (size_t)gpl * chunk * mpad * D * 8, hipMemcpyDeviceToHost, st));
     }
     HIPCHK(c, hipGetLastError());
     const size_t out_bytes = (want_quad ? 2 : 1) * (size_t)chunk * mpad * 8;
@@ -2852,15 +2894,14 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
       }
     }
     if (grad) {  // [(j*D + l)*S + s]: the samples of the chunk side by side, the output written in order
-      const double* gm = hgrad;
-      const double* gv = hgrad + (size_t)chunk * mpad * D;
+      double* outs[4] = {dlin, dquad, nullptr, nullptr};
+      if (qg) std::copy_n(qg->p, 4, outs);
       const size_t ss = (size_t)mpad * D;
-      for (size_t jl = 0; jl < (size_t)M * D; ++jl) {
-        double* om = dlin + jl * S + s0;
-        double* ov = dquad + jl * S + s0;
-        for (int i = 0; i < cnt; ++i) {
-          om[i] = gm[i * ss + jl];
-          ov[i] = gv[i * ss + jl];
+      for (int p = 0; p < gpl; ++p) {
+        const double* gp = hgrad + (size_t)p * chunk * ss;
+        for (size_t jl = 0; jl < (size_t)M * D; ++jl) {
+          double* o = outs[p] + jl * S + s0;
+          for (int i = 0; i < cnt; ++i) o[i] = gp[i * ss + jl];
         }
       }
     }
@@ -3293,7 +3334,7 @@ void gpc_destroy(gpc_ctx* c) {
   DevBuf* bufs[] = {&c->dX,   &c->dY,  &c->mA,    &c->mW,  &c->mT,   &c->xs,   &c->spb,  &c->mulb, &c->divb,
                     &c->dvec, &c->rvec,  &c->zvec, &c->avec, &c->scal, &c->parts, &c->gout, &c->diagq,
                     &c->dmb,  &c->dsn2b, &c->mg,  &c->ng,   &c->ks,   &c->vb,   &c->xss,  &c->pout, &c->kss,
-                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
+                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
   for (auto& g : c->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (DevBuf* b : bufs) b->release();
@@ -3771,6 +3812,19 @@ int gpc_predict_full(gpc_post* po, const double* xstar, int M, double* fmu, doub
                               : rhs_products<float>(po, 0, xstar, nullptr, M, false, fmu, nullptr, cov);
 }
 
+namespace {
+// z (K + sn2_eff I)^-1 z^T: |W z|^2 / sl (L_chol) or -(z . L z) (L = -inv)   (:1946-1962)
+void quad_scale_zkz(const gpc_post* po, int M, double* zKz) {
+  for (int s = 0; s < po->S; ++s) {
+    const double sl = po->sp[(size_t)s * SP_STRIDE + SP_SL];
+    for (int j = 0; j < M; ++j) {
+      double& q = zKz[(size_t)j * po->S + s];
+      q = po->lchol[s] ? q / sl : -q;
+    }
+  }
+}
+}  // namespace
+
 int gpc_quad(gpc_post* po, const double* mu, const double* sigma, int M, int compute_var, double* zalpha,
              double* zKz) {
   if (!po) return -2;
@@ -3783,14 +3837,30 @@ int gpc_quad(gpc_post* po, const double* mu, const double* sigma, int M, int com
                ? rhs_products<double>(po, 1, mu, sigma, M, compute_var != 0, zalpha, zKz, nullptr)
                : rhs_products<float>(po, 1, mu, sigma, M, compute_var != 0, zalpha, zKz, nullptr);
   if (rc || !compute_var) return rc;
-  // z (K + sn2_eff I)^-1 z^T: |W z|^2 / sl (L_chol) or -(z . L z) (L = -inv)   (:1946-1962)
-  for (int s = 0; s < po->S; ++s) {
-    const double sl = po->sp[(size_t)s * SP_STRIDE + SP_SL];
-    for (int j = 0; j < M; ++j) {
-      double& q = zKz[(size_t)j * po->S + s];
-      q = po->lchol[s] ? q / sl : -q;
-    }
-  }
+  quad_scale_zkz(po, M, zKz);
+  return 0;
+}
+
+int gpc_quad_grad(gpc_post* po, const double* mu, const double* sigma, int M, int compute_var, double* zalpha,
+                  double* zKz, double* dza_dmu, double* dza_dsigma, double* dzkz_dmu, double* dzkz_dsigma) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!mu || !sigma || !zalpha || M <= 0 || (compute_var && !zKz) || !dza_dmu || !dza_dsigma ||
+      (compute_var && (!dzkz_dmu || !dzkz_dsigma)))
+    FAIL(c, "gpc_quad_grad: bad arguments");
+  if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
+    FAIL(c, "Bayesian quadrature only supports the squared exponential kernel.");
+  for (int s = 0; s < po->S; ++s)
+    if (po->info[s] != 0) FAIL(c, "gpc_quad_grad: posterior contains a failed factorization");
+  HIPCHK(c, hipSetDevice(c->device));
+  const QuadGradOut g{{dza_dmu, dza_dsigma, compute_var ? dzkz_dmu : nullptr, compute_var ? dzkz_dsigma : nullptr}};
+  int rc = po->dtype == GPC_F64
+               ? rhs_products<double>(po, 1, mu, sigma, M, compute_var != 0, zalpha, zKz, nullptr, nullptr, nullptr,
+                                      nullptr, &g)
+               : rhs_products<float>(po, 1, mu, sigma, M, compute_var != 0, zalpha, zKz, nullptr, nullptr, nullptr,
+                                     nullptr, &g);
+  if (rc || !compute_var) return rc;
+  quad_scale_zkz(po, M, zKz);  // (the dzkz planes come back scaled on the device: qs rides in the weights)
   return 0;
 }
 

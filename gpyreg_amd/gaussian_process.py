@@ -144,6 +144,14 @@ def _mix_sample_grads(means, dmeans, dvariances):
     return dmu, ds2
 
 
+def _quad_measures(mu, sigma, D):
+    """``quad``'s reading of the Gaussian measures: a scalar fills a row of D, sigma broadcasts to mu's shape."""
+    mu = np.tile(mu, (1, D)) if np.size(mu) == 1 else np.atleast_2d(np.asarray(mu, dtype=float))
+    sigma = np.tile(sigma, (1, D)) if np.size(sigma) == 1 else np.atleast_2d(np.asarray(sigma, dtype=float))
+    sigma = np.broadcast_to(sigma, mu.shape).astype(float)
+    return mu, sigma
+
+
 def _mean_grad_x(mean, hyp, X):
     """d m(x) / dx (M, D) of a stock mean function under the mean hyperparameters ``hyp``; exact types only (a
     subclass may compute anything): other mean objects raise NotImplementedError."""
@@ -1541,10 +1549,8 @@ class GP:
         N, D = self.X.shape
         N_s = np.size(self.posteriors)
         cov_N, noise_N, _ = self._counts()
-        mu = np.tile(mu, (1, D)) if np.size(mu) == 1 else np.atleast_2d(np.asarray(mu, dtype=float))
+        mu, sigma = _quad_measures(mu, sigma, D)
         N_star = mu.shape[0]
-        sigma = np.tile(sigma, (1, D)) if np.size(sigma) == 1 else np.atleast_2d(np.asarray(sigma, dtype=float))
-        sigma = np.broadcast_to(sigma, mu.shape).astype(float)
         self._restore()
         if self._post_handle is None and self._post_range is None:
             raise ValueError("posteriors have been cleaned; call update() first")
@@ -1608,6 +1614,109 @@ class GP:
         if N_s > 1 and not separate_samples:  # (:1968-1976) the same mixture as in predict
             F, F_var, _ = _mix_samples(F, F_var)
         return (F, F_var) if compute_var else F
+
+    @_on_device
+    def quad_grad(self, mu, sigma, compute_var: bool = False, separate_samples: bool = False):
+        """``quad`` and its gradients with respect to the measures' means ``mu`` and standard deviations ``sigma``:
+        (F, dF_dmu, dF_dsigma), or with ``compute_var`` (F, F_var, dF_dmu, dF_dsigma, dFvar_dmu, dFvar_dsigma).  F is
+        ``quad``'s to the bit, F_var to rounding (the device sums the variance in another order).  The gradients are
+        (M, D), or (M, D, S) with ``separate_samples``, entry [j, l] the derivative with respect to mu[j, l] or
+        sigma[j, l] of the broadcast per-row arrays (a caller who ties parameters sums them).  The z-terms run on the
+        device (gpc_quad_grad); the mean function's terms, the self-term of the variance and the mixture on the host.
+        Where the clamp F_var = max(eps, .) is active the variance gradient is 0.  Refuses what ``quad`` refuses, and
+        (NotImplementedError) an isotropic kernel at D > 1 under ``reference_quirks``, whose z ``quad`` builds on the
+        host from a misread of the hyperparameters."""
+        from .covariance_functions import SquaredExponential
+        from .mean_functions import NegativeQuadratic, ZeroMean
+
+        if not isinstance(self.covariance, SquaredExponential):
+            raise ValueError("Bayesian quadrature only supports the squared exponential kernel.")
+        N, D = self.X.shape
+        N_s = np.size(self.posteriors)
+        cov_N, noise_N, _ = self._counts()
+        mu, sigma = _quad_measures(mu, sigma, D)
+        N_star = mu.shape[0]
+        if mu.shape[1] != D:
+            raise ValueError(f"quad_grad: the measures have {mu.shape[1]} dimensions, the GP {D}")
+        self._restore()
+        if self._post_handle is None and self._post_range is None:
+            raise ValueError("posteriors have been cleaned; call update() first")
+        quirks = self.reference_quirks
+        iso = cov_N == 2 and D != 1
+        if quirks:
+            for p in self.posteriors:  # (as quad: an IndexError without a noise hyperparameter)
+                np.exp(2 * p.hyp[cov_N])
+            if iso:
+                raise NotImplementedError("quad_grad: under reference_quirks, quad builds an isotropic kernel's z on the "
+                                          "host from a misread of its hyperparameters (D > 1); it has no device gradient")
+        self._ctx()
+        if self._post_handle is None:  # a rank without local samples
+            za, zkz = np.zeros((N_star, 0)), np.zeros((N_star, 0))
+            dza_mu = dza_sg = dzkz_mu = dzkz_sg = np.zeros((N_star, D, 0))
+        else:
+            za, zkz, dza_mu, dza_sg, dzkz_mu, dzkz_sg = self._post_handle.quad_grad(mu, sigma, compute_var)
+        if quirks and compute_var and self._post_handle is not None:  # quad's rescaling of the variance term
+            local, _ = self._local_posteriors()
+            for k, p in enumerate(local):
+                if p.L_chol:
+                    sl = 1.0 / float(np.ravel(p.sW)[0]) ** 2
+                    scale = sl / (np.exp(2 * p.hyp[cov_N]) * p.sn2_mult)
+                    zkz[:, k] *= scale
+                    dzkz_mu[:, :, k] *= scale
+                    dzkz_sg[:, :, k] *= scale
+        if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
+            k = za.shape[1]
+            planes = (dza_mu, dza_sg, dzkz_mu, dzkz_sg) if compute_var else (dza_mu, dza_sg)
+            rows = [za, zkz] if compute_var else [za]
+            rows = self._gather_samples(np.concatenate(rows + [g.reshape(N_star * D, k) for g in planes], axis=0),
+                                        mu, sigma)
+            za, rows = rows[:N_star], rows[N_star:]
+            if compute_var:
+                zkz, rows = rows[:N_star], rows[N_star:]
+            nd = N_star * D
+            planes = [rows[q * nd:(q + 1) * nd].reshape(N_star, D, -1) for q in range(len(planes))]
+            dza_mu, dza_sg = planes[:2]
+            if compute_var:
+                dzkz_mu, dzkz_sg = planes[2:]
+        quadratic = isinstance(self.mean, NegativeQuadratic)
+        F = np.zeros((N_star, N_s))
+        F_var = np.zeros((N_star, N_s)) if compute_var else None
+        dF_mu, dF_sg = dza_mu.copy(), dza_sg.copy()
+        dV_mu = dV_sg = np.zeros((N_star, D, N_s))
+        if compute_var:
+            dV_mu, dV_sg = -dzkz_mu, np.empty((N_star, D, N_s))
+        for s in range(N_s):  # quad's host terms and their derivatives
+            hyp = self.posteriors[s].hyp
+            if quirks:
+                ell, ln_sf2 = np.exp(hyp[0:D]), 2 * hyp[D]
+            else:
+                ell = np.exp(hyp[0]) * np.ones(D) if iso else np.exp(hyp[0:D])
+                ln_sf2 = 2 * hyp[cov_N - 1]
+            sum_lnell = np.sum(np.log(ell))
+            m0 = 0 if isinstance(self.mean, ZeroMean) else hyp[cov_N + noise_N]
+            F[:, s] = za[:, s] + m0
+            if quadratic:
+                xm = hyp[cov_N + noise_N + 1:cov_N + noise_N + D + 1]
+                omega = np.exp(hyp[cov_N + noise_N + D + 1:])
+                F[:, s] += -0.5 * np.sum(1 / omega**2 * (mu**2 + sigma**2 - 2 * mu * xm + xm**2), 1)
+                dF_mu[:, :, s] -= (mu - xm) / omega**2
+                dF_sg[:, :, s] -= sigma / omega**2
+            if compute_var:
+                tau_kk = np.sqrt(2 * sigma**2 + ell**2)
+                nf_kk = np.exp(ln_sf2 + sum_lnell - np.sum(np.log(tau_kk), 1))
+                F_var[:, s] = np.maximum(np.spacing(1), nf_kk - zkz[:, s])
+                dV_sg[:, :, s] = -nf_kk[:, None] * 2 * sigma / tau_kk**2 - dzkz_sg[:, :, s]
+                held = nf_kk - zkz[:, s] <= np.spacing(1)  # the clamp: no variance gradient where it holds F_var
+                dV_mu[held, :, s] = 0
+                dV_sg[held, :, s] = 0
+        if not separate_samples:  # the gradients of quad's mixture (one sample: the sample's own)
+            dF_mu, dV_mu = _mix_sample_grads(F, dF_mu, dV_mu)
+            dF_sg, dV_sg = _mix_sample_grads(F, dF_sg, dV_sg)
+            if N_s > 1:
+                F, F_var, _ = _mix_samples(F, F_var)
+        if compute_var:
+            return F, F_var, dF_mu, dF_sg, dV_mu, dV_sg
+        return F, dF_mu, dF_sg
 
     # ------------------------------------------------------------------ misc
     def _convert_shapes(self, X, y, s2):

@@ -223,6 +223,24 @@ int gpc_predict_full(gpc_post* post, const double* xstar, int M, double* fmu, do
 int gpc_quad(gpc_post* post, const double* mu, const double* sigma, int M, int compute_var,
              double* zalpha, double* zKz);
 
+/* ---- GP.quad_grad: gradients of the quadrature products with respect to the measures ---------------
+ * zalpha, zKz as gpc_quad (zKz already divided by sl or negated); for every sample s, measure j and
+ * dimension l, with tau_jl^2 = sigma_jl^2 + ell_l^2, d_ijl = mu_jl - X_il and q = (K + Sigma)^-1 z under
+ * the posterior's own scaling (W^T W z / sl for L_chol samples, -(L z) otherwise):
+ *   dza_dmu[(j*D + l)*S + s]     = d zalpha_js / d mu_jl    = -sum_i alpha_i z_ij d_ijl / tau_jl^2
+ *   dza_dsigma[(j*D + l)*S + s]  = d zalpha_js / d sigma_jl =  sum_i alpha_i z_ij sigma_jl
+ *                                                               (d_ijl^2 / tau_jl^2 - 1) / tau_jl^2
+ *   dzkz_dmu, dzkz_dsigma        = d zKz_js / d mu_jl, d sigma_jl: 2 x the same sums with q_ij for alpha_i
+ *                                  (only if compute_var; K + Sigma is symmetric)
+ * sigma is the standard deviation, as in gpc_quad.  Without compute_var no N^2 M product runs; with it
+ * V = W z is written and Q = W^T V is one more product of the same size.  The differences d_ijl are
+ * formed per pair, never expanded into moments.  The mean function's terms, the self-term nf_kk of the
+ * variance, the clamp and the mixture over samples are the caller's.  Fails with a message where
+ * gpc_quad fails, and on a posterior that holds a failed factorization.                                */
+int gpc_quad_grad(gpc_post* post, const double* mu, const double* sigma, int M, int compute_var,
+                  double* zalpha, double* zKz, double* dza_dmu, double* dza_dsigma, double* dzkz_dmu,
+                  double* dzkz_dsigma);
+
 /* ---- instrumentation -------------------------------------------------------------
  * GPU time (ms, hipEvent on the library's stream) of the last gpc_nll_batch /
  * gpc_posterior_batch: whole device section, and the part spent in the MFMA GEMM
@@ -230,7 +248,8 @@ int gpc_quad(gpc_post* post, const double* mu, const double* sigma, int M, int c
  * these events only under gpc_set_option(ctx, "small_timing", 1): both are 0 otherwise. */
 int gpc_last_timing(gpc_ctx* ctx, double* ms_total, double* ms_factor);
 /* (after gpc_predict / gpc_predict_full / gpc_quad: ms_total = device time of the call, ms_factor = the
- * duration of its N^2 M product V = W Ks, the GEMM launch of gaussian_process.py:1752-1760)            */
+ * duration of its N^2 M product V = W Ks, the GEMM launch of gaussian_process.py:1752-1760; after
+ * gpc_quad_grad: that of its products V = W z and Q = W^T V, ~0 without compute_var)                   */
 /* The dominant single kernel of the last gpc_nll_batch with gradient: the W^T W ("lauum")
  * launch of gemm_kernel<T, true, true, ...>.  ms = its duration (hipEvents on the stream it
  * was launched on; the slowest sample group), flops = its algorithmic flops
