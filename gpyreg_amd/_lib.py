@@ -72,6 +72,7 @@ SIGNATURES = {
     "gpc_post_append_K": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_double, _ip]),
     "gpc_post_recompute_K": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_predict_full": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
+    "gpc_predict_cov": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
     "gpc_draw": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_ulonglong, C.c_int, _dp, _dp, _dp]),
     "gpc_quad": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpc_quad_grad": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
@@ -540,6 +541,26 @@ class PostHandle:
         rc = self.ctx._lib.gpc_predict_full(self._h, _ptr(xs), M, _ptr(fmu), _ptr(cov))
         self.ctx._check(rc, "gpc_predict_full")
         return fmu, cov
+
+    @_serial
+    def predict_cov(self, x_a, x_b, weights=None, want_cov=True, want_fs2=False):
+        """gpc_predict_cov: (cov, wsq, fs2b).  cov (S, Ma, Mb) is the posterior covariance between the rows of x_a and
+        of x_b (None without ``want_cov``); wsq (Mb, S) = sum_i w_i cov[s, i, j]^2 for ``weights`` (Ma,) or (Ma, S)
+        (None without weights); fs2b (Mb, S) is ``predict``'s variance of x_b (None without ``want_fs2``)."""
+        xa, xb = _f64(x_a), _f64(x_b)
+        Ma, Mb = xa.shape[0], xb.shape[0]
+        w = None if weights is None else _f64(weights)
+        if w is not None and w.shape not in ((Ma,), (Ma, self.S)):
+            raise ValueError(f"predict_cov: weights must be ({Ma},) or ({Ma}, {self.S}), got {w.shape}")
+        if w is None and not want_cov:
+            raise ValueError("predict_cov: nothing to compute (neither the covariance nor a weighted reduction)")
+        cov = np.empty((self.S, Ma, Mb)) if want_cov else None
+        wsq = np.empty((Mb, self.S)) if w is not None else None
+        fs2b = np.empty((Mb, self.S)) if want_fs2 else None
+        rc = self.ctx._lib.gpc_predict_cov(self._h, _ptr(xa), Ma, _ptr(xb), Mb, _ptr(w),
+                                           1 if (w is not None and w.ndim == 2) else 0, _ptr(fs2b), _ptr(cov), _ptr(wsq))
+        self.ctx._check(rc, "gpc_predict_cov")
+        return cov, wsq, fs2b
 
     @_serial
     def draw(self, x_star, n_draws, seed, s_offset=0, noise_sd=None):

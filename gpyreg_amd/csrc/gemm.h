@@ -73,6 +73,12 @@ struct GemmArgs {
   // of tile row ti of (alpha * C[row][col])^2 -- the column sums of squares of V = W Ks (gaussian_process.py:1756-1760)
   // per tile row, in a fixed order; a small reduction over the tile rows follows
   double* colsq = nullptr;
+  // EPI = 2 launches (look-ahead, gpc_predict_cov): C is READ, not stored -- with v = C[row][col] + alpha_b acc (the
+  // value a beta = 1 launch would store), colsq[(b * tiles_m + ti) * N + col] receives the sum over the 128 rows of tile
+  // row ti of ep_w[b * ep_sw + row] v^2.  ep_alpha[b]: the factor of sample b (the samples of a launch differ in it)
+  const double* ep_w = nullptr;
+  long long ep_sw = 0;
+  const double* ep_alpha = nullptr;
 };
 inline int g_gemm_flags = 8 | 16;  // bit 3: XCD-affine tile queues in persistent launches; bit 4: XCD-aware order of plain launches
 
@@ -457,6 +463,61 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
     __syncthreads();  // (a persistent block restages LDS for its next tile)
     return;
   }
+  if constexpr (EPI == 2) {
+    // weighted column sums of squares of v = C + alpha_b acc, C (the prior cross covariance) read one accumulator row at
+    // a time as the beta = 1 path below reads it; v is rounded to T as that path would store it, squared and summed in
+    // fp64.  The order is EPI = 1's: rows first in the lane (fragment, then register), then the four lane groups, then
+    // the wave rows
+    static_assert(NW == 4 && BT == 128 && BTN == BT && HO == 0, "the reduction is laid out for 2 x 2 waves of 64 x 64");
+    const T al = (T)g.ep_alpha[by];
+    const double* __restrict__ wv = g.ep_w + (size_t)by * g.ep_sw;
+    double cs[MRN];
+#pragma unroll
+    for (int j = 0; j < MRN; ++j) cs[j] = 0.0;
+#pragma unroll
+    for (int i = 0; i < MRM; ++i) {
+      T old[MRN][4];
+      double wr4[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) wr4[r] = wv[m0 + wr * WTM + i * 16 + MM<T>::row_of(lane, r)];
+#pragma unroll
+      for (int j = 0; j < MRN; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = m0 + wr * WTM + i * 16 + MM<T>::row_of(lane, r);
+          const int col = n0 + wc * WTN + j * 16 + (lane & 15);
+          old[j][r] = C[(size_t)row * g.ldc + col];
+        }
+#pragma unroll
+      for (int j = 0; j < MRN; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          T v;
+          if constexpr (TWO_LEVEL)
+            v = al * (acc[i][j][r] + acc2[i][j][r]);
+          else
+            v = al * acc[i][j][r];
+          v += old[j][r];
+          const double d = (double)v;
+          cs[j] = fma(wr4[r] * d, d, cs[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < MRN; ++j) {
+      cs[j] += __shfl_xor(cs[j], 16, 64);
+      cs[j] += __shfl_xor(cs[j], 32, 64);
+    }
+    double* red = reinterpret_cast<double*>(smem);  // [2 wave rows][BT columns]; the k-loop is done with the stages
+    __syncthreads();
+    if ((lane >> 4) == 0) {
+#pragma unroll
+      for (int j = 0; j < MRN; ++j) red[wr * BT + wc * WTN + j * 16 + (lane & 15)] = cs[j];
+    }
+    __syncthreads();
+    if (t < BT) g.colsq[((size_t)by * g.tiles_m + ti) * (size_t)g.N + n0 + t] = red[t] + red[BT + t];
+    __syncthreads();
+    return;
+  }
   // beta = 1: the old values of one accumulator row (MRN x 4 per lane) are loaded as a batch before
   // any store of that row -- interleaved load/add/store through the same pointer serialises into
   // MRM x MRN x 4 dependent memory round trips (the 64-tile syrk of a 256-node took 12 us
@@ -782,6 +843,25 @@ inline hipError_t launch_gemm_colsq(hipStream_t st, GemmArgs g, int batch, int* 
     hipLaunchKernelGGL((gemm_persist_kernel<T, false, true, BT, 4, 1>), dim3(cap), dim3(256), 0, st, g);
   else
     hipLaunchKernelGGL((gemm_kernel<T, false, true, BT, 4, 1>), dim3(g.ntiles, batch), dim3(256), 0, st, g);
+  return hipGetLastError();
+}
+
+// The look-ahead product (gpc_predict_cov without a covariance output): A^T B with both operands k-major, 128-tiles, NOT
+// stored -- g.C holds the prior cross covariance, g.colsq receives the weighted column sums of squares of
+// C + ep_alpha[b] A^T B per tile row (gemm_tile, EPI = 2).  One plain launch for the samples of a run.
+template <typename T>
+inline hipError_t launch_gemm_wsq(hipStream_t st, GemmArgs g, int batch) {
+  constexpr int BT = 128;
+  g.tiles_m = g.M / BT;
+  g.tiles_n = g.N / BT;
+  g.flags = g_gemm_flags;
+  g.lower_only = 0;
+  g.ntiles = g.tiles_m * g.tiles_n;
+  if (g.ntiles <= 0 || batch <= 0) return hipSuccess;
+  g.batch = batch;
+  g.ctr = nullptr;
+  g.rsv = nullptr;
+  hipLaunchKernelGGL((gemm_kernel<T, true, true, BT, 4, 2>), dim3(g.ntiles, batch), dim3(256), 0, st, g);
   return hipGetLastError();
 }
 

@@ -25,6 +25,7 @@
 #include "draw.h"
 #include "gemm.h"
 #include "leaf.h"
+#include "lookahead.h"
 #include "plan.h"
 #include "quad.h"
 #ifdef GPC_EXPERIMENTS
@@ -483,6 +484,7 @@ struct gpc_ctx {
   static constexpr size_t LAND_BYTES = 64u << 10;
   unsigned long long land_seq = 0;
   unsigned long long small_polled = 0, small_synced = 0;  // statistics ("small_polled" / "small_synced")
+  unsigned long long cov_fused = 0;  // gpc_predict_cov calls whose reduction ran in the product's epilogue ("cov_fused")
   int check_queues = 0;  // debug option: verify after every pipeline that the tile queues of its persistent launches were drained
   hipEvent_t ev_up = nullptr, ev_done[MAXG] = {};
   int groups = 2;
@@ -2477,6 +2479,28 @@ int draw_chunk(gpc_post* po, const DrawReq& d, int s0, int cnt, int M, const dou
   return 0;
 }
 
+// The constants of ALL samples of a posterior on the device (see gpc_post): the kernel's scalars, the input scaling and
+// the scaled training inputs, uploaded and formed once per posterior
+int post_consts_resident(gpc_post* po) {
+  if (po->dev_consts) return 0;
+  gpc_ctx* c = po->ctx;
+  const int S = po->S, N = po->N, D = po->D, npad = po->npad;
+  hipStream_t st = c->st;
+  HIPCHK(c, po->dsp.ensure_private((size_t)S * SP_STRIDE * 8));
+  HIPCHK(c, po->dmul.ensure_private((size_t)S * D * 8));
+  HIPCHK(c, po->ddv.ensure_private((size_t)S * D * 8));
+  HIPCHK(c, po->dxs.ensure_private((size_t)S * npad * D * 8));
+  HIPCHK(c, hipMemcpyAsync(po->dsp.p, po->sp.data(), (size_t)S * SP_STRIDE * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(po->dmul.p, po->mul.data(), (size_t)S * D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(po->ddv.p, po->dv.data(), (size_t)S * D * 8, hipMemcpyHostToDevice, st));
+  const long long tot = (long long)npad * D;
+  hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), S), dim3(256), 0, st, c->dX.as<double>(), N,
+                     npad, D, po->dmul.as<double>(), po->ddv.as<double>(), po->dxs.as<double>());
+  HIPCHK(c, hipGetLastError());
+  po->dev_consts = true;
+  return 0;
+}
+
 // Shared by predict / predict_full / quad: for every posterior sample s build a right-hand
 // side matrix R_s (npad x mpad: cross covariances, or quadrature kernel means), then
 //   lin[j*S+s]  = R_s[:, j] . alpha_s
@@ -2618,20 +2642,8 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
 
   // all samples in one chunk (the usual case): the posterior's constants are resident, see gpc_post
   const bool resident = chunk == S && mode != 2;
-  if (resident && !po->dev_consts) {
-    HIPCHK(c, po->dsp.ensure_private((size_t)S * SP_STRIDE * 8));
-    HIPCHK(c, po->dmul.ensure_private((size_t)S * D * 8));
-    HIPCHK(c, po->ddv.ensure_private((size_t)S * D * 8));
-    HIPCHK(c, po->dxs.ensure_private((size_t)S * npad * D * 8));
-    HIPCHK(c, hipMemcpyAsync(po->dsp.p, po->sp.data(), (size_t)S * SP_STRIDE * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(po->dmul.p, po->mul.data(), (size_t)S * D * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(po->ddv.p, po->dv.data(), (size_t)S * D * 8, hipMemcpyHostToDevice, st));
-    const long long tot = (long long)npad * D;
-    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), S), dim3(256), 0, st, c->dX.as<double>(), N,
-                       npad, D, po->dmul.as<double>(), po->ddv.as<double>(), po->dxs.as<double>());
-    HIPCHK(c, hipGetLastError());
-    po->dev_consts = true;
-  }
+  if (resident)
+    if (int rc = post_consts_resident(po)) return rc;
   const double* spb = resident ? po->dsp.as<double>() : c->spb.as<double>();
   const double* mulb = resident ? po->dmul.as<double>() : c->mulb.as<double>();
   const double* divb = resident ? po->ddv.as<double>() : c->divb.as<double>();
@@ -2927,6 +2939,245 @@ int predict_impl(gpc_post* po, const double* xstar, int M, double* fmu, double* 
       fs2[(size_t)j * S + s] = po->lchol[s] ? sf2 - q / sl : sf2 + q;
     }
   }
+  return 0;
+}
+
+// gpc_predict_cov: the posterior covariance between two query sets, rhs_products' sibling.  Per sample
+//   Ks_a = K(X, xa) (npad x mapad), Ks_b = K(X, xb) (npad x mbpad), K_ab = K(xa, xb) (mapad x mbpad, zero padding)
+//   L_chol:    V_a = W Ks_a, V_b = W Ks_b,  C = K_ab - V_a^T V_b / sl,   fs2b_j = sf2 - |V_b[:, j]|^2 / sl
+//   low noise: G_b = L Ks_b,                C = K_ab + Ks_a^T G_b,       fs2b_j = sf2 + Ks_b[:, j] . G_b[:, j]
+//   wsq_j = sum_i w_i C_ij^2
+// Runs of equal L_chol share the triangular products' launches.  The cross product is a rectangular launch with both
+// operands k-major.  Two forms, chosen by the shape ALONE (never by the number of samples: a sample of a batch carries
+// the bits of its single evaluation):
+//   stored  C is written (one beta = 1 launch per sample, as predict_full's) and, for wsq, reduced by wsq_col_kernel;
+//   fused   (no covariance wanted and at least 64 128-tiles) C is never written: the product's epilogue reads K_ab and
+//           forms the weighted column sums of squares per tile row (gemm.h: EPI = 2), colpart_reduce_kernel adds the
+//           tile rows in ascending order.  No atomics.
+// Scratch per sample: 2 npad (mapad + mbpad) + mapad mbpad elements and small vectors, chunked over the samples under
+// the same budget as rhs_products.
+template <typename T>
+int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int Mb, const double* w, int w_per_sample,
+                 double* fs2b, double* cov, double* wsq) {
+  gpc_ctx* c = po->ctx;
+  const int S = po->S, N = po->N, D = po->D, npad = po->npad;
+  const int mapad = pad_tile(Ma), mbpad = pad_tile(Mb), mmax = std::max(mapad, mbpad);
+  hipStream_t st = c->st;
+  const long long sM = (long long)npad * npad;
+  const long long sKa = (long long)npad * mapad, sKb = (long long)npad * mbpad, sC = (long long)mapad * mbpad;
+  const int tma = mapad / TILE;
+  const bool fused = wsq && !cov && (long long)tma * (mbpad / TILE) >= 64;
+  const size_t part_per = (size_t)(npad / CT) * mmax * 8 + (fused ? (size_t)tma * mbpad * 8 : 0);
+  const size_t per = (2ull * npad * (mapad + mbpad) + (size_t)sC) * sizeof(T) + part_per +
+                     ((size_t)(mapad + mbpad) * D + mapad + 1 + 2 * mbpad) * 8;
+  const size_t held = c->ks.bytes + c->vb.bytes + c->kss.bytes;
+  int chunk = S;
+  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > held ||
+      (size_t)S * (sKa + sKb) * sizeof(T) > std::min(c->ks.bytes, c->vb.bytes) || (size_t)S * sC * sizeof(T) > c->kss.bytes) {
+    c->pool_drain();
+    const size_t budget = (size_t)((free_device_bytes() + (getenv("GPC_MEM_BUDGET_MB") ? 0 : held)) * 0.8);
+    if (budget < per)
+      FAIL(c, "gpc_predict_cov: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
+              std::to_string(npad) + ", Ma_pad = " + std::to_string(mapad) + ", Mb_pad = " + std::to_string(mbpad) +
+              ") exceeds the device memory budget (" + std::to_string(budget >> 10) + " KB)");
+    chunk = (int)std::min<size_t>(S, budget / per);
+  }
+  HIPCHK(c, c->ks.ensure((size_t)chunk * (sKa + sKb) * sizeof(T)));
+  HIPCHK(c, c->vb.ensure((size_t)chunk * (sKa + sKb) * sizeof(T)));
+  HIPCHK(c, c->kss.ensure((size_t)chunk * sC * sizeof(T)));
+  HIPCHK(c, c->xss.ensure(((size_t)chunk * (mapad + mbpad) + Ma + Mb) * D * 8));
+  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
+  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
+  HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
+  HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
+  HIPCHK(c, c->pout.ensure((size_t)chunk * mbpad * 2 * 8));
+  HIPCHK(c, c->daux.ensure((size_t)chunk * (mapad + 1) * 8));  // [weights: chunk x mapad | the products' factors: chunk]
+  HIPCHK(c, c->dbg2.ensure((size_t)chunk * (npad / CT) * mmax * 8));
+  if (fused) HIPCHK(c, c->dbg3.ensure((size_t)chunk * tma * mbpad * 8));
+  if (cov) HIPCHK(c, c->dbg1.ensure((size_t)Ma * Mb * 8));
+  double* xsa = c->xss.as<double>();
+  double* xsbq = xsa + (size_t)chunk * mapad * D;
+  double* d_xa = xsbq + (size_t)chunk * mbpad * D;
+  double* d_xb = d_xa + (size_t)Ma * D;
+  double* d_w = c->daux.as<double>();
+  double* d_al = d_w + (size_t)chunk * mapad;
+  double* d_v = c->pout.as<double>();
+  double* d_q = d_v + (size_t)chunk * mbpad;
+  c->pin.begin();
+  c->pin.begin_gather();
+  const bool timing_on = c->small_timing != 0 || npad >= 2048;
+  HIPCHK(c, c->pin.up(d_xa, xa, (size_t)Ma * D * 8, st));
+  HIPCHK(c, c->pin.up(d_xb, xb, (size_t)Mb * D * 8, st));
+  std::vector<double> hw((size_t)chunk * (mapad + 1)), hout(2 * (size_t)chunk * mbpad);
+  double* hcov = nullptr;
+  if (cov && (size_t)Ma * Mb * 8 >= PinBuf::kMin && (size_t)Ma * Mb * 8 <= PinBuf::kMax)
+    hcov = static_cast<double*>(c->pin.alloc((size_t)Ma * Mb * 8));
+
+  const bool resident = chunk == S;
+  if (resident)
+    if (int rc = post_consts_resident(po)) return rc;
+  const double* spb = resident ? po->dsp.as<double>() : c->spb.as<double>();
+  const double* mulb = resident ? po->dmul.as<double>() : c->mulb.as<double>();
+  const double* divb = resident ? po->ddv.as<double>() : c->divb.as<double>();
+  const double* xsb = resident ? po->dxs.as<double>() : c->xs.as<double>();
+
+  // gpc_last_timing: device time of the call and of its products (the first triangular product to the cross product)
+  c->ms_total = c->ms_factor = 0;
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[0], st));
+    if (!resident) {
+      HIPCHK(c, hipMemcpyAsync(c->spb.p, &po->sp[(size_t)s0 * SP_STRIDE], (size_t)cnt * SP_STRIDE * 8,
+                               hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(c->mulb.p, &po->mul[(size_t)s0 * D], (size_t)cnt * D * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(c->divb.p, &po->dv[(size_t)s0 * D], (size_t)cnt * D * 8, hipMemcpyHostToDevice, st));
+      const long long tot = (long long)npad * D;
+      hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, st, c->dX.as<double>(),
+                         N, npad, D, mulb, divb, c->xs.as<double>());
+    }
+    // the weights of the chunk's samples (zero in the padding) and the factor of each sample's cross product
+    std::fill(hw.begin(), hw.end(), 0.0);
+    for (int i = 0; i < cnt; ++i) {
+      if (w)
+        for (int r = 0; r < Ma; ++r) hw[(size_t)i * mapad + r] = w_per_sample ? w[(size_t)r * S + s0 + i] : w[r];
+      hw[(size_t)chunk * mapad + i] = po->lchol[s0 + i] ? -1.0 / po->sp[(size_t)(s0 + i) * SP_STRIDE + SP_SL] : 1.0;
+    }
+    HIPCHK(c, hipMemcpyAsync(d_w, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st));
+    T* Ksa = c->ks.as<T>();
+    T* Ksb = Ksa + (size_t)chunk * sKa;
+    T* Va = c->vb.as<T>();
+    T* Vb = Va + (size_t)chunk * sKa;
+    T* Kab = c->kss.as<T>();
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mapad * D + 255) / 256), cnt), dim3(256), 0, st,
+                       (const double*)d_xa, Ma, mapad, D, mulb, divb, xsa);
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mbpad * D + 255) / 256), cnt), dim3(256), 0, st,
+                       (const double*)d_xb, Mb, mbpad, D, mulb, divb, xsbq);
+    // (the builder's fused mean product lands in dbg2 and is not used: the covariance does not involve alpha)
+    const double* al = po->alpha.as<double>() + (size_t)s0 * npad;
+    GPC_COV_DISPATCH(cross_tile_kernel, T, po->cd, dim3(mapad / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, xsb,
+                     (const double*)xsa, spb, al, npad, N, npad, Ma, mapad, Ksa, sKa, c->dbg2.as<double>());
+    GPC_COV_DISPATCH(cross_tile_kernel, T, po->cd, dim3(mbpad / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, xsb,
+                     (const double*)xsbq, spb, al, npad, N, npad, Mb, mbpad, Ksb, sKb, c->dbg2.as<double>());
+    hipLaunchKernelGGL((cross_kernel<T>), dim3(mbpad / 64, mapad / 4, cnt), dim3(64, 4), 0, st, po->cd,
+                       (const double*)xsa, (const double*)xsbq, spb, Ma, mapad, Mb, mbpad, Kab, sC);
+    HIPCHK(c, hipGetLastError());
+    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[1], st));
+    int a = 0;
+    while (a < cnt) {
+      int e = a;
+      while (e < cnt && po->lchol[s0 + e] == po->lchol[s0 + a]) ++e;
+      const int len = e - a;
+      const bool lch = po->lchol[s0 + a] != 0;
+      // V_b = W Ks_b (and V_a = W Ks_a) | G_b = L Ks_b: the samples of the run in one launch each
+      GemmArgs g;
+      g.sA = sM;
+      g.lda = npad;
+      g.M = npad;
+      g.K = npad;
+      g.alpha = 1.0;
+      g.beta = 0;
+      g.klo = KLO_ZERO;
+      g.lower_only = 0;
+      g.A = (lch ? po->W.as<T>() : po->A.as<T>()) + (size_t)(s0 + a) * sM;
+      g.khi = lch ? KHI_ROW : KHI_FULL;
+      g.B = Ksb + (size_t)a * sKb;
+      g.C = Vb + (size_t)a * sKb;
+      g.sB = g.sC = sKb;
+      g.ldb = g.ldc = mbpad;
+      g.N = mbpad;
+      HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
+      if (lch) {
+        g.B = Ksa + (size_t)a * sKa;
+        g.C = Va + (size_t)a * sKa;
+        g.sB = g.sC = sKa;
+        g.ldb = g.ldc = mapad;
+        g.N = mapad;
+        HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
+      }
+      if (fs2b) {
+        const T* left = lch ? (const T*)(Vb + (size_t)a * sKb) : (const T*)(Ksb + (size_t)a * sKb);
+        hipLaunchKernelGGL((colsum_prod_kernel<T>), dim3(mbpad / 64, len), dim3(256), 0, st, left, sKb,
+                           (const T*)(Vb + (size_t)a * sKb), sKb, mbpad, npad, mbpad, d_v + (size_t)a * mbpad);
+      }
+      // the cross product C = K_ab + alpha A^T B, A = V_a | Ks_a, B = V_b | G_b
+      const T* Aop = lch ? Va : Ksa;
+      GemmArgs f;
+      f.lda = mapad;
+      f.ldb = f.ldc = mbpad;
+      f.M = mapad;
+      f.N = mbpad;
+      f.K = npad;
+      f.beta = 1;
+      f.klo = KLO_ZERO;
+      f.khi = KHI_FULL;
+      f.lower_only = 0;
+      if (fused) {
+        f.A = Aop + (size_t)a * sKa;
+        f.B = Vb + (size_t)a * sKb;
+        f.C = Kab + (size_t)a * sC;
+        f.sA = sKa;
+        f.sB = sKb;
+        f.sC = sC;
+        f.alpha = 0.0;  // (per sample: ep_alpha)
+        f.ep_alpha = d_al + a;
+        f.ep_w = d_w + (size_t)a * mapad;
+        f.ep_sw = mapad;
+        f.colsq = c->dbg3.as<double>() + (size_t)a * tma * mbpad;
+        HIPCHK(c, launch_gemm_wsq<T>(st, f, len));
+        hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mbpad + 255) / 256, len), dim3(256), 0, st,
+                           (const double*)f.colsq, tma, mbpad, d_q + (size_t)a * mbpad);
+      } else {
+        for (int i = a; i < e; ++i) {  // (per sample: alpha differs)
+          f.A = Aop + (size_t)i * sKa;
+          f.B = Vb + (size_t)i * sKb;
+          f.C = Kab + (size_t)i * sC;
+          f.sA = f.sB = f.sC = 0;
+          f.alpha = hw[(size_t)chunk * mapad + i];
+          HIPCHK(c, launch_gemm<T>(st, f, true, true, 1));
+        }
+        if (wsq)
+          hipLaunchKernelGGL((wsq_col_kernel<T>), dim3(mbpad / 64, len), dim3(256), 0, st,
+                             (const T*)(Kab + (size_t)a * sC), sC, mbpad, (const double*)(d_w + (size_t)a * mapad), mapad,
+                             Ma, mbpad, d_q + (size_t)a * mbpad);
+      }
+      a = e;
+    }
+    HIPCHK(c, hipGetLastError());
+    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[2], st));
+    HIPCHK(c, hipMemcpyAsync(hout.data(), d_v, 2 * (size_t)chunk * mbpad * 8, hipMemcpyDeviceToHost, st));
+    if (cov) {
+      for (int i = 0; i < cnt; ++i) {
+        hipLaunchKernelGGL((extract_rect_kernel<T>), dim3((Mb + 63) / 64, (Ma + 3) / 4), dim3(64, 4), 0, st,
+                           (const T*)(Kab + (size_t)i * sC), mbpad, Ma, Mb, c->dbg1.as<double>());
+        double* dst = cov + (size_t)(s0 + i) * Ma * Mb;
+        HIPCHK(c, hipMemcpyAsync(hcov ? hcov : dst, c->dbg1.p, (size_t)Ma * Mb * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipStreamSynchronize(st));
+        if (hcov) memcpy(dst, hcov, (size_t)Ma * Mb * 8);
+      }
+    }
+    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[3], st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->pin.finish();
+    if (timing_on) {
+      float t03 = 0, t12 = 0;
+      (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
+      (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
+      c->ms_total += t03;
+      c->ms_factor += t12;
+    }
+    for (int i = 0; i < cnt; ++i) {
+      const int s = s0 + i;
+      const double sf2 = po->sp[(size_t)s * SP_STRIDE + SP_SF2], sl = po->sp[(size_t)s * SP_STRIDE + SP_SL];
+      for (int j = 0; j < Mb; ++j) {
+        if (fs2b) {  // as gpc_predict forms it
+          const double q = hout[(size_t)i * mbpad + j];
+          fs2b[(size_t)j * S + s] = po->lchol[s] ? sf2 - q / sl : sf2 + q;
+        }
+        if (wsq) wsq[(size_t)j * S + s] = hout[((size_t)chunk + i) * mbpad + j];
+      }
+    }
+  }
+  if (fused) ++c->cov_fused;
   return 0;
 }
 
@@ -3812,6 +4063,20 @@ int gpc_predict_full(gpc_post* po, const double* xstar, int M, double* fmu, doub
                               : rhs_products<float>(po, 0, xstar, nullptr, M, false, fmu, nullptr, cov);
 }
 
+int gpc_predict_cov(gpc_post* po, const double* xa, int Ma, const double* xb, int Mb, const double* w, int w_per_sample,
+                    double* fs2b, double* cov, double* wsq) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!xa || !xb || Ma <= 0 || Mb <= 0 || (!cov && !wsq) || (wsq && !w)) FAIL(c, "gpc_predict_cov: bad arguments");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_predict_cov: this posterior was built from caller-provided K; there is no k(xa, xb) to start from");
+  for (int s = 0; s < po->S; ++s)
+    if (po->info[s] != 0) FAIL(c, "gpc_predict_cov: posterior contains a failed factorization");
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? cov_products<double>(po, xa, Ma, xb, Mb, w, w_per_sample, fs2b, cov, wsq)
+                              : cov_products<float>(po, xa, Ma, xb, Mb, w, w_per_sample, fs2b, cov, wsq);
+}
+
 namespace {
 // z (K + sn2_eff I)^-1 z^T: |W z|^2 / sl (L_chol) or -(z . L z) (L = -inv)   (:1946-1962)
 void quad_scale_zkz(const gpc_post* po, int M, double* zKz) {
@@ -3974,6 +4239,7 @@ int gpc_get_option(gpc_ctx* c, const char* name, int* value) {
   else if (n == "small_timing") *value = c->small_timing;
   else if (n == "small_polled") *value = (int)(c->small_polled & 0x7fffffff);  // one-leaf calls completed by the polled word ...
   else if (n == "small_synced") *value = (int)(c->small_synced & 0x7fffffff);  // ... and by a stream synchronisation
+  else if (n == "cov_fused") *value = (int)(c->cov_fused & 0x7fffffff);  // gpc_predict_cov calls reduced in the product's epilogue
   else if (n == "experiments") {  // 1: this library is the experiments build (tests/ and tools/ ask before they use its options)
 #ifdef GPC_EXPERIMENTS
     *value = 1;

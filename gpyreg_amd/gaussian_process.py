@@ -1373,6 +1373,109 @@ class GP:
                 cov[s, :, :] += np.dot(np.eye(N_star), sn2_star) * sn2_mult  # :1659, verbatim semantics
         return mu, cov.transpose(1, 2, 0)
 
+    def predict_cov(self, x_a, x_b):
+        """Posterior covariance of the latent function between the rows of ``x_a`` and the rows of ``x_b``, per
+        hyperparameter sample: cov (Ma, Mb, S),
+
+            cov[:, :, s] = k_s(x_a, x_b) - k_s(x_a, X) (K_s + Sigma_s)^-1 k_s(X, x_b),
+
+        the [A, B] block of ``predict_full(np.vstack([x_a, x_b]))[1][:, :, s]`` to rounding, without building the rest
+        of that matrix.  No noise term (the two sets are different points) and no symmetrisation (the block is not
+        square).  With data the products run on the device (gpc_predict_cov); a GP without data returns the prior
+        k_s(x_a, x_b) from the covariance object, on the host.  Built-in covariance functions only.  Under sharding
+        each rank computes its samples and the results are gathered: the same values as one process."""
+        if not self._builtin:
+            raise NotImplementedError(f"predict_cov: the covariance function {self.covariance!r} is user-defined; the "
+                                      "cross covariance runs on the built-in covariance functions only")
+        x_a, _, _ = self._convert_shapes(x_a, None, None)
+        x_b, _, _ = self._convert_shapes(x_b, None, None)
+        if self.y is None:  # no data: the prior
+            cov_N = self._counts()[0]
+            return np.stack([self.covariance.compute(p.hyp[0:cov_N], x_a, x_b) for p in self.posteriors], axis=2)
+        return self._cov_on_device(x_a, x_b, None)[0]
+
+    def lookahead_variance(self, x_cand, x_ref, weights=None, y_cand=None, s2_cand=None,
+                           separate_samples: bool = False):
+        """How much ONE more observation at each candidate would reduce the weighted posterior variance at the
+        reference points: reduction (Mc, S) with ``separate_samples``, else (Mc, 1),
+
+            reduction[c, s] = sum_r w_rs C_s(x_ref_r, x_cand_c)^2 / den_cs,
+            den_cs          = max(fs2_s(x_cand_c), 0) + sn2_s(x_cand_c) * sn2_mult_s,
+
+        C_s ``predict_cov``'s covariance, fs2 ``predict``'s variance of the candidate before its clamp and sn2 the noise
+        function's value at the candidate (``y_cand``, ``s2_cand`` as ``predict``'s ``y_star``, ``s2_star``), exactly
+        as ``predict(add_noise=True)`` forms it; 0 where den_cs <= 0.  This is s2_s(x_ref_r) - s2_s(x_ref_r | x_c)
+        summed with the weights, the core of integrated-variance designs.  ``weights``: None for 1 / M_ref (the mean
+        reduction over the reference points), (M_ref,) shared by the samples, or (M_ref, S) per sample; they must be
+        finite.  Without ``separate_samples`` the result is the plain mean over the samples: the expected reduction of
+        the AVERAGE WITHIN-SAMPLE variance -- the between-sample spread of the means, which ``predict``'s mixture
+        variance also holds, does not enter.  The value is reported as computed: it is not clamped against
+        sum_r w_r s2_r (the Cauchy-Schwarz bound holds in exact arithmetic).  With data the covariance never leaves
+        the device: its weighted squares are summed there (gpc_predict_cov) and Mc x S numbers come back.  A GP
+        without data applies the same formula to the prior, on the host.  Built-in covariance functions only; sharded
+        like ``predict_cov``."""
+        if not self._builtin:
+            raise NotImplementedError(f"lookahead_variance: the covariance function {self.covariance!r} is user-defined; "
+                                      "the cross covariance runs on the built-in covariance functions only")
+        x_cand, y_cand, s2_cand = self._convert_shapes(x_cand, y_cand, s2_cand)
+        x_ref, _, _ = self._convert_shapes(x_ref, None, None)
+        s_N = self.posteriors.size
+        Mc, Mr = x_cand.shape[0], x_ref.shape[0]
+        cov_N, noise_N, _ = self._counts()
+        if weights is None:
+            w = np.full(Mr, 1.0 / Mr)
+        else:
+            w = np.asarray(weights, dtype=float)
+            if w.shape not in ((Mr,), (Mr, s_N)):
+                raise ValueError(f"lookahead_variance: weights must be ({Mr},) or ({Mr}, {s_N}), got {w.shape}")
+            if not np.all(np.isfinite(w)):
+                raise ValueError("lookahead_variance: weights must be finite")
+        if self.y is None:  # no data: the prior
+            wsq = np.empty((Mc, s_N))
+            fs2 = np.empty((Mc, s_N))
+            for s in range(s_N):
+                hyp = self.posteriors[s].hyp
+                C = self.covariance.compute(hyp[0:cov_N], x_ref, x_cand)
+                ws = w[:, s] if w.ndim == 2 else w
+                wsq[:, s] = np.sum(ws[:, None] * C * C, axis=0)
+                fs2[:, s] = self.covariance.compute(hyp[0:cov_N], x_cand, compute_diag=True)[:, 0]
+        else:
+            _, wsq, fs2 = self._cov_on_device(x_ref, x_cand, w)
+        den = np.empty((Mc, s_N))
+        for s in range(s_N):
+            post = self.posteriors[s]
+            sn2_mult = 1 if post.sn2_mult is None else post.sn2_mult
+            sn2 = self.noise.compute(post.hyp[cov_N:cov_N + noise_N], x_cand, y_cand, s2_cand)
+            den[:, s:s + 1] = np.maximum(fs2[:, s:s + 1], 0) + sn2 * sn2_mult
+        red = np.where(den > 0, wsq / np.where(den > 0, den, 1.0), 0.0)
+        if not separate_samples:
+            red = np.reshape(np.sum(red, 1) / s_N, (-1, 1))
+        return red
+
+    @_on_device
+    def _cov_on_device(self, x_a, x_b, weights):
+        """The device part of ``predict_cov`` (weights None: (cov (Ma, Mb, S), None, None)) and ``lookahead_variance``
+        ((None, wsq (Mb, S), fs2 of x_b (Mb, S))), gathered over the ranks when sharded."""
+        Ma, Mb = x_a.shape[0], x_b.shape[0]
+        self._restore()
+        if self._post_handle is None and self._post_range is None:
+            raise ValueError("posteriors have been cleaned; call update() first")
+        self._ctx()
+        local_posts, lo = self._local_posteriors()
+        k = len(local_posts)
+        want_cov = weights is None
+        if not local_posts:
+            rows = np.zeros((Ma * Mb if want_cov else 2 * Mb, 0))
+        else:
+            w = weights[:, lo:lo + k] if (weights is not None and weights.ndim == 2) else weights
+            cov, wsq, fs2 = self._post_handle.predict_cov(x_a, x_b, w, want_cov=want_cov, want_fs2=not want_cov)
+            rows = cov.reshape(k, Ma * Mb).T if want_cov else np.concatenate([wsq, fs2], axis=0)
+        if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
+            rows = self._gather_samples(rows, x_a, x_b, np.zeros(0) if weights is None else weights)
+        if want_cov:
+            return rows.reshape(Ma, Mb, -1), None, None
+        return None, rows[:Mb], rows[Mb:]
+
     def random_function(self, X_star, add_noise: bool = False):
         """One function drawn from the GP at ``X_star`` (reference :2241-2329): a hyperparameter sample is picked
         with ``np.random``, the values come from that sample's posterior N(f_mu, C) -- the prior when the GP holds

@@ -215,6 +215,26 @@ int gpc_post_recompute_K(gpc_post* post, int cnt, const int* idx, const double* 
  * (the caller symmetrises and adds noise, :1647-1659).                                    */
 int gpc_predict_full(gpc_post* post, const double* xstar, int M, double* fmu, double* cov);
 
+/* ---- GP.predict_cov / GP.lookahead_variance: posterior covariance between TWO query sets ------------
+ * xa: Ma x D, xb: Mb x D.  With Ka = K_s(X, xa), Kb = K_s(X, xb) and, for L_chol samples, Va = W Ka,
+ * Vb = W Kb (sl the sample's noise scaling, as in gpc_predict):
+ *   cov[s] (Ma x Mb, row-major; may be NULL) = K_s(xa, xb) - Va^T Vb / sl      (L_chol)
+ *                                            = K_s(xa, xb) + Ka^T (L Kb)       (L = -inv)
+ *   wsq[j*S + s]  = sum_i w_i(s) cov_s[i][j]^2   (may be NULL; needs w: Ma doubles shared by the samples,
+ *                   or Ma x S as w[i*S + s] when w_per_sample)
+ *   fs2b[j*S + s] = gpc_predict's fs2 of xb (may be NULL): Vb is at hand, no second N^2 Mb product runs
+ * At least one of cov / wsq must be given.  No noise term and no symmetrisation: the block is not square.
+ * The library adds nothing else: the denominators of the look-ahead, the clamp and the mixture over
+ * samples are the caller's.  Without cov, and from 64 128-tiles of the Ma x Mb block on, the block is
+ * never written: the product's epilogue forms the weighted sums per tile row (fp64, also for fp32
+ * posteriors), which are added in ascending order; gpc_get_option(ctx, "cov_fused") counts those calls.
+ * The form depends on the shape only, so a sample's results are the same bits whatever the batch of
+ * samples or the chunking (GPC_MEM_BUDGET_MB).  Returns -2 with a message that names the sizes when one
+ * sample's scratch (2 N_pad (Ma_pad + Mb_pad) + Ma_pad Mb_pad elements) does not fit the memory budget,
+ * on a posterior from caller-provided K, on one that holds a failed factorization and on bad arguments. */
+int gpc_predict_cov(gpc_post* post, const double* xa, int Ma, const double* xb, int Mb, const double* w,
+                    int w_per_sample, double* fs2b, double* cov, double* wsq);
+
 /* ---- GP.quad: Bayesian quadrature products (gaussian_process.py:1908-1966), SE kernels ----
  * mu, sigma: M x D (means and standard deviations of the Gaussian measures).  With z the
  * kernel mean vector of measure j under sample s:
@@ -249,7 +269,8 @@ int gpc_quad_grad(gpc_post* post, const double* mu, const double* sigma, int M, 
 int gpc_last_timing(gpc_ctx* ctx, double* ms_total, double* ms_factor);
 /* (after gpc_predict / gpc_predict_full / gpc_quad: ms_total = device time of the call, ms_factor = the
  * duration of its N^2 M product V = W Ks, the GEMM launch of gaussian_process.py:1752-1760; after
- * gpc_quad_grad: that of its products V = W z and Q = W^T V, ~0 without compute_var)                   */
+ * gpc_quad_grad: that of its products V = W z and Q = W^T V, ~0 without compute_var; after
+ * gpc_predict_cov: ms_factor = its triangular products and the cross product, with the reduction)     */
 /* The dominant single kernel of the last gpc_nll_batch with gradient: the W^T W ("lauum")
  * launch of gemm_kernel<T, true, true, ...>.  ms = its duration (hipEvents on the stream it
  * was launched on; the slowest sample group), flops = its algorithmic flops
@@ -268,7 +289,8 @@ int gpc_last_lauum_timing(gpc_ctx* ctx, double* ms, double* flops);
  * launch writes into coherent host memory shows up, instead of waiting for the stream (bounded: after 0.15 - 2 ms it waits
  * for the stream after all); "small_timing" (default 0) = such calls record their timing events, so that gpc_last_timing
  * reports their device section (it reports 0 for them otherwise; from N_pad = 2048 on the events are always recorded).
- * "small_polled" / "small_synced" (get only): how many calls ended either way.                                         */
+ * "small_polled" / "small_synced" (get only): how many calls ended either way.
+ * "cov_fused" (get only): how many gpc_predict_cov calls formed their reduction in the product's epilogue.              */
 int gpc_set_option(gpc_ctx* ctx, const char* name, int value);
 /* Current value of a tuning switch (so that a caller that changes one for a measurement can put it back). */
 int gpc_get_option(gpc_ctx* ctx, const char* name, int* value);
