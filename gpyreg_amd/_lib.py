@@ -70,6 +70,8 @@ SIGNATURES = {
     "gpc_post_append": (C.c_int, [_vp, _dp, _dp, C.c_double, _ip]),
     "gpc_post_recompute": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_post_append_K": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_double, _ip]),
+    "gpc_post_append_block": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _ip]),
+    "gpc_post_append_block_K": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
     "gpc_post_recompute_K": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_predict_full": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "gpc_predict_cov": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
@@ -506,6 +508,41 @@ class PostHandle:
                                              float(y_new), ok.ctypes.data)
         self.ctx._check(rc, "gpc_post_append_K")
         self.N += 1
+        return ok.astype(bool)
+
+    @_serial
+    def append_block(self, m_star, sn2_star, y_new):
+        """Block append of the k points already added to the context's data (gpc_post_append_block): m_star (S, k),
+        sn2_star (S,), y_new (k,).  Returns the per-sample outcome (bool array): False entries were left stale and
+        must be recomputed (``recompute``)."""
+        y_new = _f64(y_new).ravel()
+        k = y_new.size
+        m_star, sn2_star = _f64(m_star).ravel(), _f64(sn2_star).ravel()
+        if m_star.size != self.S * k or sn2_star.shape != (self.S,):
+            raise ValueError("m_star must be (S, k) and sn2_star (S,)")
+        ok = np.zeros(self.S, dtype=np.int32)
+        rc = self.ctx._lib.gpc_post_append_block(self._h, k, _ptr(m_star), _ptr(sn2_star), _ptr(y_new),
+                                                 ok.ctypes.data)
+        self.ctx._check(rc, "gpc_post_append_block")
+        self.N += k
+        return ok.astype(bool)
+
+    @_serial
+    def append_block_K(self, Ks, Kss, m_star, sn2_star, y_new):
+        """``append_block`` for posteriors built from a caller's covariance object: Ks (S, n, k) = k_s(X_old, X_new),
+        Kss (S, k, k) = k_s(X_new, X_new)."""
+        y_new = _f64(y_new).ravel()
+        k = y_new.size
+        Ks, Kss = _f64(Ks), _f64(Kss)
+        m_star, sn2_star = _f64(m_star).ravel(), _f64(sn2_star).ravel()
+        if (Ks.shape != (self.S, self.N, k) or Kss.shape != (self.S, k, k) or m_star.size != self.S * k
+                or sn2_star.shape != (self.S,)):
+            raise ValueError("Ks must be (S, n, k), Kss (S, k, k), m_star (S, k) and sn2_star (S,)")
+        ok = np.zeros(self.S, dtype=np.int32)
+        rc = self.ctx._lib.gpc_post_append_block_K(self._h, k, _ptr(Ks), _ptr(Kss), _ptr(m_star), _ptr(sn2_star),
+                                                   _ptr(y_new), ok.ctypes.data)
+        self.ctx._check(rc, "gpc_post_append_block_K")
+        self.N += k
         return ok.astype(bool)
 
     @_serial

@@ -20,6 +20,7 @@
 #include <mutex>
 
 #include "blas1.h"
+#include "block_append.h"
 #include "common.h"
 #include "covfun.h"
 #include "draw.h"
@@ -566,6 +567,9 @@ struct gpc_ctx {
   // starts at 1, gaussian_process.py:2402) and samples whose rank-one append is declared unstable
   double start_mult = 1.0;
   unsigned append_fail_mask = 0;
+  int block_engine_ran = 0;  // the engine the last gpc_post_append_block ran (1: skinny kernel, 2: MFMA GEMM; get-only)
+  int block_engine = 0;  // test hook: the engine of the block append's products with W (0: by k, 1: skinny kernel, 2: MFMA GEMM)
+  long long block_appended = 0, block_stale = 0;  // samples gpc_post_append_block appended / left stale (get-only options)
   int retry_runs = 0;  // device pipelines spent on jitter retries by the last call (one per level)
 #ifdef GPC_EXPERIMENTS
   // ---- tile-level dataflow (dag.h).  Option "dag": 0 off, 1 wherever the plan supports it, -1 automatic (by what was
@@ -3447,6 +3451,288 @@ int append_impl(gpc_post* po, const double* m_star, const double* sn2_star, doub
   po->dev_consts = false;
   return 0;
 }
+
+// Block append of k points (block_append.h has the algebra and the kernels).  Everything per sample is decided on
+// the device; `ok` comes back in one download of the Schur factorizations' info.
+// Ks_h (S x n x k) / Kss_h (S x k x k): the caller's cross covariances (K-mode posteriors); nullptr: built on the device.
+template <typename T>
+int append_block_impl(gpc_post* po, int k, const double* m_star, const double* sn2_star, const double* y_new, int* ok,
+                      const double* Ks_h = nullptr, const double* Kss_h = nullptr) {
+  gpc_ctx* c = po->ctx;
+  const int S = po->S, D = po->D, n = po->N;  // the new points are rows n .. n+k-1 of the context's X
+  hipStream_t st = c->st;
+  const int npn = pad_tile(n + k);
+  const int kq = ((k + BA_R - 1) / BA_R) * BA_R, kp = pad_tile(k);
+  // scratch of one sample: four n x k panels (Bx, V | G, Pt | H, GS), the k x k products, three vectors, and the
+  // three slabs of the k x k factorization
+  const size_t panel = (size_t)npn * kq * 8;
+  const bool use_gemm = c->block_engine ? c->block_engine == 2 : k >= BA_GEMM_MIN_K;
+  c->block_engine_ran = use_gemm ? 2 : 1;
+  const size_t tpanel = use_gemm ? (size_t)npn * kp * sizeof(T) : 0;  // (MFMA engine: B, V | G and W^T V in the storage type)
+  const size_t per = 4 * panel + 3 * tpanel + (size_t)kq * kq * 8 + 3 * (size_t)kq * 8 + 3 * (size_t)kp * kp * sizeof(T) + 64;
+  const bool grow = npn > po->npad;
+  const size_t grow_bytes = grow ? (size_t)S * npn * ((size_t)npn * 2 * sizeof(T) + 8) : 0;
+  // the scratch is the context's cross-covariance buffer (gpc_predict's Ks): kept between calls, so that an
+  // acquisition loop pays no allocation per batch; budgeted like gpc_predict_cov's when it has to grow
+  const size_t held = c->ks.bytes;
+  int chunk = S;
+  // (a forced budget takes this path on every call, pool_drain included: it is the tests' way into the chunked path,
+  // not a setting for an acquisition loop, which without it allocates only when the scratch or the storage grows)
+  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > held || grow) {
+    c->pool_drain();
+    // GPC_MEM_BUDGET_MB budgets the SCRATCH (the tests' way into the chunked path); the device's real free memory
+    // has to hold the grown storage as well
+    const bool forced = getenv("GPC_MEM_BUDGET_MB") != nullptr;
+    const size_t fr = free_device_bytes() + (forced ? 0 : held);
+    const size_t avail = forced ? fr : (fr > grow_bytes ? fr - grow_bytes : 0);
+    if ((size_t)(avail * 0.8) < per)
+      FAIL(c, "gpc_post_append_block: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
+              std::to_string(npn) + ", k = " + std::to_string(k) + ") exceeds the device memory budget (" +
+              std::to_string((size_t)(avail * 0.8) >> 10) + " KB" +
+              (grow ? " beside " + std::to_string(grow_bytes >> 10) + " KB of grown storage)" : ")"));
+    chunk = (int)std::min<size_t>(S, (size_t)(avail * 0.8) / per);
+  }
+  // grow the padded storage by as many tiles as the k rows need (identity padding, like the rank-one path)
+  if (grow) {
+    const int np = po->npad;
+    DevBuf nA, nW, nal;
+    HIPCHK(c, nA.ensure((size_t)S * npn * npn * sizeof(T)));
+    HIPCHK(c, nW.ensure((size_t)S * npn * npn * sizeof(T)));
+    HIPCHK(c, nal.ensure((size_t)S * npn * sizeof(double)));
+    dim3 g(npn / 64, npn / 4, S), blk(64, 4);
+    hipLaunchKernelGGL((grow_copy_kernel<T>), g, blk, 0, st, (const T*)po->A.as<T>(), np, nA.as<T>(), npn);
+    hipLaunchKernelGGL((grow_copy_kernel<T>), g, blk, 0, st, (const T*)po->W.as<T>(), np, nW.as<T>(), npn);
+    HIPCHK(c, hipMemsetAsync(nal.p, 0, (size_t)S * npn * sizeof(double), st));
+    HIPCHK(c, hipMemcpy2DAsync(nal.p, (size_t)npn * 8, po->alpha.p, (size_t)np * 8, (size_t)np * 8, S,
+                               hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    po->A.release();
+    po->W.release();
+    po->alpha.release();
+    po->A = nA;
+    po->W = nW;
+    po->alpha = nal;
+    po->npad = npn;
+  }
+  const int npad = po->npad;
+  const long long sM = (long long)npad * npad;
+  const long long sP = (long long)npad * kq;
+  // per-sample parameters and the preconditions the host can decide: a factorized sample, the fitted scalar noise
+  std::vector<double> par((size_t)S * BA_STRIDE);
+  for (int s = 0; s < S; ++s) {
+    const double sl = po->sp[(size_t)s * SP_STRIDE + SP_SL];
+    const double sn2_eff = sn2_star[s] * po->mult[s];
+    bool pre = po->info[s] == 0 && !((c->append_fail_mask >> (s & 31)) & 1u) && sn2_eff > 0.0;
+    if (po->lchol[s]) pre = pre && std::abs(sn2_eff - sl) <= 1e-12 * sl;
+    par[(size_t)s * BA_STRIDE + BA_SL] = sl;
+    par[(size_t)s * BA_STRIDE + BA_SN2] = sn2_eff;
+    par[(size_t)s * BA_STRIDE + BA_LCH] = po->lchol[s] ? 1.0 : 0.0;
+    par[(size_t)s * BA_STRIDE + BA_PRE] = pre ? 1.0 : 0.0;
+  }
+  HIPCHK(c, c->spb.ensure((size_t)S * SP_STRIDE * 8));
+  HIPCHK(c, c->avec.ensure((size_t)S * BA_STRIDE * 8));
+  HIPCHK(c, c->rvec.ensure(((size_t)S * k + k) * 8));
+  HIPCHK(c, c->scal.ensure((size_t)S * 16));
+  double* d_par = c->avec.as<double>();
+  double* d_ms = c->rvec.as<double>();
+  double* d_y = d_ms + (size_t)S * k;
+  double* d_logdet = c->scal.as<double>();
+  int* d_info = reinterpret_cast<int*>(d_logdet + S);
+  HIPCHK(c, hipMemcpyAsync(c->spb.p, po->sp.data(), (size_t)S * SP_STRIDE * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_par, par.data(), par.size() * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_ms, m_star, (size_t)S * k * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_y, y_new, (size_t)k * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(c->scal.p, 0, (size_t)S * 16, st));
+  if (!Ks_h) {
+    HIPCHK(c, c->xs.ensure((size_t)S * npad * D * 8));
+    HIPCHK(c, c->mulb.ensure((size_t)S * D * 8));
+    HIPCHK(c, c->divb.ensure((size_t)S * D * 8));
+    HIPCHK(c, hipMemcpyAsync(c->mulb.p, po->mul.data(), (size_t)S * D * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->divb.p, po->dv.data(), (size_t)S * D * 8, hipMemcpyHostToDevice, st));
+    const long long tot = (long long)npad * D;
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), S), dim3(256), 0, st, c->dX.as<double>(),
+                       n + k, npad, D, c->mulb.as<double>(), c->divb.as<double>(), c->xs.as<double>());
+  }
+  HIPCHK(c, c->ks.ensure((size_t)chunk * per));
+  DevBuf& scr = c->ks;
+  bool any_high = false, any_low = false;
+  for (int s = 0; s < S; ++s) (po->lchol[s] ? any_high : any_low) = true;
+  // gpc_last_timing: device time of the call (after the growth) and of the skinny products (the last chunk's)
+  c->ms_total = c->ms_factor = 0;
+  HIPCHK(c, hipEventRecord(c->ev[0], st));
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    HIPCHK(c, hipMemsetAsync(scr.p, 0, (size_t)cnt * per, st));
+    double* Bx = scr.as<double>();
+    double* V = Bx + (size_t)cnt * sP;    // high noise: W B;  low noise: G = -A B
+    double* Pt = V + (size_t)cnt * sP;    // high noise: (V^T W / sl), k x n;  low noise: H = G W22^T, n x k
+    double* GS = Pt + (size_t)cnt * sP;   // low noise: G Si
+    double* Cm = GS + (size_t)cnt * sP;   // V^T V | B^T G
+    double* ev = Cm + (size_t)cnt * kq * kq;
+    double* tv = ev + (size_t)cnt * kq;
+    double* zv = tv + (size_t)cnt * kq;
+    T* fA = reinterpret_cast<T*>(zv + (size_t)cnt * kq);
+    T* fW = fA + (size_t)cnt * kp * kp;
+    T* fT = fW + (size_t)cnt * kp * kp;
+    T* Bt = fT + (size_t)cnt * kp * kp;
+    T* Vt = Bt + (size_t)cnt * npad * kp;
+    T* Qt = Vt + (size_t)cnt * npad * kp;
+    const double* parc = d_par + (size_t)s0 * BA_STRIDE;
+    T* Ac = po->A.as<T>() + (size_t)s0 * sM;
+    T* Wc = po->W.as<T>() + (size_t)s0 * sM;
+    double* alc = po->alpha.as<double>() + (size_t)s0 * npad;
+    // 1. cross covariances
+    if (Ks_h) {
+      for (int i = 0; i < cnt; ++i) {
+        HIPCHK(c, hipMemcpy2DAsync(Bx + (size_t)i * sP, (size_t)kq * 8, Ks_h + (size_t)(s0 + i) * n * k, (size_t)k * 8,
+                                   (size_t)k * 8, n, hipMemcpyHostToDevice, st));
+        HIPCHK(c, hipMemcpy2DAsync(Bx + (size_t)i * sP + (size_t)n * kq, (size_t)kq * 8,
+                                   Kss_h + (size_t)(s0 + i) * k * k, (size_t)k * 8, (size_t)k * 8, k,
+                                   hipMemcpyHostToDevice, st));
+      }
+    } else {
+      hipLaunchKernelGGL(ba_cross_kernel, dim3((unsigned)((sP + 255) / 256), cnt), dim3(256), 0, st, po->cd,
+                         (const double*)(c->xs.as<double>() + (size_t)s0 * npad * D),
+                         (const double*)(c->spb.as<double>() + (size_t)s0 * SP_STRIDE), n, k, npad, kq, Bx);
+    }
+    // 2. the skinny products and the k x k Gram matrices
+    const dim3 gn((n + BA_T - 1) / BA_T, kq / BA_R, cnt), gk((k + BA_T - 1) / BA_T, kq / BA_R, cnt);
+    HIPCHK(c, hipEventRecord(c->ev[1], st));
+    if (use_gemm) {
+      // the same products as launches of the MFMA GEMM on panels padded to 128 columns, in runs of one parametrisation
+      const long long sK = (long long)npad * kp;
+      hipLaunchKernelGGL((ba_to_panel_kernel<T>), dim3(kp / 64, npad / 4, cnt), dim3(64, 4), 0, st, (const double*)Bx, n, k,
+                         kq, npad, kp, Bt);
+      for (int a = 0; a < cnt;) {
+        const int lch = po->lchol[s0 + a];
+        int e = a + 1;
+        while (e < cnt && po->lchol[s0 + e] == lch) ++e;
+        GemmArgs g;
+        g.A = (lch ? Wc : Ac) + (size_t)a * sM;  // V = W B | G = -A B
+        g.B = Bt + (size_t)a * sK;
+        g.C = Vt + (size_t)a * sK;
+        g.sA = sM;
+        g.sB = g.sC = sK;
+        g.lda = npad;
+        g.ldb = g.ldc = kp;
+        g.M = npad;
+        g.N = kp;
+        g.K = npad;
+        g.alpha = lch ? 1.0 : -1.0;
+        g.beta = 0;
+        g.klo = KLO_ZERO;
+        g.khi = lch ? KHI_ROW : KHI_FULL;
+        g.lower_only = 0;
+        g.tiles_n = kp / TILE;
+        HIPCHK(c, launch_gemm<T>(st, g, false, true, e - a));
+        if (lch) {  // Q = W^T V (k from the tile row's diagonal block on)
+          GemmArgs q = g;
+          q.A = Wc + (size_t)a * sM;
+          q.B = Vt + (size_t)a * sK;
+          q.C = Qt + (size_t)a * sK;
+          q.klo = KLO_ROW;
+          q.khi = KHI_FULL;
+          HIPCHK(c, launch_gemm<T>(st, q, true, true, e - a));
+        }
+        a = e;
+      }
+      const dim3 gf((n + 63) / 64, kq / 4, cnt);
+      for (int want = 0; want < 2; ++want) {
+        if (!(want ? any_high : any_low)) continue;
+        hipLaunchKernelGGL((ba_from_panel_kernel<T>), gf, dim3(64, 4), 0, st, (const T*)Vt, n, kq, npad, kp, 0, parc, want, V);
+        if (want)
+          hipLaunchKernelGGL((ba_from_panel_kernel<T>), gf, dim3(64, 4), 0, st, (const T*)Qt, n, kq, npad, kp, 1, parc, 1, Pt);
+        hipLaunchKernelGGL((ba_skinny_kernel<double, true, false, false>), gk, dim3(256), 0, st,
+                           (const double*)(want ? V : Bx), sP, kq, n, k, (const double*)V, sP, kq, Cm, (long long)kq * kq, kq,
+                           1.0, 0, parc, want);
+      }
+    } else {
+    if (any_high) {
+      hipLaunchKernelGGL((ba_skinny_kernel<T, false, true, false>), gn, dim3(256), 0, st, (const T*)Wc, sM, npad, n, n,
+                         (const double*)Bx, sP, kq, V, sP, kq, 1.0, 0, parc, 1);
+      hipLaunchKernelGGL((ba_skinny_kernel<double, true, false, false>), gk, dim3(256), 0, st, (const double*)V, sP, kq, n,
+                         k, (const double*)V, sP, kq, Cm, (long long)kq * kq, kq, 1.0, 0, parc, 1);
+      hipLaunchKernelGGL((ba_skinny_kernel<T, true, true, true>), gn, dim3(256), 0, st, (const T*)Wc, sM, npad, n, n,
+                         (const double*)V, sP, kq, Pt, sP, npad, 1.0, 1, parc, 1);
+    }
+    if (any_low) {
+      hipLaunchKernelGGL((ba_skinny_kernel<T, false, false, false>), gn, dim3(256), 0, st, (const T*)Ac, sM, npad, n, n,
+                         (const double*)Bx, sP, kq, V, sP, kq, -1.0, 0, parc, 0);
+      hipLaunchKernelGGL((ba_skinny_kernel<double, true, false, false>), gk, dim3(256), 0, st, (const double*)Bx, sP, kq,
+                         n, k, (const double*)V, sP, kq, Cm, (long long)kq * kq, kq, 1.0, 0, parc, 0);
+    }
+    }
+    HIPCHK(c, hipEventRecord(c->ev[2], st));
+    // 3. Schur complement, its factor and inverse factor: the blocked factorization, no jitter
+    hipLaunchKernelGGL((ba_schur_kernel<T>), dim3(kp / 64, kp / 4, cnt), dim3(64, 4), 0, st, (const double*)Bx, sP, n, k,
+                       kq, (const double*)Cm, parc, kp, fA);
+    HIPCHK(c, hipGetLastError());
+    Factor<T> F;
+    F.st = st;
+    F.batch = cnt;
+    F.npad = kp;
+    F.A = fA;
+    F.W = fW;
+    F.Tm = fT;
+    F.sA = F.sW = F.sT = (long long)kp * kp;
+    F.logdet = d_logdet + s0;
+    F.info = d_info + s0;
+    F.nvalid = k;
+    F.potrf_inv(0, kp, true, true);
+    HIPCHK(c, F.err);
+    HIPCHK(c, hipGetLastError());
+    const int* infoc = d_info + s0;
+    // 4. the new alpha and the new rows, placed where the factorization succeeded
+    hipLaunchKernelGGL(ba_innov_kernel, dim3(k, cnt), dim3(256), 0, st, (const double*)Bx, sP, n, kq, (const double*)alc,
+                       npad, (const double*)d_y, (const double*)(d_ms + (size_t)s0 * k), k, ev);
+    hipLaunchKernelGGL((ba_small_vec_kernel<T>), dim3(cnt), dim3(256), 0, st, (const T*)fW, kp, k, kq, (const double*)ev,
+                       tv, zv);
+    hipLaunchKernelGGL(ba_alpha_kernel, dim3((npad + 255) / 256, cnt), dim3(256), 0, st, alc, npad, n, k, kq,
+                       (const double*)Pt, (const double*)V, (const double*)zv, parc, infoc);
+    if (any_high)
+      hipLaunchKernelGGL((ba_place_high_kernel<T>), dim3((npad + 255) / 256, k, cnt), dim3(256), 0, st, Ac, Wc, sM, npad,
+                         n, k, kq, kp, (const double*)V, (const double*)Pt, (const T*)fA, (const T*)fW, parc, infoc);
+    if (any_low) {
+      const dim3 gp((unsigned)(((long long)n * k + 255) / 256), cnt);
+      hipLaunchKernelGGL((ba_panel_w22_kernel<T>), gp, dim3(256), 0, st, (const double*)V, Pt, sP, n, k, kq,
+                         (const T*)fW, kp, 0, parc);
+      hipLaunchKernelGGL((ba_panel_w22_kernel<T>), gp, dim3(256), 0, st, (const double*)Pt, GS, sP, n, k, kq,
+                         (const T*)fW, kp, 1, parc);
+      hipLaunchKernelGGL((ba_place_low_kernel<T>), dim3((n + k + 63) / 64, (n + k + 15) / 16, cnt), dim3(64, 4), 0, st,
+                         Ac, sM, npad, n, k, kq, kp, (const double*)V, (const double*)GS, (const T*)fW, parc, infoc);
+    }
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipEventRecord(c->ev[3], st));
+  std::vector<int> info(S);
+  HIPCHK(c, hipMemcpyAsync(info.data(), d_info, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  {
+    float t03 = 0, t12 = 0;
+    (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
+    (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
+    c->ms_total = t03;
+    c->ms_factor = t12;
+  }
+  for (int s = 0; s < S; ++s) {
+    ok[s] = (par[(size_t)s * BA_STRIDE + BA_PRE] != 0.0 && info[s] == 0) ? 1 : 0;
+    ++(ok[s] ? c->block_appended : c->block_stale);
+  }
+  po->N = n + k;
+  po->dev_consts = false;
+  return 0;
+}
+
+int append_block_check(gpc_post* po, int k, const char* fn) {
+  gpc_ctx* c = po->ctx;
+  const std::string f(fn);
+  if (k < 1) FAIL(c, f + ": k must be at least 1");
+  if ((long long)po->N + k > gpc_max_n(po->dtype))
+    FAIL(c, f + ": N + k = " + std::to_string((long long)po->N + k) + " exceeds gpc_max_n = " +
+            std::to_string(gpc_max_n(po->dtype)));
+  if (c->N != po->N + k) FAIL(c, f + ": call gpc_set_data with the extended X, y (N + k rows) first");
+  return 0;
+}
 }  // namespace
 
 
@@ -3984,6 +4270,32 @@ int gpc_post_recompute(gpc_post* po, int cnt, const int* idx, const double* hyp_
   return recompute_impl(po, cnt, idx, hyp_cov, nullptr, m, sn2, sn2_is_vector, sn2_mult, L_chol, info);
 }
 
+int gpc_post_append_block(gpc_post* po, int k, const double* m_star, const double* sn2_star, const double* y_new,
+                          int* ok) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!m_star || !sn2_star || !y_new || !ok) FAIL(c, "gpc_post_append_block: null argument");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_post_append_block: not available for posteriors built from caller-provided K; use gpc_post_append_block_K");
+  if (int rc = append_block_check(po, k, "gpc_post_append_block")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? append_block_impl<double>(po, k, m_star, sn2_star, y_new, ok)
+                              : append_block_impl<float>(po, k, m_star, sn2_star, y_new, ok);
+}
+
+int gpc_post_append_block_K(gpc_post* po, int k, const double* Ks, const double* Kss, const double* m_star,
+                            const double* sn2_star, const double* y_new, int* ok) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!Ks || !Kss || !m_star || !sn2_star || !y_new || !ok) FAIL(c, "gpc_post_append_block_K: null argument");
+  if (po->cd.kind >= 0)
+    FAIL(c, "gpc_post_append_block_K: this posterior was built from a device kernel; use gpc_post_append_block");
+  if (int rc = append_block_check(po, k, "gpc_post_append_block_K")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? append_block_impl<double>(po, k, m_star, sn2_star, y_new, ok, Ks, Kss)
+                              : append_block_impl<float>(po, k, m_star, sn2_star, y_new, ok, Ks, Kss);
+}
+
 int gpc_post_recompute_K(gpc_post* po, int cnt, const int* idx, const double* K, const double* m, const double* sn2,
                          int sn2_is_vector, double* sn2_mult, int* L_chol, int* info) {
   if (!po) return -2;
@@ -4209,6 +4521,8 @@ int gpc_set_option(gpc_ctx* c, const char* name, int value) {
     c->start_mult = std::pow(10.0, std::max(0, std::min(9, value)));
   else if (n == "append_fail_mask")  // test hook: samples whose rank-one append is declared unstable
     c->append_fail_mask = (unsigned)value;
+  else if (n == "block_engine")  // test hook: 1 / 2 force the skinny kernel / the MFMA GEMM in gpc_post_append_block (0: by k)
+    c->block_engine = value == 1 || value == 2 ? value : 0;
   else {
 #ifdef GPC_EXPERIMENTS
     if (int* slot = experiment_option(c, n))
@@ -4240,6 +4554,10 @@ int gpc_get_option(gpc_ctx* c, const char* name, int* value) {
   else if (n == "small_polled") *value = (int)(c->small_polled & 0x7fffffff);  // one-leaf calls completed by the polled word ...
   else if (n == "small_synced") *value = (int)(c->small_synced & 0x7fffffff);  // ... and by a stream synchronisation
   else if (n == "cov_fused") *value = (int)(c->cov_fused & 0x7fffffff);  // gpc_predict_cov calls reduced in the product's epilogue
+  else if (n == "block_engine") *value = c->block_engine;
+  else if (n == "block_engine_ran") *value = c->block_engine_ran;  // 1 / 2: what the last block append ran (0: none yet)
+  else if (n == "block_appended") *value = (int)(c->block_appended & 0x7fffffff);  // samples gpc_post_append_block appended ...
+  else if (n == "block_stale") *value = (int)(c->block_stale & 0x7fffffff);  // ... and left stale for gpc_post_recompute
   else if (n == "experiments") {  // 1: this library is the experiments build (tests/ and tools/ ask before they use its options)
 #ifdef GPC_EXPERIMENTS
     *value = 1;

@@ -898,14 +898,29 @@ class GP:
         return arr
 
     # ------------------------------------------------------------------ data / posterior
-    def update(self, X_new=None, y_new=None, s2_new=None, hyp=None, compute_posterior: bool = True):
+    def update(self, X_new=None, y_new=None, s2_new=None, hyp=None, compute_posterior: bool = True,
+               block_append: bool = False):
         """Add data and/or replace hyperparameters, then rebuild every posterior
         (reference :691-884).  A single new observation (no ``s2``, no new ``hyp``, existing
         posteriors with scalar noise) takes the reference's rank-one path (:750-844) on the
         device in O(N^2): high-noise posteriors get a new last row of the factor, of its inverse
         and of alpha; low-noise posteriors the rank-one update of -inv (:819-827).  A posterior
         whose append is numerically unstable (``sqrt_arg <= 0``, :789-798) is recomputed alone,
-        like the reference's ``full_updates``.  Anything else is the full recompute loop (:870-884)."""
+        like the reference's ``full_updates``.  Anything else is the full recompute loop (:870-884).
+
+        ``block_append=True`` asks for the same fast path for k >= 2 new observations in one call (the reference has
+        none: it recomputes).  Where the rank-one path's other conditions hold -- resident posteriors, ``y_new``
+        given, no ``s2``, no new ``hyp``, scalar noise, ``compute_posterior`` -- all k rows are appended to every
+        resident posterior in one device call in O(S N^2 k) (``gpc_post_append_block``: the rank-one algebra with a
+        k x k Schur block, factorized without jitter); a sample whose block is not positive definite is recomputed
+        alone, the others keep their appended rows, and the posterior handle stays the same object.  Where they do
+        not hold the call is the full recompute, silently; k = 1 is the rank-one path, same bits.  The result
+        agrees with the full recompute to rounding (1e-8 relative in fp64), not to the bit, which is why it is a
+        keyword and not the default.  Measured on an MI355X (``profiles/block_append_cfg3.json``, wall time): at
+        N = 4096, S = 16 the block append is 3.0x / 2.5x faster than the full recompute at k = 5 / 128 and the two are
+        level at k = 512 (k / N = 1/8); at N = 400, S = 8 it is about 2x faster for k = 5 .. 64 and the full recompute overtakes
+        it from k = 128 on (k / N about 1/3, where the storage also has to grow by a tile).  Against k one-point
+        updates it wins from k = 5 on; at k = 2 on the large problem two one-point updates are 1.3x faster."""
         X_new, y_new, s2_new = self._convert_shapes(X_new, y_new, s2_new)
         if X_new is not None:
             X_new = X_new.copy()
@@ -924,34 +939,22 @@ class GP:
 
         if X_new is not None and hyp is None:
             self._restore()  # (a copied GP: the rank-one path below extends RESIDENT posteriors)
-        rank_one = (X_new is not None and y_new is not None and compute_posterior
-                    and self.X is not None and self.y is not None and X_new.shape[0] == 1
-                    and y_new.shape[0] == 1 and s2_new is None and hyp is None
-                    and self.s2 is None and self.posteriors is not None
-                    and (self._post_handle is not None or self._post_range is not None))
+        # the append path: one new row (the reference's rank-one path) or, under ``block_append``, k >= 2 rows at once
+        append = (X_new is not None and y_new is not None and compute_posterior
+                  and self.X is not None and self.y is not None
+                  and (X_new.shape[0] == 1 or (block_append and X_new.shape[0] >= 2))
+                  and y_new.shape[0] == X_new.shape[0] and s2_new is None and hyp is None
+                  and self.s2 is None and self.posteriors is not None
+                  and (self._post_handle is not None or self._post_range is not None))
         append_args = None
-        if rank_one:
+        if append:
             cov_N, noise_N, mean_N = self._counts()
-            m_star, sn2_star = [], []
             local_posts, first = self._local_posteriors()
             # per-point noise: the append formulas do not apply.  Decided on a record EVERY rank holds (a rank of a
             # sharded set may have no local posterior), so that all ranks take the same path
             if not np.isscalar(self.noise.compute(self.posteriors[0].hyp[cov_N:cov_N + noise_N], X_new, y_new, 0)):
-                rank_one, local_posts = False, []
-            for p in local_posts:
-                h = p.hyp
-                sn2 = self.noise.compute(h[cov_N:cov_N + noise_N], X_new, y_new, 0)
-                sn2_star.append(float(sn2))
-                m_star.append(float(np.ravel(self.mean.compute(
-                    h[cov_N + noise_N:cov_N + noise_N + mean_N], X_new))[0]))
-            append_args = (m_star, sn2_star, float(y_new[0, 0]))
-            if rank_one and not self._builtin and local_posts:
-                # a user-defined covariance object supplies its own cross covariances, like the reference's
-                # rank-one path does whatever the object is (gaussian_process.py:771-772)
-                Ks = np.stack([np.ravel(self.covariance.compute(p.hyp[0:cov_N], self.X, X_new)) for p in local_posts])
-                kss = np.array([float(np.ravel(self.covariance.compute(p.hyp[0:cov_N], X_new, compute_diag=True))[0])
-                                for p in local_posts])
-                append_args = (Ks, kss) + append_args
+                append, local_posts = False, []
+            append_args = self._append_args(local_posts, X_new, y_new)
 
         if X_new is not None:
             self.X = X_new if self.X is None else np.concatenate((self.X, X_new))
@@ -960,8 +963,8 @@ class GP:
         if s2_new is not None:
             self.s2 = s2_new if self.s2 is None else np.concatenate((self.s2, s2_new))
 
-        if rank_one:
-            self._append_point(local_posts, append_args, X_new, y_new)
+        if append:
+            self._append_points(local_posts, append_args, X_new, y_new)
             return
 
         if hyp is None:
@@ -975,9 +978,37 @@ class GP:
             for i in range(s_N):
                 self.posteriors[i] = Posterior(hyp[i, :], None, None, None, None, None)
 
+    def _append_args(self, local_posts, X_new, y_new):
+        """What the device's append entry points take for this rank's posteriors, evaluated on the data BEFORE the new
+        rows are stored: (m_star, sn2_star, y_new), led by the cross covariances (Ks, kss | Kss) when the covariance is
+        a user-defined object -- it supplies its own, like the reference's rank-one path does whatever the object is
+        (gaussian_process.py:771-772).  One new row: scalars per sample (``append`` / ``append_K``); k rows: k-vectors
+        and, for an object, Ks (S, n, k) and Kss (S, k, k) (``append_block`` / ``append_block_K``)."""
+        cov_N, noise_N, mean_N = self._counts()
+        k = X_new.shape[0]
+        one = k == 1
+        m_star, sn2_star, Ks, kss = [], [], [], []
+        for p in local_posts:
+            h = p.hyp
+            sn2_star.append(float(self.noise.compute(h[cov_N:cov_N + noise_N], X_new, y_new, 0)))
+            m_new = np.ravel(self.mean.compute(h[cov_N + noise_N:cov_N + noise_N + mean_N], X_new))
+            m_star.append(float(m_new[0]) if one else np.array(m_new, dtype=float))
+            if not self._builtin:
+                cross = np.asarray(self.covariance.compute(h[0:cov_N], self.X, X_new), dtype=float)
+                Ks.append(np.ravel(cross) if one else cross.reshape(self.X.shape[0], k))
+                if one:
+                    kss.append(float(np.ravel(self.covariance.compute(h[0:cov_N], X_new, compute_diag=True))[0]))
+                else:
+                    kss.append(np.asarray(self.covariance.compute(h[0:cov_N], X_new), dtype=float).reshape(k, k))
+        args = (m_star, sn2_star, float(y_new[0, 0]) if one else np.ravel(y_new).astype(float))
+        if not self._builtin and local_posts:
+            args = (np.stack(Ks), np.array(kss) if one else np.stack(kss)) + args
+        return args
+
     @_on_device
-    def _append_point(self, local_posts, append_args, X_new, y_new):
-        """The rank-one path on this rank's posteriors (all of them unless the set is sharded): append on the device,
+    def _append_points(self, local_posts, append_args, X_new, y_new):
+        """The append path (one new row: rank-one; k >= 2 rows under ``block_append``: one block append) on this
+        rank's posteriors (all of them unless the set is sharded): append on the device,
         recompute alone the ones whose append is unstable (``sqrt_arg <= 0``, :789-798, :866-869), then -- under a
         process group -- exchange (sn2_mult, L_chol, failed) so that every rank updates its records or raises alike."""
         cov_N, _, _ = self._counts()
@@ -988,7 +1019,10 @@ class GP:
                 return np.zeros((0, 2)), np.zeros(0, bool)
             self._ctx()  # uploads the extended X, y
             h = self._post_handle
-            ok = h.append(*append_args) if self._builtin else h.append_K(*append_args)
+            if X_new.shape[0] == 1:
+                ok = h.append(*append_args) if self._builtin else h.append_K(*append_args)
+            else:
+                ok = h.append_block(*append_args) if self._builtin else h.append_block_K(*append_args)
             rows = np.array([[float(p.sn2_mult), float(p.L_chol)] for p in local_posts])
             bad = np.zeros(len(local_posts), bool)
             redo = np.flatnonzero(~ok)

@@ -210,6 +210,46 @@ int gpc_post_append_K(gpc_post* post, const double* Ks, const double* kss, const
 int gpc_post_recompute_K(gpc_post* post, int cnt, const int* idx, const double* K, const double* m,
                          const double* sn2, int sn2_is_vector, double* sn2_mult, int* L_chol, int* info);
 
+/* ---- block append of k >= 1 training points to resident posteriors in O(N^2 k) (GP.update(block_append=True);
+ *      scalar noise).  The reference has no such path (it recomputes); the algebra is the rank-one path's with a
+ *      k x k block where that has a scalar.
+ * Call gpc_set_data with the extended X (N+k rows; the new points last, in order) and y first.
+ *   m_star[s*k + j]  mean function of sample s at new point j
+ *   sn2_star[s]      noise variance of sample s at the new points (scalar noise: one value)
+ *   y_new[j]         the new observations
+ * With n old points, B = K(X_old, X_new) (n x k), Knn = K(X_new, X_new), e = y_new - m_star - B^T alpha, sl the
+ * fitted noise of the sample (sn2_eff = sn2_star * sn2_mult must equal it to 1e-12 relative):
+ *   high-noise samples (L_chol; A = Lo, W = Lo^-1):  V = W B,  S = Knn / sl + I - V^T V / sl^2,  L22 = chol(S),
+ *     W22 = L22^-1;  new rows Lo[n:, :n] = V^T / sl, Lo[n:, n:] = L22,  W[n:, :n] = -W22 (V^T W) / sl, W[n:, n:] = W22;
+ *     alpha = [alpha - W21^T u2 ... ] with u2 = W22 e:  alpha[:n] += W21^T u2 / sl,  alpha[n:] = W22^T u2 / sl.
+ *   low-noise samples (Posterior.L = -(K + Sigma)^-1, full symmetric):  G = inv B,  S = Knn + sn2_eff I - B^T G,
+ *     Si = S^-1 through its Cholesky factor;  inv <- [[inv + G Si G^T, -G Si], [-(G Si)^T, Si]];  a2 = Si e,
+ *     alpha = [alpha - G a2 ; a2].
+ * The two products with W (and the one with the low-noise inverse) have two engines: for k <= 16 a skinny kernel
+ * that streams the N x N matrix once per product with the 16 right-hand sides in LDS, for larger k launches of the
+ * MFMA GEMM on panels padded to 128 columns (block_append.h: BA_GEMM_MIN_K, with the measurement; the test option
+ * "block_engine" = 1 / 2 forces one of them; the get-only option "block_engine_ran" tells which one the last call ran).  The bits of a sample depend on the engine, not on the batch.
+ * S is factorized by the library's blocked factorization WITHOUT jitter, for all samples at once, and every sample
+ * is decided on the device: ok comes back in one download.  The storage of EVERY sample grows to N+k (by as many
+ * 128-tiles as that needs).  ok[s] = 1 if sample s was appended; ok[s] = 0 (S not positive definite, a sample whose
+ * own factorization had failed, a noise value that is not the fitted scalar, or a sample named by the test option
+ * "append_fail_mask") leaves sample s exactly as it was apart from the growth: the caller recomputes exactly those
+ * samples with gpc_post_recompute.  Scratch (four fp64 N_pad x k panels per sample, three more in the storage type
+ * for the MFMA engine) lives in the context's cross-covariance buffer, is budgeted like gpc_predict_cov's
+ * (GPC_MEM_BUDGET_MB) and chunked over the samples.  gpc_last_timing: the device section after the growth, and
+ * the products with W.
+ * Returns -2 with a message for k < 1, N + k > gpc_max_n, data that was not extended first, a posterior of the
+ * other origin (device kernel / caller-provided K), null arguments, or one sample's scratch exceeding the budget.
+ * The get-only options "block_appended" / "block_stale" count the samples that ended either way (ok = 1 / ok = 0)
+ * over the life of the context.                                                                          */
+int gpc_post_append_block(gpc_post* post, int k, const double* m_star, const double* sn2_star,
+                          const double* y_new, int* ok);
+/* The same for a posterior set built from caller-provided covariances (gpc_posterior_batch_K):
+ * Ks: S x n x k (Ks[s] = k_s(X_old, X_new)), Kss: S x k x k (k_s(X_new, X_new)); the stale samples are
+ * recomputed with gpc_post_recompute_K.                                                                  */
+int gpc_post_append_block_K(gpc_post* post, int k, const double* Ks, const double* Kss, const double* m_star,
+                            const double* sn2_star, const double* y_new, int* ok);
+
 /* ---- GP.predict_full (gaussian_process.py:1603-1650) -------------------------------------
  * fmu[j*S + s] = Ks^T alpha;  cov[s] (M x M, row-major) = K** - V^T V  or  K** + Ks^T (L Ks)
  * (the caller symmetrises and adds noise, :1647-1659).                                    */
