@@ -78,6 +78,8 @@ SIGNATURES = {
     "gpc_draw": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_ulonglong, C.c_int, _dp, _dp, _dp]),
     "gpc_quad": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpc_quad_grad": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "gpc_quad_cov": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, _dp]),
+    "gpc_quad_mix": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int] + [_dp] * 10),
     "gpc_last_timing": (C.c_int, [_vp, _dp, _dp]),
     "gpc_last_lauum_timing": (C.c_int, [_vp, _dp, _dp]),
     "gpc_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
@@ -641,6 +643,42 @@ class PostHandle:
                                          _ptr(zkz), _ptr(dza[0]), _ptr(dza[1]), _ptr(dzkz[0]), _ptr(dzkz[1]))
         self.ctx._check(rc, "gpc_quad_grad")
         return za, zkz, dza[0], dza[1], dzkz[0], dzkz[1]
+
+    @_serial
+    def quad_cov(self, mu, sigma):
+        """gpc_quad_cov: za (M, S) as quad, and cov (S, M, M) = Gamma_s - Z^T (K + Sigma)^-1 Z, neither symmetrised nor
+        clamped."""
+        mu, sigma = _f64(mu), _f64(sigma)
+        if mu.ndim != 2 or sigma.shape != mu.shape:
+            raise ValueError(f"quad_cov: mu and sigma must both be (M, D), got {mu.shape} and {sigma.shape}")
+        M = mu.shape[0]
+        za = np.empty((M, self.S))
+        cov = np.empty((self.S, M, M))
+        rc = self.ctx._lib.gpc_quad_cov(self._h, _ptr(mu), _ptr(sigma), M, _ptr(za), _ptr(cov))
+        self.ctx._check(rc, "gpc_quad_cov")
+        return za, cov
+
+    @_serial
+    def quad_mix(self, mu, sigma, w, compute_var, compute_grad):
+        """gpc_quad_mix, the device's share of GP.quad_mixture as a dict: za (M, S); with compute_var zbkzb (S,), gw and
+        zq (M, S); with compute_grad dza_dmu, dza_dsigma (M, D, S); with both dzq_dmu, dzq_dsigma, dgw_dmu, dgw_dsigma
+        (M, D, S).  What a flag does not ask for is None."""
+        mu, sigma, w = _f64(mu), _f64(sigma), _f64(w)
+        if mu.ndim != 2 or sigma.shape != mu.shape or w.shape != (mu.shape[0],):
+            raise ValueError(f"quad_mix: mu and sigma must both be (M, D) and w (M,), got {mu.shape}, {sigma.shape} "
+                             f"and {w.shape}")
+        M, D = mu.shape
+        S = self.S
+        row = lambda on: np.empty((M, S)) if on else None
+        plane = lambda on: np.empty((M, D, S)) if on else None
+        both = compute_var and compute_grad
+        r = dict(za=row(True), zbkzb=np.empty(S) if compute_var else None, gw=row(compute_var), zq=row(compute_var),
+                 dza_dmu=plane(compute_grad), dza_dsigma=plane(compute_grad), dzq_dmu=plane(both),
+                 dzq_dsigma=plane(both), dgw_dmu=plane(both), dgw_dsigma=plane(both))
+        rc = self.ctx._lib.gpc_quad_mix(self._h, _ptr(mu), _ptr(sigma), _ptr(w), M, 1 if compute_var else 0,
+                                        1 if compute_grad else 0, *[_ptr(v) for v in r.values()])
+        self.ctx._check(rc, "gpc_quad_mix")
+        return r
 
     @_serial
     def free(self):

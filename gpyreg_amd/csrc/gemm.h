@@ -668,6 +668,7 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_persist_kernel(GemmArgs 
 }
 
 inline int g_persist_spare = 0;     // tunable: GPC_PERSIST_SPARE (block slots a persistent launch leaves free)
+inline long long g_gemm_launches = 0;  // MFMA GEMM launches of this process (gpc_quad_mix checks that it adds none)
 inline int g_block_slots = 512;     // two 128-tile blocks per CU (set from the device's CU count)
 template <typename T, int BT, int NW>
 inline hipError_t launch_gemm_bt(hipStream_t st, GemmArgs g, bool akm, bool bkm, int batch, int* ctr = nullptr,
@@ -678,6 +679,7 @@ inline hipError_t launch_gemm_bt(hipStream_t st, GemmArgs g, bool akm, bool bkm,
   g.flags = g_gemm_flags;
   const int ntiles = g.lower_only ? tm * (tm + 1) / 2 : tm * tn;
   if (ntiles <= 0 || batch <= 0) return hipSuccess;
+  ++g_gemm_launches;
   g.ntiles = ntiles;
   g.batch = batch;
   g.ctr = ctr;
@@ -722,6 +724,7 @@ inline hipError_t launch_gemm_rect(hipStream_t st, GemmArgs g, bool akm, bool bk
   g.flags = g_gemm_flags;
   const int ntiles = g.lower_only ? g.tiles_m * (g.tiles_m + 1) : g.tiles_m * g.tiles_n;
   if (ntiles <= 0 || batch <= 0) return hipSuccess;
+  ++g_gemm_launches;
   g.ntiles = ntiles;
   g.batch = batch;
   g.ctr = nullptr;
@@ -747,6 +750,7 @@ inline hipError_t launch_gemm_w8(hipStream_t st, GemmArgs g, bool akm, bool bkm,
   g.flags = g_gemm_flags;
   const int ntiles = g.lower_only ? g.tiles_m * (g.tiles_m + 1) / 2 : g.tiles_m * g.tiles_n;
   if (ntiles <= 0 || batch <= 0) return hipSuccess;
+  ++g_gemm_launches;
   g.ntiles = ntiles;
   g.batch = batch;
   g.ctr = nullptr;
@@ -818,6 +822,7 @@ inline hipError_t launch_gemm_dual_small(hipStream_t st, GemmArgs g1, GemmArgs g
     g.rsv = nullptr;
   }
   if (n[0] + n[1] <= 0 || batch <= 0) return hipSuccess;
+  ++g_gemm_launches;
   hipLaunchKernelGGL((gemm_dual_kernel<T, false, false, false, true, BT, 4>), dim3(n[0] + n[1], batch), dim3(256), 0, st,
                      g1, g2, n[0]);
   return hipGetLastError();
@@ -835,6 +840,7 @@ inline hipError_t launch_gemm_colsq(hipStream_t st, GemmArgs g, int batch, int* 
   g.lower_only = 0;
   g.ntiles = g.tiles_m * g.tiles_n;
   if (g.ntiles <= 0 || batch <= 0) return hipSuccess;
+  ++g_gemm_launches;
   g.batch = batch;
   g.ctr = ctr;
   g.rsv = nullptr;
@@ -858,6 +864,7 @@ inline hipError_t launch_gemm_wsq(hipStream_t st, GemmArgs g, int batch) {
   g.lower_only = 0;
   g.ntiles = g.tiles_m * g.tiles_n;
   if (g.ntiles <= 0 || batch <= 0) return hipSuccess;
+  ++g_gemm_launches;
   g.batch = batch;
   g.ctr = nullptr;
   g.rsv = nullptr;

@@ -29,6 +29,7 @@
 #include "lookahead.h"
 #include "plan.h"
 #include "quad.h"
+#include "quad_mix.h"
 #ifdef GPC_EXPERIMENTS
 // Schedules that were built, measured and rejected -- the tile-level dataflow graph, independent
 // per-sample pipelines, rectangular / eight-wave tiles, right-looking panels -- are compiled only into the experiments
@@ -486,6 +487,7 @@ struct gpc_ctx {
   unsigned long long land_seq = 0;
   unsigned long long small_polled = 0, small_synced = 0;  // statistics ("small_polled" / "small_synced")
   unsigned long long cov_fused = 0;  // gpc_predict_cov calls whose reduction ran in the product's epilogue ("cov_fused")
+  unsigned long long quad_mix_gemms = 0;  // MFMA GEMM launches inside gpc_quad_mix ("quad_mix_gemms"; there should be none)
   int check_queues = 0;  // debug option: verify after every pipeline that the tile queues of its persistent launches were drained
   hipEvent_t ev_up = nullptr, ev_done[MAXG] = {};
   int groups = 2;
@@ -510,6 +512,7 @@ struct gpc_ctx {
   DevBuf ks, vb, kss, xss, pout; // predict / predict_full / quad
   DevBuf qb, gpart, gres;        // predict_grad / quad_grad: Q = W^T V, per-tile partials, the gradients
   DevBuf qcon;                   // quad_grad: the measures' constants (quad.h: quad_grad_prep_kernel)
+  DevBuf qmix;                   // quad_mix: the whole scratch of a chunk, carved up in quad_mix_impl
   DevBuf zb, fb, dout, daux;     // draw: Z, F = L Z, the draws, [logdet | info | noise sd] (the factor: mA mW mT)
   DevBuf dbg1, dbg2, dbg3;       // debug hooks / fetch staging
   PinBuf pin;                    // pinned staging for host<->device transfers (see PinBuf)
@@ -2705,6 +2708,9 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
       if (qg)
         hipLaunchKernelGGL(quad_grad_prep_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
                            (const double*)d_xa, (const double*)d_xb, divb, spb, M, mpad, D, d_mut, d_qcon);
+      if (full)  // gpc_quad_cov: Gamma where mode 0 puts K** (quad_mix.h)
+        hipLaunchKernelGGL((quad_gamma_kernel<T>), dim3(mpad / 64, mpad / 4, cnt), dim3(64, 4), 0, st,
+                           (const double*)d_xa, (const double*)d_xb, divb, spb, M, mpad, D, c->kss.as<T>(), sKss);
     }
     double* d_mu = c->pout.as<double>();
     double* d_v = d_mu + (size_t)chunk * mpad;
@@ -3761,6 +3767,218 @@ __global__ void tile_hash_kernel(const T* __restrict__ M, int npad, unsigned lon
 }
 }  // namespace
 
+namespace {
+struct QuadMixOut {
+  double *zalpha, *zbkzb, *gw, *zq;
+  double* plane[6];  // dza_dmu, dza_dsigma, dzq_dmu, dzq_dsigma, dgw_dmu, dgw_dsigma
+};
+
+// gpc_quad_mix (quad_mix.h).  Per chunk of samples, all launches on the library's stream:
+//   1  the measures' constants (quad_grad_prep_kernel, quad_mix_prep_kernel)
+//   2  quad_mix_sum_tile_kernel + two ascending reductions: z . alpha (mpad) and zbar = Z w (npad)
+//   3  (var) the solve, runs of equal L_chol sharing launches: v = W zbar, q = W^T v / sl with v . v riding in the
+//      transposed product (the launches that form alpha), or q = -(L zbar) and zbar . q
+//   4  (var) quad_mix_q_tile_kernel: z_j . q and, with grad, the four contractions; (grad only) quad_grad_tile_kernel's
+//      alpha weights; quad_grad_reduce_kernel
+//   5  (var) quad_mix_gamma_tile_kernel + quad_mix_gamma_reduce_kernel
+// and ONE download of [za | zq | gw | scal | the planes].  No MFMA GEMM launch.
+template <typename T>
+int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const double* w, int M, bool var, bool grad,
+                  const QuadMixOut& o) {
+  gpc_ctx* c = po->ctx;
+  const int S = po->S, N = po->N, D = po->D, npad = po->npad;
+  const int mpad = pad_tile(M);
+  hipStream_t st = c->st;
+  const long long sM = (long long)npad * npad;
+  const int gnt = npad / CT, mnt = mpad / CT, nch = npad / TRC;
+  const int gpl = grad ? (var ? 4 : 2) : 0;      // planes of quad_grad_reduce_kernel
+  const int gnq = var ? (grad ? 1 + 2 * D : 1) : 0;  // quantities of the pair kernel
+  const int npl = gpl + (var && grad ? 2 : 0);
+  const size_t ss = (size_t)mpad * D;
+  // doubles per sample
+  const size_t n_con = (size_t)(D + 1) * mpad, n_cpart = (size_t)gnt * mpad, n_rpart = (size_t)mnt * npad;
+  const size_t n_vec = var ? 2 * (size_t)npad : 0, n_tpart = var ? (size_t)nch * npad : 0;
+  const size_t n_zqpart = var ? (size_t)gnt * mpad : 0, n_gpart = (size_t)gnt * gpl * D * mpad;
+  const size_t n_gmpart = (size_t)mnt * gnq * mpad;
+  const size_t n_res = 3 * (size_t)mpad + 2 + (size_t)npl * ss;
+  const size_t per = (n_con + n_cpart + n_rpart + (size_t)npad + n_vec + n_tpart + n_zqpart + n_gpart + n_gmpart + n_res) * 8;
+  const size_t shared = (2 * ss + (size_t)mpad + 2 * (size_t)M * D + M) * 8;
+  int chunk = S;
+  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per + shared > c->qmix.bytes) {
+    c->pool_drain();
+    const size_t budget = (size_t)((free_device_bytes() + (getenv("GPC_MEM_BUDGET_MB") ? 0 : c->qmix.bytes)) * 0.8);
+    if (budget < per + shared)
+      FAIL(c, "gpc_quad_mix: the scratch of one sample (" + std::to_string((per + shared) >> 10) + " KB: N_pad = " +
+              std::to_string(npad) + ", M_pad = " + std::to_string(mpad) + ", D = " + std::to_string(D) +
+              ") exceeds the device memory budget (" + std::to_string(budget >> 10) + " KB)");
+    chunk = (int)std::min<size_t>(S, (budget - shared) / per);
+  }
+  HIPCHK(c, c->qmix.ensure((size_t)chunk * per + shared));
+  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
+  HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
+  double* p = c->qmix.as<double>();
+  auto take = [&](size_t n) {
+    double* r = p;
+    p += n;
+    return r;
+  };
+  double* d_mut = take(ss);
+  double* d_sgt = take(ss);
+  double* d_wpad = take(mpad);
+  double* d_mu = take((size_t)M * D);
+  double* d_sg = take((size_t)M * D);
+  double* d_w = take(M);
+  double* d_con = take(chunk * n_con);
+  double* d_cpart = take(chunk * n_cpart);
+  double* d_rpart = take(chunk * n_rpart);
+  double* d_zbar = take((size_t)chunk * npad);
+  double* d_v = take(var ? (size_t)chunk * npad : 0);
+  double* d_q = take(var ? (size_t)chunk * npad : 0);
+  double* d_tpart = take(chunk * n_tpart);
+  double* d_zqpart = take(chunk * n_zqpart);
+  double* d_gpart = take(chunk * n_gpart);
+  double* d_gmpart = take(chunk * n_gmpart);
+  // the results, one block: [za | zq | gw | scal (2 per sample) | planes of the tile pass | planes of the pair pass]
+  double* d_res = take(chunk * n_res);
+  double* d_za = d_res;
+  double* d_zq = d_za + (size_t)chunk * mpad;
+  double* d_gw = d_zq + (size_t)chunk * mpad;
+  double* d_scal = d_gw + (size_t)chunk * mpad;
+  double* d_gres = d_scal + 2 * (size_t)chunk;
+  double* d_gmres = d_gres + (size_t)gpl * chunk * ss;
+  std::unique_ptr<double[]> hres(new double[chunk * n_res]);  // (uninitialised: every entry read is downloaded first)
+  const double* spb = c->spb.as<double>();
+  const double* divb = c->divb.as<double>();
+  const double* X = c->dX.as<double>();
+  HIPCHK(c, hipMemcpyAsync(d_mu, mu, (size_t)M * D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_sg, sigma, (size_t)M * D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_w, w, (size_t)M * 8, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(quad_mix_prep_kernel, dim3((mpad + 255) / 256), dim3(256), 0, st, (const double*)d_sg,
+                     (const double*)d_w, M, mpad, D, d_sgt, d_wpad);
+  const bool timing_on = c->small_timing != 0 || npad >= 2048;
+  // gpc_last_timing: device time of the call and, as ms_factor, of the solve (step 3), summed over the chunks
+  c->ms_total = c->ms_factor = 0;
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[0], st));
+    HIPCHK(c, hipMemcpyAsync(c->spb.p, &po->sp[(size_t)s0 * SP_STRIDE], (size_t)cnt * SP_STRIDE * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->divb.p, &po->dv[(size_t)s0 * D], (size_t)cnt * D * 8, hipMemcpyHostToDevice, st));
+    const double* alpha = po->alpha.as<double>() + (size_t)s0 * npad;
+    hipLaunchKernelGGL(quad_grad_prep_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st, (const double*)d_mu,
+                       (const double*)d_sg, divb, spb, M, mpad, D, d_mut, d_con);
+    hipLaunchKernelGGL(quad_mix_sum_tile_kernel, dim3(mnt, gnt, cnt), dim3(256), 0, st, X, D, (const double*)d_mut,
+                       (const double*)d_con, alpha, npad, (const double*)d_wpad, N, M, mpad, npad, d_cpart, d_rpart);
+    hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st, (const double*)d_cpart,
+                       gnt, mpad, d_za);
+    hipLaunchKernelGGL(colpart_reduce_kernel, dim3((npad + 255) / 256, cnt), dim3(256), 0, st, (const double*)d_rpart,
+                       mnt, npad, d_zbar);
+    HIPCHK(c, hipGetLastError());
+    if (timing_on) {
+      HIPCHK(c, hipEventRecord(c->ev[1], st));
+      if (!var) HIPCHK(c, hipEventRecord(c->ev[2], st));
+    }
+    if (var) {
+      for (int a = 0; a < cnt;) {  // runs of equal L_chol share launches
+        int e = a;
+        while (e < cnt && po->lchol[s0 + e] == po->lchol[s0 + a]) ++e;
+        const int len = e - a;
+        const double* zb = d_zbar + (size_t)a * npad;
+        if (po->lchol[s0 + a]) {
+          const T* W = po->W.as<T>() + (size_t)(s0 + a) * sM;
+          double* tp = d_tpart + (size_t)a * nch * npad;
+          hipLaunchKernelGGL((trmv_kernel<T>), dim3(npad / 4, len), dim3(256), 0, st, W, sM, npad, zb, npad,
+                             d_v + (size_t)a * npad, 0);
+          hipLaunchKernelGGL((trmv_t_part_kernel<T, 8>), dim3((npad + 64 * MM<T>::VEC - 1) / (64 * MM<T>::VEC), nch, len),
+                             dim3(256), 0, st, W, sM, npad, (const double*)(d_v + (size_t)a * npad), npad, tp, d_scal + a);
+          hipLaunchKernelGGL(trmv_t_sum_kernel, dim3(npad / 128, len), dim3(128), 0, st, (const double*)tp, npad,
+                             spb + (size_t)a * SP_STRIDE, (int)SP_STRIDE, (int)SP_SL, d_q + (size_t)a * npad);
+        } else {  // q = 0 - L zbar (L = -(K + Sigma)^-1, full symmetric)
+          HIPCHK(c, hipMemsetAsync(d_q + (size_t)a * npad, 0, (size_t)len * npad * 8, st));
+          hipLaunchKernelGGL((gemv_sub_kernel<T>), dim3(npad / 4, len), dim3(256), 0, st,
+                             (const T*)(po->A.as<T>() + (size_t)(s0 + a) * sM), sM, npad, zb, d_q + (size_t)a * npad, npad,
+                             0, 0, npad);
+          hipLaunchKernelGGL(dot_kernel, dim3(1, len), dim3(256), 0, st, zb, (const double*)(d_q + (size_t)a * npad), N,
+                             npad, d_scal + a);
+        }
+        a = e;
+      }
+      HIPCHK(c, hipGetLastError());
+      if (timing_on) HIPCHK(c, hipEventRecord(c->ev[2], st));
+      if (grad)
+        hipLaunchKernelGGL((quad_mix_q_tile_kernel<true>), dim3(mnt, gnt, cnt), dim3(256), 0, st, X, D,
+                           (const double*)d_mut, (const double*)d_con, alpha, npad, (const double*)d_q, N, M, mpad, npad,
+                           d_zqpart, d_gpart);
+      else
+        hipLaunchKernelGGL((quad_mix_q_tile_kernel<false>), dim3(mnt, gnt, cnt), dim3(256), 0, st, X, D,
+                           (const double*)d_mut, (const double*)d_con, alpha, npad, (const double*)d_q, N, M, mpad, npad,
+                           d_zqpart, (double*)nullptr);
+      hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
+                         (const double*)d_zqpart, gnt, mpad, d_zq);
+      if (grad)
+        hipLaunchKernelGGL((quad_mix_gamma_tile_kernel<true>), dim3(mnt, mnt, cnt), dim3(256), 0, st,
+                           (const double*)d_mut, (const double*)d_sgt, (const double*)d_wpad, divb, spb, D, M, mpad,
+                           d_gmpart);
+      else
+        hipLaunchKernelGGL((quad_mix_gamma_tile_kernel<false>), dim3(mnt, mnt, cnt), dim3(256), 0, st,
+                           (const double*)d_mut, (const double*)d_sgt, (const double*)d_wpad, divb, spb, D, M, mpad,
+                           d_gmpart);
+      hipLaunchKernelGGL(quad_mix_gamma_reduce_kernel, dim3((mpad + 255) / 256, gnq, cnt), dim3(256), 0, st,
+                         (const double*)d_gmpart, mnt, D, gnq, mpad, d_gw, d_gmres, (size_t)chunk * ss);
+    } else if (grad) {  // the alpha weights only: quad_grad's own pass
+      hipLaunchKernelGGL((quad_grad_tile_kernel<T, false>), dim3(mnt, gnt, cnt), dim3(256), 0, st, X, D,
+                         (const double*)d_mut, (const double*)d_con, alpha, npad, (const T*)nullptr, 0LL, spb, 0, N, M,
+                         mpad, d_gpart);
+    }
+    if (grad)
+      hipLaunchKernelGGL(quad_grad_reduce_kernel, dim3((mpad + 255) / 256, gpl * D, cnt), dim3(256), 0, st,
+                         (const double*)d_gpart, gnt, D, gpl, M, mpad, (const double*)d_sg, (const double*)d_con, d_gres,
+                         (size_t)chunk * ss);
+    HIPCHK(c, hipGetLastError());
+    // (without var the blocks zq, gw and scal come back unwritten and unread)
+    HIPCHK(c, hipMemcpyAsync(hres.get(), d_res, chunk * n_res * 8, hipMemcpyDeviceToHost, st));
+    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[3], st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (timing_on) {
+      float t03 = 0, t12 = 0;
+      (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
+      (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
+      c->ms_total += t03;
+      c->ms_factor += t12;
+    }
+    const double* hza = hres.get();
+    const double* hzq = hza + (size_t)chunk * mpad;
+    const double* hgw = hzq + (size_t)chunk * mpad;
+    const double* hsc = hgw + (size_t)chunk * mpad;
+    const double* hpl = hsc + 2 * (size_t)chunk;
+    for (int i = 0; i < cnt; ++i) {
+      const int s = s0 + i;
+      for (int j = 0; j < M; ++j) {
+        o.zalpha[(size_t)j * S + s] = hza[(size_t)i * mpad + j];
+        if (var) {
+          o.zq[(size_t)j * S + s] = hzq[(size_t)i * mpad + j];
+          o.gw[(size_t)j * S + s] = hgw[(size_t)i * mpad + j];
+        }
+      }
+      // zbar (K + Sigma)^-1 zbar: |W zbar|^2 / sl (L_chol) or zbar . q = -(zbar . L zbar)
+      if (var) o.zbkzb[s] = po->lchol[s] ? hsc[i] / po->sp[(size_t)s * SP_STRIDE + SP_SL] : hsc[i];
+    }
+    for (int pl = 0; pl < npl; ++pl) {  // [(j*D + l)*S + s]
+      // tile pass: dza_dmu, dza_dsigma (, dzq_dmu, dzq_dsigma: the reduce kernel doubled them for quad_grad -- halved
+      // here, exactly); pair pass: dgw_dmu, dgw_dsigma
+      double* out = o.plane[pl < gpl ? pl : 4 + (pl - gpl)];
+      const double f = (pl >= 2 && pl < gpl) ? 0.5 : 1.0;
+      const double* gp = hpl + (size_t)pl * chunk * ss;
+      for (size_t jl = 0; jl < (size_t)M * D; ++jl) {
+        double* dst = out + jl * S + s0;
+        for (int i = 0; i < cnt; ++i) dst[i] = f * gp[i * ss + jl];
+      }
+    }
+  }
+  return 0;
+}
+}  // namespace
+
+
 extern "C" {
 
 int gpc_create(int device, gpc_ctx** out) {
@@ -3871,7 +4089,7 @@ void gpc_destroy(gpc_ctx* c) {
   DevBuf* bufs[] = {&c->dX,   &c->dY,  &c->mA,    &c->mW,  &c->mT,   &c->xs,   &c->spb,  &c->mulb, &c->divb,
                     &c->dvec, &c->rvec,  &c->zvec, &c->avec, &c->scal, &c->parts, &c->gout, &c->diagq,
                     &c->dmb,  &c->dsn2b, &c->mg,  &c->ng,   &c->ks,   &c->vb,   &c->xss,  &c->pout, &c->kss,
-                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
+                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->qmix, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
   for (auto& g : c->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (DevBuf* b : bufs) b->release();
@@ -4441,6 +4659,45 @@ int gpc_quad_grad(gpc_post* po, const double* mu, const double* sigma, int M, in
   return 0;
 }
 
+int gpc_quad_cov(gpc_post* po, const double* mu, const double* sigma, int M, double* zalpha, double* cov) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!mu || !sigma || !zalpha || !cov || M <= 0) FAIL(c, "gpc_quad_cov: bad arguments");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_quad_cov: this posterior was built from caller-provided K; it has no kernel to integrate");
+  if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
+    FAIL(c, "Bayesian quadrature only supports the squared exponential kernel.");
+  for (int s = 0; s < po->S; ++s)
+    if (po->info[s] != 0) FAIL(c, "gpc_quad_cov: posterior contains a failed factorization");
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? rhs_products<double>(po, 1, mu, sigma, M, false, zalpha, nullptr, cov)
+                              : rhs_products<float>(po, 1, mu, sigma, M, false, zalpha, nullptr, cov);
+}
+
+int gpc_quad_mix(gpc_post* po, const double* mu, const double* sigma, const double* w, int M, int compute_var,
+                 int compute_grad, double* zalpha, double* zbkzb, double* gw, double* zq, double* dza_dmu,
+                 double* dza_dsigma, double* dzq_dmu, double* dzq_dsigma, double* dgw_dmu, double* dgw_dsigma) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  const bool var = compute_var != 0, grad = compute_grad != 0;
+  if (!mu || !sigma || !w || !zalpha || M <= 0 || (var && (!zbkzb || !gw || !zq)) || (grad && (!dza_dmu || !dza_dsigma)) ||
+      (var && grad && (!dzq_dmu || !dzq_dsigma || !dgw_dmu || !dgw_dsigma)))
+    FAIL(c, "gpc_quad_mix: bad arguments");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_quad_mix: this posterior was built from caller-provided K; it has no kernel to integrate");
+  if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
+    FAIL(c, "Bayesian quadrature only supports the squared exponential kernel.");
+  for (int s = 0; s < po->S; ++s)
+    if (po->info[s] != 0) FAIL(c, "gpc_quad_mix: posterior contains a failed factorization");
+  HIPCHK(c, hipSetDevice(c->device));
+  const QuadMixOut o{zalpha, zbkzb, gw, zq, {dza_dmu, dza_dsigma, dzq_dmu, dzq_dsigma, dgw_dmu, dgw_dsigma}};
+  const long long gemms0 = gpc::g_gemm_launches;
+  const int rc = po->dtype == GPC_F64 ? quad_mix_impl<double>(po, mu, sigma, w, M, var, grad, o)
+                                      : quad_mix_impl<float>(po, mu, sigma, w, M, var, grad, o);
+  c->quad_mix_gemms += (unsigned long long)(gpc::g_gemm_launches - gemms0);
+  return rc;
+}
+
 int gpc_last_timing(gpc_ctx* c, double* ms_total, double* ms_factor) {
   if (!c) return -2;
   if (ms_total) *ms_total = c->ms_total;
@@ -4554,6 +4811,7 @@ int gpc_get_option(gpc_ctx* c, const char* name, int* value) {
   else if (n == "small_polled") *value = (int)(c->small_polled & 0x7fffffff);  // one-leaf calls completed by the polled word ...
   else if (n == "small_synced") *value = (int)(c->small_synced & 0x7fffffff);  // ... and by a stream synchronisation
   else if (n == "cov_fused") *value = (int)(c->cov_fused & 0x7fffffff);  // gpc_predict_cov calls reduced in the product's epilogue
+  else if (n == "quad_mix_gemms") *value = (int)(c->quad_mix_gemms & 0x7fffffff);  // MFMA GEMM launches inside gpc_quad_mix
   else if (n == "block_engine") *value = c->block_engine;
   else if (n == "block_engine_ran") *value = c->block_engine_ran;  // 1 / 2: what the last block append ran (0: none yet)
   else if (n == "block_appended") *value = (int)(c->block_appended & 0x7fffffff);  // samples gpc_post_append_block appended ...

@@ -152,6 +152,14 @@ def _quad_measures(mu, sigma, D):
     return mu, sigma
 
 
+def _quad_gamma(mu, sigma, ell, ln_sf2):
+    """Gamma (M, M), the prior covariance between the integrals against the measures: sf2 prod_l ell_l / sqrt(t_jkl)
+    exp(-1/2 sum_l (mu_jl - mu_kl)^2 / t_jkl), t_jkl = ell_l^2 + sigma_jl^2 + sigma_kl^2 (its diagonal: quad's nf_kk)."""
+    t = ell**2 + sigma[:, None, :]**2 + sigma[None, :, :]**2
+    d = mu[:, None, :] - mu[None, :, :]
+    return np.exp(ln_sf2 + np.sum(np.log(ell)) - 0.5 * np.sum(np.log(t), 2) - 0.5 * np.sum(d**2 / t, 2))
+
+
 def _mean_grad_x(mean, hyp, X):
     """d m(x) / dx (M, D) of a stock mean function under the mean hyperparameters ``hyp``; exact types only (a
     subclass may compute anything): other mean objects raise NotImplementedError."""
@@ -1854,6 +1862,180 @@ class GP:
         if compute_var:
             return F, F_var, dF_mu, dF_sg, dV_mu, dV_sg
         return F, dF_mu, dF_sg
+
+    def _quad_mixture_prepare(self, name, mu, sigma):
+        """What ``quad_cov`` and ``quad_mixture`` check before any device work, as ``quad_grad`` does: (mu, sigma, D, N_s,
+        cov_N, noise_N, iso)."""
+        from .covariance_functions import SquaredExponential
+
+        if not isinstance(self.covariance, SquaredExponential):
+            raise ValueError("Bayesian quadrature only supports the squared exponential kernel.")
+        D = self.X.shape[1]
+        cov_N, noise_N, _ = self._counts()
+        mu, sigma = _quad_measures(mu, sigma, D)
+        if mu.shape[1] != D:
+            raise ValueError(f"{name}: the measures have {mu.shape[1]} dimensions, the GP {D}")
+        self._restore()
+        if self._post_handle is None and self._post_range is None:
+            raise ValueError("posteriors have been cleaned; call update() first")
+        iso = cov_N == 2 and D != 1
+        if self.reference_quirks:
+            for p in self.posteriors:  # (as quad: an IndexError without a noise hyperparameter)
+                np.exp(2 * p.hyp[cov_N])
+            if iso:
+                raise NotImplementedError(f"{name}: under reference_quirks, quad builds an isotropic kernel's z on the "
+                                          "host from a misread of its hyperparameters (D > 1); it has no device form")
+        return mu, sigma, D, np.size(self.posteriors), cov_N, noise_N, iso
+
+    def _quad_solve_scales(self, cov_N):
+        """``quad``'s ``reference_quirks`` rescaling of the solve term, per local sample (1 where it does not apply): the
+        factor was scaled by sl = min(sn2) sn2_mult, the reference divides by exp(2 hyp[cov_N]) sn2_mult."""
+        local, _ = self._local_posteriors()
+        scale = np.ones(len(local))
+        if self.reference_quirks:
+            for k, p in enumerate(local):
+                if p.L_chol:
+                    sl = 1.0 / float(np.ravel(p.sW)[0]) ** 2
+                    scale[k] = sl / (np.exp(2 * p.hyp[cov_N]) * p.sn2_mult)
+        return scale
+
+    def _quad_mean_terms(self, s, mu, sigma, cov_N, noise_N):
+        """The mean function's part of sample s's integrals, as ``quad`` and ``quad_grad`` form it: (nu (M,), dnu_dmu,
+        dnu_dsigma (M, D))."""
+        from .mean_functions import NegativeQuadratic, ZeroMean
+
+        hyp = self.posteriors[s].hyp
+        D = mu.shape[1]
+        nu = np.full(mu.shape[0], 0.0 if isinstance(self.mean, ZeroMean) else hyp[cov_N + noise_N])
+        if not isinstance(self.mean, NegativeQuadratic):
+            return nu, np.zeros(mu.shape), np.zeros(mu.shape)
+        xm = hyp[cov_N + noise_N + 1:cov_N + noise_N + D + 1]
+        omega = np.exp(hyp[cov_N + noise_N + D + 1:])
+        nu = nu - 0.5 * np.sum(1 / omega**2 * (mu**2 + sigma**2 - 2 * mu * xm + xm**2), 1)
+        return nu, -(mu - xm) / omega**2, -sigma / omega**2
+
+    @_on_device
+    def quad_cov(self, mu, sigma, separate_samples: bool = False):
+        """The integrals of the GP against the Gaussian measures N(mu_j, diag(sigma_j^2)) and the covariance between
+        them: (F, C) with F (M, S) and C (M, M, S) under ``separate_samples``, else F (M, 1) and C (M, M).
+        C_s = Gamma_s - Z^T (K + Sigma)^-1 Z is formed on the device (gpc_quad_cov), symmetrised here and NOT clamped:
+        its diagonal is ``quad``'s variance before the clamp.  The mixture over samples is the law of total covariance,
+        the mean of the C_s plus the covariance of the F_s (with ``_mix_samples``' 1 / (S - 1)).  Refuses what
+        ``quad_grad`` refuses."""
+        mu, sigma, D, N_s, cov_N, noise_N, iso = self._quad_mixture_prepare("quad_cov", mu, sigma)
+        M = mu.shape[0]
+        self._ctx()
+        if self._post_handle is None:  # a rank without local samples
+            za, C = np.zeros((M, 0)), np.zeros((0, M, M))
+        else:
+            za, C = self._post_handle.quad_cov(mu, sigma)
+            for k, sc in enumerate(self._quad_solve_scales(cov_N)):
+                if sc != 1.0:  # quirks: Gamma - sc (Gamma - C)
+                    hyp = self._local_posteriors()[0][k].hyp
+                    G = _quad_gamma(mu, sigma, np.exp(hyp[0:D]), 2 * hyp[D])
+                    C[k] = G - sc * (G - C[k])
+        rows = np.concatenate([za, C.reshape(C.shape[0], M * M).T], axis=0)
+        if self._post_range is not None:  # one all-gather of the stacked rows
+            rows = self._gather_samples(rows, mu, sigma)
+        za, C = rows[:M], rows[M:].reshape(M, M, N_s)
+        C = 0.5 * (C + C.transpose(1, 0, 2))
+        F = np.stack([za[:, s] + self._quad_mean_terms(s, mu, sigma, cov_N, noise_N)[0] for s in range(N_s)], 1)
+        if separate_samples:
+            return F, C
+        if N_s > 1:
+            dev = F - np.sum(F, 1, keepdims=True) / N_s
+            C = np.sum(C, 2) / N_s + dev @ dev.T / (N_s - 1)
+            F, _, _ = _mix_samples(F, None)
+        else:
+            C = C[:, :, 0]
+        return F, C
+
+    @_on_device
+    def quad_mixture(self, mu, sigma, weights, compute_var: bool = False, compute_grad: bool = False,
+                     separate_samples: bool = False):
+        """Bayesian quadrature against the MIXTURE sum_j w_j N(mu_j, diag(sigma_j^2)): the mean E = sum_j w_j F_j of the
+        integral and, with ``compute_var``, its variance V = w^T C w (C as ``quad_cov``), without forming C: the cross
+        term collapses to zbar^T (K + Sigma)^-1 zbar with zbar = Z w, one solve per sample (gpc_quad_mix).  The weights
+        are any finite reals and are not normalised.  Returns E, then V (``compute_var``), then with ``compute_grad``
+        dE_dmu, dE_dsigma (M, D), dE_dw (M,) and, with ``compute_var``, dV_dmu, dV_dsigma, dV_dw of the same shapes.
+        E and V are scalars, or (S,) with ``separate_samples``, which also appends a sample axis to every gradient.
+        The mean function's terms, the clamp V = max(eps, .) (zero variance gradient where it holds), the mixture over
+        samples and the ``reference_quirks`` rescaling are the host's, exactly as in ``quad`` and ``quad_grad``; refuses
+        what ``quad_grad`` refuses."""
+        from .mean_functions import NegativeQuadratic
+
+        mu, sigma, D, N_s, cov_N, noise_N, iso = self._quad_mixture_prepare("quad_mixture", mu, sigma)
+        M = mu.shape[0]
+        w = np.asarray(weights, dtype=float).reshape(-1)
+        if w.shape != (M,):
+            raise ValueError(f"quad_mixture: {M} measures but {w.size} weights")
+        if not np.all(np.isfinite(w)):
+            raise ValueError("quad_mixture: the weights must be finite")
+        self._ctx()
+        var, grad = bool(compute_var), bool(compute_grad)
+        # the device's rows, one block (R, S_local): za | gw | zq | zbkzb | the planes
+        names = ["za"] + (["gw", "zq", "zbkzb"] if var else [])
+        planes = (["dza_dmu", "dza_dsigma"] if grad else []) + \
+                 (["dzq_dmu", "dzq_dsigma", "dgw_dmu", "dgw_dsigma"] if var and grad else [])
+        height = {n: (1 if n == "zbkzb" else M) for n in names}
+        height.update({n: M * D for n in planes})
+        if self._post_handle is None:  # a rank without local samples
+            d = {n: np.zeros((height[n], 0)) for n in names + planes}
+        else:
+            d = self._post_handle.quad_mix(mu, sigma, w, var, grad)
+            scale = self._quad_solve_scales(cov_N)
+            if var and np.any(scale != 1.0):  # quad's rescaling of the solve term
+                for n in ("zbkzb", "zq", "dzq_dmu", "dzq_dsigma"):
+                    if d[n] is not None:
+                        d[n] = d[n] * scale
+        if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
+            rows = np.concatenate([np.reshape(d[n], (height[n], -1)) for n in names + planes], axis=0)
+            rows = self._gather_samples(rows, mu, sigma, w)
+            at = 0
+            for n in names + planes:
+                d[n] = rows[at:at + height[n]]
+                at += height[n]
+        for n in planes:
+            d[n] = np.reshape(d[n], (M, D, N_s))
+        # the host terms, for all samples at once; the two dot products with w run per sample on contiguous rows, so
+        # that their order of summation -- a sample's bits -- does not depend on the batch
+        terms = [self._quad_mean_terms(s, mu, sigma, cov_N, noise_N) for s in range(N_s)]
+        F = np.reshape(d["za"], (M, N_s)) + np.stack([t[0] for t in terms], 1)
+        dot_w = lambda A: np.array([w @ row for row in np.ascontiguousarray(A.T)])
+        E, V = dot_w(F)[None, :], None
+        dE = dV = None
+        if grad:
+            quadratic = isinstance(self.mean, NegativeQuadratic)
+            g_mu = d["dza_dmu"] + np.stack([t[1] for t in terms], 2) if quadratic else d["dza_dmu"]
+            g_sg = d["dza_dsigma"] + np.stack([t[2] for t in terms], 2) if quadratic else d["dza_dsigma"]
+            dE = [(w[:, None, None] * g_mu).reshape(1, M * D, N_s), (w[:, None, None] * g_sg).reshape(1, M * D, N_s),
+                  F[None]]
+            if not var:
+                dV = [np.zeros_like(g) for g in dE]
+        if var:
+            gw, zq = np.reshape(d["gw"], (M, N_s)), np.reshape(d["zq"], (M, N_s))
+            raw = dot_w(gw) - np.reshape(d["zbkzb"], -1)
+            V = np.maximum(np.spacing(1), raw)[None, :]
+            if grad:  # the clamp: no variance gradient where it holds V
+                free = raw > np.spacing(1)
+                w2 = (2 * w)[:, None, None]
+                dV = [np.where(free, w2 * (d["dgw_dmu"] - d["dzq_dmu"]), 0.0).reshape(1, M * D, N_s),
+                      np.where(free, w2 * (d["dgw_dsigma"] - d["dzq_dsigma"]), 0.0).reshape(1, M * D, N_s),
+                      np.where(free, 2 * gw - 2 * zq, 0.0)[None]]
+        if separate_samples:
+            out = [E[0]] + ([V[0]] if var else [])
+            shaped = lambda g: [g[0][0].reshape(M, D, N_s), g[1][0].reshape(M, D, N_s), g[2][0]]
+        else:  # quad's mixture and its gradients (one sample: the sample's own)
+            if grad:
+                mixed = [_mix_sample_grads(E, a, b) for a, b in zip(dE, dV)]
+                dE, dV = [m[0] for m in mixed], [m[1] for m in mixed]
+            if N_s > 1:
+                E, V, _ = _mix_samples(E, V)
+            out = [float(E[0, 0])] + ([float(V[0, 0])] if var else [])
+            shaped = lambda g: [g[0][0].reshape(M, D), g[1][0].reshape(M, D), g[2][0]]
+        if grad:
+            out += shaped(dE) + (shaped(dV) if var else [])
+        return out[0] if len(out) == 1 else tuple(out)
 
     # ------------------------------------------------------------------ misc
     def _convert_shapes(self, X, y, s2):

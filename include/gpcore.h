@@ -301,6 +301,42 @@ int gpc_quad_grad(gpc_post* post, const double* mu, const double* sigma, int M, 
                   double* zalpha, double* zKz, double* dza_dmu, double* dza_dsigma, double* dzkz_dmu,
                   double* dzkz_dsigma);
 
+/* ---- GP.quad_cov: covariance between the integrals against the single measures --------------------
+ * With Z_s the N x M matrix of kernel means of sample s and
+ *   Gamma_jk = sf2 prod_l ell_l / sqrt(t_jkl) exp(-1/2 sum_l (mu_jl - mu_kl)^2 / t_jkl),
+ *   t_jkl = ell_l^2 + sigma_jl^2 + sigma_kl^2                      (Gamma_jj is the self-term of gpc_quad's variance)
+ *   zalpha[j*S + s] = z_j . alpha                                  (as gpc_quad)
+ *   cov[s] (M x M, row-major) = Gamma_s - Z^T (K + Sigma)^-1 Z     under the posterior's own scaling, as gpc_quad
+ *                               scales zKz: Gamma - V^T V / sl (L_chol, V = W Z) or Gamma + Z^T (L Z)
+ * Gamma is formed on the device where gpc_predict_full puts K**; the products, the chunking over samples and the
+ * memory budget are gpc_predict_full's.  No symmetrisation and no clamp: both are the caller's.  Fails with a
+ * message where gpc_quad_grad fails.                                                                   */
+int gpc_quad_cov(gpc_post* post, const double* mu, const double* sigma, int M, double* zalpha, double* cov);
+
+/* ---- GP.quad_mixture: quadrature against the mixture sum_j w_j N(mu_j, diag(sigma_j^2)) -------------
+ * w: M finite reals, not normalised.  With zbar = Z w and q = (K + Sigma)^-1 zbar under the posterior's own
+ * scaling (W^T W zbar / sl for L_chol samples, -(L zbar) otherwise) the library returns the device's share:
+ *   zalpha[j*S + s] = z_j . alpha                                        (always)
+ *   zbkzb[s]        = zbar . q                                           (compute_var)
+ *   gw[j*S + s]     = (Gamma_s w)_j                                      (compute_var)
+ *   zq[j*S + s]     = z_j . q                                            (compute_var)
+ *   dza_dmu, dza_dsigma [(j*D + l)*S + s]   as gpc_quad_grad             (compute_grad)
+ *   dzq_dmu, dzq_dsigma [(j*D + l)*S + s] = sum_i q_i dz_ij / dmu_jl, dsigma_jl           (both flags)
+ *   dgw_dmu, dgw_dsigma [(j*D + l)*S + s] = sum_k w_k d1 Gamma_jk / dmu_jl, dsigma_jl     (both flags; d1: the
+ *                                           derivative in the first slot only)
+ * so that the mixture mean is sum_j w_j (zalpha_j + nu_j), the variance w . gw - zbkzb, dV/dw_j = 2 gw_j - 2 zq_j
+ * and dV/dmu_jl = 2 w_j (dgw_dmu_jl - dzq_dmu_jl); the factors w_j and 2, the mean function's terms, the clamp and the
+ * mixture over samples are the caller's.  Outputs a flag does not ask for may be NULL.  z is recomputed per pair in
+ * fp64 in two passes over 64 x 64 tiles and never stored; the solve is one pair of triangular matrix-vector products
+ * per sample; no MFMA GEMM launch runs (gpc_get_option "quad_mix_gemms" counts any that do).  Every order of
+ * summation is fixed by the shape: a sample's bits do not depend on the batch or on the chunking
+ * (GPC_MEM_BUDGET_MB).  fp32 posteriors form z, zbar, Gamma and every reduction in fp64; only the products with W
+ * (or L) read the storage type.  Returns -2 with a message that names the sizes when one sample's scratch does not
+ * fit the memory budget; fails with a message where gpc_quad_grad fails, and on a posterior from caller-provided K. */
+int gpc_quad_mix(gpc_post* post, const double* mu, const double* sigma, const double* w, int M, int compute_var,
+                 int compute_grad, double* zalpha, double* zbkzb, double* gw, double* zq, double* dza_dmu,
+                 double* dza_dsigma, double* dzq_dmu, double* dzq_dsigma, double* dgw_dmu, double* dgw_dsigma);
+
 /* ---- instrumentation -------------------------------------------------------------
  * GPU time (ms, hipEvent on the library's stream) of the last gpc_nll_batch /
  * gpc_posterior_batch: whole device section, and the part spent in the MFMA GEMM
@@ -310,7 +346,8 @@ int gpc_last_timing(gpc_ctx* ctx, double* ms_total, double* ms_factor);
 /* (after gpc_predict / gpc_predict_full / gpc_quad: ms_total = device time of the call, ms_factor = the
  * duration of its N^2 M product V = W Ks, the GEMM launch of gaussian_process.py:1752-1760; after
  * gpc_quad_grad: that of its products V = W z and Q = W^T V, ~0 without compute_var; after
- * gpc_predict_cov: ms_factor = its triangular products and the cross product, with the reduction)     */
+ * gpc_predict_cov: ms_factor = its triangular products and the cross product, with the reduction;
+ * after gpc_quad_mix: ms_factor = its solve, the triangular matrix-vector products, 0 without compute_var) */
 /* The dominant single kernel of the last gpc_nll_batch with gradient: the W^T W ("lauum")
  * launch of gemm_kernel<T, true, true, ...>.  ms = its duration (hipEvents on the stream it
  * was launched on; the slowest sample group), flops = its algorithmic flops
@@ -330,7 +367,8 @@ int gpc_last_lauum_timing(gpc_ctx* ctx, double* ms, double* flops);
  * for the stream after all); "small_timing" (default 0) = such calls record their timing events, so that gpc_last_timing
  * reports their device section (it reports 0 for them otherwise; from N_pad = 2048 on the events are always recorded).
  * "small_polled" / "small_synced" (get only): how many calls ended either way.
- * "cov_fused" (get only): how many gpc_predict_cov calls formed their reduction in the product's epilogue.              */
+ * "cov_fused" (get only): how many gpc_predict_cov calls formed their reduction in the product's epilogue.
+ * "quad_mix_gemms" (get only): MFMA GEMM launches issued inside gpc_quad_mix over the life of the context (0 by design). */
 int gpc_set_option(gpc_ctx* ctx, const char* name, int value);
 /* Current value of a tuning switch (so that a caller that changes one for a measurement can put it back). */
 int gpc_get_option(gpc_ctx* ctx, const char* name, int* value);
