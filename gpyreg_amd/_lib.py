@@ -92,6 +92,11 @@ SIGNATURES = {
     ),
     "gpc_debug_leaf": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _ip]),
     "gpc_debug_factor": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "gpc_debug_cov": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, C.c_int, C.c_int, _dp,
+         C.c_int, _dp, _dp, _dp, _dp, _dp],
+    ),
     "gpc_debug_normals": (C.c_int, [_vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "gpc_debug_workspace_hash": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
 }
@@ -421,6 +426,42 @@ class Context:
                                         C.byref(logdet), C.byref(info))
         self._check(rc, "gpc_debug_factor")
         return L, W, Ainv, logdet.value, info.value
+
+    @_serial
+    def debug_cov(self, which, kid, degree, hyp_cov, X, dtype=F64, kscale=1.0, sl=1.0, dvec=None, X_star=None,
+                  mat=None, vec=None):
+        """gpc_debug_cov on one sample.  which = "build" | "front": A (npad, npad); "cross": Ks (npad, mpad) and the
+        fused column sums Ks^T vec (mpad,); "trace": the cov_N + 1 sums and diag(Q) (npad,) for Q = mat / sl - vec vec^T.
+        The last entry of the returned tuple is always the scaled inputs (npad, D) -- for "cross" the pair (Xs, Xss)."""
+        code = {"build": 0, "front": 1, "cross": 2, "trace": 3}[which]
+        X, hyp_cov = _f64(X), _f64(hyp_cov).ravel()
+        N, D = X.shape
+        npad = -(-N // 128) * 128
+        dvec = None if dvec is None else _f64(dvec).ravel()
+        vec = None if vec is None else _f64(vec).ravel()
+        mat = None if mat is None else _f64(mat)
+        Xq = None if X_star is None else _f64(X_star)
+        M = 0 if Xq is None else Xq.shape[0]
+        mpad = -(-M // 128) * 128
+        if (dvec is not None and dvec.size != N) or (vec is not None and vec.size != N) or \
+                (mat is not None and mat.shape != (N, N)) or (Xq is not None and Xq.shape[1] != D):
+            raise ValueError("debug_cov: dvec (N,), vec (N,), mat (N, N), X_star (M, D)")
+        xs = np.empty((npad + (mpad if code == 2 else 0), D))
+        if code < 2:
+            out0, out1 = np.empty((npad, npad)), None
+        elif code == 2:
+            out0, out1 = np.empty((npad, mpad)), np.empty(mpad)
+        else:
+            out0, out1 = np.empty(self._lib.gpc_cov_count(kid, D) + 1), np.empty(npad)
+        rc = self._lib.gpc_debug_cov(self._h, code, kid, degree, dtype, _ptr(hyp_cov), float(kscale), float(sl),
+                                     _ptr(dvec), _ptr(X), N, D, _ptr(Xq), M, _ptr(mat), _ptr(vec), _ptr(out0),
+                                     _ptr(out1), _ptr(xs))
+        self._check(rc, "gpc_debug_cov")
+        if code < 2:
+            return out0, xs
+        if code == 2:
+            return out0, out1, (xs[:npad], xs[npad:])
+        return out0, out1, xs
 
     @_serial
     def debug_normals(self, seed, stream, s, r, j0, count):

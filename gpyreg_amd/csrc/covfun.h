@@ -101,13 +101,19 @@ __device__ __forceinline__ void stage_x(double (*sh)[DCH + 1], const double* __r
 // sqrt) and the rational quadratic needs one log, one exp and one reciprocal instead of two pows
 // and a log:  M^-a = exp(-a log M),  M^(-a-1) = M^-a / M.
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ double sqrt_fast(double x) {
+__device__ __forceinline__ double sqrt_fast(double x0) {
+  // below 2^-700 the estimate's square r * r (~1 / x) leaves the fp64 range for subnormal x (x < 5.6e-309: r * r = inf,
+  // and the steps below turn that into NaN): such arguments are scaled by 2^600 and the root by 2^-300, both exact;
+  // every other argument passes through ldexp(., 0) unchanged, to the bit
+  const bool tiny = x0 < 0x1p-700;
+  const double x = __builtin_ldexp(x0, tiny ? 600 : 0);
   double r = __builtin_amdgcn_rsq(x);      // ~5e-8 relative; +inf at 0
   r = r * fma(-0.5 * x, r * r, 1.5);        // one Newton step: ~4e-15
   double t = x * r;
   const double e = fma(-t, t, x);           // residual x - t^2
   t = fma(e, 0.5 * r, t);                   // t + e / (2 sqrt(x)): <= 1 ulp
-  return x > 0.0 ? t : 0.0;
+  t = __builtin_ldexp(t, tiny ? -300 : 0);
+  return x0 > 0.0 ? t : 0.0;
 }
 __device__ __forceinline__ double rcp_fast(double x) {
   double r = __builtin_amdgcn_rcp(x);
@@ -255,7 +261,10 @@ __device__ __forceinline__ double wave_sum4(double v0, double v1, double v2, dou
 // Here:  * the scaled inputs are staged in LDS as floats and read two DIMENSIONS at a time (ds_read_b64), the
 //          differences and squares are packed fp32 (v_pk_add_f32 / v_pk_fma_f32: two dimensions per lane and
 //          instruction, the fp32 vector peak), even and odd dimensions summed separately and added at the end --
-//          direct differences, never |x|^2 + |y|^2 - 2 x.y: near-duplicate points keep their relative accuracy;
+//          direct differences, never |x|^2 + |y|^2 - 2 x.y, of coordinates that are rounded to float RELATIVE TO THE
+//          SAMPLE'S ROW 0 (stage_x32): near-duplicate points keep their relative accuracy wherever the data lie, not
+//          only around the origin (the staged values are as large as the data's extent in length scales, not as its
+//          offset from the origin);
 //        * exp, log, reciprocal and square root are the hardware's v_exp_f32 / v_log_f32 / v_rcp_f32 / v_sqrt_f32
 //          (~1 ulp, 8 cycles per wave each) instead of fp64 polynomial code;
 //        * per-thread partial sums over the thread's 16 pairs are fp32, everything across lanes, waves and tiles
@@ -302,12 +311,18 @@ __device__ __forceinline__ PairVal32 pair_eval32(float r2, float sf2, float rqa,
   return o;
 }
 
-// rows [r0, r0+64), dims [h0, h0+dc) of Xs (double) -> sh[64][XLD32] floats; dims dc .. dc rounded up to even are 0
+// rows [r0, r0+64), dims [h0, h0+dc) of Xs (double) -> sh[64][XLD32] floats; dims dc .. dc rounded up to even are 0.
+// The sample's own row 0 is subtracted in fp64 BEFORE the rounding to float (one more L2-resident load): only the
+// differences of staged values are used, so the centre cancels, and what is rounded is the distance to a data point
+// instead of the distance to the origin -- the covariance stays translation invariant (inputs at c + [-3 ell, 3 ell]
+// lost 1e-3 of nlZ at c / ell = 2e4 to the rounding of c / ell itself).  Padding rows (Xs = 0) hold -centre: finite,
+// and masked by every caller.
 __device__ __forceinline__ void stage_x32(float* __restrict__ sh, const double* __restrict__ Xs, int D, int r0, int h0,
                                           int dc, int t) {
   const int r = t >> 2;
   const int dce = (dc + 1) & ~1;
-  for (int h = t & 3; h < dce; h += 4) sh[r * XLD32 + h] = h < dc ? (float)Xs[(size_t)(r0 + r) * D + h0 + h] : 0.f;
+  for (int h = t & 3; h < dce; h += 4)
+    sh[r * XLD32 + h] = h < dc ? (float)(Xs[(size_t)(r0 + r) * D + h0 + h] - Xs[h0 + h]) : 0.f;
 }
 
 // squared distances of the thread's 4 x 4 pairs, two dimensions per packed instruction; leaves the last chunk staged

@@ -3303,6 +3303,131 @@ int debug_factor_impl(gpc_ctx* c, int n, const double* A, double* L, double* W, 
   if (info) memcpy(info, &h[1], sizeof(int));
   return 0;
 }
+
+// gpc_debug_cov: the covariance kernels of the evaluation and prediction paths on one sample, launched as
+// device_section / small_section / predict launch them (same scaling kernel, same grids), on buffers of its own.
+struct ScratchDev {
+  std::vector<void*> ps;
+  ~ScratchDev() {
+    for (void* p : ps) (void)hipFree(p);
+  }
+  template <typename U>
+  U* get(size_t n) {
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(U)) != hipSuccess) return nullptr;
+    ps.push_back(p);
+    return static_cast<U*>(p);
+  }
+};
+
+template <typename T>
+int debug_cov_impl(gpc_ctx* c, int which, CovDesc cd, const double* hyp, double kscale, double sl, const double* dvec,
+                   const double* X, int N, const double* Xstar, int M, const double* mat, const double* vec,
+                   double* out0, double* out1, double* xs_out) {
+  hipStream_t st = c->st;
+  const int D = cd.D, npad = pad_tile(N), mpad = M > 0 ? pad_tile(M) : 0, Pn = cd.cov_N + 1;
+  const int t64 = npad / CT, ntl = t64 * (t64 + 1) / 2;
+  std::vector<double> mul(D), dv(D), sp(SP_STRIDE, 0.0), hd(npad, 1.0), hv(npad, 0.0);
+  double sf2 = 0.0, rqa = 1.0;
+  scaling_of(cd.kind, cd.degree, D, hyp, mul.data(), dv.data(), &sf2, &rqa);
+  sp[SP_SF2] = sf2;
+  sp[SP_RQA] = rqa;
+  sp[SP_KSCALE] = kscale;
+  sp[SP_SL] = sl;
+  if (dvec) std::copy(dvec, dvec + N, hd.begin());
+  if (vec) std::copy(vec, vec + N, hv.begin());
+  ScratchDev sd;
+  double* dX = sd.get<double>((size_t)N * D);
+  double* dmul = sd.get<double>(D);
+  double* ddv = sd.get<double>(D);
+  double* dsp = sd.get<double>(SP_STRIDE);
+  double* dd = sd.get<double>(npad);
+  double* dvv = sd.get<double>(npad);
+  double* xs = sd.get<double>((size_t)npad * D);
+  if (!dX || !dmul || !ddv || !dsp || !dd || !dvv || !xs) FAIL(c, "gpc_debug_cov: out of device memory");
+  HIPCHK(c, hipMemcpyAsync(dX, X, (size_t)N * D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(dmul, mul.data(), (size_t)D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(ddv, dv.data(), (size_t)D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(dsp, sp.data(), SP_STRIDE * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(dd, hd.data(), (size_t)npad * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(dvv, hv.data(), (size_t)npad * 8, hipMemcpyHostToDevice, st));
+  const long long tot = (long long)npad * D;
+  if (which != 1)  // (the small front scales the inputs itself)
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), 1), dim3(256), 0, st, (const double*)dX, N, npad,
+                       D, (const double*)dmul, (const double*)ddv, xs);
+  const size_t msz = (size_t)npad * npad;
+  if (which == 0 || which == 1) {
+    T* A = sd.get<T>(msz);
+    if (!A) FAIL(c, "gpc_debug_cov: out of device memory");
+    HIPCHK(c, hipMemsetAsync(A, 0, msz * sizeof(T), st));  // the tiles above the diagonal are not built
+    if (which == 0) {
+      GPC_COV_DISPATCH(build_kernel, T, cd, dim3(ntl, 1), dim3(256), 0, st, cd, (const double*)xs, (const double*)dsp,
+                       (const double*)dd, N, npad, A, (long long)msz, npad, 0);
+    } else {
+      XferDesc u{};
+      u.nseg = 0;
+      u.X = dX;
+      u.mul = dmul;
+      u.dv = ddv;
+      u.xs = xs;
+      u.n = N;
+      u.npad = npad;
+      u.D = D;
+      u.cnt = 1;
+      GPC_COV_DISPATCH(small_front_kernel, T, cd, dim3(3, 1), dim3(256), 0, st, u, cd, (const double*)dsp,
+                       (const double*)dd, 1, A, (long long)msz);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (download_as<T>(c, A, out0, msz)) return -1;
+  } else if (which == 2) {
+    double* dXq = sd.get<double>((size_t)M * D);
+    double* xss = sd.get<double>((size_t)mpad * D);
+    T* Ks = sd.get<T>((size_t)npad * mpad);
+    double* mupart = sd.get<double>((size_t)t64 * mpad);
+    double* mu = sd.get<double>(mpad);
+    if (!dXq || !xss || !Ks || !mupart || !mu) FAIL(c, "gpc_debug_cov: out of device memory");
+    HIPCHK(c, hipMemcpyAsync(dXq, Xstar, (size_t)M * D * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mpad * D + 255) / 256), 1), dim3(256), 0, st,
+                       (const double*)dXq, M, mpad, D, (const double*)dmul, (const double*)ddv, xss);
+    GPC_COV_DISPATCH(cross_tile_kernel, T, cd, dim3(mpad / CT, npad / CT, 1), dim3(256), 0, st, cd, (const double*)xs,
+                     (const double*)xss, (const double*)dsp, (const double*)dvv, npad, N, npad, M, mpad, Ks,
+                     (long long)npad * mpad, mupart);
+    hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mpad + 255) / 256, 1), dim3(256), 0, st, (const double*)mupart, t64,
+                       mpad, mu);
+    HIPCHK(c, hipGetLastError());
+    if (download_as<T>(c, Ks, out0, (size_t)npad * mpad)) return -1;
+    HIPCHK(c, hipMemcpyAsync(out1, mu, (size_t)mpad * 8, hipMemcpyDeviceToHost, st));
+    if (xs_out) HIPCHK(c, hipMemcpyAsync(xs_out + (size_t)npad * D, xss, (size_t)mpad * D * 8, hipMemcpyDeviceToHost, st));
+  } else {
+    std::vector<double> hT(msz, 0.0);
+    for (int i = 0; i < N; ++i) std::copy(mat + (size_t)i * N, mat + (size_t)i * N + N, hT.begin() + (size_t)i * npad);
+    T* Tm = sd.get<T>(msz);
+    double* parts = sd.get<double>((size_t)ntl * Pn);
+    double* diagq = sd.get<double>(npad);
+    double* gout = sd.get<double>(Pn);
+    if (!Tm || !parts || !diagq || !gout) FAIL(c, "gpc_debug_cov: out of device memory");
+    if constexpr (sizeof(T) == 8) {
+      HIPCHK(c, hipMemcpyAsync(Tm, hT.data(), msz * 8, hipMemcpyHostToDevice, st));
+    } else {
+      std::vector<float> tmp(hT.begin(), hT.end());
+      HIPCHK(c, hipMemcpyAsync(Tm, tmp.data(), msz * 4, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipStreamSynchronize(st));
+    }
+    HIPCHK(c, hipMemsetAsync(diagq, 0, (size_t)npad * 8, st));
+    GPC_COV_DISPATCH(trace_kernel, T, cd, dim3(ntl, 1), dim3(256), 4 * (((Pn + 3) & ~3) + 4) * sizeof(double), st, cd,
+                     (const double*)xs, (const double*)dsp, (const double*)dvv, N, npad, (const T*)Tm, (long long)msz, npad,
+                     parts, ntl, diagq);
+    hipLaunchKernelGGL(grad_tail_kernel, dim3(Pn, 1), dim3(256), 0, st, (const double*)parts, ntl, Pn, gout,
+                       (const double*)nullptr, N, 0, (const double*)dvv, (double*)nullptr, (const double*)nullptr, 0,
+                       (const double*)diagq, (double*)nullptr, npad);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out0, gout, (size_t)Pn * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(out1, diagq, (size_t)npad * 8, hipMemcpyDeviceToHost, st));
+  }
+  if (xs_out) HIPCHK(c, hipMemcpyAsync(xs_out, xs, (size_t)npad * D * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+}
 }  // namespace
 
 namespace {
@@ -4951,6 +5076,26 @@ int gpc_debug_factor(gpc_ctx* c, int dtype, int n, const double* A, double* L, d
   HIPCHK(c, hipSetDevice(c->device));
   return dtype == GPC_F64 ? debug_factor_impl<double>(c, n, A, L, W, Ainv, logdet, info)
                           : debug_factor_impl<float>(c, n, A, L, W, Ainv, logdet, info);
+}
+
+int gpc_debug_cov(gpc_ctx* c, int which, int kernel_id, int degree, int dtype, const double* hyp_cov, double kscale,
+                  double sl, const double* dvec, const double* X, int N, int D, const double* Xstar, int M,
+                  const double* mat, const double* vec, double* out0, double* out1, double* xs_out) {
+  if (!c) return -2;
+  if (!valid_kernel(kernel_id, degree) || !hyp_cov || !X || N <= 0 || D <= 0 || !out0 || which < 0 || which > 3)
+    FAIL(c, "gpc_debug_cov: bad arguments");
+  if (which == 1 && N > TILE) FAIL(c, "gpc_debug_cov: the small front builds one 128 x 128 leaf (N <= 128)");
+  if (which == 2 && (!Xstar || M <= 0 || !vec || !out1)) FAIL(c, "gpc_debug_cov: cross needs X*, alpha and both outputs");
+  if (which == 3 && (!mat || !vec || !out1)) FAIL(c, "gpc_debug_cov: trace needs T, a and both outputs");
+  HIPCHK(c, hipSetDevice(c->device));
+  CovDesc cd;
+  cd.kind = kernel_id;
+  cd.degree = degree;
+  cd.D = D;
+  cd.cov_N = cov_count_of(kernel_id, D);
+  return dtype == GPC_F64
+             ? debug_cov_impl<double>(c, which, cd, hyp_cov, kscale, sl, dvec, X, N, Xstar, M, mat, vec, out0, out1, xs_out)
+             : debug_cov_impl<float>(c, which, cd, hyp_cov, kscale, sl, dvec, X, N, Xstar, M, mat, vec, out0, out1, xs_out);
 }
 
 // Debug: a 64-bit hash (sum of the bit patterns, wrapping) of every 128 x 128 tile of one workspace matrix of the LAST call

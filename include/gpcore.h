@@ -394,6 +394,19 @@ int gpc_debug_leaf(gpc_ctx* ctx, int dtype, const double* A, double* L, double* 
 /* Blocked factorization of an n x n SPD matrix (any n): L, W = L^-1, Ainv (lower).   */
 int gpc_debug_factor(gpc_ctx* ctx, int dtype, int n, const double* A, double* L,
                      double* W, double* Ainv, double* logdet, int* info);
+/* The covariance kernels of the evaluation and prediction paths on ONE sample, launched as those paths launch them
+ * (the inputs scaled by scale_x_kernel from hyp_cov, the per-sample scalars sf2 / alpha_rq from hyp_cov, kscale and sl
+ * from the caller), on buffers of the hook's own; npad / mpad = N / M rounded up to 128.  which:
+ *   0  build_kernel:        out0[npad x npad] = K / kscale + diag(dvec[N]), identity padding (tiles above the diagonal 0)
+ *   1  small_front_kernel:  the same through the one-leaf front (N <= 128)
+ *   2  cross_tile_kernel:   out0[npad x mpad] = K(X, Xstar[M x D]), out1[mpad] = the fused column sums Ks^T vec[N]
+ *   3  trace_kernel + the reduction of its partials: Q = mat / sl - vec vec^T over the lower triangle of mat[N x N]
+ *      (stored in `dtype`): out0[cov_N + 1] = sum_ij w_ij Q_ij dK_ij/dtheta_p, last slot trace(Q); out1[npad] = diag(Q)
+ * xs_out (optional): the scaled inputs, npad x D (which = 2: followed by the mpad x D of Xstar).                        */
+int gpc_debug_cov(gpc_ctx* ctx, int which, int kernel_id, int degree, int dtype, const double* hyp_cov,
+                  double kscale, double sl, const double* dvec, const double* X, int N, int D,
+                  const double* Xstar, int M, const double* mat, const double* vec, double* out0,
+                  double* out1, double* xs_out);
 
 /* Debug: wrapping-sum hash of every 128 x 128 tile of one workspace matrix as the LAST call left it (which: 0 = A, 1 = W,
  * 2 = T; sample: position in the last chunk); out[(npad/128)^2].  Finds the tile where two schedules differ.          */

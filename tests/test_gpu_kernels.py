@@ -65,6 +65,62 @@ def test_gemm_modes_fp64(ctx, bt, akm, bkm, M, N, K, klo, khi, lower, alpha, bet
         assert np.array_equal(got[~mask], C0[~mask])
 
 
+def _gemm_fp32_bound(A, B, M, N, K, akm, bkm, alpha, klo, khi, tile=128):
+    """Per element: 2 k_len 2^-24 |alpha| (|A| |B|)_ij over the k-range of the element's tile (k_len its length) -- the
+    standard bound of a dot product of k_len terms accumulated in fp32 (unit roundoff 2^-24), with as much again for the
+    order of the sum and the final rounding."""
+    out = np.zeros((M, N))
+    for ti in range(M // tile):
+        for tj in range(N // tile):
+            k0 = {0: 0, 1: ti * tile, 2: tj * tile}[klo]
+            k1 = min({0: K, 1: (ti + 1) * tile, 2: (tj + 1) * tile}[khi], K)
+            r, c = slice(ti * tile, (ti + 1) * tile), slice(tj * tile, (tj + 1) * tile)
+            if k1 > k0:
+                a = A[k0:k1, r].T if akm else A[r, k0:k1]
+                b = B[k0:k1, c] if bkm else B[c, k0:k1].T
+                out[r, c] = 2 * (k1 - k0) * 2.0 ** -24 * abs(alpha) * (np.abs(a) @ np.abs(b))
+    return out
+
+
+@pytest.mark.parametrize("bt", [128, 64])
+@pytest.mark.parametrize("akm,bkm", [(0, 0), (0, 1), (1, 1), (1, 0)])
+@pytest.mark.parametrize(
+    "M,N,K,klo,khi,lower,alpha,beta",
+    [
+        (128, 128, 128, 0, 0, 0, 1.0, 0),
+        (256, 384, 128, 0, 0, 0, -1.0, 1),
+        (384, 384, 384, 0, 0, 1, -1.0, 1),   # syrk-like
+        (384, 256, 256, 0, 2, 0, 1.0, 0),    # k <= col tile (trsm as product)
+        (256, 384, 384, 2, 0, 0, 1.0, 0),    # k >= col tile
+        (384, 256, 384, 0, 1, 0, -1.0, 0),   # k <= row tile
+        (384, 384, 384, 1, 0, 1, 1.0, 0),    # lauum: k >= row tile, lower tiles
+    ],
+)
+def test_gemm_modes_fp32(ctx, bt, akm, bkm, M, N, K, klo, khi, lower, alpha, beta):
+    """The cases of test_gemm_modes_fp64 -- every k-range mode, every operand orientation, both tile sizes -- on the
+    product build's fp32 GEMM.  Reference: fp64 arithmetic on the fp32-rounded operands; bar: the dot-product bound of
+    each element's own k-range (_gemm_fp32_bound)."""
+    from gpyreg_amd import _lib
+
+    rng = np.random.default_rng(M + 3 * N + 7 * K + 11 * klo + 13 * khi + akm * 17 + bkm * 19)
+    r32 = lambda a: a.astype(np.float32).astype(np.float64)
+    A = r32(rng.standard_normal((K, M) if akm else (M, K)))
+    B = r32(rng.standard_normal((K, N) if bkm else (N, K)))
+    C0 = r32(rng.standard_normal((M, N)))
+    got = ctx.debug_gemm(A, B, C0, M, N, K, akm, bkm, alpha, beta, klo, khi, lower, dtype=_lib.F32, force_bt=bt)
+    ref = _ref_gemm(A, B, C0, M, N, K, akm, bkm, alpha, beta, klo, khi, lower)
+    bound = _gemm_fp32_bound(A, B, M, N, K, akm, bkm, alpha, klo, khi)
+    mask = np.ones((M, N), bool)
+    if lower:
+        for ti in range(M // bt):
+            for tj in range(ti + 1, N // bt):
+                mask[ti * bt:(ti + 1) * bt, tj * bt:(tj + 1) * bt] = False
+    err = np.abs(got - ref)
+    assert (err[mask] <= bound[mask]).all(), float((err[mask] / np.maximum(bound[mask], 1e-300)).max())
+    if lower:
+        assert np.array_equal(got[~mask], C0[~mask])
+
+
 @pytest.mark.experiments
 @pytest.mark.parametrize("akm,bkm", [(0, 0), (0, 1), (1, 1), (1, 0)])
 @pytest.mark.parametrize(
