@@ -13,11 +13,12 @@ from . import (
     mean_functions,
     noise_functions,
 )
-from .gaussian_process import GP, Posterior
+from .gaussian_process import GP, Posterior, PosteriorPaths
 
 __all__ = [
     "GP",
     "Posterior",
+    "PosteriorPaths",
     "covariance_functions",
     "isotropic_covariance_functions",
     "mean_functions",

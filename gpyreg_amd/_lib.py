@@ -76,6 +76,10 @@ SIGNATURES = {
     "gpc_predict_full": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "gpc_predict_cov": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
     "gpc_draw": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_ulonglong, C.c_int, _dp, _dp, _dp]),
+    "gpc_paths_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_ulonglong, C.c_int, _dp, _dp, C.POINTER(_vp)]),
+    "gpc_paths_eval": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
+    "gpc_paths_free": (C.c_int, [_vp]),
+    "gpc_debug_paths_fetch": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp]),
     "gpc_quad": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp]),
     "gpc_quad_grad": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpc_quad_cov": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, _dp]),
@@ -659,6 +663,20 @@ class PostHandle:
         return f, tau
 
     @_serial
+    def paths(self, n_paths, n_features, seed, s_offset, ym, noise_sd):
+        """gpc_paths_create: a ``Paths`` handle of ``n_paths`` pathwise samples per posterior sample.  ym (S, N) =
+        y - m_s(X), noise_sd (N, S) = sqrt(sn2 sn2_mult); s_offset is the global index of this posterior's first sample."""
+        ym, nsd = _f64(ym), _f64(noise_sd)
+        if ym.shape != (self.S, self.N) or nsd.shape != (self.N, self.S):
+            raise ValueError(f"paths: ym must be (S, N) = {(self.S, self.N)} and noise_sd (N, S), got {ym.shape} and "
+                             f"{nsd.shape}")
+        h = _vp()
+        rc = self.ctx._lib.gpc_paths_create(self._h, int(n_paths), int(n_features), int(seed), int(s_offset), _ptr(ym),
+                                            _ptr(nsd), C.byref(h))
+        self.ctx._check(rc, "gpc_paths_create")
+        return Paths(self.ctx, h, self.S, self.N, self.ctx.D, int(n_paths), int(n_features))
+
+    @_serial
     def quad(self, mu, sigma, compute_var):
         mu, sigma = _f64(mu), _f64(sigma)
         M = mu.shape[0]
@@ -725,6 +743,50 @@ class PostHandle:
     def free(self):
         if self._h:
             self.ctx._lib.gpc_post_free(self._h)
+            self._h = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            if self.ctx._h:
+                self.free()
+        except Exception:
+            pass
+
+
+class Paths:
+    """Pathwise posterior samples of one posterior set (gpc_paths): owns its device copies, outlives the PostHandle."""
+
+    def __init__(self, ctx: Context, h, S: int, N: int, D: int, R: int, F: int):
+        self.ctx, self._h, self.S, self.N, self.D, self.R, self.F = ctx, h, S, N, D, R, F
+
+    @_serial
+    def eval(self, x_star, compute_grad=False):
+        """gpc_paths_eval: f (M, R, S) and, with the gradient, df (M, D, R, S), without the mean function."""
+        if not self._h:
+            raise ValueError("paths: the handle has been closed")
+        xs = _f64(x_star)
+        if xs.ndim != 2 or xs.shape[1] != self.D:
+            raise ValueError(f"paths: x_star must be (M, {self.D}), got {xs.shape}")
+        M = xs.shape[0]
+        f = np.empty((M, self.R, self.S))
+        df = np.empty((M, self.D, self.R, self.S)) if compute_grad else None
+        rc = self.ctx._lib.gpc_paths_eval(self._h, _ptr(xs), M, _ptr(f), _ptr(df))
+        self.ctx._check(rc, "gpc_paths_eval")
+        return (f, df) if compute_grad else f
+
+    @_serial
+    def fetch(self, s):
+        """gpc_debug_paths_fetch: (theta (F, D), b (F,), wt (F, R), v (N, R)) of sample ``s`` (tests)."""
+        theta, b = np.empty((self.F, self.D)), np.empty(self.F)
+        wt, v = np.empty((self.F, self.R)), np.empty((self.N, self.R))
+        rc = self.ctx._lib.gpc_debug_paths_fetch(self._h, int(s), _ptr(theta), _ptr(b), _ptr(wt), _ptr(v))
+        self.ctx._check(rc, "gpc_debug_paths_fetch")
+        return theta, b, wt, v
+
+    @_serial
+    def free(self):
+        if self._h:
+            self.ctx._lib.gpc_paths_free(self._h)
             self._h = None
 
     def __del__(self):  # pragma: no cover

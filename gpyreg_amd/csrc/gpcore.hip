@@ -27,6 +27,7 @@
 #include "gemm.h"
 #include "leaf.h"
 #include "lookahead.h"
+#include "paths.h"
 #include "plan.h"
 #include "quad.h"
 #include "quad_mix.h"
@@ -573,6 +574,10 @@ struct gpc_ctx {
   int block_engine_ran = 0;  // the engine the last gpc_post_append_block ran (1: skinny kernel, 2: MFMA GEMM; get-only)
   int block_engine = 0;  // test hook: the engine of the block append's products with W (0: by k, 1: skinny kernel, 2: MFMA GEMM)
   long long block_appended = 0, block_stale = 0;  // samples gpc_post_append_block appended / left stale (get-only options)
+  int paths_engine = 0;      // test hook: the engine of gpc_paths_eval (0: paths.h's PA_DEFAULT_ENGINE, 1: fused kernel, 2: operand matrices + library GEMM)
+  int paths_engine_ran = 0;  // the engine the last gpc_paths_eval ran (get-only)
+  int paths_solve_engine = 0;      // test hook: the products of gpc_paths_create's solve (0 / 1: skinny kernel, 2: MFMA GEMM)
+  int paths_solve_engine_ran = 0;  // the engine the last gpc_paths_create ran (get-only)
   int retry_runs = 0;  // device pipelines spent on jitter retries by the last call (one per level)
 #ifdef GPC_EXPERIMENTS
   // ---- tile-level dataflow (dag.h).  Option "dag": 0 off, 1 wherever the plan supports it, -1 automatic (by what was
@@ -621,6 +626,22 @@ struct gpc_post {
   // kernel less per call); any change of sp / mul / dv / N clears the flag.
   DevBuf dsp, dmul, ddv, dxs;
   bool dev_consts = false;
+};
+
+// Pathwise posterior samples (paths.h): everything an evaluation needs, copied at creation -- the handle describes the
+// posterior as it was then and outlives it.  All fp64, whatever the posterior's storage type.
+struct gpc_paths {
+  gpc_ctx* ctx = nullptr;
+  int S = 0, N = 0, D = 0, npad = 0, R = 0, F = 0;
+  int kq = 0;    // R rounded up to 16: leading dimension of v and wt
+  int fpad = 0;  // F rounded up to 128
+  CovDesc cd{};
+  DevBuf xs, sp, mul, dv;  // scaled training inputs (S x npad x D), per-sample scalars and scaling
+  DevBuf theta, bph, wt;   // features (S x fpad x D, S x fpad) and weights (S x fpad x kq)
+  DevBuf v;                // S x npad x kq
+  void release() {
+    for (DevBuf* b : {&xs, &sp, &mul, &dv, &theta, &bph, &wt, &v}) b->release();
+  }
 };
 
 #define HIPCHK(ctx, expr)                                                                   \
@@ -3867,6 +3888,332 @@ int append_block_check(gpc_post* po, int k, const char* fn) {
 }  // namespace
 
 
+// ---- pathwise posterior samples (paths.h; DESIGN.md "Pathwise samples") -------------------------------------------
+namespace {
+
+hipError_t launch_paths_eval(hipStream_t st, const CovDesc& cd, const PathsEvalArgs& a, int cnt) {
+  const int ncb = (a.kq + 16 * PA_CG - 1) / (16 * PA_CG), nsg = (a.nslots + PA_SLOTS - 1) / PA_SLOTS;
+  const dim3 grid((a.m + CT - 1) / CT, nsg * ncb, cnt);
+  GPC_COV_DISPATCH(paths_eval_kernel, double, cd, grid, dim3(256), 0, st, cd, a);
+  return hipGetLastError();
+}
+
+// Features, weights, the panel p(X) + eps and the solve for v, chunked over the samples.  The panel p(X) comes from the
+// evaluation kernel itself (no training tiles, the training inputs as query points): the N x F feature matrix is never
+// stored.  The solve is gpc_predict_grad's Q = (K + Sigma)^-1 R with block_append.h's product engines:
+//   L_chol:    V1 = W P (lower triangular),  v = W^T V1 / sl          low noise (A = -(K + Sigma)^-1):  v = -(A P)
+// The skinny kernel serves every 16 columns by itself, so a path's v does not depend on R; the MFMA engine (test option
+// "paths_solve_engine" = 2) pads the panel to 128 columns in the storage type.
+template <typename T>
+int paths_create_impl(gpc_post* po, gpc_paths* pa, unsigned long long seed, int s_offset, const double* ym,
+                      const double* noise_sd) {
+  gpc_ctx* c = po->ctx;
+  hipStream_t st = c->st;
+  const int S = po->S, N = po->N, D = po->D, npad = po->npad, R = pa->R, F = pa->F, kq = pa->kq, fpad = pa->fpad;
+  const int kp = pad_tile(R);
+  const bool use_gemm = c->paths_solve_engine == 2;
+  c->paths_solve_engine_ran = use_gemm ? 2 : 1;
+  // scratch of one sample: three fp64 N_pad x kq panels (p(X), P, V1) and, for the MFMA engine, three N_pad x kp
+  // panels in the storage type
+  const size_t panel = (size_t)npad * kq * 8, tpanel = use_gemm ? (size_t)npad * kp * sizeof(T) : 0;
+  const size_t per = 3 * panel + 3 * tpanel + 64;
+  const size_t held = c->ks.bytes;
+  int chunk = S;
+  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > held) {
+    c->pool_drain();
+    const bool forced = getenv("GPC_MEM_BUDGET_MB") != nullptr;
+    const size_t budget = (size_t)((free_device_bytes() + (forced ? 0 : held)) * 0.8);
+    if (budget < per)
+      FAIL(c, "gpc_paths_create: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
+              std::to_string(npad) + ", R = " + std::to_string(R) + ") exceeds the device memory budget (" +
+              std::to_string(budget >> 10) + " KB)");
+    chunk = (int)std::min<size_t>(S, budget / per);
+  }
+  // the handle's own constants
+  HIPCHK(c, pa->sp.ensure_private((size_t)S * SP_STRIDE * 8));
+  HIPCHK(c, pa->mul.ensure_private((size_t)S * D * 8));
+  HIPCHK(c, pa->dv.ensure_private((size_t)S * D * 8));
+  HIPCHK(c, pa->xs.ensure_private((size_t)S * npad * D * 8));
+  HIPCHK(c, pa->theta.ensure_private((size_t)S * fpad * D * 8));
+  HIPCHK(c, pa->bph.ensure_private((size_t)S * fpad * 8));
+  HIPCHK(c, pa->wt.ensure_private((size_t)S * fpad * kq * 8));
+  HIPCHK(c, pa->v.ensure_private((size_t)S * npad * kq * 8));
+  HIPCHK(c, hipMemcpyAsync(pa->sp.p, po->sp.data(), (size_t)S * SP_STRIDE * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(pa->mul.p, po->mul.data(), (size_t)S * D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(pa->dv.p, po->dv.data(), (size_t)S * D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(pa->v.p, 0, (size_t)S * npad * kq * 8, st));
+  std::vector<double> par((size_t)S * BA_STRIDE, 0.0);
+  bool any_high = false, any_low = false;
+  for (int s = 0; s < S; ++s) {
+    par[(size_t)s * BA_STRIDE + BA_SL] = po->sp[(size_t)s * SP_STRIDE + SP_SL];
+    par[(size_t)s * BA_STRIDE + BA_LCH] = po->lchol[s] ? 1.0 : 0.0;
+    par[(size_t)s * BA_STRIDE + BA_PRE] = 1.0;
+    (po->lchol[s] ? any_high : any_low) = true;
+  }
+  HIPCHK(c, c->avec.ensure((size_t)S * BA_STRIDE * 8));
+  HIPCHK(c, c->rvec.ensure(2 * (size_t)S * N * 8));
+  double* d_par = c->avec.as<double>();
+  double* d_ym = c->rvec.as<double>();
+  double* d_nsd = d_ym + (size_t)S * N;
+  HIPCHK(c, hipMemcpyAsync(d_par, par.data(), par.size() * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_ym, ym, (size_t)S * N * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_nsd, noise_sd, (size_t)S * N * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, c->ks.ensure((size_t)chunk * per));
+  c->ms_total = c->ms_factor = 0;
+  HIPCHK(c, hipEventRecord(c->ev[0], st));
+  {
+    const long long tot = (long long)npad * D;
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), S), dim3(256), 0, st, c->dX.as<double>(), N,
+                       npad, D, pa->mul.as<double>(), pa->dv.as<double>(), pa->xs.as<double>());
+    const dim3 gf((fpad / 4 + 63) / 64, (D + 3) / 4, S), blk(64, 4);
+    const bool matern = pa->cd.kind == K_MATERN || pa->cd.kind == K_MATERN_ISO;
+    const int deg = matern ? pa->cd.degree : 0;
+    double* th = pa->theta.as<double>();
+    double* bp = pa->bph.as<double>();
+    const long long sb = s_offset;
+    if (deg == 0) hipLaunchKernelGGL((paths_features_kernel<0>), gf, blk, 0, st, seed, sb, F, fpad, D, th, bp);
+    else if (deg == 1) hipLaunchKernelGGL((paths_features_kernel<1>), gf, blk, 0, st, seed, sb, F, fpad, D, th, bp);
+    else if (deg == 3) hipLaunchKernelGGL((paths_features_kernel<3>), gf, blk, 0, st, seed, sb, F, fpad, D, th, bp);
+    else hipLaunchKernelGGL((paths_features_kernel<5>), gf, blk, 0, st, seed, sb, F, fpad, D, th, bp);
+    hipLaunchKernelGGL(paths_weights_kernel, dim3((kq + 63) / 64, fpad / 16, S), blk, 0, st, seed, sb, F, fpad, R, kq,
+                       pa->wt.as<double>());
+    HIPCHK(c, hipGetLastError());
+  }
+  const long long sM = (long long)npad * npad, sP = (long long)npad * kq, sK = (long long)npad * kp;
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    double* pX = c->ks.as<double>();
+    double* P = pX + (size_t)cnt * sP;
+    double* V1 = P + (size_t)cnt * sP;
+    T* Bt = reinterpret_cast<T*>(V1 + (size_t)cnt * sP);
+    T* Vt = Bt + (size_t)cnt * sK;
+    T* Qt = Vt + (size_t)cnt * sK;
+    const double* parc = d_par + (size_t)s0 * BA_STRIDE;
+    const T* Wc = po->W.as<T>() + (size_t)s0 * sM;
+    const T* Ac = po->A.as<T>() + (size_t)s0 * sM;
+    double* vc = pa->v.as<double>() + (size_t)s0 * sP;
+    // 1. p(X): the evaluation kernel on the training inputs, features only
+    PathsEvalArgs a{};
+    a.xq = pa->xs.as<double>() + (size_t)s0 * npad * D;
+    a.sp = pa->sp.as<double>() + (size_t)s0 * SP_STRIDE;
+    a.mul = pa->mul.as<double>() + (size_t)s0 * D;
+    a.dv = pa->dv.as<double>() + (size_t)s0 * D;
+    a.theta = pa->theta.as<double>() + (size_t)s0 * fpad * D;
+    a.bph = pa->bph.as<double>() + (size_t)s0 * fpad;
+    a.wt = pa->wt.as<double>() + (size_t)s0 * fpad * kq;
+    a.n = 0;
+    a.npad = npad;
+    a.m = N;
+    a.mpad = npad;
+    a.F = F;
+    a.fpad = fpad;
+    a.R = R;
+    a.kq = kq;
+    a.nslots = 1;
+    a.f = pX;
+    a.S_out = cnt;
+    a.s_out0 = 0;
+    HIPCHK(c, launch_paths_eval(st, pa->cd, a, cnt));
+    // 2. P = y - m(X) - p(X) - eps
+    hipLaunchKernelGGL(paths_rhs_kernel, dim3((kq + 63) / 64, npad / 16, cnt), dim3(64, 4), 0, st, seed,
+                       (long long)s_offset + s0, N, npad, R, kq, (const double*)(d_ym + (size_t)s0 * N), (const double*)pX,
+                       cnt, (const double*)d_nsd, S, s0, P);
+    HIPCHK(c, hipGetLastError());
+    // 3. v = (K + Sigma)^-1 P
+    HIPCHK(c, hipEventRecord(c->ev[1], st));
+    if (use_gemm) {
+      hipLaunchKernelGGL((ba_to_panel_kernel<T>), dim3(kp / 64, npad / 4, cnt), dim3(64, 4), 0, st, (const double*)P, N, R,
+                         kq, npad, kp, Bt);
+      for (int i = 0; i < cnt;) {
+        const int lch = po->lchol[s0 + i];
+        int e = i + 1;
+        while (e < cnt && po->lchol[s0 + e] == lch) ++e;
+        GemmArgs g;
+        g.A = (lch ? Wc : Ac) + (size_t)i * sM;  // V1 = W P | -(A P)
+        g.B = Bt + (size_t)i * sK;
+        g.C = Vt + (size_t)i * sK;
+        g.sA = sM;
+        g.sB = g.sC = sK;
+        g.lda = npad;
+        g.ldb = g.ldc = kp;
+        g.M = npad;
+        g.N = kp;
+        g.K = npad;
+        g.alpha = lch ? 1.0 : -1.0;
+        g.beta = 0;
+        g.klo = KLO_ZERO;
+        g.khi = lch ? KHI_ROW : KHI_FULL;
+        g.lower_only = 0;
+        HIPCHK(c, launch_gemm<T>(st, g, false, true, e - i));
+        if (lch) {  // W^T V1 (k from the tile row's diagonal block on)
+          GemmArgs q = g;
+          q.B = Vt + (size_t)i * sK;
+          q.C = Qt + (size_t)i * sK;
+          q.klo = KLO_ROW;
+          q.khi = KHI_FULL;
+          HIPCHK(c, launch_gemm<T>(st, q, true, true, e - i));
+        }
+        i = e;
+      }
+      const dim3 gp((kq + 63) / 64, (N + 3) / 4, cnt);
+      if (any_high)
+        hipLaunchKernelGGL((paths_from_panel_kernel<T>), gp, dim3(64, 4), 0, st, (const T*)Qt, N, kq, npad, kp, 1.0, 1, parc,
+                           1, vc);
+      if (any_low)
+        hipLaunchKernelGGL((paths_from_panel_kernel<T>), gp, dim3(64, 4), 0, st, (const T*)Vt, N, kq, npad, kp, 1.0, 0, parc,
+                           0, vc);
+    } else {
+      const dim3 gn((N + BA_T - 1) / BA_T, kq / BA_R, cnt);
+      if (any_high) {
+        hipLaunchKernelGGL((ba_skinny_kernel<T, false, true, false>), gn, dim3(256), 0, st, Wc, sM, npad, N, N,
+                           (const double*)P, sP, kq, V1, sP, kq, 1.0, 0, parc, 1);
+        hipLaunchKernelGGL((ba_skinny_kernel<T, true, true, false>), gn, dim3(256), 0, st, Wc, sM, npad, N, N,
+                           (const double*)V1, sP, kq, vc, sP, kq, 1.0, 1, parc, 1);
+      }
+      if (any_low)
+        hipLaunchKernelGGL((ba_skinny_kernel<T, false, false, false>), gn, dim3(256), 0, st, Ac, sM, npad, N, N,
+                           (const double*)P, sP, kq, vc, sP, kq, -1.0, 0, parc, 0);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev[2], st));
+  }
+  HIPCHK(c, hipEventRecord(c->ev[3], st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  float t03 = 0, t12 = 0;
+  (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
+  (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
+  c->ms_total = t03;
+  c->ms_factor = t12;
+  return 0;
+}
+
+// f and (optionally) df of all samples of the handle at M query points; the results are written on the device in the
+// caller's layout and come back in one copy each.  Scratch per sample: the scaled query points and, for the unfused
+// engine, one operand matrix, the widened panels and the product; chunked over the samples under the budget of
+// gpc_predict_cov, beside the results themselves.
+int paths_eval_impl(gpc_paths* pa, const double* xstar, int M, double* f, double* df) {
+  gpc_ctx* c = pa->ctx;
+  hipStream_t st = c->st;
+  const int S = pa->S, N = pa->N, D = pa->D, npad = pa->npad, R = pa->R, F = pa->F, kq = pa->kq, fpad = pa->fpad;
+  const int mpad = pad_tile(M), rp = pad_tile(R), nslots = df ? 1 + D : 1;
+  const int engine = c->paths_engine ? c->paths_engine : PA_DEFAULT_ENGINE;
+  c->paths_engine_ran = engine;
+  const size_t fbytes = (size_t)M * R * S * 8, dfbytes = df ? fbytes * D : 0;
+  const size_t opsz = (size_t)std::max(npad, fpad) * mpad;  // one operand matrix (elements)
+  const size_t xq_per = (size_t)mpad * D * 8;
+  const size_t eng_per = engine == 2 ? (opsz + (size_t)mpad * rp + (size_t)npad * rp + (size_t)fpad * rp) * 8 : 0;
+  const size_t per = xq_per + eng_per;
+  const size_t held = c->dout.bytes + c->gres.bytes + c->xss.bytes + (engine == 2 ? c->ks.bytes : 0);
+  int chunk = S;
+  if (getenv("GPC_MEM_BUDGET_MB") || fbytes + dfbytes + (size_t)S * per > held) {
+    c->pool_drain();
+    const bool forced = getenv("GPC_MEM_BUDGET_MB") != nullptr;
+    const size_t budget = (size_t)((free_device_bytes() + (forced ? 0 : held)) * 0.8);
+    if (budget < fbytes + dfbytes + per)
+      FAIL(c, "gpc_paths_eval: the results (" + std::to_string((fbytes + dfbytes) >> 10) + " KB) and the scratch of one "
+              "sample (" + std::to_string(per >> 10) + " KB: M_pad = " + std::to_string(mpad) + ") exceed the device "
+              "memory budget (" + std::to_string(budget >> 10) + " KB)");
+    chunk = (int)std::min<size_t>(S, (budget - fbytes - dfbytes) / per);
+  }
+  HIPCHK(c, c->dout.ensure(fbytes));
+  if (df) HIPCHK(c, c->gres.ensure(dfbytes));
+  HIPCHK(c, c->xss.ensure((size_t)chunk * xq_per + (size_t)M * D * 8));
+  if (engine == 2) HIPCHK(c, c->ks.ensure((size_t)chunk * eng_per));
+  double* xq = c->xss.as<double>();
+  double* d_x = xq + (size_t)chunk * mpad * D;
+  c->pin.begin();
+  HIPCHK(c, hipEventRecord(c->ev[0], st));
+  HIPCHK(c, c->pin.up(d_x, xstar, (size_t)M * D * 8, st));
+  HIPCHK(c, hipEventRecord(c->ev[1], st));
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    const long long tot = (long long)mpad * D;
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, st, (const double*)d_x, M,
+                       mpad, D, (const double*)(pa->mul.as<double>() + (size_t)s0 * D),
+                       (const double*)(pa->dv.as<double>() + (size_t)s0 * D), xq);
+    PathsEvalArgs a{};
+    a.xs = pa->xs.as<double>() + (size_t)s0 * npad * D;
+    a.xq = xq;
+    a.sp = pa->sp.as<double>() + (size_t)s0 * SP_STRIDE;
+    a.mul = pa->mul.as<double>() + (size_t)s0 * D;
+    a.dv = pa->dv.as<double>() + (size_t)s0 * D;
+    a.v = pa->v.as<double>() + (size_t)s0 * npad * kq;
+    a.theta = pa->theta.as<double>() + (size_t)s0 * fpad * D;
+    a.bph = pa->bph.as<double>() + (size_t)s0 * fpad;
+    a.wt = pa->wt.as<double>() + (size_t)s0 * fpad * kq;
+    a.n = N;
+    a.npad = npad;
+    a.m = M;
+    a.mpad = mpad;
+    a.F = F;
+    a.fpad = fpad;
+    a.R = R;
+    a.kq = kq;
+    a.nslots = nslots;
+    a.f = c->dout.as<double>();
+    a.df = df ? c->gres.as<double>() : nullptr;
+    a.S_out = S;
+    a.s_out0 = s0;
+    if (engine != 2) {
+      HIPCHK(c, launch_paths_eval(st, pa->cd, a, cnt));
+      continue;
+    }
+    double* op = c->ks.as<double>();
+    double* Cb = op + (size_t)cnt * opsz;
+    double* Vp = Cb + (size_t)cnt * mpad * rp;
+    double* Wp = Vp + (size_t)cnt * npad * rp;
+    const dim3 blk(64, 4);
+    hipLaunchKernelGGL(paths_widen_kernel, dim3(rp / 64, npad / 4, cnt), blk, 0, st, a.v, npad, kq, rp, Vp);
+    hipLaunchKernelGGL(paths_widen_kernel, dim3(rp / 64, fpad / 4, cnt), blk, 0, st, a.wt, fpad, kq, rp, Wp);
+    for (int slot = 0; slot < nslots; ++slot) {
+      hipLaunchKernelGGL(paths_cross_op_kernel, dim3(mpad / 64, npad / 4, cnt), blk, 0, st, pa->cd, a.xs, a.xq, a.sp, a.mul,
+                         a.dv, N, npad, M, mpad, slot, op);
+      GemmArgs g;  // C = op^T Vp: both operands k-major
+      g.A = op;
+      g.B = Vp;
+      g.C = Cb;
+      g.sA = (long long)npad * mpad;
+      g.sB = (long long)npad * rp;
+      g.sC = (long long)mpad * rp;
+      g.lda = mpad;
+      g.ldb = g.ldc = rp;
+      g.M = mpad;
+      g.N = rp;
+      g.K = npad;
+      g.alpha = 1.0;
+      g.beta = 0;
+      g.klo = KLO_ZERO;
+      g.khi = KHI_FULL;
+      g.lower_only = 0;
+      HIPCHK(c, launch_gemm<double>(st, g, true, true, cnt));
+      hipLaunchKernelGGL(paths_feat_op_kernel, dim3(mpad / 64, fpad / 4, cnt), blk, 0, st, D, a.theta, a.bph, a.xq, a.sp,
+                         a.mul, a.dv, F, fpad, M, mpad, slot, op);
+      g.B = Wp;
+      g.sA = (long long)fpad * mpad;
+      g.sB = (long long)fpad * rp;
+      g.K = fpad;
+      g.beta = 1;
+      HIPCHK(c, launch_gemm<double>(st, g, true, true, cnt));
+      hipLaunchKernelGGL(paths_scatter_kernel, dim3((R + 63) / 64, (M + 3) / 4, cnt), blk, 0, st, (const double*)Cb, M, mpad,
+                         rp, R, D, slot, S, s0, a.f, a.df);
+    }
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipEventRecord(c->ev[2], st));
+  HIPCHK(c, hipMemcpyAsync(f, c->dout.p, fbytes, hipMemcpyDeviceToHost, st));
+  if (df) HIPCHK(c, hipMemcpyAsync(df, c->gres.p, dfbytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipEventRecord(c->ev[3], st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  c->pin.finish();
+  float t03 = 0, t12 = 0;
+  (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
+  (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
+  c->ms_total = t03;
+  c->ms_factor = t12;
+  return 0;
+}
+}  // namespace
+
 // =====================================================================================
 // C ABI
 // =====================================================================================
@@ -4706,6 +5053,85 @@ int gpc_debug_normals(gpc_ctx* c, unsigned long long seed, int stream, int s, in
   return 0;
 }
 
+int gpc_paths_create(gpc_post* po, int R, int F, unsigned long long seed, int s_offset, const double* ym,
+                     const double* noise_sd, gpc_paths** out) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!ym || !noise_sd || !out) FAIL(c, "gpc_paths_create: null argument (ym, noise_sd and out are required)");
+  if (R < 1 || F < 1) FAIL(c, "gpc_paths_create: R and F must be at least 1 (R = " + std::to_string(R) + ", F = " + std::to_string(F) + ")");
+  if (R > (1 << 16) || F > (1 << 22) || s_offset < 0) FAIL(c, "gpc_paths_create: bad arguments (R <= 65536, F <= 4194304, s_offset >= 0)");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_paths_create: this posterior was built from caller-provided K; a caller-provided kernel has no "
+            "spectral density to draw features from");
+  if (po->cd.kind == K_RQ)
+    FAIL(c, "gpc_paths_create: the rational-quadratic kernel is not supported (spectral draws exist for the "
+            "squared-exponential and Matern kernels)");
+  for (int s = 0; s < po->S; ++s)
+    if (po->info[s] != 0) FAIL(c, "gpc_paths_create: posterior contains a failed factorization");
+  if (c->N != po->N || c->D != po->D)
+    FAIL(c, "gpc_paths_create: the context's data (gpc_set_data) is not the data this posterior was built on");
+  HIPCHK(c, hipSetDevice(c->device));
+  gpc_paths* pa = new gpc_paths;
+  pa->ctx = c;
+  pa->S = po->S;
+  pa->N = po->N;
+  pa->D = po->D;
+  pa->npad = po->npad;
+  pa->R = R;
+  pa->F = F;
+  pa->kq = ((R + BA_R - 1) / BA_R) * BA_R;
+  pa->fpad = pad_tile(F);
+  pa->cd = po->cd;
+  const int rc = po->dtype == GPC_F64 ? paths_create_impl<double>(po, pa, seed, s_offset, ym, noise_sd)
+                                      : paths_create_impl<float>(po, pa, seed, s_offset, ym, noise_sd);
+  if (rc) {
+    (void)hipStreamSynchronize(c->st);
+    pa->release();
+    delete pa;
+    return rc;
+  }
+  *out = pa;
+  return 0;
+}
+
+int gpc_paths_eval(gpc_paths* pa, const double* xstar, int M, double* f, double* df) {
+  if (!pa) return -2;
+  gpc_ctx* c = pa->ctx;
+  if (!xstar || !f || M <= 0) FAIL(c, "gpc_paths_eval: bad arguments");
+  HIPCHK(c, hipSetDevice(c->device));
+  return paths_eval_impl(pa, xstar, M, f, df);
+}
+
+int gpc_paths_free(gpc_paths* pa) {
+  if (!pa) return 0;
+  (void)hipSetDevice(pa->ctx->device);
+  (void)hipStreamSynchronize(pa->ctx->st);
+  pa->release();
+  delete pa;
+  return 0;
+}
+
+int gpc_debug_paths_fetch(gpc_paths* pa, int s, double* theta, double* b, double* wt, double* v) {
+  if (!pa) return -2;
+  gpc_ctx* c = pa->ctx;
+  if (s < 0 || s >= pa->S) FAIL(c, "gpc_debug_paths_fetch: sample index out of range");
+  HIPCHK(c, hipSetDevice(c->device));
+  hipStream_t st = c->st;
+  const int D = pa->D, F = pa->F, R = pa->R, N = pa->N, kq = pa->kq;
+  if (theta)
+    HIPCHK(c, hipMemcpyAsync(theta, pa->theta.as<double>() + (size_t)s * pa->fpad * D, (size_t)F * D * 8,
+                             hipMemcpyDeviceToHost, st));
+  if (b) HIPCHK(c, hipMemcpyAsync(b, pa->bph.as<double>() + (size_t)s * pa->fpad, (size_t)F * 8, hipMemcpyDeviceToHost, st));
+  if (wt)
+    HIPCHK(c, hipMemcpy2DAsync(wt, (size_t)R * 8, pa->wt.as<double>() + (size_t)s * pa->fpad * kq, (size_t)kq * 8,
+                               (size_t)R * 8, F, hipMemcpyDeviceToHost, st));
+  if (v)
+    HIPCHK(c, hipMemcpy2DAsync(v, (size_t)R * 8, pa->v.as<double>() + (size_t)s * pa->npad * kq, (size_t)kq * 8,
+                               (size_t)R * 8, N, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+}
+
 int gpc_predict_full(gpc_post* po, const double* xstar, int M, double* fmu, double* cov) {
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
@@ -4905,6 +5331,10 @@ int gpc_set_option(gpc_ctx* c, const char* name, int value) {
     c->append_fail_mask = (unsigned)value;
   else if (n == "block_engine")  // test hook: 1 / 2 force the skinny kernel / the MFMA GEMM in gpc_post_append_block (0: by k)
     c->block_engine = value == 1 || value == 2 ? value : 0;
+  else if (n == "paths_engine")  // test hook: 1 / 2 force the fused kernel / the unfused composition in gpc_paths_eval (0: the default)
+    c->paths_engine = value == 1 || value == 2 ? value : 0;
+  else if (n == "paths_solve_engine")  // test hook: 2 runs the solve of gpc_paths_create on the MFMA GEMM (0 / 1: skinny kernel)
+    c->paths_solve_engine = value == 1 || value == 2 ? value : 0;
   else {
 #ifdef GPC_EXPERIMENTS
     if (int* slot = experiment_option(c, n))
@@ -4939,6 +5369,10 @@ int gpc_get_option(gpc_ctx* c, const char* name, int* value) {
   else if (n == "quad_mix_gemms") *value = (int)(c->quad_mix_gemms & 0x7fffffff);  // MFMA GEMM launches inside gpc_quad_mix
   else if (n == "block_engine") *value = c->block_engine;
   else if (n == "block_engine_ran") *value = c->block_engine_ran;  // 1 / 2: what the last block append ran (0: none yet)
+  else if (n == "paths_engine") *value = c->paths_engine;
+  else if (n == "paths_engine_ran") *value = c->paths_engine_ran;  // 1 / 2: what the last gpc_paths_eval ran (0: none yet)
+  else if (n == "paths_solve_engine") *value = c->paths_solve_engine;
+  else if (n == "paths_solve_engine_ran") *value = c->paths_solve_engine_ran;  // 1 / 2: what the last gpc_paths_create ran
   else if (n == "block_appended") *value = (int)(c->block_appended & 0x7fffffff);  // samples gpc_post_append_block appended ...
   else if (n == "block_stale") *value = (int)(c->block_stale & 0x7fffffff);  // ... and left stale for gpc_post_recompute
   else if (n == "experiments") {  // 1: this library is the experiments build (tests/ and tools/ ask before they use its options)

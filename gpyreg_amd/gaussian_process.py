@@ -174,6 +174,81 @@ def _mean_grad_x(mean, hyp, X):
                               "respect to x_star is unknown")
 
 
+class PosteriorPaths:
+    """``GP.sample_paths``' result: ``n_paths`` sampled posterior FUNCTIONS per hyperparameter sample, evaluable --
+    with their gradient -- at any points, any number of times (``_paths`` has the formulas).  ``paths(x_star)`` returns
+    f (M, n_paths, S), ``paths(x_star, compute_grad=True)`` (f, df) with df (M, D, n_paths, S), entry [j, l] the
+    derivative with respect to x_star[j, l]; ``f[:, r, s]`` is the same function in every call.  The object owns device
+    copies of what evaluation needs: it describes the posterior as it was when ``sample_paths`` ran and stays valid after
+    the GP is updated.  ``close()`` frees the device memory (garbage collection does too).  It cannot be pickled or
+    copied: the handle cannot be recreated once the posterior has moved on."""
+
+    def __init__(self, n_paths, n_features, seed, D, kid, degree, mean, hyps, counts, handle=None, host=None,
+                 post_range=None, group=None):
+        self.n_paths, self.n_features, self.seed = n_paths, n_features, seed
+        self._D, self._kid, self._degree, self._mean, self._hyps, self._counts = D, kid, degree, mean, hyps, counts
+        self._handle, self._host, self._range, self._group = handle, host, post_range, group
+        self._closed = False
+
+    def __call__(self, x_star, compute_grad: bool = False):
+        from . import _paths
+
+        if self._closed:
+            raise ValueError("PosteriorPaths has been closed")
+        x_star = np.atleast_2d(np.asarray(x_star, dtype=float))
+        if x_star.ndim != 2 or x_star.shape[1] != self._D:
+            raise ValueError(f"x_star must be (M, {self._D}), got {x_star.shape}")
+        M, D, R = x_star.shape[0], self._D, self.n_paths
+        cov_N, noise_N, mean_N = self._counts
+        S = len(self._hyps)
+        h_mean = [h[cov_N + noise_N:cov_N + noise_N + mean_N] for h in self._hyps]
+        dm = [_mean_grad_x(self._mean, h, x_star) for h in h_mean] if compute_grad else None
+        if self._host is not None:  # a GP without data: prior paths (v = 0) on the host
+            f = np.empty((M, R, S))
+            df = np.empty((M, D, R, S)) if compute_grad else None
+            for s, (theta, b, wt) in enumerate(self._host):
+                out = _paths.evaluate(self._kid, self._degree, self._hyps[s][:cov_N], None, None, theta, b, wt, x_star,
+                                      compute_grad)
+                if compute_grad:
+                    f[:, :, s], df[:, :, :, s] = out
+                else:
+                    f[:, :, s] = out
+        else:
+            if self._handle is None:  # (a rank that holds no sample of the set)
+                f, df = np.zeros((M, R, 0)), np.zeros((M, D, R, 0))
+            elif compute_grad:
+                f, df = self._handle.eval(x_star, True)
+            else:
+                f, df = self._handle.eval(x_star, False), None
+            if self._range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
+                k = f.shape[2]
+                rows = f.reshape(M * R, k)
+                if compute_grad:
+                    rows = np.concatenate([rows, df.reshape(M * D * R, k)], axis=0)
+                full, _ = _sh.gather_rows(self._range[2], rows.shape[0], lambda a, b: (rows.T, np.zeros(b - a, bool)),
+                                          self._group, _sh.fingerprint(x_star, bool(compute_grad), self.seed))
+                rows = full.T.copy()
+                f = rows[:M * R].reshape(M, R, -1)
+                if compute_grad:
+                    df = rows[M * R:].reshape(M, D, R, -1)
+        for s in range(S):
+            f[:, :, s] += np.reshape(self._mean.compute(h_mean[s], x_star), (-1, 1))
+            if compute_grad:
+                df[:, :, :, s] += dm[s][:, :, None]
+        return (f, df) if compute_grad else f
+
+    def close(self):
+        """Free the device copies; the object cannot be called afterwards."""
+        self._closed = True
+        if self._handle is not None:
+            self._handle.free()
+            self._handle = None
+
+    def __reduce_ex__(self, protocol):
+        raise TypeError("PosteriorPaths cannot be pickled or copied: it owns device memory that describes the posterior "
+                        "at the time sample_paths ran and cannot be recreated; call sample_paths again")
+
+
 # GP.fit's options with the reference's defaults (gaussian_process.py:991-1006; "burn": thin * n_samples when unset)
 _FIT_DEFAULTS = {"opts_N": 3, "init_N": 2**10, "init_method": "sobol", "thin": 5, "df_base": 7, "widths": None,
                  "tol_opt": 1e-5, "tol_opt_mcmc": 1e-3, "sampler": "slicesample", "n_samples": 10, "burn": None,
@@ -1617,6 +1692,62 @@ class GP:
             rows = self._gather_samples(rows, x_star, n_draws, seed, nsd is not None)
             f, tau = rows[:M * n_draws].reshape(M, n_draws, -1), rows[M * n_draws].copy()
         return f, tau
+
+    def sample_paths(self, n_paths: int = 1, n_features: int = 1024, seed: int = 0):
+        """``n_paths`` sampled posterior functions per hyperparameter sample, as a ``PosteriorPaths`` object that
+        evaluates them -- and their gradients with respect to x -- at any points afterwards (Thompson sampling,
+        max-value and entropy searches, Monte-Carlo acquisitions); ``draw_functions`` draws at fixed points only.
+        Matheron's rule with ``n_features`` random Fourier features (``_paths``): the update term is exact, the prior part
+        approximate.  A path depends on (seed, sample, path index) only -- not on ``n_paths``, the batch of samples or the
+        sharding.  With data the features, the solve and every evaluation run on the device (gpc_paths_create /
+        gpc_paths_eval, fp64 also for fp32 posteriors); a GP without data gives prior paths on the host.  Squared-
+        exponential and Matern covariance functions (ARD and isotropic) only: the rational quadratic and user-defined
+        covariance objects raise NotImplementedError.  Under sharding each rank holds the paths of its samples and the
+        evaluations are gathered: the same values as one process."""
+        from . import _paths
+
+        if not self._builtin:
+            raise NotImplementedError(f"sample_paths: the covariance function {self.covariance!r} is user-defined; "
+                                      "paths need the spectral density of a built-in covariance function")
+        kid, degree = self._kid()
+        if kid == _paths.K_RQ:
+            raise NotImplementedError("sample_paths: the rational-quadratic covariance function is not supported; "
+                                      "spectral draws exist for the squared-exponential and Matern kernels")
+        for name, val in (("n_paths", n_paths), ("n_features", n_features)):
+            if isinstance(val, bool) or int(val) != val or val < 1:
+                raise ValueError(f"{name} must be a positive integer, got {val!r}")
+        n_paths, n_features = int(n_paths), int(n_features)
+        if isinstance(seed, bool) or int(seed) != seed or not 0 <= int(seed) < 2**64:
+            raise ValueError(f"seed must be an integer in [0, 2**64), got {seed!r}")
+        seed = int(seed)
+        s_N = self.posteriors.size
+        counts = self._counts()
+        cov_N = counts[0]
+        hyps = [np.array(self.posteriors[s].hyp, dtype=float) for s in range(s_N)]
+        if self.y is None:  # no data: prior paths, v = 0, on the host
+            host = [_paths.features(kid, degree, self.D, n_features, seed, s) + (_paths.weights(n_features, n_paths, seed, s),)
+                    for s in range(s_N)]
+            return PosteriorPaths(n_paths, n_features, seed, self.D, kid, degree, self.mean, hyps, counts, host=host)
+        handle, post_range = self._paths_on_device(n_paths, n_features, seed)
+        return PosteriorPaths(n_paths, n_features, seed, self.D, kid, degree, self.mean, hyps, counts, handle=handle,
+                              post_range=post_range, group=self.process_group)
+
+    @_on_device
+    def _paths_on_device(self, n_paths, n_features, seed):
+        """sample_paths' device part: (the ``_lib.Paths`` handle of this rank's samples or None, the shard range)."""
+        self._restore()
+        if self._post_handle is None and self._post_range is None:
+            raise ValueError("posteriors have been cleaned; call update() first")
+        self._ctx()
+        local_posts, lo = self._local_posteriors()
+        if not local_posts:
+            return None, self._post_range
+        pv = self._plugin_values(np.stack([p.hyp for p in local_posts]), False)
+        N = self.X.shape[0]
+        ym = np.reshape(self.y, (1, -1)) - pv["m"]
+        mult = np.array([1.0 if p.sn2_mult is None else float(p.sn2_mult) for p in local_posts])
+        nsd = np.sqrt(np.broadcast_to(pv["sn2"], (len(local_posts), N)) * mult[:, None]).T
+        return self._post_handle.paths(n_paths, n_features, seed, lo, ym, nsd), self._post_range
 
     @staticmethod
     def _jittered_cholesky(C, s):

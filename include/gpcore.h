@@ -182,6 +182,59 @@ int gpc_draw(gpc_post* post, const double* xstar, int M, int R, unsigned long lo
 int gpc_debug_normals(gpc_ctx* ctx, unsigned long long seed, int stream, int s, int r, int j0, int count,
                       double* out);
 
+/* ---- GP.sample_paths: pathwise posterior samples (Matheron's rule with random Fourier features) ------------
+ * A posterior FUNCTION per hyperparameter sample s and path r < R, to be evaluated -- with its gradient -- at any
+ * points afterwards (Thompson sampling, max-value and entropy searches, Monte-Carlo acquisitions):
+ *   f_{s,r}(x) = p_{s,r}(x) + k_s(x, X) v_{s,r}                                    (the mean function is the caller's)
+ *   p_{s,r}(x) = sqrt(2 sf2_s / F) sum_{f<F} wt_s[f][r] cos(theta_s[f] . xs(x) + b_s[f])
+ *   v_{s,r}    = (K_s + Sigma_s)^-1 (ym_s - p_{s,r}(X) - eps_{s,r}),   eps_{s,r}[i] = noise_sd[i*S + s] e_s[i][r]
+ * xs = x mul / dv are the scaled inputs of the kernel family (as gpc_predict_grad).  On scaled inputs the spectral
+ * draw is theta[f][l] = z[f][l] for GPC_K_SE / GPC_K_SE_ISO and z[f][l] / sqrt(c[f]), c[f] = sum_{q<d} g[f][q]^2, for
+ * Matern of degree d (the multivariate Student-t with d degrees of freedom).  The update term is exact; only the
+ * prior part is approximated, and F is the caller's choice.  Features are shared by the R paths of a sample.
+ * Random stream: gpc_draw's Philox4x64-10 and Box-Muller, key (seed, stream), sample index s_offset + s:
+ *   stream 2: z[f][l] = normal(r = l, j = f)     stream 3: g[f][q] = normal(r = q, j = f)
+ *   stream 4: b[f] = 2 pi (word(r = 0, j = f) >> 11) 2^-53
+ *   stream 5: wt[f][r] = normal(r, j = f)        stream 6: e[i][r] = normal(r, j = i)
+ * (gpyreg_amd/_paths.py restates all of it), so path r of sample s does not depend on R, on the batch of samples, on
+ * the chunking or on the sharding.
+ *
+ * gpc_paths_create: ym (S x N) = y - m_s(X), noise_sd (N x S) = sqrt(sn2_s[i] sn2_mult_s), both the caller's.
+ * Generates theta, b and wt on the device, forms the N x R panel p(X) + eps with the evaluation kernel (the N x F
+ * feature matrix is never stored) and solves for v with the resident factors as gpc_predict_grad forms Q: W^T (W r) / sl
+ * for L_chol samples, -(A r) otherwise.  The products are the skinny kernel of gpc_post_append_block, 16 right-hand
+ * sides per pass whatever R is -- so v of path r carries the same bits for any R; the test option
+ * "paths_solve_engine" = 2 runs them as MFMA GEMM launches on panels padded to 128 columns instead (get-only
+ * "paths_solve_engine_ran" tells which ran).  v, the features and the evaluation are fp64 whatever the posterior's
+ * storage type; fp32 posteriors only change what the solve reads.  The handle owns copies of everything evaluation
+ * needs (scaled training inputs, per-sample scalars and scaling, v, theta, b, wt): it describes the posterior at
+ * creation time and stays valid after the posterior is updated, appended to or freed (not after gpc_destroy).
+ * Scratch (three fp64 N_pad x R_pad16 panels per sample, three N_pad x R_pad128 panels in the storage type more for
+ * the MFMA engine) is budgeted like gpc_predict_cov's (GPC_MEM_BUDGET_MB) and chunked over the samples.  Returns -2
+ * with a message for R < 1 or F < 1, a posterior from caller-provided K, a sample whose factorization failed,
+ * GPC_K_RQ, null arguments, a context whose data is no longer the posterior's, or one sample's scratch exceeding
+ * the budget.  gpc_last_timing: the device section, and the solve's products.
+ *
+ * gpc_paths_eval: xstar M x D.  f[(j*R + r)*S + s]; df (may be NULL) [((j*D + l)*R + r)*S + s] = d f / d x*_jl:
+ *   d/dx*_jl k(x*_j, X_i) = -c_l F_ij (xs*_jl - xs_il)   (F, c_l of gpc_predict_grad; a pair at distance 0 gives 0)
+ *   d/dx*_jl p            = -c_l sqrt(2 sf2 / F) sum_f wt[f][r] theta[f][l] sin(theta[f] . xs* + b[f])
+ * One fused kernel: per 64-row tile of query points it forms 64 x 64 operand tiles in LDS -- cross covariances by the
+ * compile-time pair functor of gpc_predict, then the features -- and multiplies each straight into the v (wt) panel
+ * with v_mfma_f64_16x16x4_f64; neither K* nor the feature matrix is written.  Sums run over the tiles in ascending
+ * order without atomics: a value depends on (x, s, r) only -- not on M, the row's place, the other rows, or on
+ * whether df was asked for.  The test option "paths_engine" = 2 runs the unfused composition instead (operand
+ * matrices written to memory, then the library GEMM; equal to rounding), get-only "paths_engine_ran" tells which
+ * ran.  The results and the scratch (the scaled query points; for the unfused engine an operand matrix and padded
+ * panels per sample) are budgeted and chunked as above; -2 with a message when they do not fit.
+ * gpc_last_timing: the device section with the transfers, and the kernels alone.
+ * gpc_debug_paths_fetch (tests): theta (F x D), b (F), wt (F x R), v (N x R) of sample s; any may be NULL. */
+typedef struct gpc_paths gpc_paths;
+int gpc_paths_create(gpc_post* post, int R, int F, unsigned long long seed, int s_offset, const double* ym,
+                     const double* noise_sd, gpc_paths** out);
+int gpc_paths_eval(gpc_paths* p, const double* xstar, int M, double* f, double* df);
+int gpc_paths_free(gpc_paths* p);
+int gpc_debug_paths_fetch(gpc_paths* p, int s, double* theta, double* b, double* wt, double* v);
+
 /* ---- rank-one append of ONE training point to resident posteriors (GP.update fast path,
  *      gaussian_process.py:750-844; scalar noise) ------------------------------------------------
  * Call gpc_set_data with the extended X (N+1 rows; the new point last) and y first.
@@ -368,7 +421,9 @@ int gpc_last_lauum_timing(gpc_ctx* ctx, double* ms, double* flops);
  * reports their device section (it reports 0 for them otherwise; from N_pad = 2048 on the events are always recorded).
  * "small_polled" / "small_synced" (get only): how many calls ended either way.
  * "cov_fused" (get only): how many gpc_predict_cov calls formed their reduction in the product's epilogue.
- * "quad_mix_gemms" (get only): MFMA GEMM launches issued inside gpc_quad_mix over the life of the context (0 by design). */
+ * "quad_mix_gemms" (get only): MFMA GEMM launches issued inside gpc_quad_mix over the life of the context (0 by design).
+ * "paths_engine" / "paths_solve_engine" (test hooks) and "paths_engine_ran" / "paths_solve_engine_ran" (get only): see
+ * gpc_paths_create / gpc_paths_eval. */
 int gpc_set_option(gpc_ctx* ctx, const char* name, int value);
 /* Current value of a tuning switch (so that a caller that changes one for a measurement can put it back). */
 int gpc_get_option(gpc_ctx* ctx, const char* name, int* value);

@@ -1,0 +1,432 @@
+"""GP.sample_paths / gpc_paths_create / gpc_paths_eval: pathwise posterior samples on the device.  Parity with the host
+model (gpyreg_amd/_paths.py) fed the device's own posterior, the data identity paths(X) + eps + Sigma v = y, bitwise
+invariance of a path over batches of rows, paths, samples and ranks, both evaluation engines, the handle outliving the
+posterior, the empirical moments and the refusals.
+
+Base problem: N = 150 (N_pad = 256, the last 64-tile partial), D = 3, F = 96 (no multiple of 64), M = 70 (two row
+tiles, the second partial), S = 3 -- two samples with noise sd >= 0.05 sqrt(sf2) (L_chol) around one with
+sn2 = 5e-7 (Posterior.L = -(K + Sigma)^-1)."""
+
+import os
+import pickle
+import socket
+import sys
+
+import numpy as np
+import pytest
+
+from gpyreg_amd import _paths
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EPS = np.finfo(float).eps
+
+N, D, F, M = 150, 3, 96, 70
+SN2 = (1e-2, 5e-7, 4e-3)  # sf2 = 1: noise sd 0.1 and 0.063 >= 0.05 sqrt(sf2); 5e-7 < 1e-6 gives the -inv form
+KINDS = [("se", 0), ("matern", 1), ("matern", 3), ("matern", 5), ("se_iso", 0), ("matern_iso", 5)]
+KID = {"se": _paths.K_SE, "matern": _paths.K_MATERN, "se_iso": _paths.K_SE_ISO, "matern_iso": _paths.K_MATERN_ISO}
+
+
+def _gp(kernel, degree, dtype="f64"):
+    from test_gpu_api import _gp as make
+
+    return make(dict(kernel=kernel, degree=degree, mean="const", noise=(1, 0, 0)), D, dtype)
+
+
+def _data():
+    rng = np.random.default_rng(21)
+    X = rng.uniform(-3, 3, (N, D))
+    y = np.sin(X.sum(1, keepdims=True)) + 0.05 * rng.standard_normal((N, 1))
+    xq = rng.uniform(-3, 3, (M, D))
+    return X, y, xq
+
+
+def _hyp(kernel, sn2s=SN2):
+    """One row per noise variance: length scales near 1 (cond(K + Sigma) of the low-noise sample stays below 1e4, see
+    test_parity_with_the_host_model), sf2 = 1, constant mean 0.1."""
+    rng = np.random.default_rng(5)
+    n_ell = 1 if kernel.endswith("_iso") else D
+    return np.array([np.r_[0.05 * rng.standard_normal(n_ell), 0.0, 0.5 * np.log(v), 0.1] for v in sn2s])
+
+
+_CACHE = {}
+
+
+def _problem(kernel="matern", degree=5, dtype="f64", sn2s=SN2):
+    """(gp, X, y, xq, hyp) of the base problem, built once per configuration and left unchanged."""
+    key = (kernel, degree, dtype, sn2s)
+    if key not in _CACHE:
+        X, y, xq = _data()
+        hyp = _hyp(kernel, sn2s)
+        gp = _gp(kernel, degree, dtype)
+        gp.update(X_new=X, y_new=y, hyp=hyp)
+        assert [bool(p.L_chol) for p in gp.posteriors] == [v >= 1e-6 for v in sn2s]
+        _CACHE[key] = (gp, X, y, xq, hyp)
+    return _CACHE[key]
+
+
+def _cov_part(kernel, hyp_row):
+    return hyp_row[:(1 if kernel.endswith("_iso") else D) + 1]
+
+
+def _host_paths(gp, kernel, degree, X, y, hyp, R, seed, s, s_global=None):
+    """The host model of sample s with the DEVICE's posterior: (theta, b, wt, v, eps, Sigma diag, cond(K + Sigma))."""
+    s_global = s if s_global is None else s_global
+    kid = KID[kernel]
+    hc = _cov_part(kernel, hyp[s])
+    p = gp.posteriors[s]
+    theta, b = _paths.features(kid, degree, D, F, seed, s_global)
+    wt = _paths.weights(F, R, seed, s_global)
+    sn2 = np.exp(2 * hyp[s, len(hc)]) * p.sn2_mult
+    eps = np.sqrt(sn2) * _paths.noise(N, R, seed, s_global)
+    xs, c, sf2 = _paths.scale_inputs(kid, degree, hc, X)
+    pX = _paths.prior_part(xs, c, sf2, theta, b, wt)
+    rhs = y - hyp[s, -1] - pX - eps
+    if p.L_chol:  # (K + Sigma)^-1 = sW U^-1 U^-T sW, U the device's upper factor
+        v = p.sW * np.linalg.solve(p.L, np.linalg.solve(p.L.T, p.sW * rhs))
+    else:
+        v = -(p.L @ rhs)
+    d = xs[:, None] - xs[None]
+    K, _ = _paths.pair(kid, degree, np.sum(d * d, 2), sf2)
+    return theta, b, wt, v, eps, sn2, np.linalg.cond(K + sn2 * np.eye(N))
+
+
+def _rel(a, ref):
+    return np.max(np.abs(a - ref)) / np.max(np.abs(ref))
+
+
+@pytest.mark.parametrize("R", [5, 20])
+@pytest.mark.parametrize("kernel,degree", KINDS)
+def test_parity_with_the_host_model(kernel, degree, R):
+    """theta, b, wt, v, f and df against _paths.py fed the device's posterior.  L_chol samples: 1e-8 x max|f|, the
+    project's fp64 parity.  The -inv sample: 100 eps cond(K + Sigma) x max|f| with cond computed here -- a condition,
+    not a measurement; the sample's hyperparameters keep it below 1e-6 (checked on the host when this was written:
+    cond <= 7.7e3, bound <= 1.7e-10 over the six kinds).  R = 5: one skinny pass, the panel padded to 16; R = 20: two
+    16-column groups -- and the MFMA engine of the solve under the test option."""
+    from gpyreg_amd import _lib
+
+    gp, X, y, xq, hyp = _problem(kernel, degree)
+    ctx = _lib.context()
+    seed = 7
+    for solve_engine in ((0, 2) if R == 20 else (0,)):
+        ctx.set_option("paths_solve_engine", solve_engine)
+        try:
+            paths = gp.sample_paths(n_paths=R, n_features=F, seed=seed)
+        finally:
+            ctx.set_option("paths_solve_engine", 0)
+        assert ctx.get_option("paths_solve_engine_ran") == (2 if solve_engine == 2 else 1)
+        f, df = paths(xq, compute_grad=True)
+        assert f.shape == (M, R, 3) and df.shape == (M, D, R, 3)
+        for s in range(3):
+            theta, b, wt, v, _, _, cond = _host_paths(gp, kernel, degree, X, y, hyp, R, seed, s)
+            tol = 1e-8 if gp.posteriors[s].L_chol else 100 * EPS * cond
+            assert tol < 1e-6
+            dth, db, dwt, dv = paths._handle.fetch(s)
+            for name, dev, ref in (("theta", dth, theta), ("b", db, b), ("wt", dwt, wt)):
+                err = np.max(np.abs(dev - ref) / np.maximum(1.0, np.abs(ref)))
+                print(kernel, degree, R, s, name, err)
+                assert err <= 1e-12, (name, s, err)  # a few ulp of the two math libraries through sqrt and a quotient
+            print(kernel, degree, R, solve_engine, s, "v", _rel(dv, v), "tol", tol)
+            assert _rel(dv, v) <= tol, (s, _rel(dv, v), tol)
+            rf, rdf = _paths.evaluate(KID[kernel], degree, _cov_part(kernel, hyp[s]), X, v, theta, b, wt, xq, True)
+            rf = rf + hyp[s, -1]
+            print(kernel, degree, R, solve_engine, s, "f", _rel(f[:, :, s], rf), "df", _rel(df[:, :, :, s], rdf))
+            assert _rel(f[:, :, s], rf) <= tol and _rel(df[:, :, :, s], rdf) <= tol, (s, tol)
+        paths.close()
+
+
+def test_fp32_posterior_parity():
+    """fp32 posteriors only change what the solve reads: v, f and df within 1e-3 of the host model."""
+    kernel, degree, R, seed = "matern", 5, 20, 7
+    gp, X, y, xq, hyp = _problem(kernel, degree, "f32")
+    paths = gp.sample_paths(n_paths=R, n_features=F, seed=seed)
+    f, df = paths(xq, compute_grad=True)
+    for s in range(3):
+        theta, b, wt, v, _, _, _ = _host_paths(gp, kernel, degree, X, y, hyp, R, seed, s)
+        dv = paths._handle.fetch(s)[3]
+        rf, rdf = _paths.evaluate(KID[kernel], degree, _cov_part(kernel, hyp[s]), X, v, theta, b, wt, xq, True)
+        errs = _rel(dv, v), _rel(f[:, :, s], rf + hyp[s, -1]), _rel(df[:, :, :, s], rdf)
+        print(s, errs)
+        assert max(errs) <= 1e-3, (s, errs)
+
+
+@pytest.mark.parametrize("kernel,degree", [("matern", 5), ("se", 0), ("matern", 1)])
+def test_data_identity(kernel, degree):
+    """paths(X)[:, r, s] + eps + Sigma v = y for every r and s, to 1e-8 x max|y|: no model needed -- it ties the
+    evaluation kernel's cross covariances (and features) to what the solve inverted."""
+    gp, X, y, xq, hyp = _problem(kernel, degree)
+    R, seed = 20, 3
+    paths = gp.sample_paths(n_paths=R, n_features=F, seed=seed)
+    fX = paths(X)
+    for s in range(3):
+        v = paths._handle.fetch(s)[3]
+        sn2 = np.exp(2 * hyp[s, -2]) * gp.posteriors[s].sn2_mult
+        eps = np.sqrt(sn2) * _paths.noise(N, R, seed, s)
+        err = np.max(np.abs(fX[:, :, s] + eps + sn2 * v - y))
+        print(kernel, degree, s, err / np.max(np.abs(y)))
+        assert err <= 1e-8 * np.max(np.abs(y)), (s, err)
+
+
+def test_a_path_is_a_function():
+    """All 70 rows, rows 0..63 then 64..69, and a permutation give the same bits row by row, with and without the
+    gradient; f is the same bits with and without it; a second call gives the same bits."""
+    gp, X, y, xq, hyp = _problem()
+    paths = gp.sample_paths(n_paths=20, n_features=F, seed=1)
+    f = paths(xq)
+    fg, dfg = paths(xq, compute_grad=True)
+    assert np.array_equal(f, fg)
+    assert np.array_equal(paths(xq), f)
+    f2, df2 = paths(xq, compute_grad=True)
+    assert np.array_equal(f2, fg) and np.array_equal(df2, dfg)
+    assert np.array_equal(np.concatenate([paths(xq[:64]), paths(xq[64:])]), f)
+    a, da = paths(xq[:64], compute_grad=True)
+    b, db = paths(xq[64:], compute_grad=True)
+    assert np.array_equal(np.concatenate([a, b]), f) and np.array_equal(np.concatenate([da, db]), dfg)
+    perm = np.random.default_rng(0).permutation(M)
+    assert np.array_equal(paths(xq[perm]), f[perm])
+    fp, dfp = paths(xq[perm], compute_grad=True)
+    assert np.array_equal(fp, f[perm]) and np.array_equal(dfp, dfg[perm])
+    assert np.all(np.isfinite(f)) and np.all(np.isfinite(dfg))
+
+
+def test_independence_of_the_batch_of_paths_and_samples():
+    gp, X, y, xq, hyp = _problem()
+    seed = 4
+    p5 = gp.sample_paths(n_paths=5, n_features=F, seed=seed)
+    p20 = gp.sample_paths(n_paths=20, n_features=F, seed=seed)
+    f5, d5 = p5(xq, compute_grad=True)
+    f20, d20 = p20(xq, compute_grad=True)
+    assert np.array_equal(f5, f20[:, :5]) and np.array_equal(d5, d20[:, :, :5])
+    # a sample by itself under its global index: the GP holds only that sample's hyperparameters
+    for s in range(3):
+        one = _gp("matern", 5)
+        one.update(X_new=X, y_new=y, hyp=hyp[s:s + 1])
+        pv = one._plugin_values(hyp[s:s + 1], False)
+        ym = y.reshape(1, -1) - pv["m"]
+        nsd = np.sqrt(np.broadcast_to(pv["sn2"], (1, N)) * float(one.posteriors[0].sn2_mult)).T
+        h = one._post_handle.paths(5, F, seed, s, ym, nsd)
+        fs, ds = h.eval(xq, True)
+        assert np.array_equal(fs[:, :, 0] + hyp[s, -1], f5[:, :, s]) and np.array_equal(ds[:, :, :, 0], d5[:, :, :, s])
+        h.free()
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _shard_worker(rank, world, port, q):
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+                      GPYREG_AMD_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
+    import torch.distributed as dist
+
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import test_gpu_sample_paths as t
+
+        X, y, xq = t._data()
+        hyp = t._hyp("matern")
+        out = {}
+        res = []
+        for shard in (False, True):
+            gp = t._gp("matern", 5)
+            gp.shard = shard
+            gp.update(X_new=X, y_new=y, hyp=hyp)
+            paths = gp.sample_paths(n_paths=5, n_features=t.F, seed=9)
+            res.append((paths(xq),) + paths(xq, compute_grad=True))
+            out["sharded" if shard else "local"] = gp._post_range is not None
+        out["equal"] = bool(all(np.array_equal(a, b) for a, b in zip(*res)))
+        q.put((rank, out))
+    except Exception:  # noqa: BLE001
+        import traceback
+
+        q.put((rank, {"exception": traceback.format_exc()}))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_two_ranks_on_one_gpu_equal_one_process_bitwise():
+    import torch.multiprocessing as mp
+
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_shard_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = dict(q.get(timeout=300) for _ in procs)
+    for p in procs:
+        p.join(60)
+        assert p.exitcode == 0
+    for rank in (0, 1):
+        r = res[rank]
+        assert "exception" not in r, r.get("exception")
+        assert r == dict(local=False, sharded=True, equal=True), (rank, r)
+
+
+def test_both_evaluation_engines_agree():
+    from gpyreg_amd import _lib
+
+    gp, X, y, xq, hyp = _problem()
+    ctx = _lib.context()
+    paths = gp.sample_paths(n_paths=20, n_features=F, seed=2)
+    out = {}
+    try:
+        for engine in (1, 2):
+            ctx.set_option("paths_engine", engine)
+            out[engine] = paths(xq, compute_grad=True)
+            assert ctx.get_option("paths_engine_ran") == engine
+    finally:
+        ctx.set_option("paths_engine", 0)
+    paths(xq[:3])
+    assert ctx.get_option("paths_engine_ran") in (1, 2) and ctx.get_option("paths_engine") == 0
+    for a, b in zip(out[1], out[2]):
+        print(_rel(a, b))
+        assert _rel(a, b) <= 1e-10
+
+
+def test_the_handle_outlives_the_posterior():
+    X, y, xq = _data()
+    hyp = _hyp("matern")
+    gp = _gp("matern", 5)
+    gp.update(X_new=X[:120], y_new=y[:120], hyp=hyp)
+    old = gp.sample_paths(n_paths=5, n_features=F, seed=6)
+    before = old(xq, compute_grad=True)
+    gp.update(X_new=X[120:], y_new=y[120:])  # 30 more points: the posterior set is replaced
+    after = old(xq, compute_grad=True)
+    assert all(np.array_equal(a, b) for a, b in zip(before, after))
+    new = gp.sample_paths(n_paths=5, n_features=F, seed=6)(xq)
+    assert not np.array_equal(new, before[0])
+    gp.clean()
+    assert np.array_equal(old(xq), before[0])
+
+
+def _moments_problem():
+    rng = np.random.default_rng(8)
+    Nm, Dm = 40, 2
+    X = rng.uniform(-3, 3, (Nm, Dm))
+    y = np.sin(X.sum(1, keepdims=True)) + 0.1 * rng.standard_normal((Nm, 1))
+    xq = rng.uniform(-3, 3, (8, Dm))
+    hyp = np.array([[0.0, 0.1, 0.0, np.log(0.1), 0.0], [0.2, -0.1, 0.1, np.log(0.2), 0.1]])
+    return X, y, xq, hyp
+
+
+def _moments_host_deviation(seeds, R=1024, n_features=4096):
+    """The host model alone (no device): worst |var over paths - fs2| / fs2 over the given seeds, both samples and the 8
+    points, fs2 the exact posterior variance."""
+    X, y, xq, hyp = _moments_problem()
+    worst = 0.0
+    for seed in seeds:
+        for s in range(2):
+            hc, sn2, m0 = hyp[s, :3], np.exp(2 * hyp[s, 3]), hyp[s, 4]
+            theta, b = _paths.features(_paths.K_SE, 0, 2, n_features, seed, s)
+            wt = _paths.weights(n_features, R, seed, s)
+            xs, c, sf2 = _paths.scale_inputs(_paths.K_SE, 0, hc, X)
+            xqs = _paths.scale_inputs(_paths.K_SE, 0, hc, xq)[0]
+            K = _paths.pair(_paths.K_SE, 0, np.sum((xs[:, None] - xs[None]) ** 2, 2), sf2)[0]
+            Ks = _paths.pair(_paths.K_SE, 0, np.sum((xs[:, None] - xqs[None]) ** 2, 2), sf2)[0]
+            A = K + sn2 * np.eye(len(X))
+            rhs = y - m0 - _paths.prior_part(xs, c, sf2, theta, b, wt) - np.sqrt(sn2) * _paths.noise(len(X), R, seed, s)
+            f = _paths.evaluate(_paths.K_SE, 0, hc, X, np.linalg.solve(A, rhs), theta, b, wt, xq)
+            fs2 = sf2 - np.sum(Ks * np.linalg.solve(A, Ks), 0)
+            worst = max(worst, float(np.max(np.abs(f.var(axis=1, ddof=1) - fs2) / fs2)))
+    return worst
+
+
+# _moments_host_deviation(range(1, 21)), measured on the host when this test was written: the random-feature bias does
+# not shrink with R, so the variance bound of test_moments is twice this measurement, not a derivation
+MOMENTS_VAR_DEV_HOST = 0.23279  # seed 2; the other seeds 0.10 .. 0.19
+
+
+def test_moments():
+    """N = 40, D = 2, SE, S = 2, M = 8, R = 1024, F = 4096, seed 0.  The mean over paths lies within 5 empirical
+    standard errors of predict's mean (the estimator is unbiased given the features).  The variance over paths
+    against predict's fs2: bound 2 x MOMENTS_VAR_DEV_HOST = 0.466, the host model's own worst deviation over seeds
+    1..20 (measured 0.23279)."""
+    from test_gpu_api import _gp as make
+
+    X, y, xq, hyp = _moments_problem()
+    gp = make(dict(kernel="se", degree=0, mean="const", noise=(1, 0, 0)), 2)
+    gp.update(X_new=X, y_new=y, hyp=hyp)
+    R = 1024
+    f = gp.sample_paths(n_paths=R, n_features=4096, seed=0)(xq)
+    mu, s2 = gp.predict(xq, separate_samples=True)
+    mean, var = f.mean(axis=1), f.var(axis=1, ddof=1)
+    z = np.abs(mean - mu) / np.sqrt(var / R)
+    dev = np.abs(var - s2) / s2
+    print("mean z-scores", z.max(), "variance deviation", dev.max())
+    assert z.max() <= 5.0
+    assert dev.max() <= 2 * MOMENTS_VAR_DEV_HOST
+
+
+def test_refusals(monkeypatch):
+    import gpyreg_amd as gpr
+    from gpyreg_amd import _lib
+    from test_gpu_user_kernel import PySquaredExponential
+
+    gp, X, y, xq, hyp = _problem()
+    # a posterior built from a caller's K: refused by GP.sample_paths and by the library itself
+    user = gpr.GP(D, PySquaredExponential(), gpr.mean_functions.ConstantMean(),
+                  gpr.noise_functions.GaussianNoise(constant_add=True))
+    user.update(X_new=X, y_new=y, hyp=_hyp("se")[:1])
+    with pytest.raises(NotImplementedError, match="user-defined"):
+        user.sample_paths()
+    with pytest.raises(RuntimeError, match="caller-provided K"):
+        user._post_handle.paths(2, 8, 0, 0, np.zeros((1, N)), np.ones((N, 1)))
+    rq = _gp("rq", 0)
+    rq.update(X_new=X, y_new=y, hyp=np.array([[0.0, 0.0, 0.0, 0.0, 0.0, np.log(0.1), 0.0]]))
+    with pytest.raises(NotImplementedError, match="rational-quadratic"):
+        rq.sample_paths()
+    with pytest.raises(RuntimeError, match="rational-quadratic"):
+        rq._post_handle.paths(2, 8, 0, 0, np.zeros((1, N)), np.ones((N, 1)))
+    h = gp._post_handle
+    for R_, F_ in ((0, 8), (2, 0), (-1, 8)):
+        with pytest.raises(RuntimeError, match="at least 1"):
+            h.paths(R_, F_, 0, 0, np.zeros((3, N)), np.ones((N, 3)))
+    with pytest.raises(ValueError, match="n_paths"):
+        gp.sample_paths(n_paths=0)
+    paths = gp.sample_paths(n_paths=2, n_features=8)
+    with pytest.raises(TypeError, match="cannot be pickled"):
+        pickle.dumps(paths)
+    # a budget too small for one sample
+    monkeypatch.setenv("GPC_MEM_BUDGET_MB", "0")
+    with pytest.raises(RuntimeError, match="exceeds the device memory budget"):
+        gp.sample_paths(n_paths=2, n_features=8)
+    with pytest.raises(RuntimeError, match="exceed the device memory budget"):
+        paths(xq)
+    monkeypatch.delenv("GPC_MEM_BUDGET_MB")
+    assert paths(xq).shape == (M, 2, 3)
+    # cleaned posteriors
+    cleaned = _gp("matern", 5)
+    cleaned.update(X_new=X, y_new=y, hyp=hyp)
+    cleaned.clean()
+    with pytest.raises(ValueError, match="cleaned"):
+        cleaned.sample_paths()
+
+
+def test_chunked_creation_and_evaluation_keep_the_bits(monkeypatch):
+    """Budgets that hold two samples' scratch of the solve (GPC_MEM_BUDGET_MB = 1 at R = 40: three 96 KB panels each) and
+    one sample's of the unfused engine (2 MB: 789 KB each beside 268 KB of results): the same bits as one chunk."""
+    from gpyreg_amd import _lib
+
+    gp, X, y, xq, hyp = _problem()
+    ctx = _lib.context()
+    ref = gp.sample_paths(n_paths=40, n_features=F, seed=5)
+    monkeypatch.setenv("GPC_MEM_BUDGET_MB", "1")
+    paths = gp.sample_paths(n_paths=40, n_features=F, seed=5)
+    monkeypatch.delenv("GPC_MEM_BUDGET_MB")
+    try:
+        for engine in (1, 2):
+            ctx.set_option("paths_engine", engine)
+            want = ref(xq, compute_grad=True)
+            monkeypatch.setenv("GPC_MEM_BUDGET_MB", "2")
+            got = paths(xq, compute_grad=True)
+            monkeypatch.delenv("GPC_MEM_BUDGET_MB")
+            assert all(np.array_equal(a, b) for a, b in zip(want, got)), engine
+    finally:
+        ctx.set_option("paths_engine", 0)
