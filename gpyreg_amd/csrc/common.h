@@ -16,6 +16,16 @@ constexpr int WAVE = 64;
 
 inline int pad_tile(int n) { return ((n + TILE - 1) / TILE) * TILE; }
 
+// How many of S samples a consumer works on at a time: each needs `per` bytes of scratch beside `shared` bytes the
+// whole call needs once, and `budget` bytes may be used (the caller has taken its 80 % already; gpcore.hip:
+// plan_chunk).  0: not even one sample fits and the caller refuses -- or, with clamp_to_one, runs one sample at a time
+// whatever the budget says (the evaluations and predictions, which have always done so).  Host only, no HIP call.
+inline int chunk_from_budget(int S, size_t per, size_t shared, size_t budget, bool clamp_to_one) {
+  if (budget < shared + per) return clamp_to_one ? 1 : 0;
+  const size_t fit = (budget - shared) / per;
+  return (int)(fit < (size_t)S ? fit : (size_t)S);
+}
+
 // `info` of a factorization: 0 = done, k > 0 = the pivot of row k was not positive (LAPACK's convention; the host
 // retries with more jitter, gaussian_process.py:2413-2421), bit 30 = a hand-off inside a leaf timed out (leaf.h) --
 // an internal error, reported as such and never retried

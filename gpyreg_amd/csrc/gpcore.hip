@@ -2168,6 +2168,104 @@ size_t free_device_bytes() {
   return f;
 }
 
+// ---- what every posterior consumer shares (DESIGN.md "Posterior consumers") ---------------------------------------
+// The samples per chunk of a call (common.h: chunk_from_budget): all S when the scratch held from earlier calls `fits`
+// and no budget is forced (GPC_MEM_BUDGET_MB, the tests' way into the chunked paths).  Otherwise the pool is given back
+// and 80 % of [free memory + `held`, the scratch this call may regrow, - `reserve`, what it allocates beside] is divided;
+// a forced budget stands for the scratch alone.  Returns 0 with c->err = what(budget) when a caller that does not clamp
+// to one sample cannot fit one.  (hipMemGetInfo is slow: consulted here only.)
+template <typename What = std::string (*)(size_t)>
+int plan_chunk(gpc_ctx* c, int S, size_t per, size_t shared, size_t held, bool fits, size_t reserve, bool clamp_to_one,
+               What&& what = nullptr) {
+  const bool forced = getenv("GPC_MEM_BUDGET_MB") != nullptr;
+  if (!forced && fits) return S;
+  c->pool_drain();
+  size_t avail = free_device_bytes() + (forced ? 0 : held);
+  if (!forced) avail = avail > reserve ? avail - reserve : 0;
+  const size_t budget = (size_t)(avail * 0.8);
+  const int chunk = chunk_from_budget(S, per, shared, budget, clamp_to_one);
+  if (!chunk) c->err = what(budget);
+  return chunk;
+}
+
+// A consumer reads every sample's factor: none may have failed
+inline int require_factorized(const gpc_post* po, const char* fn) {
+  for (int s = 0; s < po->S; ++s)
+    if (po->info[s] != 0) FAIL(po->ctx, std::string(fn) + ": posterior contains a failed factorization");
+  return 0;
+}
+
+// fn(a, len, lch) for every run of equal L_chol among samples s0 .. s0 + cnt - 1 (the run starts at s0 + a and shares
+// launches).  Every kernel works per sample in an order fixed by the shape: cutting runs or chunks changes no bit.
+template <typename Fn>
+int for_lchol_runs(const gpc_post* po, int s0, int cnt, Fn&& fn) {
+  for (int a = 0; a < cnt;) {
+    int e = a;
+    while (e < cnt && po->lchol[s0 + e] == po->lchol[s0 + a]) ++e;
+    if (int rc = fn(a, e - a, po->lchol[s0 + a] != 0)) return rc;
+    a = e;
+  }
+  return 0;
+}
+
+// C = A B for a batch of n x n left operands A (stride sA) and n x ncols panels B, C (stride sB, leading dimension
+// ld): `lower` = A is lower triangular, tile row ti needs k < (ti + 1) 128 only (KHI_ROW)
+inline GemmArgs tri_gemm_args(const void* A, long long sA, int n, bool lower, const void* B, void* C, long long sB, int ld,
+                              int ncols) {
+  GemmArgs g;
+  g.A = A, g.B = B, g.C = C;
+  g.sA = sA, g.sB = g.sC = sB;
+  g.lda = n, g.ldb = g.ldc = ld;
+  g.M = n, g.N = ncols, g.K = n;
+  g.alpha = 1.0, g.beta = 0;
+  g.klo = KLO_ZERO, g.khi = lower ? KHI_ROW : KHI_FULL, g.lower_only = 0;
+  return g;
+}
+// ... with the posterior's own left operand from sample s_first on: V = W R (L_chol) | G = L R (L = -inv, full)
+template <typename T>
+GemmArgs tri_product_args(const gpc_post* po, int s_first, bool lch, const T* B, T* C, long long sB, int ldb, int ncols) {
+  const long long sM = (long long)po->npad * po->npad;
+  return tri_gemm_args((lch ? po->W.as<T>() : po->A.as<T>()) + (size_t)s_first * sM, sM, po->npad, lch, B, C, sB, ldb, ncols);
+}
+
+// The four timing events of a call: gpc_last_timing reports ev[0] -> ev[3] as its device time, ev[1] -> ev[2] as its
+// products'.  Each is a barrier packet on the stream: below N_pad = 2048 recorded on request only ("small_timing").
+struct CallTimer {
+  gpc_ctx* c;
+  bool on;
+  static bool wanted(const gpc_ctx* c, int npad) { return c->small_timing != 0 || npad >= 2048; }
+  hipError_t record(int i) { return on ? hipEventRecord(c->ev[i], c->st) : hipSuccess; }
+  hipError_t start() { return record(0); }
+  hipError_t mark1() { return record(1); }
+  hipError_t mark2() { return record(2); }
+  hipError_t stop() { return record(3); }
+  void accumulate() {  // (after the stream has been waited for)
+    if (!on) return;
+    float t03 = 0, t12 = 0;
+    (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
+    (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
+    c->ms_total += t03;
+    c->ms_factor += t12;
+  }
+};
+
+// Landing block of a chunk's results: pinned when there is room, else pageable (uninitialised: all of it is downloaded)
+inline double* landing_block(gpc_ctx* c, size_t bytes, std::unique_ptr<double[]>& spare) {
+  double* p = bytes <= PinBuf::kMax ? static_cast<double*>(c->pin.alloc(bytes)) : nullptr;
+  if (!p) {
+    spare.reset(new double[bytes / 8]);
+    p = spare.get();
+  }
+  return p;
+}
+// out[jl * S + s0 + i] = f * plane[i * ss + jl], jl < n: the chunk's samples side by side, the output written in order
+inline void scatter_plane(double* out, const double* plane, size_t n, size_t ss, int S, int s0, int cnt, double f = 1.0) {
+  for (size_t jl = 0; jl < n; ++jl) {
+    double* o = out + jl * S + s0;
+    for (int i = 0; i < cnt; ++i) o[i] = f * plane[i * ss + jl];
+  }
+}
+
 // caller-provided covariance matrices (K-mode): S matrices of N x N doubles, and the dK plane callback
 struct KArgs {
   const double* K = nullptr;
@@ -2188,17 +2286,10 @@ int nll_impl(gpc_ctx* c, Batch& b, int want_grad, const double* dm, int mean_N, 
              const KArgs* km = nullptr) {
   const int S = b.S, npad = b.npad, N = b.N;
   const size_t per = 3ull * npad * npad * sizeof(T);
-  int chunk = S;
-  const bool forced = getenv("GPC_MEM_BUDGET_MB") != nullptr;
   const size_t one = (size_t)npad * npad * sizeof(T);
-  if (forced || (size_t)S * one > std::min(c->mA.bytes, std::min(c->mW.bytes, c->mT.bytes))) {
-    // the workspace must grow: size the chunk to what is free (hipMemGetInfo is slow, so it is
-    // only consulted here)
-    c->pool_drain();
-    size_t budget = free_device_bytes() + (forced ? 0 : c->mA.bytes + c->mW.bytes + c->mT.bytes);
-    budget = (size_t)(budget * 0.8);
-    chunk = (int)std::max<size_t>(1, std::min<size_t>(S, budget / per));
-  }
+  // (when the workspace must grow, the chunk is sized to what is free; one sample runs whatever the budget says)
+  const int chunk = plan_chunk(c, S, per, 0, c->mA.bytes + c->mW.bytes + c->mT.bytes,
+                               (size_t)S * one <= std::min(c->mA.bytes, std::min(c->mW.bytes, c->mT.bytes)), 0, true);
   HIPCHK(c, c->mA.ensure((size_t)chunk * npad * npad * sizeof(T)));
   HIPCHK(c, c->mW.ensure((size_t)chunk * npad * npad * sizeof(T)));
   HIPCHK(c, c->mT.ensure((size_t)chunk * npad * npad * sizeof(T)));
@@ -2304,12 +2395,7 @@ int post_impl(gpc_ctx* c, Batch& b, gpc_post* po, double* sn2_mult, int* L_chol,
   HIPCHK(c, po->W.ensure(S * msz));
   HIPCHK(c, po->alpha.ensure((size_t)S * npad * sizeof(double)));
   hc.lap("alloc A,W");
-  int chunk = S;
-  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * msz > c->mT.bytes) {
-    c->pool_drain();
-    size_t budget = (size_t)((free_device_bytes() + (getenv("GPC_MEM_BUDGET_MB") ? 0 : c->mT.bytes)) * 0.8);
-    chunk = (int)std::max<size_t>(1, std::min<size_t>(S, budget / msz));
-  }
+  const int chunk = plan_chunk(c, S, msz, 0, c->mT.bytes, (size_t)S * msz <= c->mT.bytes, 0, true);
   HIPCHK(c, c->mT.ensure((size_t)chunk * msz));
   hc.lap("alloc T");
 
@@ -2483,22 +2569,7 @@ int draw_chunk(gpc_post* po, const DrawReq& d, int s0, int cnt, int M, const dou
   const long long s_base = (long long)d.s_offset + s0;
   hipLaunchKernelGGL((normals_kernel<T>), dim3(rpad / 64, mpad / 16, cnt), blk, 0, st, d.seed, 0, s_base, M, R, mpad,
                      rpad, c->zb.as<T>(), sZ);
-  GemmArgs g;
-  g.A = A;
-  g.B = c->zb.as<T>();
-  g.C = c->fb.as<T>();
-  g.sA = sKss;
-  g.sB = g.sC = sZ;
-  g.lda = mpad;
-  g.ldb = g.ldc = rpad;
-  g.M = mpad;
-  g.N = rpad;
-  g.K = mpad;
-  g.alpha = 1.0;
-  g.beta = 0;
-  g.klo = KLO_ZERO;
-  g.khi = KHI_ROW;  // L lower triangular: tile row ti needs k < (ti + 1) 128 only
-  g.lower_only = 0;
+  const GemmArgs g = tri_gemm_args(A, sKss, mpad, true, c->zb.as<T>(), c->fb.as<T>(), sZ, rpad, rpad);  // F = L Z
   HIPCHK(c, launch_gemm<T>(st, g, false, true, cnt));
   hipLaunchKernelGGL((draw_assemble_kernel<T>), dim3((R + 63) / 64, mpad / 16, cnt), blk, 0, st, (const T*)c->fb.as<T>(),
                      sZ, rpad, d_mu, mpad, M, R, (const double*)d_nsd, po->S, s0, d.seed, s_base, c->dout.as<double>());
@@ -2529,364 +2600,371 @@ int post_consts_resident(gpc_post* po) {
   return 0;
 }
 
+// The posterior's per-sample constants as the kernels of a chunk read them: the resident copies when the call works on
+// all samples at once (the usual case), else the context's buffers, refilled for every chunk by stage()
+struct ChunkConsts {
+  gpc_post* po = nullptr;
+  bool resident = false;
+  const double *spb = nullptr, *mulb = nullptr, *divb = nullptr, *xsb = nullptr;
+  int init(gpc_post* po_, bool resident_) {
+    po = po_;
+    resident = resident_;
+    if (resident)
+      if (int rc = post_consts_resident(po)) return rc;
+    gpc_ctx* c = po->ctx;
+    spb = resident ? po->dsp.as<double>() : c->spb.as<double>();
+    mulb = resident ? po->dmul.as<double>() : c->mulb.as<double>();
+    divb = resident ? po->ddv.as<double>() : c->divb.as<double>();
+    xsb = resident ? po->dxs.as<double>() : c->xs.as<double>();
+    return 0;
+  }
+  // samples s0 .. s0 + cnt - 1 into the context's buffers; need_xs: the scaled training inputs too
+  int stage(int s0, int cnt, bool need_xs) {
+    if (resident) return 0;
+    gpc_ctx* c = po->ctx;
+    const int D = po->D;
+    HIPCHK(c, hipMemcpyAsync(c->spb.p, &po->sp[(size_t)s0 * SP_STRIDE], (size_t)cnt * SP_STRIDE * 8,
+                             hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(c->mulb.p, &po->mul[(size_t)s0 * D], (size_t)cnt * D * 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(c->divb.p, &po->dv[(size_t)s0 * D], (size_t)cnt * D * 8, hipMemcpyHostToDevice, c->st));
+    if (need_xs) {
+      const long long tot = (long long)po->npad * D;
+      hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, c->st,
+                         c->dX.as<double>(), po->N, po->npad, D, mulb, divb, c->xs.as<double>());
+    }
+    return 0;
+  }
+};
+
 // Shared by predict / predict_full / quad: for every posterior sample s build a right-hand
 // side matrix R_s (npad x mpad: cross covariances, or quadrature kernel means), then
 //   lin[j*S+s]  = R_s[:, j] . alpha_s
 //   quad[j*S+s] = |W_s R_s[:, j]|^2          (L_chol;  the caller divides by sl)
 //               = R_s[:, j] . (L_s R_s[:, j]) (low noise, L = -inv)
-//   full[s]     = Kss_s - (W R)^T (W R) / sl   or   Kss_s + R^T (L R)     (mode_full)
-//   dlin / dquad [(j*D + l)*S + s] = d lin / dx*_jl and d(kss - k*^T (K + Sigma)^-1 k*) / dx*_jl  (mode 0 with
+//   full[s]     = Kss_s - (W R)^T (W R) / sl   or   Kss_s + R^T (L R)
+//   dlin / dquad [(j*D + l)*S + s] = d lin / dx*_jl and d(kss - k*^T (K + Sigma)^-1 k*) / dx*_jl  (CROSS with
 //                 want_quad only; covfun.h: cross_grad_tile_kernel): V is written (no EPI = 1 product), Q = W^T V
 //                 is one more product of the same size (L_chol; the other samples use G = L R as it is)
 //   draw        with `full`: C_s is factored and multiplied on the device (draw_chunk), not downloaded
-//   qg          (mode 1 only; quad.h) d lin / d xa, d lin / d xb and, with want_quad, d quad / d xa, d quad / d xb, the
+//   qg          (QUAD_Z only; quad.h) d lin / d xa, d lin / d xb and, with want_quad, d quad / d xa, d quad / d xb, the
 //                 last two under quad's convention (scaled by 1/sl or negated) and complete, [(j*D + l)*S + s].  Without
 //                 want_quad there is no product at all; with it V is written as for dlin and Q = W^T V is formed
-// mode: 0 = cross covariance of xa (M x D) with the training inputs; 1 = quadrature
-// vectors z for Gaussian measures N(xa[j], diag(xb[j]^2)) (gaussian_process.py:1908-1921).
 struct QuadGradOut {
   double* p[4];  // dza_dmu, dza_dsigma, dzkz_dmu, dzkz_dsigma
 };
+struct RhsRequest {
+  enum Rhs {
+    CROSS,    // cross covariance of xa (M x D) with the training inputs
+    QUAD_Z,   // quadrature vectors z of the Gaussian measures N(xa[j], diag(xb[j]^2)) (gaussian_process.py:1908-1921)
+    GIVEN_KS  // the caller's own Ks_s (xa: S x N x M doubles) and, with `full`, K**_s (xb: S x M x M): K-mode posteriors
+  };
+  Rhs rhs = CROSS;
+  const double* xa = nullptr;
+  const double* xb = nullptr;
+  int M = 0;
+  bool want_quad = false;
+  double* lin = nullptr;    // M x S, always
+  double* quad = nullptr;   // M x S (want_quad)
+  double* full = nullptr;   // S x M x M; with `draw`: only says that C_s is formed (it stays on the device)
+  double* dlin = nullptr;   // CROSS with want_quad: the gradients of lin and of the variance, M x D x S each
+  double* dquad = nullptr;
+  const DrawReq* draw = nullptr;
+  const QuadGradOut* qg = nullptr;  // QUAD_Z: the gradients with respect to the measures
+};
 
+// One rhs_products call: the sizes, the scratch and the landing blocks of the call, and the steps of a chunk in the
+// order they go onto the stream.  Every step works per sample in an order fixed by the shape, so a sample carries the
+// same bits in any batch, chunk or run.
 template <typename T>
-int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int M, bool want_quad,
-                 double* lin, double* quad, double* full, double* dlin = nullptr, double* dquad = nullptr,
-                 const DrawReq* draw = nullptr, const QuadGradOut* qg = nullptr) {
-  gpc_ctx* c = po->ctx;
-  const int S = po->S, N = po->N, D = po->D, npad = po->npad;
-  const int mpad = pad_tile(M);
-  hipStream_t st = c->st;
-  const long long sM = (long long)npad * npad;
-  const long long sKs = (long long)npad * mpad;
-  const long long sKss = (long long)mpad * mpad;
-  const bool grad = dlin != nullptr || qg != nullptr;
-  const int gnt = npad / CT;  // tile rows of the gradient pass
-  // result planes of the gradient pass: [dmu | ds2] (mode 0), [dza_dmu | dza_dsigma (| dzkz_dmu | dzkz_dsigma)] (qg)
-  const int gpl = qg && want_quad ? 4 : 2;
-  // gradient scratch per sample: Q (as V; not without a product), the per-tile partials, the results and (qg) the
-  // measures' constants
-  const bool gq = grad && (!qg || want_quad);
-  const size_t gpart_per = grad ? (size_t)gnt * gpl * D * mpad * 8 : 0, gres_per = grad ? (size_t)gpl * mpad * D * 8 : 0;
-  const size_t qcon_per = qg ? (size_t)(D + 1) * mpad * 8 : 0;
-  // draw scratch per sample: the factor's three slabs (mA mW mT), Z and F (mpad x rpad), the draws
-  const int rpad = draw ? pad_tile(draw->R) : 0;
-  const size_t sZ = (size_t)mpad * rpad;
-  const size_t draw_per = draw ? (3 * (size_t)sKss + 2 * sZ) * sizeof(T) + (size_t)M * draw->R * 8 : 0;
-  const size_t per = (2ull * npad * mpad + (full ? (size_t)mpad * mpad : 0) + (gq ? (size_t)npad * mpad : 0)) * sizeof(T) +
-                     gpart_per + gres_per + qcon_per + draw_per;
-  const size_t held = c->ks.bytes + c->vb.bytes + c->kss.bytes + (grad ? c->qb.bytes + c->gpart.bytes + c->gres.bytes : 0) +
-                      (qg ? c->qcon.bytes : 0) +
-                      (draw ? c->mA.bytes + c->mW.bytes + c->mT.bytes + c->zb.bytes + c->fb.bytes + c->dout.bytes : 0);
-  int chunk = S;
-  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > held ||
-      (size_t)S * sKs * sizeof(T) > std::min(c->ks.bytes, c->vb.bytes) ||
-      (full && (size_t)S * sKss * sizeof(T) > c->kss.bytes) ||
-      (grad && ((gq && (size_t)S * sKs * sizeof(T) > c->qb.bytes) || (size_t)S * gpart_per > c->gpart.bytes)) ||
-      (qg && (size_t)(S + 1) * qcon_per > c->qcon.bytes) ||
-      (draw && ((size_t)S * sKss * sizeof(T) > std::min({c->mA.bytes, c->mW.bytes, c->mT.bytes}) ||
-                (size_t)S * sZ * sizeof(T) > std::min(c->zb.bytes, c->fb.bytes) ||
-                (size_t)S * M * draw->R * 8 > c->dout.bytes))) {
-    c->pool_drain();
-    size_t budget = (size_t)((free_device_bytes() + (getenv("GPC_MEM_BUDGET_MB") ? 0 : held)) * 0.8);
-    if (draw && budget < per)
-      FAIL(c, "gpc_draw: the scratch of one sample (" + std::to_string(per >> 20) + " MB) exceeds the device memory "
-              "budget (" + std::to_string(budget >> 20) + " MB)");
-    chunk = (int)std::max<size_t>(1, std::min<size_t>(S, budget / per));
-  }
-  HIPCHK(c, c->ks.ensure((size_t)chunk * sKs * sizeof(T)));
-  HIPCHK(c, c->vb.ensure((size_t)chunk * sKs * sizeof(T)));
-  if (full) HIPCHK(c, c->kss.ensure((size_t)chunk * sKss * sizeof(T)));
-  if (draw) {
-    HIPCHK(c, c->mA.ensure((size_t)chunk * sKss * sizeof(T)));
-    HIPCHK(c, c->mW.ensure((size_t)chunk * sKss * sizeof(T)));
-    HIPCHK(c, c->mT.ensure((size_t)chunk * sKss * sizeof(T)));
-    HIPCHK(c, c->zb.ensure((size_t)chunk * sZ * sizeof(T)));
-    HIPCHK(c, c->fb.ensure((size_t)chunk * sZ * sizeof(T)));
-    HIPCHK(c, c->dout.ensure((size_t)chunk * M * draw->R * 8));
-    HIPCHK(c, c->daux.ensure(((size_t)M * S + 2 * (size_t)chunk) * 8));
-  }
-  if (grad) {
-    if (gq) HIPCHK(c, c->qb.ensure((size_t)chunk * sKs * sizeof(T)));
-    HIPCHK(c, c->gpart.ensure((size_t)chunk * gpart_per));
-    HIPCHK(c, c->gres.ensure((size_t)chunk * gres_per));
-  }
-  // (qg) [mu_jl transposed: D x mpad | per sample: 1/tau_jl, D x mpad, and ln nf_j, mpad]
-  if (qg) HIPCHK(c, c->qcon.ensure((size_t)(chunk + 1) * qcon_per));
-  double* d_mut = qg ? c->qcon.as<double>() : nullptr;
-  double* d_qcon = qg ? d_mut + (size_t)D * mpad : nullptr;
-  HIPCHK(c, c->xss.ensure(((size_t)chunk * mpad * D + 2 * (size_t)M * D) * 8));
-  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
-  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
-  HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
-  HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
-  HIPCHK(c, c->pout.ensure((size_t)chunk * mpad * 2 * 8));
-  double* d_xa = c->xss.as<double>() + (size_t)chunk * mpad * D;
-  double* d_xb = d_xa + (size_t)M * D;
-  c->pin.begin();
-  c->pin.begin_gather();
-  // (round 6, as for the evaluations: below N_pad = 2048 -- the posterior of a small training set queried in a loop by an
-  // acquisition function -- timing events are recorded on request only and the call returns on the polled word of its
-  // download launch)
-  const bool timing_on = c->small_timing != 0 || npad >= 2048;
-  if (mode != 2) {
-    HIPCHK(c, c->pin.up(d_xa, xa, (size_t)M * D * 8, st));
-    if (xb) HIPCHK(c, c->pin.up(d_xb, xb, (size_t)M * D * 8, st));
-  }
-  // landing buffers of the per-chunk results (pinned when available)
-  // (one block for both: the device keeps [mu | v] contiguous too, so a call's results come back in ONE copy)
-  std::vector<double> hmu_v;
-  double* hmu = static_cast<double*>(c->pin.alloc(2 * (size_t)chunk * mpad * 8));
-  if (!hmu) {
-    hmu_v.resize(2 * (size_t)chunk * mpad);
-    hmu = hmu_v.data();
-  }
-  double* hv = hmu + (size_t)chunk * mpad;
-  double* hfull = nullptr;
-  if (full && !draw && (size_t)M * M * 8 >= PinBuf::kMin && (size_t)M * M * 8 <= PinBuf::kMax)
-    hfull = static_cast<double*>(c->pin.alloc((size_t)M * M * 8));
-  // landing block of a chunk's draws (M x R per sample): pinned when it fits, else uninitialised pageable memory
-  std::unique_ptr<double[]> hdraw_v;
-  double* hdraw = nullptr;
-  if (draw) {
-    const size_t dbytes = (size_t)chunk * M * draw->R * 8;
-    if (dbytes <= PinBuf::kMax) hdraw = static_cast<double*>(c->pin.alloc(dbytes));
-    if (!hdraw) {
-      hdraw_v.reset(new double[dbytes / 8]);
-      hdraw = hdraw_v.get();
-    }
-    if (draw->nsd) HIPCHK(c, hipMemcpyAsync(c->daux.p, draw->nsd, (size_t)M * S * 8, hipMemcpyHostToDevice, st));
-  }
-  // landing block of the gradient planes of a chunk: pinned when it fits, else uninitialised pageable memory
-  std::unique_ptr<double[]> hgrad_v;
-  double* hgrad = nullptr;
-  if (grad) {
-    const size_t gbytes = gres_per * (size_t)chunk;
-    if (gbytes <= PinBuf::kMax) hgrad = static_cast<double*>(c->pin.alloc(gbytes));
-    if (!hgrad) {
-      hgrad_v.reset(new double[gbytes / 8]);
-      hgrad = hgrad_v.get();
-    }
-  }
+struct RhsCall {
+  gpc_post* const po;
+  const RhsRequest& r;
+  gpc_ctx* const c;
+  const hipStream_t st;
+  const int S, N, D, npad, M, mpad;
+  const long long sKs, sKss;
+  const bool full, grad, gq;  // gq: the gradient pass reads Q (not without a product)
+  // gnt: tile rows of the gradient pass; gpl: its result planes, [dmu | ds2] (CROSS) or [dza_dmu | dza_dsigma (| dzkz_dmu |
+  // dzkz_dsigma)] (qg)
+  const int gnt, gpl, rpad;
+  const size_t gpart_per, gres_per, qcon_per, sZ;
+  int chunk = 0;
+  CallTimer tm;
+  ChunkConsts k;
+  double *d_mut = nullptr, *d_qcon = nullptr, *d_xa = nullptr, *d_xb = nullptr;
+  // landing blocks of the per-chunk results
+  std::unique_ptr<double[]> hmu_v, hdraw_v, hgrad_v;
+  double *hmu = nullptr, *hv = nullptr, *hfull = nullptr, *hdraw = nullptr, *hgrad = nullptr;
 
-  // all samples in one chunk (the usual case): the posterior's constants are resident, see gpc_post
-  const bool resident = chunk == S && mode != 2;
-  if (resident)
-    if (int rc = post_consts_resident(po)) return rc;
-  const double* spb = resident ? po->dsp.as<double>() : c->spb.as<double>();
-  const double* mulb = resident ? po->dmul.as<double>() : c->mulb.as<double>();
-  const double* divb = resident ? po->ddv.as<double>() : c->divb.as<double>();
-  const double* xsb = resident ? po->dxs.as<double>() : c->xs.as<double>();
+  RhsCall(gpc_post* po_, const RhsRequest& r_)
+      : po(po_), r(r_), c(po_->ctx), st(po_->ctx->st), S(po_->S), N(po_->N), D(po_->D), npad(po_->npad), M(r_.M),
+        mpad(pad_tile(r_.M)), sKs((long long)npad * mpad), sKss((long long)mpad * mpad), full(r_.full != nullptr),
+        grad(r_.dlin != nullptr || r_.qg != nullptr), gq(grad && (!r_.qg || r_.want_quad)), gnt(npad / CT),
+        gpl(r_.qg && r_.want_quad ? 4 : 2), rpad(r_.draw ? pad_tile(r_.draw->R) : 0),
+        gpart_per(grad ? (size_t)gnt * gpl * D * mpad * 8 : 0), gres_per(grad ? (size_t)gpl * mpad * D * 8 : 0),
+        qcon_per(r_.qg ? (size_t)(D + 1) * mpad * 8 : 0), sZ((size_t)mpad * rpad),
+        tm{po_->ctx, CallTimer::wanted(po_->ctx, po_->npad)} {}
 
-  // gpc_last_timing after a predict / predict_full / quad call: device time of the call (first upload to last result
-  // ready) and of its N^2 M products V = W Ks (the launches of gemm.h), summed over the chunks
-  c->ms_total = c->ms_factor = 0;
-  for (int s0 = 0; s0 < S; s0 += chunk) {
-    const int cnt = std::min(chunk, S - s0);
-    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[0], st));
-    if (!resident) {
-      HIPCHK(c, hipMemcpyAsync(c->spb.p, &po->sp[(size_t)s0 * SP_STRIDE], (size_t)cnt * SP_STRIDE * 8,
-                               hipMemcpyHostToDevice, st));
-      HIPCHK(c, hipMemcpyAsync(c->mulb.p, &po->mul[(size_t)s0 * D], (size_t)cnt * D * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(c, hipMemcpyAsync(c->divb.p, &po->dv[(size_t)s0 * D], (size_t)cnt * D * 8, hipMemcpyHostToDevice, st));
-    }
-    T* Ks = c->ks.as<T>();
-    T* V = c->vb.as<T>();
-    bool fused_mu = false;
-    if (mode == 0) {
-      long long tot = (long long)npad * D;
-      if (!resident)
-        hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, st,
-                           c->dX.as<double>(), N, npad, D, mulb, divb, c->xs.as<double>());
-      tot = (long long)mpad * D;
-      hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, st,
-                         (const double*)d_xa, M, mpad, D, mulb, divb, c->xss.as<double>());
-      // cross covariances in 64 x 64 tiles with the mean product fused in (covfun.h: cross_tile_kernel)
-      HIPCHK(c, c->dbg2.ensure((size_t)cnt * (npad / CT) * mpad * 8));
-      GPC_COV_DISPATCH(cross_tile_kernel, T, po->cd, dim3(mpad / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, xsb,
-                       (const double*)c->xss.as<double>(), spb, (const double*)(po->alpha.as<double>() + (size_t)s0 * npad),
-                       npad, N, npad, M, mpad, Ks, sKs, c->dbg2.as<double>());
-      fused_mu = true;
-      if (full)
-        hipLaunchKernelGGL((cross_kernel<T>), dim3(mpad / 64, mpad / 4, cnt), dim3(64, 4), 0, st, po->cd,
-                           c->xss.as<double>(), c->xss.as<double>(), spb, M, mpad, M, mpad, c->kss.as<T>(), sKss);
-    } else if (mode == 2) {
-      // caller-provided cross covariances Ks_s (N x M doubles, xa) and, with `full`, K**_s (M x M, xb)
-      HIPCHK(c, c->dbg1.ensure((size_t)std::max(N, M) * M * sizeof(double)));
-      for (int i = 0; i < cnt; ++i) {
-        HIPCHK(c, hipMemcpyAsync(c->dbg1.p, xa + (size_t)(s0 + i) * N * M, (size_t)N * M * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL((pad_rect_kernel<T>), dim3(mpad / 64, npad / 4), dim3(64, 4), 0, st, (const double*)c->dbg1.p, N,
-                           M, npad, mpad, Ks + (size_t)i * sKs);
-        if (full) {
-          HIPCHK(c, hipMemcpyAsync(c->dbg1.p, xb + (size_t)(s0 + i) * M * M, (size_t)M * M * 8, hipMemcpyHostToDevice, st));
-          hipLaunchKernelGGL((pad_rect_kernel<T>), dim3(mpad / 64, mpad / 4), dim3(64, 4), 0, st, (const double*)c->dbg1.p,
-                             M, M, mpad, mpad, c->kss.as<T>() + (size_t)i * sKss);
-        }
-      }
-    } else {
-      hipLaunchKernelGGL((quad_z_kernel<T>), dim3(mpad / 64, npad / 4, cnt), dim3(64, 4), 0, st,
-                         c->dX.as<double>(), (const double*)d_xa, (const double*)d_xb, mulb, divb, spb, N, npad, M, mpad,
-                         D, Ks, sKs);
-      if (qg)
-        hipLaunchKernelGGL(quad_grad_prep_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
-                           (const double*)d_xa, (const double*)d_xb, divb, spb, M, mpad, D, d_mut, d_qcon);
-      if (full)  // gpc_quad_cov: Gamma where mode 0 puts K** (quad_mix.h)
-        hipLaunchKernelGGL((quad_gamma_kernel<T>), dim3(mpad / 64, mpad / 4, cnt), dim3(64, 4), 0, st,
-                           (const double*)d_xa, (const double*)d_xb, divb, spb, M, mpad, D, c->kss.as<T>(), sKss);
-    }
-    double* d_mu = c->pout.as<double>();
-    double* d_v = d_mu + (size_t)chunk * mpad;
-    if (fused_mu)
-      hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
-                         (const double*)c->dbg2.as<double>(), npad / CT, mpad, d_mu);
-    else
-      hipLaunchKernelGGL((colsum_vec_kernel<T>), dim3(mpad / 64, cnt), dim3(256), 0, st, (const T*)Ks, sKs, mpad,
-                         po->alpha.as<double>() + (size_t)s0 * npad, npad, npad, mpad, d_mu);
-    HIPCHK(c, hipGetLastError());
-    // runs of equal L_chol share launches
-    int a = 0;
-    if (timing_on) {
-      HIPCHK(c, hipEventRecord(c->ev[1], st));
-      HIPCHK(c, hipEventRecord(c->ev[2], st));
-    }
-    while ((want_quad || full) && a < cnt) {
-      int e = a;
-      while (e < cnt && po->lchol[s0 + e] == po->lchol[s0 + a]) ++e;
-      const int len = e - a;
-      const bool lch = po->lchol[s0 + a] != 0;
-      GemmArgs g;
-      g.B = Ks + (size_t)a * sKs;
-      g.C = V + (size_t)a * sKs;
-      g.sB = g.sC = sKs;
-      g.sA = sM;
-      g.lda = npad;
-      g.ldb = g.ldc = mpad;
-      g.M = npad;
-      g.N = mpad;
-      g.K = npad;
-      g.alpha = 1.0;
-      g.beta = 0;
-      g.klo = KLO_ZERO;
-      g.lower_only = 0;
-      g.A = (lch ? po->W.as<T>() : po->A.as<T>()) + (size_t)(s0 + a) * sM;  // V = W R | G = L R
-      g.khi = lch ? KHI_ROW : KHI_FULL;
-      // (problems whose product is a handful of 128-tiles keep the 64-tile product + column-sum pass: latency regime.
-      // Decided by the problem size only, never by the number of samples: the two forms add in different orders, and a
-      // sample of a batch must carry the bits of its single evaluation)
-      const long long tiles128 = (long long)(npad / TILE) * (mpad / TILE);
-      if (lch && !full && !grad && tiles128 >= 64) {
-        // the variance needs the column sums of squares of V only: the product's epilogue forms them per tile row and V
-        // is never written (gemm.h: EPI = 1); a small reduction over the tile rows follows
-        const int tm = npad / TILE;
-        HIPCHK(c, c->dbg3.ensure((size_t)cnt * tm * mpad * 8));  // (the whole chunk: no reallocation between runs)
-        int* qctr = c->tile_ctr.as<int>() + (size_t)gpc_ctx::MAXG * gpc_ctx::CTR_PER_GROUP;
-        HIPCHK(c, hipMemsetAsync(qctr, 0, CTR_STRIDE * sizeof(int), st));
-        if (timing_on) HIPCHK(c, hipEventRecord(c->ev[1], st));
-        g.colsq = c->dbg3.as<double>();
-        HIPCHK(c, launch_gemm_colsq<T>(st, g, len, qctr));
-        if (e == cnt && timing_on) HIPCHK(c, hipEventRecord(c->ev[2], st));
-        hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mpad + 255) / 256, len), dim3(256), 0, st,
-                           (const double*)c->dbg3.as<double>(), tm, mpad, d_v + (size_t)a * mpad);
-        a = e;
-        continue;
-      }
-      HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
-      if (e == cnt && timing_on) HIPCHK(c, hipEventRecord(c->ev[2], st));  // (several runs: the first launch to the last, with what lies between)
-      const T* left = lch ? (const T*)(V + (size_t)a * sKs) : (const T*)(Ks + (size_t)a * sKs);
-      hipLaunchKernelGGL((colsum_prod_kernel<T>), dim3(mpad / 64, len), dim3(256), 0, st, left, sKs,
-                         (const T*)(V + (size_t)a * sKs), sKs, mpad, npad, mpad, d_v + (size_t)a * mpad);
-      if (grad) {
-        // Q = W^T V (L_chol: the upper triangular A operand W^T, k from the tile row's diagonal block on) | G as it is
-        const T* Qs = V + (size_t)a * sKs;
-        if (lch) {
-          GemmArgs q = g;
-          q.A = po->W.as<T>() + (size_t)(s0 + a) * sM;
-          q.B = V + (size_t)a * sKs;
-          q.C = c->qb.as<T>() + (size_t)a * sKs;
-          q.klo = KLO_ROW;
-          q.khi = KHI_FULL;
-          HIPCHK(c, launch_gemm<T>(st, q, true, true, len));
-          Qs = c->qb.as<T>() + (size_t)a * sKs;
-        }
-        if (mode == 1 && e == cnt && timing_on) HIPCHK(c, hipEventRecord(c->ev[2], st));  // (quad_grad: with Q)
-        if (mode == 1)
-          hipLaunchKernelGGL((quad_grad_tile_kernel<T, true>), dim3(mpad / CT, npad / CT, len), dim3(256), 0, st,
-                             (const double*)c->dX.as<double>(), D, (const double*)d_mut,
-                             (const double*)(d_qcon + (size_t)a * (D + 1) * mpad),
-                             (const double*)(po->alpha.as<double>() + (size_t)(s0 + a) * npad), npad, Qs, sKs,
-                             spb + (size_t)a * SP_STRIDE, lch ? 1 : 0, N, M, mpad,
-                             c->gpart.as<double>() + (size_t)a * gnt * gpl * D * mpad);
-        else
-          GPC_COV_DISPATCH(cross_grad_tile_kernel, T, po->cd, dim3(mpad / CT, npad / CT, len), dim3(256), 0, st, po->cd,
-                           xsb + (size_t)a * npad * D, (const double*)(c->xss.as<double>() + (size_t)a * mpad * D),
-                           spb + (size_t)a * SP_STRIDE, (const double*)(po->alpha.as<double>() + (size_t)(s0 + a) * npad),
-                           npad, Qs, sKs, lch ? 1 : 0, N, npad, M, mpad,
-                           c->gpart.as<double>() + (size_t)a * gnt * 2 * D * mpad);
-      }
-      if (full) {
-        // Kss -= V^T V / sl  (per sample: alpha differs)   |   Kss += R^T G
-        for (int i = a; i < e; ++i) {
-          GemmArgs f;
-          f.A = lch ? (const void*)(V + (size_t)i * sKs) : (const void*)(Ks + (size_t)i * sKs);
-          f.B = V + (size_t)i * sKs;
-          f.C = c->kss.as<T>() + (size_t)i * sKss;
-          f.sA = f.sB = f.sC = 0;
-          f.lda = f.ldb = f.ldc = mpad;
-          f.M = f.N = mpad;
-          f.K = npad;
-          f.alpha = lch ? -1.0 / po->sp[(size_t)(s0 + i) * SP_STRIDE + SP_SL] : 1.0;
-          f.beta = 1;
-          f.klo = KLO_ZERO;
-          f.khi = KHI_FULL;
-          f.lower_only = 0;
-          HIPCHK(c, launch_gemm<T>(st, f, true, true, 1));
-        }
-      }
-      a = e;
-    }
-    if (qg && !want_quad)  // no product: the alpha weights only, the whole chunk in one launch
-      hipLaunchKernelGGL((quad_grad_tile_kernel<T, false>), dim3(mpad / CT, npad / CT, cnt), dim3(256), 0, st,
-                         (const double*)c->dX.as<double>(), D, (const double*)d_mut, (const double*)d_qcon,
-                         (const double*)(po->alpha.as<double>() + (size_t)s0 * npad), npad, (const T*)nullptr, 0LL, spb,
-                         0, N, M, mpad, c->gpart.as<double>());
-    if (grad) {
-      double* d_dmu = c->gres.as<double>();
-      double* d_ds2 = d_dmu + (size_t)chunk * mpad * D;
-      if (qg)
-        hipLaunchKernelGGL(quad_grad_reduce_kernel, dim3((mpad + 255) / 256, gpl * D, cnt), dim3(256), 0, st,
-                           (const double*)c->gpart.as<double>(), gnt, D, gpl, M, mpad, (const double*)d_xb,
-                           (const double*)d_qcon, d_dmu, (size_t)chunk * mpad * D);
-      else
-        hipLaunchKernelGGL(grad_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
-                           (const double*)c->gpart.as<double>(), gnt, D, mpad, mulb, divb, d_dmu, d_ds2);
-      HIPCHK(c, hipMemcpyAsync(hgrad, d_dmu, (size_t)gpl * chunk * mpad * D * 8, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(c, hipGetLastError());
-    const size_t out_bytes = (want_quad ? 2 : 1) * (size_t)chunk * mpad * 8;
-    const bool poll = !timing_on && !full && !grad && c->small_poll && c->land_blk && cnt == chunk && out_bytes <= PinBuf::kGather / 8;
-    if (poll) {  // the results through the gathered download launch, which carries the completion word
-      HIPCHK(c, c->pin.gather(hmu, d_mu, want_quad ? out_bytes : (size_t)cnt * mpad * 8, st));
-    } else if (want_quad && cnt == chunk)  // d_v = d_mu + chunk * mpad: one contiguous block
-      HIPCHK(c, hipMemcpyAsync(hmu, d_mu, 2 * (size_t)chunk * mpad * 8, hipMemcpyDeviceToHost, st));
-    else {
-      HIPCHK(c, hipMemcpyAsync(hmu, d_mu, (size_t)cnt * mpad * 8, hipMemcpyDeviceToHost, st));
-      if (want_quad) HIPCHK(c, hipMemcpyAsync(hv, d_v, (size_t)cnt * mpad * 8, hipMemcpyDeviceToHost, st));
-    }
+  T* Ks() const { return c->ks.as<T>(); }
+  T* V() const { return c->vb.as<T>(); }
+  double* d_mu() const { return c->pout.as<double>(); }
+  double* d_v() const { return d_mu() + (size_t)chunk * mpad; }
+  const double* alpha(int s) const { return po->alpha.as<double>() + (size_t)s * npad; }
+
+  // The scratch of one sample, the samples per chunk, and the buffers of a chunk
+  int plan() {
+    const DrawReq* draw = r.draw;
+    const bool qg = r.qg != nullptr;
+    // gradient scratch per sample: Q (as V), the per-tile partials, the results and (qg) the measures' constants;
+    // draw scratch per sample: the factor's three slabs (mA mW mT), Z and F (mpad x rpad), the draws
+    const size_t draw_per = draw ? (3 * (size_t)sKss + 2 * sZ) * sizeof(T) + (size_t)M * draw->R * 8 : 0;
+    const size_t per = (2ull * npad * mpad + (full ? (size_t)mpad * mpad : 0) + (gq ? (size_t)npad * mpad : 0)) * sizeof(T) +
+                       gpart_per + gres_per + qcon_per + draw_per;
+    const size_t held = c->ks.bytes + c->vb.bytes + c->kss.bytes + (grad ? c->qb.bytes + c->gpart.bytes + c->gres.bytes : 0) +
+                        (qg ? c->qcon.bytes : 0) +
+                        (draw ? c->mA.bytes + c->mW.bytes + c->mT.bytes + c->zb.bytes + c->fb.bytes + c->dout.bytes : 0);
+    const bool fits =
+        !((size_t)S * per > held || (size_t)S * sKs * sizeof(T) > std::min(c->ks.bytes, c->vb.bytes) ||
+          (full && (size_t)S * sKss * sizeof(T) > c->kss.bytes) ||
+          (grad && ((gq && (size_t)S * sKs * sizeof(T) > c->qb.bytes) || (size_t)S * gpart_per > c->gpart.bytes)) ||
+          (qg && (size_t)(S + 1) * qcon_per > c->qcon.bytes) ||
+          (draw && ((size_t)S * sKss * sizeof(T) > std::min({c->mA.bytes, c->mW.bytes, c->mT.bytes}) ||
+                    (size_t)S * sZ * sizeof(T) > std::min(c->zb.bytes, c->fb.bytes) ||
+                    (size_t)S * M * draw->R * 8 > c->dout.bytes)));
+    // (draws refuse a sample that does not fit; everything else runs one sample at a time whatever the budget says)
+    chunk = plan_chunk(c, S, per, 0, held, fits, 0, !draw, [&](size_t budget) {
+      return "gpc_draw: the scratch of one sample (" + std::to_string(per >> 20) + " MB) exceeds the device memory "
+             "budget (" + std::to_string(budget >> 20) + " MB)";
+    });
+    if (!chunk) return -2;
+    HIPCHK(c, c->ks.ensure((size_t)chunk * sKs * sizeof(T)));
+    HIPCHK(c, c->vb.ensure((size_t)chunk * sKs * sizeof(T)));
+    if (full) HIPCHK(c, c->kss.ensure((size_t)chunk * sKss * sizeof(T)));
     if (draw) {
-      const int rc = draw_chunk<T>(po, *draw, s0, cnt, M, d_mu, hdraw);
-      if (rc) return rc;
-    } else if (full) {
+      HIPCHK(c, c->mA.ensure((size_t)chunk * sKss * sizeof(T)));
+      HIPCHK(c, c->mW.ensure((size_t)chunk * sKss * sizeof(T)));
+      HIPCHK(c, c->mT.ensure((size_t)chunk * sKss * sizeof(T)));
+      HIPCHK(c, c->zb.ensure((size_t)chunk * sZ * sizeof(T)));
+      HIPCHK(c, c->fb.ensure((size_t)chunk * sZ * sizeof(T)));
+      HIPCHK(c, c->dout.ensure((size_t)chunk * M * draw->R * 8));
+      HIPCHK(c, c->daux.ensure(((size_t)M * S + 2 * (size_t)chunk) * 8));
+    }
+    if (grad) {
+      if (gq) HIPCHK(c, c->qb.ensure((size_t)chunk * sKs * sizeof(T)));
+      HIPCHK(c, c->gpart.ensure((size_t)chunk * gpart_per));
+      HIPCHK(c, c->gres.ensure((size_t)chunk * gres_per));
+    }
+    // (qg) [mu_jl transposed: D x mpad | per sample: 1/tau_jl, D x mpad, and ln nf_j, mpad]
+    if (qg) HIPCHK(c, c->qcon.ensure((size_t)(chunk + 1) * qcon_per));
+    d_mut = qg ? c->qcon.as<double>() : nullptr;
+    d_qcon = qg ? d_mut + (size_t)D * mpad : nullptr;
+    HIPCHK(c, c->xss.ensure(((size_t)chunk * mpad * D + 2 * (size_t)M * D) * 8));
+    HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
+    HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
+    HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
+    HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
+    HIPCHK(c, c->pout.ensure((size_t)chunk * mpad * 2 * 8));
+    d_xa = c->xss.as<double>() + (size_t)chunk * mpad * D;
+    d_xb = d_xa + (size_t)M * D;
+    return 0;
+  }
+
+  // The call's own uploads, the landing blocks of the per-chunk results and the posterior's constants
+  int begin() {
+    c->pin.begin();
+    c->pin.begin_gather();
+    if (r.rhs != RhsRequest::GIVEN_KS) {
+      HIPCHK(c, c->pin.up(d_xa, r.xa, (size_t)M * D * 8, st));
+      if (r.xb) HIPCHK(c, c->pin.up(d_xb, r.xb, (size_t)M * D * 8, st));
+    }
+    // (one block for lin and quad: the device keeps [mu | v] contiguous too, so a call's results come back in ONE copy)
+    hmu = landing_block(c, 2 * (size_t)chunk * mpad * 8, hmu_v);
+    hv = hmu + (size_t)chunk * mpad;
+    if (full && !r.draw && (size_t)M * M * 8 >= PinBuf::kMin && (size_t)M * M * 8 <= PinBuf::kMax)
+      hfull = static_cast<double*>(c->pin.alloc((size_t)M * M * 8));
+    if (r.draw) {  // a chunk's draws, M x R per sample
+      hdraw = landing_block(c, (size_t)chunk * M * r.draw->R * 8, hdraw_v);
+      if (r.draw->nsd) HIPCHK(c, hipMemcpyAsync(c->daux.p, r.draw->nsd, (size_t)M * S * 8, hipMemcpyHostToDevice, st));
+    }
+    if (grad) hgrad = landing_block(c, gres_per * (size_t)chunk, hgrad_v);  // the gradient planes of a chunk
+    // all samples in one chunk (the usual case): the posterior's constants are resident, see gpc_post
+    return k.init(po, chunk == S && r.rhs != RhsRequest::GIVEN_KS);
+  }
+
+  // ---- the right-hand sides R_s of a chunk (into Ks) and lin = R_s^T alpha_s ----
+  // cross covariances in 64 x 64 tiles with the mean product fused in (covfun.h: cross_tile_kernel)
+  int build_cross(int s0, int cnt) {
+    const long long tot = (long long)mpad * D;
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, st,
+                       (const double*)d_xa, M, mpad, D, k.mulb, k.divb, c->xss.as<double>());
+    HIPCHK(c, c->dbg2.ensure((size_t)cnt * (npad / CT) * mpad * 8));
+    GPC_COV_DISPATCH(cross_tile_kernel, T, po->cd, dim3(mpad / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
+                     (const double*)c->xss.as<double>(), k.spb, alpha(s0), npad, N, npad, M, mpad, Ks(), sKs,
+                     c->dbg2.as<double>());
+    if (full)
+      hipLaunchKernelGGL((cross_kernel<T>), dim3(mpad / 64, mpad / 4, cnt), dim3(64, 4), 0, st, po->cd,
+                         c->xss.as<double>(), c->xss.as<double>(), k.spb, M, mpad, M, mpad, c->kss.as<T>(), sKss);
+    hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
+                       (const double*)c->dbg2.as<double>(), npad / CT, mpad, d_mu());
+    return 0;
+  }
+  // caller-provided cross covariances Ks_s (N x M doubles, xa) and, with `full`, K**_s (M x M, xb)
+  int build_given(int s0, int cnt) {
+    HIPCHK(c, c->dbg1.ensure((size_t)std::max(N, M) * M * sizeof(double)));
+    for (int i = 0; i < cnt; ++i) {
+      HIPCHK(c, hipMemcpyAsync(c->dbg1.p, r.xa + (size_t)(s0 + i) * N * M, (size_t)N * M * 8, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL((pad_rect_kernel<T>), dim3(mpad / 64, npad / 4), dim3(64, 4), 0, st, (const double*)c->dbg1.p, N,
+                         M, npad, mpad, Ks() + (size_t)i * sKs);
+      if (full) {
+        HIPCHK(c, hipMemcpyAsync(c->dbg1.p, r.xb + (size_t)(s0 + i) * M * M, (size_t)M * M * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL((pad_rect_kernel<T>), dim3(mpad / 64, mpad / 4), dim3(64, 4), 0, st, (const double*)c->dbg1.p,
+                           M, M, mpad, mpad, c->kss.as<T>() + (size_t)i * sKss);
+      }
+    }
+    return column_sums(s0, cnt);
+  }
+  int build_quad_z(int s0, int cnt) {
+    hipLaunchKernelGGL((quad_z_kernel<T>), dim3(mpad / 64, npad / 4, cnt), dim3(64, 4), 0, st, c->dX.as<double>(),
+                       (const double*)d_xa, (const double*)d_xb, k.mulb, k.divb, k.spb, N, npad, M, mpad, D, Ks(), sKs);
+    if (r.qg)
+      hipLaunchKernelGGL(quad_grad_prep_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st, (const double*)d_xa,
+                         (const double*)d_xb, k.divb, k.spb, M, mpad, D, d_mut, d_qcon);
+    if (full)  // gpc_quad_cov: Gamma where CROSS puts K** (quad_mix.h)
+      hipLaunchKernelGGL((quad_gamma_kernel<T>), dim3(mpad / 64, mpad / 4, cnt), dim3(64, 4), 0, st,
+                         (const double*)d_xa, (const double*)d_xb, k.divb, k.spb, M, mpad, D, c->kss.as<T>(), sKss);
+    return column_sums(s0, cnt);
+  }
+  int column_sums(int s0, int cnt) {  // (the builders without a fused mean product)
+    hipLaunchKernelGGL((colsum_vec_kernel<T>), dim3(mpad / 64, cnt), dim3(256), 0, st, (const T*)Ks(), sKs, mpad,
+                       alpha(s0), npad, npad, mpad, d_mu());
+    return 0;
+  }
+
+  // ---- one run of equal L_chol: the product, the variance term, the gradient tiles, the full covariance ----
+  int run_products(int s0, int cnt, int a, int len, bool lch) {
+    const bool last = a + len == cnt;
+    T* const Ksa = Ks() + (size_t)a * sKs;
+    T* const Va = V() + (size_t)a * sKs;
+    GemmArgs g = tri_product_args<T>(po, s0 + a, lch, Ksa, Va, sKs, mpad, mpad);  // V = W R | G = L R
+    // (problems whose product is a handful of 128-tiles keep the 64-tile product + column-sum pass: latency regime.
+    // Decided by the problem size only, never by the number of samples: the two forms add in different orders, and a
+    // sample of a batch must carry the bits of its single evaluation)
+    const long long tiles128 = (long long)(npad / TILE) * (mpad / TILE);
+    if (lch && !full && !grad && tiles128 >= 64) {
+      // the variance needs the column sums of squares of V only: the product's epilogue forms them per tile row and V
+      // is never written (gemm.h: EPI = 1); a small reduction over the tile rows follows
+      const int tmr = npad / TILE;
+      HIPCHK(c, c->dbg3.ensure((size_t)cnt * tmr * mpad * 8));  // (the whole chunk: no reallocation between runs)
+      int* qctr = c->tile_ctr.as<int>() + (size_t)gpc_ctx::MAXG * gpc_ctx::CTR_PER_GROUP;
+      HIPCHK(c, hipMemsetAsync(qctr, 0, CTR_STRIDE * sizeof(int), st));
+      HIPCHK(c, tm.mark1());
+      g.colsq = c->dbg3.as<double>();
+      HIPCHK(c, launch_gemm_colsq<T>(st, g, len, qctr));
+      if (last) HIPCHK(c, tm.mark2());
+      hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mpad + 255) / 256, len), dim3(256), 0, st,
+                         (const double*)c->dbg3.as<double>(), tmr, mpad, d_v() + (size_t)a * mpad);
+      return 0;
+    }
+    HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
+    if (last) HIPCHK(c, tm.mark2());  // (several runs: the first launch to the last, with what lies between)
+    hipLaunchKernelGGL((colsum_prod_kernel<T>), dim3(mpad / 64, len), dim3(256), 0, st, (const T*)(lch ? Va : Ksa), sKs,
+                       (const T*)Va, sKs, mpad, npad, mpad, d_v() + (size_t)a * mpad);
+    if (grad) {
+      // Q = W^T V (L_chol: the upper triangular A operand W^T, k from the tile row's diagonal block on) | G as it is
+      const T* Qs = Va;
+      if (lch) {
+        GemmArgs q = g;
+        q.B = Va;
+        q.C = c->qb.as<T>() + (size_t)a * sKs;
+        q.klo = KLO_ROW;
+        q.khi = KHI_FULL;
+        HIPCHK(c, launch_gemm<T>(st, q, true, true, len));
+        Qs = c->qb.as<T>() + (size_t)a * sKs;
+      }
+      if (r.rhs == RhsRequest::QUAD_Z) {
+        if (last) HIPCHK(c, tm.mark2());  // (quad_grad: with Q)
+        hipLaunchKernelGGL((quad_grad_tile_kernel<T, true>), dim3(mpad / CT, npad / CT, len), dim3(256), 0, st,
+                           (const double*)c->dX.as<double>(), D, (const double*)d_mut,
+                           (const double*)(d_qcon + (size_t)a * (D + 1) * mpad), alpha(s0 + a), npad, Qs, sKs,
+                           k.spb + (size_t)a * SP_STRIDE, lch ? 1 : 0, N, M, mpad,
+                           c->gpart.as<double>() + (size_t)a * gnt * gpl * D * mpad);
+      } else {
+        GPC_COV_DISPATCH(cross_grad_tile_kernel, T, po->cd, dim3(mpad / CT, npad / CT, len), dim3(256), 0, st, po->cd,
+                         k.xsb + (size_t)a * npad * D, (const double*)(c->xss.as<double>() + (size_t)a * mpad * D),
+                         k.spb + (size_t)a * SP_STRIDE, alpha(s0 + a), npad, Qs, sKs, lch ? 1 : 0, N, npad, M, mpad,
+                         c->gpart.as<double>() + (size_t)a * gnt * 2 * D * mpad);
+      }
+    }
+    if (full) {
+      // Kss -= V^T V / sl  (per sample: alpha differs)   |   Kss += R^T G
+      for (int i = a; i < a + len; ++i) {
+        GemmArgs f;
+        f.A = lch ? (const void*)(V() + (size_t)i * sKs) : (const void*)(Ks() + (size_t)i * sKs);
+        f.B = V() + (size_t)i * sKs;
+        f.C = c->kss.as<T>() + (size_t)i * sKss;
+        f.sA = f.sB = f.sC = 0;
+        f.lda = f.ldb = f.ldc = mpad;
+        f.M = f.N = mpad, f.K = npad;
+        f.alpha = lch ? -1.0 / po->sp[(size_t)(s0 + i) * SP_STRIDE + SP_SL] : 1.0, f.beta = 1;
+        f.klo = KLO_ZERO, f.khi = KHI_FULL, f.lower_only = 0;
+        HIPCHK(c, launch_gemm<T>(st, f, true, true, 1));
+      }
+    }
+    return 0;
+  }
+
+  // ---- the gradient planes of a chunk: the tile partials reduced and on their way to the host ----
+  int reduce_gradients(int s0, int cnt) {
+    if (r.qg && !r.want_quad)  // no product: the alpha weights only, the whole chunk in one launch
+      hipLaunchKernelGGL((quad_grad_tile_kernel<T, false>), dim3(mpad / CT, npad / CT, cnt), dim3(256), 0, st,
+                         (const double*)c->dX.as<double>(), D, (const double*)d_mut, (const double*)d_qcon, alpha(s0), npad,
+                         (const T*)nullptr, 0LL, k.spb, 0, N, M, mpad, c->gpart.as<double>());
+    if (!grad) return 0;
+    double* d_dmu = c->gres.as<double>();
+    double* d_ds2 = d_dmu + (size_t)chunk * mpad * D;
+    if (r.qg)
+      hipLaunchKernelGGL(quad_grad_reduce_kernel, dim3((mpad + 255) / 256, gpl * D, cnt), dim3(256), 0, st,
+                         (const double*)c->gpart.as<double>(), gnt, D, gpl, M, mpad, (const double*)d_xb,
+                         (const double*)d_qcon, d_dmu, (size_t)chunk * mpad * D);
+    else
+      hipLaunchKernelGGL(grad_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
+                         (const double*)c->gpart.as<double>(), gnt, D, mpad, k.mulb, k.divb, d_dmu, d_ds2);
+    HIPCHK(c, hipMemcpyAsync(hgrad, d_dmu, (size_t)gpl * chunk * mpad * D * 8, hipMemcpyDeviceToHost, st));
+    return 0;
+  }
+
+  // ---- lin and quad to the host (`poll`: through the gathered download launch, which carries the completion word),
+  // then the draws or the full covariances ----
+  int download(int s0, int cnt, bool poll) {
+    const bool want_quad = r.want_quad;
+    if (poll) {
+      const size_t out_bytes = (want_quad ? 2 : 1) * (size_t)chunk * mpad * 8;
+      HIPCHK(c, c->pin.gather(hmu, d_mu(), want_quad ? out_bytes : (size_t)cnt * mpad * 8, st));
+    } else if (want_quad && cnt == chunk)  // d_v = d_mu + chunk * mpad: one contiguous block
+      HIPCHK(c, hipMemcpyAsync(hmu, d_mu(), 2 * (size_t)chunk * mpad * 8, hipMemcpyDeviceToHost, st));
+    else {
+      HIPCHK(c, hipMemcpyAsync(hmu, d_mu(), (size_t)cnt * mpad * 8, hipMemcpyDeviceToHost, st));
+      if (want_quad) HIPCHK(c, hipMemcpyAsync(hv, d_v(), (size_t)cnt * mpad * 8, hipMemcpyDeviceToHost, st));
+    }
+    if (r.draw) return draw_chunk<T>(po, *r.draw, s0, cnt, M, d_mu(), hdraw);
+    if (full) {
       HIPCHK(c, c->dbg3.ensure((size_t)M * M * 8));
       for (int i = 0; i < cnt; ++i) {
         dim3 gn((M + 63) / 64, (M + 3) / 4), blk(64, 4);
         hipLaunchKernelGGL((extract_kernel<T>), gn, blk, 0, st, (const T*)(c->kss.as<T>() + (size_t)i * sKss),
                            mpad, M, 2, c->dbg3.as<double>());
-        double* dst = full + (size_t)(s0 + i) * M * M;
+        double* dst = r.full + (size_t)(s0 + i) * M * M;
         HIPCHK(c, hipMemcpyAsync(hfull ? hfull : dst, c->dbg3.p, (size_t)M * M * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if (hfull) memcpy(dst, hfull, (size_t)M * M * 8);
       }
     }
-    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[3], st));
+    return 0;
+  }
+
+  // ---- the end of a chunk on the host: on the polled word of the download launch when there is one (bounded: after
+  // 2 ms the stream is waited for after all), else on the stream ----
+  int wait(bool poll) {
     bool seen = false;
     if (poll && !c->pin.down_plain) {
       unsigned long long* flag = reinterpret_cast<unsigned long long*>(c->land_blk + (gpc_ctx::LAND_BYTES / 8 - 1));
@@ -2915,41 +2993,74 @@ int rhs_products(gpc_post* po, int mode, const double* xa, const double* xb, int
       if (poll) ++c->small_synced;
     }
     c->pin.finish();
-    if (timing_on) {
-      float t03 = 0, t12 = 0;
-      (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
-      (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
-      c->ms_total += t03;
-      c->ms_factor += t12;
-    }
-    for (int i = 0; i < cnt; ++i) {
-      const int s = s0 + i;
-      for (int j = 0; j < M; ++j) {
-        lin[(size_t)j * S + s] = hmu[(size_t)i * mpad + j];
-        if (want_quad) quad[(size_t)j * S + s] = hv[(size_t)i * mpad + j];
-      }
-    }
-    if (draw) {  // f[(j*R + r)*S + s]
-      const int R = draw->R;
-      for (size_t jr = 0; jr < (size_t)M * R; ++jr) {
-        double* o = draw->f + jr * S + s0;
-        for (int i = 0; i < cnt; ++i) o[i] = hdraw[(size_t)i * M * R + jr];
-      }
-    }
-    if (grad) {  // [(j*D + l)*S + s]: the samples of the chunk side by side, the output written in order
-      double* outs[4] = {dlin, dquad, nullptr, nullptr};
-      if (qg) std::copy_n(qg->p, 4, outs);
+    return 0;
+  }
+
+  // ---- a chunk's results into the caller's layout: [j*S + s], f[(j*R + r)*S + s], [(j*D + l)*S + s] ----
+  void scatter(int s0, int cnt) {
+    scatter_plane(r.lin, hmu, M, mpad, S, s0, cnt);
+    if (r.want_quad) scatter_plane(r.quad, hv, M, mpad, S, s0, cnt);
+    if (r.draw) scatter_plane(r.draw->f, hdraw, (size_t)M * r.draw->R, (size_t)M * r.draw->R, S, s0, cnt);
+    if (grad) {
+      double* outs[4] = {r.dlin, r.dquad, nullptr, nullptr};
+      if (r.qg) std::copy_n(r.qg->p, 4, outs);
       const size_t ss = (size_t)mpad * D;
-      for (int p = 0; p < gpl; ++p) {
-        const double* gp = hgrad + (size_t)p * chunk * ss;
-        for (size_t jl = 0; jl < (size_t)M * D; ++jl) {
-          double* o = outs[p] + jl * S + s0;
-          for (int i = 0; i < cnt; ++i) o[i] = gp[i * ss + jl];
-        }
-      }
+      for (int p = 0; p < gpl; ++p) scatter_plane(outs[p], hgrad + (size_t)p * chunk * ss, (size_t)M * D, ss, S, s0, cnt);
     }
   }
+
+  int chunk_steps(int s0, int cnt) {
+    HIPCHK(c, tm.start());
+    if (int rc = k.stage(s0, cnt, r.rhs == RhsRequest::CROSS)) return rc;
+    if (int rc = r.rhs == RhsRequest::CROSS      ? build_cross(s0, cnt)
+                 : r.rhs == RhsRequest::GIVEN_KS ? build_given(s0, cnt)
+                                                 : build_quad_z(s0, cnt))
+      return rc;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, tm.mark1());
+    HIPCHK(c, tm.mark2());
+    if (r.want_quad || full)
+      if (int rc = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) { return run_products(s0, cnt, a, len, lch); }))
+        return rc;
+    if (int rc = reduce_gradients(s0, cnt)) return rc;
+    HIPCHK(c, hipGetLastError());
+    const size_t out_bytes = (r.want_quad ? 2 : 1) * (size_t)chunk * mpad * 8;
+    const bool poll = !tm.on && !full && !grad && c->small_poll && c->land_blk && cnt == chunk && out_bytes <= PinBuf::kGather / 8;
+    if (int rc = download(s0, cnt, poll)) return rc;
+    HIPCHK(c, tm.stop());
+    if (int rc = wait(poll)) return rc;
+    tm.accumulate();
+    scatter(s0, cnt);
+    return 0;
+  }
+};
+
+template <typename T>
+int rhs_products(gpc_post* po, const RhsRequest& r) {
+  RhsCall<T> call(po, r);
+  if (int rc = call.plan()) return rc;
+  if (int rc = call.begin()) return rc;
+  // gpc_last_timing after a predict / predict_full / quad call: device time of the call (first upload to last result
+  // ready) and of its N^2 M products V = W Ks (the launches of gemm.h), summed over the chunks
+  po->ctx->ms_total = po->ctx->ms_factor = 0;
+  for (int s0 = 0; s0 < po->S; s0 += call.chunk)
+    if (int rc = call.chunk_steps(s0, std::min(call.chunk, po->S - s0))) return rc;
   return 0;
+}
+int rhs_products(gpc_post* po, const RhsRequest& r) {
+  return po->dtype == GPC_F64 ? rhs_products<double>(po, r) : rhs_products<float>(po, r);
+}
+// gpc_quad, gpc_quad_grad, gpc_quad_cov: z . alpha and, with want_var, z (K + Sigma)^-1 z of the measures N(mu_j, sigma_j^2)
+RhsRequest quad_request(const double* mu, const double* sigma, int M, bool want_var, double* zalpha, double* zKz) {
+  RhsRequest r;
+  r.rhs = RhsRequest::QUAD_Z;
+  r.xa = mu;
+  r.xb = sigma;
+  r.M = M;
+  r.want_quad = want_var;
+  r.lin = zalpha;
+  r.quad = zKz;
+  return r;
 }
 
 template <typename T>
@@ -2957,7 +3068,15 @@ int predict_impl(gpc_post* po, const double* xstar, int M, double* fmu, double* 
                  double* dfs2 = nullptr) {
   // (with dfmu: the gradients come back complete -- kss is constant for stationary kernels, and the 1/sl of the
   // L_chol samples is applied to Q on the device)
-  int rc = rhs_products<T>(po, 0, xstar, nullptr, M, true, fmu, fs2, nullptr, dfmu, dfs2);
+  RhsRequest r;
+  r.xa = xstar;
+  r.M = M;
+  r.want_quad = true;
+  r.lin = fmu;
+  r.quad = fs2;
+  r.dlin = dfmu;
+  r.dquad = dfs2;
+  int rc = rhs_products<T>(po, r);
   if (rc) return rc;
   const int S = po->S;
   for (int s = 0; s < S; ++s) {
@@ -2994,7 +3113,6 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
   const int S = po->S, N = po->N, D = po->D, npad = po->npad;
   const int mapad = pad_tile(Ma), mbpad = pad_tile(Mb), mmax = std::max(mapad, mbpad);
   hipStream_t st = c->st;
-  const long long sM = (long long)npad * npad;
   const long long sKa = (long long)npad * mapad, sKb = (long long)npad * mbpad, sC = (long long)mapad * mbpad;
   const int tma = mapad / TILE;
   const bool fused = wsq && !cov && (long long)tma * (mbpad / TILE) >= 64;
@@ -3002,17 +3120,14 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
   const size_t per = (2ull * npad * (mapad + mbpad) + (size_t)sC) * sizeof(T) + part_per +
                      ((size_t)(mapad + mbpad) * D + mapad + 1 + 2 * mbpad) * 8;
   const size_t held = c->ks.bytes + c->vb.bytes + c->kss.bytes;
-  int chunk = S;
-  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > held ||
-      (size_t)S * (sKa + sKb) * sizeof(T) > std::min(c->ks.bytes, c->vb.bytes) || (size_t)S * sC * sizeof(T) > c->kss.bytes) {
-    c->pool_drain();
-    const size_t budget = (size_t)((free_device_bytes() + (getenv("GPC_MEM_BUDGET_MB") ? 0 : held)) * 0.8);
-    if (budget < per)
-      FAIL(c, "gpc_predict_cov: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
-              std::to_string(npad) + ", Ma_pad = " + std::to_string(mapad) + ", Mb_pad = " + std::to_string(mbpad) +
-              ") exceeds the device memory budget (" + std::to_string(budget >> 10) + " KB)");
-    chunk = (int)std::min<size_t>(S, budget / per);
-  }
+  const bool fits = (size_t)S * per <= held && (size_t)S * (sKa + sKb) * sizeof(T) <= std::min(c->ks.bytes, c->vb.bytes) &&
+                    (size_t)S * sC * sizeof(T) <= c->kss.bytes;
+  const int chunk = plan_chunk(c, S, per, 0, held, fits, 0, false, [&](size_t budget) {
+    return "gpc_predict_cov: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
+           std::to_string(npad) + ", Ma_pad = " + std::to_string(mapad) + ", Mb_pad = " + std::to_string(mbpad) +
+           ") exceeds the device memory budget (" + std::to_string(budget >> 10) + " KB)";
+  });
+  if (!chunk) return -2;
   HIPCHK(c, c->ks.ensure((size_t)chunk * (sKa + sKb) * sizeof(T)));
   HIPCHK(c, c->vb.ensure((size_t)chunk * (sKa + sKb) * sizeof(T)));
   HIPCHK(c, c->kss.ensure((size_t)chunk * sC * sizeof(T)));
@@ -3036,7 +3151,7 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
   double* d_q = d_v + (size_t)chunk * mbpad;
   c->pin.begin();
   c->pin.begin_gather();
-  const bool timing_on = c->small_timing != 0 || npad >= 2048;
+  CallTimer tm{c, CallTimer::wanted(c, npad)};
   HIPCHK(c, c->pin.up(d_xa, xa, (size_t)Ma * D * 8, st));
   HIPCHK(c, c->pin.up(d_xb, xb, (size_t)Mb * D * 8, st));
   std::vector<double> hw((size_t)chunk * (mapad + 1)), hout(2 * (size_t)chunk * mbpad);
@@ -3044,28 +3159,16 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
   if (cov && (size_t)Ma * Mb * 8 >= PinBuf::kMin && (size_t)Ma * Mb * 8 <= PinBuf::kMax)
     hcov = static_cast<double*>(c->pin.alloc((size_t)Ma * Mb * 8));
 
-  const bool resident = chunk == S;
-  if (resident)
-    if (int rc = post_consts_resident(po)) return rc;
-  const double* spb = resident ? po->dsp.as<double>() : c->spb.as<double>();
-  const double* mulb = resident ? po->dmul.as<double>() : c->mulb.as<double>();
-  const double* divb = resident ? po->ddv.as<double>() : c->divb.as<double>();
-  const double* xsb = resident ? po->dxs.as<double>() : c->xs.as<double>();
+  ChunkConsts k;
+  if (int rc = k.init(po, chunk == S)) return rc;
+  const double *spb = k.spb, *mulb = k.mulb, *divb = k.divb, *xsb = k.xsb;
 
   // gpc_last_timing: device time of the call and of its products (the first triangular product to the cross product)
   c->ms_total = c->ms_factor = 0;
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
-    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[0], st));
-    if (!resident) {
-      HIPCHK(c, hipMemcpyAsync(c->spb.p, &po->sp[(size_t)s0 * SP_STRIDE], (size_t)cnt * SP_STRIDE * 8,
-                               hipMemcpyHostToDevice, st));
-      HIPCHK(c, hipMemcpyAsync(c->mulb.p, &po->mul[(size_t)s0 * D], (size_t)cnt * D * 8, hipMemcpyHostToDevice, st));
-      HIPCHK(c, hipMemcpyAsync(c->divb.p, &po->dv[(size_t)s0 * D], (size_t)cnt * D * 8, hipMemcpyHostToDevice, st));
-      const long long tot = (long long)npad * D;
-      hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, st, c->dX.as<double>(),
-                         N, npad, D, mulb, divb, c->xs.as<double>());
-    }
+    HIPCHK(c, tm.start());
+    if (int rc = k.stage(s0, cnt, true)) return rc;
     // the weights of the chunk's samples (zero in the padding) and the factor of each sample's cross product
     std::fill(hw.begin(), hw.end(), 0.0);
     for (int i = 0; i < cnt; ++i) {
@@ -3092,39 +3195,14 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
     hipLaunchKernelGGL((cross_kernel<T>), dim3(mbpad / 64, mapad / 4, cnt), dim3(64, 4), 0, st, po->cd,
                        (const double*)xsa, (const double*)xsbq, spb, Ma, mapad, Mb, mbpad, Kab, sC);
     HIPCHK(c, hipGetLastError());
-    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[1], st));
-    int a = 0;
-    while (a < cnt) {
-      int e = a;
-      while (e < cnt && po->lchol[s0 + e] == po->lchol[s0 + a]) ++e;
-      const int len = e - a;
-      const bool lch = po->lchol[s0 + a] != 0;
+    HIPCHK(c, tm.mark1());
+    const int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
       // V_b = W Ks_b (and V_a = W Ks_a) | G_b = L Ks_b: the samples of the run in one launch each
-      GemmArgs g;
-      g.sA = sM;
-      g.lda = npad;
-      g.M = npad;
-      g.K = npad;
-      g.alpha = 1.0;
-      g.beta = 0;
-      g.klo = KLO_ZERO;
-      g.lower_only = 0;
-      g.A = (lch ? po->W.as<T>() : po->A.as<T>()) + (size_t)(s0 + a) * sM;
-      g.khi = lch ? KHI_ROW : KHI_FULL;
-      g.B = Ksb + (size_t)a * sKb;
-      g.C = Vb + (size_t)a * sKb;
-      g.sB = g.sC = sKb;
-      g.ldb = g.ldc = mbpad;
-      g.N = mbpad;
-      HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
-      if (lch) {
-        g.B = Ksa + (size_t)a * sKa;
-        g.C = Va + (size_t)a * sKa;
-        g.sB = g.sC = sKa;
-        g.ldb = g.ldc = mapad;
-        g.N = mapad;
-        HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
-      }
+      HIPCHK(c, launch_gemm<T>(st, tri_product_args<T>(po, s0 + a, lch, Ksb + (size_t)a * sKb, Vb + (size_t)a * sKb, sKb, mbpad, mbpad),
+                               false, true, len));
+      if (lch)
+        HIPCHK(c, launch_gemm<T>(st, tri_product_args<T>(po, s0 + a, lch, Ksa + (size_t)a * sKa, Va + (size_t)a * sKa, sKa, mapad, mapad),
+                                 false, true, len));
       if (fs2b) {
         const T* left = lch ? (const T*)(Vb + (size_t)a * sKb) : (const T*)(Ksb + (size_t)a * sKb);
         hipLaunchKernelGGL((colsum_prod_kernel<T>), dim3(mbpad / 64, len), dim3(256), 0, st, left, sKb,
@@ -3158,7 +3236,7 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
         hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mbpad + 255) / 256, len), dim3(256), 0, st,
                            (const double*)f.colsq, tma, mbpad, d_q + (size_t)a * mbpad);
       } else {
-        for (int i = a; i < e; ++i) {  // (per sample: alpha differs)
+        for (int i = a; i < a + len; ++i) {  // (per sample: alpha differs)
           f.A = Aop + (size_t)i * sKa;
           f.B = Vb + (size_t)i * sKb;
           f.C = Kab + (size_t)i * sC;
@@ -3171,10 +3249,11 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
                              (const T*)(Kab + (size_t)a * sC), sC, mbpad, (const double*)(d_w + (size_t)a * mapad), mapad,
                              Ma, mbpad, d_q + (size_t)a * mbpad);
       }
-      a = e;
-    }
+      return 0;
+    });
+    if (rc_runs) return rc_runs;
     HIPCHK(c, hipGetLastError());
-    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[2], st));
+    HIPCHK(c, tm.mark2());
     HIPCHK(c, hipMemcpyAsync(hout.data(), d_v, 2 * (size_t)chunk * mbpad * 8, hipMemcpyDeviceToHost, st));
     if (cov) {
       for (int i = 0; i < cnt; ++i) {
@@ -3186,16 +3265,10 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
         if (hcov) memcpy(dst, hcov, (size_t)Ma * Mb * 8);
       }
     }
-    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[3], st));
+    HIPCHK(c, tm.stop());
     HIPCHK(c, hipStreamSynchronize(st));
     c->pin.finish();
-    if (timing_on) {
-      float t03 = 0, t12 = 0;
-      (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
-      (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
-      c->ms_total += t03;
-      c->ms_factor += t12;
-    }
+    tm.accumulate();
     for (int i = 0; i < cnt; ++i) {
       const int s = s0 + i;
       const double sf2 = po->sp[(size_t)s * SP_STRIDE + SP_SF2], sl = po->sp[(size_t)s * SP_STRIDE + SP_SL];
@@ -3452,6 +3525,37 @@ int debug_cov_impl(gpc_ctx* c, int which, CovDesc cd, const double* hyp, double 
 }  // namespace
 
 namespace {
+// The posterior's storage regrown to npn padded rows: A and W copied with identity padding, alpha with zeros.  The
+// old buffers go to the context's pool (the next gpc_posterior_batch reuses them) or back to the device.
+template <typename T>
+int grow_storage(gpc_post* po, int npn, bool to_pool) {
+  gpc_ctx* c = po->ctx;
+  hipStream_t st = c->st;
+  const int S = po->S, np = po->npad;
+  DevBuf nA, nW, nal;
+  HIPCHK(c, nA.ensure((size_t)S * npn * npn * sizeof(T)));
+  HIPCHK(c, nW.ensure((size_t)S * npn * npn * sizeof(T)));
+  HIPCHK(c, nal.ensure((size_t)S * npn * sizeof(double)));
+  dim3 g(npn / 64, npn / 4, S), blk(64, 4);
+  hipLaunchKernelGGL((grow_copy_kernel<T>), g, blk, 0, st, (const T*)po->A.as<T>(), np, nA.as<T>(), npn);
+  hipLaunchKernelGGL((grow_copy_kernel<T>), g, blk, 0, st, (const T*)po->W.as<T>(), np, nW.as<T>(), npn);
+  HIPCHK(c, hipMemsetAsync(nal.p, 0, (size_t)S * npn * sizeof(double), st));
+  HIPCHK(c, hipMemcpy2DAsync(nal.p, (size_t)npn * 8, po->alpha.p, (size_t)np * 8, (size_t)np * 8, S,
+                             hipMemcpyDeviceToDevice, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  for (DevBuf* b : {&po->A, &po->W, &po->alpha}) {
+    if (to_pool)
+      c->pool_give(*b);
+    else
+      b->release();
+  }
+  po->A = nA;
+  po->W = nW;
+  po->alpha = nal;
+  po->npad = npn;
+  return 0;
+}
+
 // rank-one append (scalar noise; checked by the caller): high-noise samples get a new last row
 // of the factor and of its inverse (:776-817), low-noise samples a rank-one update of -inv (:819-827)
 // Ks_h / kss_h: the cross covariances and prior variances at the new point from the caller's own covariance object
@@ -3464,27 +3568,8 @@ int append_impl(gpc_post* po, const double* m_star, const double* sn2_star, doub
   hipStream_t st = c->st;
   if (c->N != n + 1) FAIL(c, "gpc_post_append: call gpc_set_data with the extended X, y first");
   // grow the padded storage by one tile when the new row does not fit
-  if (n + 1 > po->npad) {
-    const int np = po->npad, npn = np + TILE;
-    DevBuf nA, nW, nal;
-    HIPCHK(c, nA.ensure((size_t)S * npn * npn * sizeof(T)));
-    HIPCHK(c, nW.ensure((size_t)S * npn * npn * sizeof(T)));
-    HIPCHK(c, nal.ensure((size_t)S * npn * sizeof(double)));
-    dim3 g(npn / 64, npn / 4, S), blk(64, 4);
-    hipLaunchKernelGGL((grow_copy_kernel<T>), g, blk, 0, st, (const T*)po->A.as<T>(), np, nA.as<T>(), npn);
-    hipLaunchKernelGGL((grow_copy_kernel<T>), g, blk, 0, st, (const T*)po->W.as<T>(), np, nW.as<T>(), npn);
-    HIPCHK(c, hipMemsetAsync(nal.p, 0, (size_t)S * npn * sizeof(double), st));
-    HIPCHK(c, hipMemcpy2DAsync(nal.p, (size_t)npn * 8, po->alpha.p, (size_t)np * 8, (size_t)np * 8, S,
-                               hipMemcpyDeviceToDevice, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    c->pool_give(po->A);
-    c->pool_give(po->W);
-    c->pool_give(po->alpha);
-    po->A = nA;
-    po->W = nW;
-    po->alpha = nal;
-    po->npad = npn;
-  }
+  if (n + 1 > po->npad)
+    if (int rc = grow_storage<T>(po, po->npad + TILE, true)) return rc;
   const int npad = po->npad;
   const long long sM = (long long)npad * npad;
   const size_t vb = (size_t)npad * 8;
@@ -3627,45 +3712,20 @@ int append_block_impl(gpc_post* po, int k, const double* m_star, const double* s
   // the scratch is the context's cross-covariance buffer (gpc_predict's Ks): kept between calls, so that an
   // acquisition loop pays no allocation per batch; budgeted like gpc_predict_cov's when it has to grow
   const size_t held = c->ks.bytes;
-  int chunk = S;
-  // (a forced budget takes this path on every call, pool_drain included: it is the tests' way into the chunked path,
-  // not a setting for an acquisition loop, which without it allocates only when the scratch or the storage grows)
-  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > held || grow) {
-    c->pool_drain();
-    // GPC_MEM_BUDGET_MB budgets the SCRATCH (the tests' way into the chunked path); the device's real free memory
-    // has to hold the grown storage as well
-    const bool forced = getenv("GPC_MEM_BUDGET_MB") != nullptr;
-    const size_t fr = free_device_bytes() + (forced ? 0 : held);
-    const size_t avail = forced ? fr : (fr > grow_bytes ? fr - grow_bytes : 0);
-    if ((size_t)(avail * 0.8) < per)
-      FAIL(c, "gpc_post_append_block: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
-              std::to_string(npn) + ", k = " + std::to_string(k) + ") exceeds the device memory budget (" +
-              std::to_string((size_t)(avail * 0.8) >> 10) + " KB" +
-              (grow ? " beside " + std::to_string(grow_bytes >> 10) + " KB of grown storage)" : ")"));
-    chunk = (int)std::min<size_t>(S, (size_t)(avail * 0.8) / per);
-  }
-  // grow the padded storage by as many tiles as the k rows need (identity padding, like the rank-one path)
-  if (grow) {
-    const int np = po->npad;
-    DevBuf nA, nW, nal;
-    HIPCHK(c, nA.ensure((size_t)S * npn * npn * sizeof(T)));
-    HIPCHK(c, nW.ensure((size_t)S * npn * npn * sizeof(T)));
-    HIPCHK(c, nal.ensure((size_t)S * npn * sizeof(double)));
-    dim3 g(npn / 64, npn / 4, S), blk(64, 4);
-    hipLaunchKernelGGL((grow_copy_kernel<T>), g, blk, 0, st, (const T*)po->A.as<T>(), np, nA.as<T>(), npn);
-    hipLaunchKernelGGL((grow_copy_kernel<T>), g, blk, 0, st, (const T*)po->W.as<T>(), np, nW.as<T>(), npn);
-    HIPCHK(c, hipMemsetAsync(nal.p, 0, (size_t)S * npn * sizeof(double), st));
-    HIPCHK(c, hipMemcpy2DAsync(nal.p, (size_t)npn * 8, po->alpha.p, (size_t)np * 8, (size_t)np * 8, S,
-                               hipMemcpyDeviceToDevice, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    po->A.release();
-    po->W.release();
-    po->alpha.release();
-    po->A = nA;
-    po->W = nW;
-    po->alpha = nal;
-    po->npad = npn;
-  }
+  // (a forced budget plans on every call, pool_drain included: it is the tests' way into the chunked path, not a
+  // setting for an acquisition loop, which without it allocates only when the scratch or the storage grows.
+  // GPC_MEM_BUDGET_MB budgets the SCRATCH; the device's real free memory has to hold the grown storage as well)
+  const int chunk = plan_chunk(c, S, per, 0, held, (size_t)S * per <= held && !grow, grow_bytes, false, [&](size_t budget) {
+    return "gpc_post_append_block: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
+           std::to_string(npn) + ", k = " + std::to_string(k) + ") exceeds the device memory budget (" +
+           std::to_string(budget >> 10) + " KB" +
+           (grow ? " beside " + std::to_string(grow_bytes >> 10) + " KB of grown storage)" : ")");
+  });
+  if (!chunk) return -2;
+  // grow the padded storage by as many tiles as the k rows need (the old storage goes back to the device: the scratch
+  // was budgeted beside the grown one)
+  if (grow)
+    if (int rc = grow_storage<T>(po, npn, false)) return rc;
   const int npad = po->npad;
   const long long sM = (long long)npad * npad;
   const long long sP = (long long)npad * kq;
@@ -3711,7 +3771,8 @@ int append_block_impl(gpc_post* po, int k, const double* m_star, const double* s
   for (int s = 0; s < S; ++s) (po->lchol[s] ? any_high : any_low) = true;
   // gpc_last_timing: device time of the call (after the growth) and of the skinny products (the last chunk's)
   c->ms_total = c->ms_factor = 0;
-  HIPCHK(c, hipEventRecord(c->ev[0], st));
+  CallTimer tm{c, true};
+  HIPCHK(c, tm.start());
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
     HIPCHK(c, hipMemsetAsync(scr.p, 0, (size_t)cnt * per, st));
@@ -3749,45 +3810,28 @@ int append_block_impl(gpc_post* po, int k, const double* m_star, const double* s
     }
     // 2. the skinny products and the k x k Gram matrices
     const dim3 gn((n + BA_T - 1) / BA_T, kq / BA_R, cnt), gk((k + BA_T - 1) / BA_T, kq / BA_R, cnt);
-    HIPCHK(c, hipEventRecord(c->ev[1], st));
+    HIPCHK(c, tm.mark1());
     if (use_gemm) {
       // the same products as launches of the MFMA GEMM on panels padded to 128 columns, in runs of one parametrisation
       const long long sK = (long long)npad * kp;
       hipLaunchKernelGGL((ba_to_panel_kernel<T>), dim3(kp / 64, npad / 4, cnt), dim3(64, 4), 0, st, (const double*)Bx, n, k,
                          kq, npad, kp, Bt);
-      for (int a = 0; a < cnt;) {
-        const int lch = po->lchol[s0 + a];
-        int e = a + 1;
-        while (e < cnt && po->lchol[s0 + e] == lch) ++e;
-        GemmArgs g;
-        g.A = (lch ? Wc : Ac) + (size_t)a * sM;  // V = W B | G = -A B
-        g.B = Bt + (size_t)a * sK;
-        g.C = Vt + (size_t)a * sK;
-        g.sA = sM;
-        g.sB = g.sC = sK;
-        g.lda = npad;
-        g.ldb = g.ldc = kp;
-        g.M = npad;
-        g.N = kp;
-        g.K = npad;
+      const int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+        GemmArgs g = tri_product_args<T>(po, s0 + a, lch, Bt + (size_t)a * sK, Vt + (size_t)a * sK, sK, kp, kp);  // V = W B | G = -A B
         g.alpha = lch ? 1.0 : -1.0;
-        g.beta = 0;
-        g.klo = KLO_ZERO;
-        g.khi = lch ? KHI_ROW : KHI_FULL;
-        g.lower_only = 0;
         g.tiles_n = kp / TILE;
-        HIPCHK(c, launch_gemm<T>(st, g, false, true, e - a));
+        HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
         if (lch) {  // Q = W^T V (k from the tile row's diagonal block on)
           GemmArgs q = g;
-          q.A = Wc + (size_t)a * sM;
           q.B = Vt + (size_t)a * sK;
           q.C = Qt + (size_t)a * sK;
           q.klo = KLO_ROW;
           q.khi = KHI_FULL;
-          HIPCHK(c, launch_gemm<T>(st, q, true, true, e - a));
+          HIPCHK(c, launch_gemm<T>(st, q, true, true, len));
         }
-        a = e;
-      }
+        return 0;
+      });
+      if (rc_runs) return rc_runs;
       const dim3 gf((n + 63) / 64, kq / 4, cnt);
       for (int want = 0; want < 2; ++want) {
         if (!(want ? any_high : any_low)) continue;
@@ -3814,7 +3858,7 @@ int append_block_impl(gpc_post* po, int k, const double* m_star, const double* s
                          n, k, (const double*)V, sP, kq, Cm, (long long)kq * kq, kq, 1.0, 0, parc, 0);
     }
     }
-    HIPCHK(c, hipEventRecord(c->ev[2], st));
+    HIPCHK(c, tm.mark2());
     // 3. Schur complement, its factor and inverse factor: the blocked factorization, no jitter
     hipLaunchKernelGGL((ba_schur_kernel<T>), dim3(kp / 64, kp / 4, cnt), dim3(64, 4), 0, st, (const double*)Bx, sP, n, k,
                        kq, (const double*)Cm, parc, kp, fA);
@@ -3855,17 +3899,11 @@ int append_block_impl(gpc_post* po, int k, const double* m_star, const double* s
     }
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipEventRecord(c->ev[3], st));
+  HIPCHK(c, tm.stop());
   std::vector<int> info(S);
   HIPCHK(c, hipMemcpyAsync(info.data(), d_info, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
-  {
-    float t03 = 0, t12 = 0;
-    (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
-    (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
-    c->ms_total = t03;
-    c->ms_factor = t12;
-  }
+  tm.accumulate();  // (one span over all chunks; the products' time is the last chunk's)
   for (int s = 0; s < S; ++s) {
     ok[s] = (par[(size_t)s * BA_STRIDE + BA_PRE] != 0.0 && info[s] == 0) ? 1 : 0;
     ++(ok[s] ? c->block_appended : c->block_stale);
@@ -4275,16 +4313,12 @@ int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const dou
   const size_t n_res = 3 * (size_t)mpad + 2 + (size_t)npl * ss;
   const size_t per = (n_con + n_cpart + n_rpart + (size_t)npad + n_vec + n_tpart + n_zqpart + n_gpart + n_gmpart + n_res) * 8;
   const size_t shared = (2 * ss + (size_t)mpad + 2 * (size_t)M * D + M) * 8;
-  int chunk = S;
-  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per + shared > c->qmix.bytes) {
-    c->pool_drain();
-    const size_t budget = (size_t)((free_device_bytes() + (getenv("GPC_MEM_BUDGET_MB") ? 0 : c->qmix.bytes)) * 0.8);
-    if (budget < per + shared)
-      FAIL(c, "gpc_quad_mix: the scratch of one sample (" + std::to_string((per + shared) >> 10) + " KB: N_pad = " +
-              std::to_string(npad) + ", M_pad = " + std::to_string(mpad) + ", D = " + std::to_string(D) +
-              ") exceeds the device memory budget (" + std::to_string(budget >> 10) + " KB)");
-    chunk = (int)std::min<size_t>(S, (budget - shared) / per);
-  }
+  const int chunk = plan_chunk(c, S, per, shared, c->qmix.bytes, (size_t)S * per + shared <= c->qmix.bytes, 0, false, [&](size_t budget) {
+    return "gpc_quad_mix: the scratch of one sample (" + std::to_string((per + shared) >> 10) + " KB: N_pad = " +
+           std::to_string(npad) + ", M_pad = " + std::to_string(mpad) + ", D = " + std::to_string(D) +
+           ") exceeds the device memory budget (" + std::to_string(budget >> 10) + " KB)";
+  });
+  if (!chunk) return -2;
   HIPCHK(c, c->qmix.ensure((size_t)chunk * per + shared));
   HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
   HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
@@ -4327,12 +4361,12 @@ int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const dou
   HIPCHK(c, hipMemcpyAsync(d_w, w, (size_t)M * 8, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(quad_mix_prep_kernel, dim3((mpad + 255) / 256), dim3(256), 0, st, (const double*)d_sg,
                      (const double*)d_w, M, mpad, D, d_sgt, d_wpad);
-  const bool timing_on = c->small_timing != 0 || npad >= 2048;
+  CallTimer tm{c, CallTimer::wanted(c, npad)};
   // gpc_last_timing: device time of the call and, as ms_factor, of the solve (step 3), summed over the chunks
   c->ms_total = c->ms_factor = 0;
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
-    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[0], st));
+    HIPCHK(c, tm.start());
     HIPCHK(c, hipMemcpyAsync(c->spb.p, &po->sp[(size_t)s0 * SP_STRIDE], (size_t)cnt * SP_STRIDE * 8, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->divb.p, &po->dv[(size_t)s0 * D], (size_t)cnt * D * 8, hipMemcpyHostToDevice, st));
     const double* alpha = po->alpha.as<double>() + (size_t)s0 * npad;
@@ -4345,17 +4379,12 @@ int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const dou
     hipLaunchKernelGGL(colpart_reduce_kernel, dim3((npad + 255) / 256, cnt), dim3(256), 0, st, (const double*)d_rpart,
                        mnt, npad, d_zbar);
     HIPCHK(c, hipGetLastError());
-    if (timing_on) {
-      HIPCHK(c, hipEventRecord(c->ev[1], st));
-      if (!var) HIPCHK(c, hipEventRecord(c->ev[2], st));
-    }
+    HIPCHK(c, tm.mark1());
+    if (!var) HIPCHK(c, tm.mark2());
     if (var) {
-      for (int a = 0; a < cnt;) {  // runs of equal L_chol share launches
-        int e = a;
-        while (e < cnt && po->lchol[s0 + e] == po->lchol[s0 + a]) ++e;
-        const int len = e - a;
+      const int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {  // runs of equal L_chol share launches
         const double* zb = d_zbar + (size_t)a * npad;
-        if (po->lchol[s0 + a]) {
+        if (lch) {
           const T* W = po->W.as<T>() + (size_t)(s0 + a) * sM;
           double* tp = d_tpart + (size_t)a * nch * npad;
           hipLaunchKernelGGL((trmv_kernel<T>), dim3(npad / 4, len), dim3(256), 0, st, W, sM, npad, zb, npad,
@@ -4372,10 +4401,11 @@ int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const dou
           hipLaunchKernelGGL(dot_kernel, dim3(1, len), dim3(256), 0, st, zb, (const double*)(d_q + (size_t)a * npad), N,
                              npad, d_scal + a);
         }
-        a = e;
-      }
+        return 0;
+      });
+      if (rc_runs) return rc_runs;
       HIPCHK(c, hipGetLastError());
-      if (timing_on) HIPCHK(c, hipEventRecord(c->ev[2], st));
+      HIPCHK(c, tm.mark2());
       if (grad)
         hipLaunchKernelGGL((quad_mix_q_tile_kernel<true>), dim3(mnt, gnt, cnt), dim3(256), 0, st, X, D,
                            (const double*)d_mut, (const double*)d_con, alpha, npad, (const double*)d_q, N, M, mpad, npad,
@@ -4408,43 +4438,27 @@ int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const dou
     HIPCHK(c, hipGetLastError());
     // (without var the blocks zq, gw and scal come back unwritten and unread)
     HIPCHK(c, hipMemcpyAsync(hres.get(), d_res, chunk * n_res * 8, hipMemcpyDeviceToHost, st));
-    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[3], st));
+    HIPCHK(c, tm.stop());
     HIPCHK(c, hipStreamSynchronize(st));
-    if (timing_on) {
-      float t03 = 0, t12 = 0;
-      (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
-      (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
-      c->ms_total += t03;
-      c->ms_factor += t12;
-    }
+    tm.accumulate();
     const double* hza = hres.get();
     const double* hzq = hza + (size_t)chunk * mpad;
     const double* hgw = hzq + (size_t)chunk * mpad;
     const double* hsc = hgw + (size_t)chunk * mpad;
     const double* hpl = hsc + 2 * (size_t)chunk;
-    for (int i = 0; i < cnt; ++i) {
-      const int s = s0 + i;
-      for (int j = 0; j < M; ++j) {
-        o.zalpha[(size_t)j * S + s] = hza[(size_t)i * mpad + j];
-        if (var) {
-          o.zq[(size_t)j * S + s] = hzq[(size_t)i * mpad + j];
-          o.gw[(size_t)j * S + s] = hgw[(size_t)i * mpad + j];
-        }
-      }
+    scatter_plane(o.zalpha, hza, M, mpad, S, s0, cnt);
+    if (var) {
+      scatter_plane(o.zq, hzq, M, mpad, S, s0, cnt);
+      scatter_plane(o.gw, hgw, M, mpad, S, s0, cnt);
       // zbar (K + Sigma)^-1 zbar: |W zbar|^2 / sl (L_chol) or zbar . q = -(zbar . L zbar)
-      if (var) o.zbkzb[s] = po->lchol[s] ? hsc[i] / po->sp[(size_t)s * SP_STRIDE + SP_SL] : hsc[i];
+      for (int i = 0; i < cnt; ++i)
+        o.zbkzb[s0 + i] = po->lchol[s0 + i] ? hsc[i] / po->sp[(size_t)(s0 + i) * SP_STRIDE + SP_SL] : hsc[i];
     }
-    for (int pl = 0; pl < npl; ++pl) {  // [(j*D + l)*S + s]
-      // tile pass: dza_dmu, dza_dsigma (, dzq_dmu, dzq_dsigma: the reduce kernel doubled them for quad_grad -- halved
-      // here, exactly); pair pass: dgw_dmu, dgw_dsigma
-      double* out = o.plane[pl < gpl ? pl : 4 + (pl - gpl)];
-      const double f = (pl >= 2 && pl < gpl) ? 0.5 : 1.0;
-      const double* gp = hpl + (size_t)pl * chunk * ss;
-      for (size_t jl = 0; jl < (size_t)M * D; ++jl) {
-        double* dst = out + jl * S + s0;
-        for (int i = 0; i < cnt; ++i) dst[i] = f * gp[i * ss + jl];
-      }
-    }
+    // [(j*D + l)*S + s].  Tile pass: dza_dmu, dza_dsigma (, dzq_dmu, dzq_dsigma: the reduce kernel doubled them for
+    // quad_grad -- halved here, exactly); pair pass: dgw_dmu, dgw_dsigma
+    for (int pl = 0; pl < npl; ++pl)
+      scatter_plane(o.plane[pl < gpl ? pl : 4 + (pl - gpl)], hpl + (size_t)pl * chunk * ss, (size_t)M * D, ss, S, s0, cnt,
+                    (pl >= 2 && pl < gpl) ? 0.5 : 1.0);
   }
   return 0;
 }
@@ -4595,6 +4609,12 @@ const char* gpc_last_error(const gpc_ctx* c) { return c ? c->err.c_str() : g_cre
 const char* gpc_device_info(gpc_ctx* c) { return c ? c->devinfo.c_str() : ""; }
 
 int gpc_cov_count(int kernel_id, int D) { return cov_count_of(kernel_id, D); }
+
+int gpc_debug_chunk_plan(int S, unsigned long long per, unsigned long long shared, unsigned long long budget,
+                         int clamp_to_one) {
+  if (S <= 0 || per == 0) return -2;
+  return chunk_from_budget(S, (size_t)per, (size_t)shared, (size_t)budget, clamp_to_one != 0);
+}
 
 int gpc_max_n(int dtype) {
   // A memory-budget answer (round 6; rounds 1-5: 16384 / 23168, the reach of one 32-bit byte offset over a k-major
@@ -4807,11 +4827,18 @@ int gpc_predict_K(gpc_post* po, int M, const double* Ks, const double* Kss, doub
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!Ks || !fmu || M <= 0 || (!fq && !cov) || (cov && !Kss)) FAIL(c, "gpc_predict_K: bad arguments");
-  for (int s = 0; s < po->S; ++s)
-    if (po->info[s] != 0) FAIL(c, "gpc_predict_K: posterior contains a failed factorization");
+  if (int rc = require_factorized(po, "gpc_predict_K")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  int rc = po->dtype == GPC_F64 ? rhs_products<double>(po, 2, Ks, Kss, M, fq != nullptr, fmu, fq, cov)
-                                : rhs_products<float>(po, 2, Ks, Kss, M, fq != nullptr, fmu, fq, cov);
+  RhsRequest r;
+  r.rhs = RhsRequest::GIVEN_KS;
+  r.xa = Ks;
+  r.xb = Kss;
+  r.M = M;
+  r.want_quad = fq != nullptr;
+  r.lin = fmu;
+  r.quad = fq;
+  r.full = cov;
+  int rc = rhs_products(po, r);
   if (rc || !fq) return rc;
   for (int s = 0; s < po->S; ++s) {  // the term the caller adds to kss (:1752-1764)
     const double sl = po->sp[(size_t)s * SP_STRIDE + SP_SL];
@@ -5001,8 +5028,7 @@ int gpc_predict(gpc_post* po, const double* xstar, int M, double* fmu, double* f
   gpc_ctx* c = po->ctx;
   if (!xstar || !fmu || !fs2 || M <= 0) FAIL(c, "gpc_predict: bad arguments");
   if (po->cd.kind < 0) FAIL(c, "gpc_predict: this posterior was built from caller-provided K; use gpc_predict_K");
-  for (int s = 0; s < po->S; ++s)
-    if (po->info[s] != 0) FAIL(c, "gpc_predict: posterior contains a failed factorization");
+  if (int rc = require_factorized(po, "gpc_predict")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   return po->dtype == GPC_F64 ? predict_impl<double>(po, xstar, M, fmu, fs2)
                               : predict_impl<float>(po, xstar, M, fmu, fs2);
@@ -5015,8 +5041,7 @@ int gpc_predict_grad(gpc_post* po, const double* xstar, int M, double* fmu, doub
   if (po->cd.kind < 0)
     FAIL(c, "gpc_predict_grad: this posterior was built from caller-provided K; a caller-provided kernel has no "
             "derivative with respect to x*");
-  for (int s = 0; s < po->S; ++s)
-    if (po->info[s] != 0) FAIL(c, "gpc_predict_grad: posterior contains a failed factorization");
+  if (int rc = require_factorized(po, "gpc_predict_grad")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   return po->dtype == GPC_F64 ? predict_impl<double>(po, xstar, M, fmu, fs2, dfmu, dfs2)
                               : predict_impl<float>(po, xstar, M, fmu, fs2, dfmu, dfs2);
@@ -5028,15 +5053,18 @@ int gpc_draw(gpc_post* po, const double* xstar, int M, int R, unsigned long long
   gpc_ctx* c = po->ctx;
   if (!xstar || !f || !tau || M <= 0 || R <= 0 || s_offset < 0) FAIL(c, "gpc_draw: bad arguments");
   if (po->cd.kind < 0) FAIL(c, "gpc_draw: this posterior was built from caller-provided K; there is no K** to draw from");
-  for (int s = 0; s < po->S; ++s)
-    if (po->info[s] != 0) FAIL(c, "gpc_draw: posterior contains a failed factorization");
+  if (int rc = require_factorized(po, "gpc_draw")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   DrawReq req{seed, R, s_offset, noise_sd, f, tau};
   std::vector<double> fmu((size_t)M * po->S);
   // (`full` only marks the covariance build: draw_chunk consumes C_s on the device, nothing M x M is written)
-  return po->dtype == GPC_F64
-             ? rhs_products<double>(po, 0, xstar, nullptr, M, false, fmu.data(), nullptr, f, nullptr, nullptr, &req)
-             : rhs_products<float>(po, 0, xstar, nullptr, M, false, fmu.data(), nullptr, f, nullptr, nullptr, &req);
+  RhsRequest r;
+  r.xa = xstar;
+  r.M = M;
+  r.lin = fmu.data();
+  r.full = f;
+  r.draw = &req;
+  return rhs_products(po, r);
 }
 
 int gpc_debug_normals(gpc_ctx* c, unsigned long long seed, int stream, int s, int r, int j0, int count, double* out) {
@@ -5066,8 +5094,7 @@ int gpc_paths_create(gpc_post* po, int R, int F, unsigned long long seed, int s_
   if (po->cd.kind == K_RQ)
     FAIL(c, "gpc_paths_create: the rational-quadratic kernel is not supported (spectral draws exist for the "
             "squared-exponential and Matern kernels)");
-  for (int s = 0; s < po->S; ++s)
-    if (po->info[s] != 0) FAIL(c, "gpc_paths_create: posterior contains a failed factorization");
+  if (int rc = require_factorized(po, "gpc_paths_create")) return rc;
   if (c->N != po->N || c->D != po->D)
     FAIL(c, "gpc_paths_create: the context's data (gpc_set_data) is not the data this posterior was built on");
   HIPCHK(c, hipSetDevice(c->device));
@@ -5137,11 +5164,14 @@ int gpc_predict_full(gpc_post* po, const double* xstar, int M, double* fmu, doub
   gpc_ctx* c = po->ctx;
   if (!xstar || !fmu || !cov || M <= 0) FAIL(c, "gpc_predict_full: bad arguments");
   if (po->cd.kind < 0) FAIL(c, "gpc_predict_full: this posterior was built from caller-provided K; use gpc_predict_K");
-  for (int s = 0; s < po->S; ++s)
-    if (po->info[s] != 0) FAIL(c, "gpc_predict_full: posterior contains a failed factorization");
+  if (int rc = require_factorized(po, "gpc_predict_full")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  return po->dtype == GPC_F64 ? rhs_products<double>(po, 0, xstar, nullptr, M, false, fmu, nullptr, cov)
-                              : rhs_products<float>(po, 0, xstar, nullptr, M, false, fmu, nullptr, cov);
+  RhsRequest r;
+  r.xa = xstar;
+  r.M = M;
+  r.lin = fmu;
+  r.full = cov;
+  return rhs_products(po, r);
 }
 
 int gpc_predict_cov(gpc_post* po, const double* xa, int Ma, const double* xb, int Mb, const double* w, int w_per_sample,
@@ -5151,8 +5181,7 @@ int gpc_predict_cov(gpc_post* po, const double* xa, int Ma, const double* xb, in
   if (!xa || !xb || Ma <= 0 || Mb <= 0 || (!cov && !wsq) || (wsq && !w)) FAIL(c, "gpc_predict_cov: bad arguments");
   if (po->cd.kind < 0)
     FAIL(c, "gpc_predict_cov: this posterior was built from caller-provided K; there is no k(xa, xb) to start from");
-  for (int s = 0; s < po->S; ++s)
-    if (po->info[s] != 0) FAIL(c, "gpc_predict_cov: posterior contains a failed factorization");
+  if (int rc = require_factorized(po, "gpc_predict_cov")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   return po->dtype == GPC_F64 ? cov_products<double>(po, xa, Ma, xb, Mb, w, w_per_sample, fs2b, cov, wsq)
                               : cov_products<float>(po, xa, Ma, xb, Mb, w, w_per_sample, fs2b, cov, wsq);
@@ -5179,9 +5208,7 @@ int gpc_quad(gpc_post* po, const double* mu, const double* sigma, int M, int com
   if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
     FAIL(c, "Bayesian quadrature only supports the squared exponential kernel.");
   HIPCHK(c, hipSetDevice(c->device));
-  int rc = po->dtype == GPC_F64
-               ? rhs_products<double>(po, 1, mu, sigma, M, compute_var != 0, zalpha, zKz, nullptr)
-               : rhs_products<float>(po, 1, mu, sigma, M, compute_var != 0, zalpha, zKz, nullptr);
+  int rc = rhs_products(po, quad_request(mu, sigma, M, compute_var != 0, zalpha, zKz));
   if (rc || !compute_var) return rc;
   quad_scale_zkz(po, M, zKz);
   return 0;
@@ -5196,15 +5223,12 @@ int gpc_quad_grad(gpc_post* po, const double* mu, const double* sigma, int M, in
     FAIL(c, "gpc_quad_grad: bad arguments");
   if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
     FAIL(c, "Bayesian quadrature only supports the squared exponential kernel.");
-  for (int s = 0; s < po->S; ++s)
-    if (po->info[s] != 0) FAIL(c, "gpc_quad_grad: posterior contains a failed factorization");
+  if (int rc = require_factorized(po, "gpc_quad_grad")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const QuadGradOut g{{dza_dmu, dza_dsigma, compute_var ? dzkz_dmu : nullptr, compute_var ? dzkz_dsigma : nullptr}};
-  int rc = po->dtype == GPC_F64
-               ? rhs_products<double>(po, 1, mu, sigma, M, compute_var != 0, zalpha, zKz, nullptr, nullptr, nullptr,
-                                      nullptr, &g)
-               : rhs_products<float>(po, 1, mu, sigma, M, compute_var != 0, zalpha, zKz, nullptr, nullptr, nullptr,
-                                     nullptr, &g);
+  RhsRequest r = quad_request(mu, sigma, M, compute_var != 0, zalpha, zKz);
+  r.qg = &g;
+  int rc = rhs_products(po, r);
   if (rc || !compute_var) return rc;
   quad_scale_zkz(po, M, zKz);  // (the dzkz planes come back scaled on the device: qs rides in the weights)
   return 0;
@@ -5218,11 +5242,11 @@ int gpc_quad_cov(gpc_post* po, const double* mu, const double* sigma, int M, dou
     FAIL(c, "gpc_quad_cov: this posterior was built from caller-provided K; it has no kernel to integrate");
   if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
     FAIL(c, "Bayesian quadrature only supports the squared exponential kernel.");
-  for (int s = 0; s < po->S; ++s)
-    if (po->info[s] != 0) FAIL(c, "gpc_quad_cov: posterior contains a failed factorization");
+  if (int rc = require_factorized(po, "gpc_quad_cov")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  return po->dtype == GPC_F64 ? rhs_products<double>(po, 1, mu, sigma, M, false, zalpha, nullptr, cov)
-                              : rhs_products<float>(po, 1, mu, sigma, M, false, zalpha, nullptr, cov);
+  RhsRequest r = quad_request(mu, sigma, M, false, zalpha, nullptr);
+  r.full = cov;
+  return rhs_products(po, r);
 }
 
 int gpc_quad_mix(gpc_post* po, const double* mu, const double* sigma, const double* w, int M, int compute_var,
@@ -5238,8 +5262,7 @@ int gpc_quad_mix(gpc_post* po, const double* mu, const double* sigma, const doub
     FAIL(c, "gpc_quad_mix: this posterior was built from caller-provided K; it has no kernel to integrate");
   if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
     FAIL(c, "Bayesian quadrature only supports the squared exponential kernel.");
-  for (int s = 0; s < po->S; ++s)
-    if (po->info[s] != 0) FAIL(c, "gpc_quad_mix: posterior contains a failed factorization");
+  if (int rc = require_factorized(po, "gpc_quad_mix")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   const QuadMixOut o{zalpha, zbkzb, gw, zq, {dza_dmu, dza_dsigma, dzq_dmu, dzq_dsigma, dgw_dmu, dgw_dsigma}};
   const long long gemms0 = gpc::g_gemm_launches;
@@ -5257,138 +5280,113 @@ int gpc_last_timing(gpc_ctx* c, double* ms_total, double* ms_factor) {
 }
 
 namespace {
+// One row per name of gpc_set_option / gpc_get_option.  `get` reads the value (null: a test hook that is only ever
+// set), `set` stores it with the option's own clamp and returns non-zero when what it triggers fails (null: a counter
+// or a report, get only).
+struct Option {
+  const char* name;
+  int (*get)(gpc_ctx*);
+  int (*set)(gpc_ctx*, int);
+};
+#ifdef GPC_EXPERIMENTS
+constexpr int IS_EXPERIMENTS_BUILD = 1;
+#else
+constexpr int IS_EXPERIMENTS_BUILD = 0;
+#endif
+int clamp_to(int lo, int hi, int v) { return std::max(lo, std::min(hi, v)); }
+int tile_multiple(int v) { return std::max(TILE, (v / TILE) * TILE); }
+int engine_choice(int v) { return v == 1 || v == 2 ? v : 0; }
+#define GPC_GET(expr) [](gpc_ctx* c) -> int { (void)c; return (int)(expr); }
+#define GPC_SET(stmt) [](gpc_ctx* c, int v) -> int { (void)c; stmt; return 0; }
+#define GPC_COUNTER(field) GPC_GET(c->field & 0x7fffffff), nullptr
+const Option OPTIONS[] = {
+    {"groups", GPC_GET(c->groups), GPC_SET(c->groups = clamp_to(1, gpc_ctx::MAXG, v))},
+    {"small_blocks", GPC_GET(gpc::g_small_launch_blocks), GPC_SET(gpc::g_small_launch_blocks = v)},
+    {"dual_launch", GPC_GET(gpc::g_dual_launch ? 1 : 0), GPC_SET(gpc::g_dual_launch = v != 0)},  // syrk + inverse product of a node in one launch (default 1)
+    {"leaf", GPC_GET(gpc::g_leaf_version), GPC_SET(gpc::g_leaf_version = v == 3 ? 3 : 5)},  // 5: pipelined leaf (default), 3: barrier-per-phase leaf (A/B and bit-identity tests)
+    {"defer_min", GPC_GET(c->defer_min), GPC_SET(c->defer_min = v)},  // deferred inverse products: node size from which U runs on the side stream (0 off, -1 auto)
+    // CUs per XCD a deferred launch stays off (2, 4, 8, 12; >= 32: all of them, a test hook): the table is rebuilt
+    {"defer_reserve", GPC_GET(c->defer_reserve), [](gpc_ctx* c, int v) -> int { return c->defer_reserve = v, build_reserve_table(c); }},
+    {"leaf_fault", nullptr, GPC_SET(gpc::g_leaf_fault = v != 0)},  // test hook: the pipelined leaf runs with a missing wave, its hand-offs time out
+    {"nll_block", GPC_GET(c->nll_block), GPC_SET(c->nll_block = v < 0 ? -1 : (v == 0 ? 0 : tile_multiple(v)))},  // NLL-only: largest diagonal block with an inverse (multiple of 128; 0: left children inverted)
+    {"solves_beside_lauum", GPC_GET(c->solves_beside_lauum), GPC_SET(c->solves_beside_lauum = v != 0)},  // 0: the triangular mat-vecs after the W^T W launch (round-2 order)
+    {"stable", GPC_GET(c->stable), GPC_SET(c->stable = v != 0)},  // every factorization in stable mode (refined panel solves, plan.h), not only the jitter retries
+    {"small_path", GPC_GET(c->small_path), GPC_SET(c->small_path = v != 0)},  // 0: problems of one leaf take the general pipeline too (A/B and cross-checks)
+    {"check_queues", GPC_GET(c->check_queues), GPC_SET(c->check_queues = v != 0)},  // debug: verify the tile queues of persistent launches after every pipeline
+    {"small_poll", GPC_GET(c->small_poll), GPC_SET(c->small_poll = v != 0)},  // 0: one-leaf evaluations wait on the stream instead of polling their landing block
+    {"small_timing", GPC_GET(c->small_timing), GPC_SET(c->small_timing = v != 0)},  // 1: one-leaf evaluations record their timing events (gpc_last_timing is 0 for them otherwise)
+    {"small_polled", GPC_COUNTER(small_polled)},  // one-leaf calls completed by the polled word ...
+    {"small_synced", GPC_COUNTER(small_synced)},  // ... and by a stream synchronisation
+    {"cov_fused", GPC_COUNTER(cov_fused)},        // gpc_predict_cov calls reduced in the product's epilogue
+    {"quad_mix_gemms", GPC_COUNTER(quad_mix_gemms)},  // MFMA GEMM launches inside gpc_quad_mix
+    {"start_mult_log10", nullptr, GPC_SET(c->start_mult = std::pow(10.0, clamp_to(0, 9, v)))},  // test hook: first jitter multiplier 10^value
+    {"append_fail_mask", nullptr, GPC_SET(c->append_fail_mask = (unsigned)v)},  // test hook: samples whose rank-one append is declared unstable
+    // test hooks: 1 / 2 force an engine (0: the default), and what the last call ran (1 / 2; 0: none yet) --
+    // gpc_post_append_block: skinny kernel / MFMA GEMM, by k
+    {"block_engine", GPC_GET(c->block_engine), GPC_SET(c->block_engine = engine_choice(v))},
+    {"block_engine_ran", GPC_GET(c->block_engine_ran), nullptr},
+    {"paths_engine", GPC_GET(c->paths_engine), GPC_SET(c->paths_engine = engine_choice(v))},  // gpc_paths_eval: fused kernel / unfused composition
+    {"paths_engine_ran", GPC_GET(c->paths_engine_ran), nullptr},
+    {"paths_solve_engine", GPC_GET(c->paths_solve_engine), GPC_SET(c->paths_solve_engine = engine_choice(v))},  // the solve of gpc_paths_create: skinny kernel (0 / 1) / MFMA GEMM
+    {"paths_solve_engine_ran", GPC_GET(c->paths_solve_engine_ran), nullptr},
+    {"block_appended", GPC_COUNTER(block_appended)},  // samples gpc_post_append_block appended ...
+    {"block_stale", GPC_COUNTER(block_stale)},        // ... and left stale for gpc_post_recompute
+    {"experiments", GPC_GET(IS_EXPERIMENTS_BUILD), nullptr},  // 1: this library is the experiments build (tests/ and tools/ ask before they use its options)
+};
 #ifdef GPC_EXPERIMENTS
 // options of the schedules that exist in the experiments build only (see the include of dag.h)
-int* experiment_option(gpc_ctx* c, const std::string& n) {
-  if (n == "rect_min") return &gpc::g_rect_min_blocks;  // launches of at least this many 128-tiles (x samples) below the 128-tile threshold run as 128 x 64 tiles (0: off)
-  if (n == "rect_mode") return &gpc::g_rect_mode;       // what "rect_min" selects: 0 = 128 x 64 tiles of four waves, 1 = 128 x 128 tiles of eight waves
-  if (n == "indep") return &c->indep;                   // independent pipelines for batches of 2 .. indep_max samples at npad >= 2048 (0: lock-step)
-  if (n == "indep_max") return &c->indep_max;
-  if (n == "indep_min_tiles") return &c->indep_min_tiles;
-  if (n == "rl_ahead_max") return &c->rl_ahead_max;     // look-ahead of the right-looking plan only up to this batch work S (npad/4096)^3
-  if (n == "rl_panel") return &c->rl_panel;             // NLL-only: right-looking panels of this many rows with look-ahead (0: off)
-  if (n == "dag") return &c->dag;
-  if (n == "dag_small_tiles") return &c->dag_small_tiles;
-  if (n == "dag_lauum") return &c->dag_lauum;
-  if (n == "dag_leaf_blocks") return &c->dag_leaf_blocks;
-  if (n == "dag_aborts") return &c->dag_aborts;         // (tests: forget earlier aborts -- three of them switch the graph off for the context)
-  if (n == "dag_runs") return &c->dag_runs;
-  if (n == "dag_urgent_cus") return &c->dag_urgent_cus;
-  if (n == "dag_gate") return &c->dag_gate;
-  if (n == "dag_gate_pct") return &c->dag_gate_pct;
-  if (n == "dag_crit_pct") return &c->dag_crit_pct;
-  if (n == "dag_timeout_ms") return &c->dag_timeout_ms;
+#define GPC_INT_OPTION(name, lvalue, clamped) {name, GPC_GET(lvalue), GPC_SET(lvalue = (clamped))}
+const Option EXPERIMENT_OPTIONS[] = {
+    GPC_INT_OPTION("rect_min", gpc::g_rect_min_blocks, v),  // launches of at least this many 128-tiles (x samples) below the 128-tile threshold run as 128 x 64 tiles (0: off)
+    GPC_INT_OPTION("rect_mode", gpc::g_rect_mode, v != 0),  // what "rect_min" selects: 0 = 128 x 64 tiles of four waves, 1 = 128 x 128 tiles of eight waves
+    GPC_INT_OPTION("indep", c->indep, v),  // independent pipelines for batches of 2 .. indep_max samples at npad >= 2048 (0: lock-step)
+    GPC_INT_OPTION("indep_max", c->indep_max, clamp_to(2, gpc_ctx::MAXG, v)),
+    GPC_INT_OPTION("indep_min_tiles", c->indep_min_tiles, std::max(1, v)),
+    GPC_INT_OPTION("rl_ahead_max", c->rl_ahead_max, v),  // look-ahead of the right-looking plan only up to this batch work S (npad/4096)^3
+    GPC_INT_OPTION("rl_panel", c->rl_panel, v <= 0 ? 0 : tile_multiple(v)),  // NLL-only: right-looking panels of this many rows with look-ahead (0: off)
+    GPC_INT_OPTION("dag", c->dag, v),
+    GPC_INT_OPTION("dag_small_tiles", c->dag_small_tiles, v),
+    GPC_INT_OPTION("dag_lauum", c->dag_lauum, v),
+    GPC_INT_OPTION("dag_leaf_blocks", c->dag_leaf_blocks, v),
+    GPC_INT_OPTION("dag_aborts", c->dag_aborts, v),  // (tests: forget earlier aborts -- three of them switch the graph off for the context)
+    GPC_INT_OPTION("dag_runs", c->dag_runs, v),
+    GPC_INT_OPTION("dag_urgent_cus", c->dag_urgent_cus, clamp_to(0, 15, v)),
+    GPC_INT_OPTION("dag_gate", c->dag_gate, v),
+    GPC_INT_OPTION("dag_gate_pct", c->dag_gate_pct, clamp_to(0, 100, v)),
+    GPC_INT_OPTION("dag_crit_pct", c->dag_crit_pct, clamp_to(0, 100, v)),
+    GPC_INT_OPTION("dag_timeout_ms", c->dag_timeout_ms, std::max(1, v)),  // (a wait of no length would abort every graph at once: ADVICE r5)
+};
+#undef GPC_INT_OPTION
+#endif
+#undef GPC_GET
+#undef GPC_SET
+#undef GPC_COUNTER
+
+const Option* find_option(const char* name) {
+  for (const Option& o : OPTIONS)
+    if (!strcmp(o.name, name)) return &o;
+#ifdef GPC_EXPERIMENTS
+  for (const Option& o : EXPERIMENT_OPTIONS)
+    if (!strcmp(o.name, name)) return &o;
+#endif
   return nullptr;
 }
-int clamp_experiment_option(const std::string& n, int value) {
-  if (n == "indep_max") return std::max(2, std::min((int)gpc_ctx::MAXG, value));
-  if (n == "indep_min_tiles") return std::max(1, value);
-  if (n == "rect_mode") return value != 0;
-  if (n == "rl_panel") return value <= 0 ? 0 : std::max(TILE, (value / TILE) * TILE);
-  if (n == "dag_urgent_cus") return std::max(0, std::min(15, value));
-  if (n == "dag_gate_pct" || n == "dag_crit_pct") return std::max(0, std::min(100, value));
-  if (n == "dag_timeout_ms") return std::max(1, value);  // (a wait of no length would abort every graph at once: ADVICE r5)
-  return value;
-}
-#endif
 }  // namespace
 
 int gpc_set_option(gpc_ctx* c, const char* name, int value) {
   if (!c || !name) return -2;
-  const std::string n(name);
-  if (n == "groups")
-    c->groups = std::max(1, std::min((int)gpc_ctx::MAXG, value));
-  else if (n == "small_blocks")
-    gpc::g_small_launch_blocks = value;
-  else if (n == "dual_launch")  // syrk + inverse product of a node in one launch (default 1)
-    gpc::g_dual_launch = value != 0;
-  else if (n == "leaf")  // 5: pipelined leaf (default), 3: barrier-per-phase leaf (A/B and bit-identity tests)
-    gpc::g_leaf_version = value == 3 ? 3 : 5;
-  else if (n == "defer_min")  // deferred inverse products: node size from which U runs on the side stream (0 off, -1 auto)
-    c->defer_min = value;
-  else if (n == "defer_reserve") {  // CUs per XCD a deferred launch stays off (2, 4, 8, 12; >= 32: all of them, a test hook)
-    c->defer_reserve = value;
-    if (build_reserve_table(c)) return -1;
-  } else if (n == "leaf_fault")  // test hook: the pipelined leaf runs with a missing wave, its hand-offs time out
-    gpc::g_leaf_fault = value != 0;
-  else if (n == "nll_block")  // NLL-only: largest diagonal block with an inverse (multiple of 128; 0: left children inverted)
-    c->nll_block = value < 0 ? -1 : (value == 0 ? 0 : std::max(TILE, (value / TILE) * TILE));
-  else if (n == "solves_beside_lauum")  // 0: the triangular mat-vecs after the W^T W launch (round-2 order)
-    c->solves_beside_lauum = value != 0;
-  else if (n == "stable")  // every factorization in stable mode (refined panel solves, plan.h), not only the jitter retries
-    c->stable = value != 0;
-  else if (n == "small_path")  // 0: problems of one leaf take the general pipeline too (A/B and cross-checks)
-    c->small_path = value != 0;
-  else if (n == "check_queues")  // debug: verify the tile queues of persistent launches after every pipeline
-    c->check_queues = value != 0;
-  else if (n == "small_poll")  // 0: one-leaf evaluations wait on the stream instead of polling their landing block
-    c->small_poll = value != 0;
-  else if (n == "small_timing")  // 1: one-leaf evaluations record their timing events (gpc_last_timing is 0 for them otherwise)
-    c->small_timing = value != 0;
-  else if (n == "start_mult_log10")  // test hook: first jitter multiplier 10^value
-    c->start_mult = std::pow(10.0, std::max(0, std::min(9, value)));
-  else if (n == "append_fail_mask")  // test hook: samples whose rank-one append is declared unstable
-    c->append_fail_mask = (unsigned)value;
-  else if (n == "block_engine")  // test hook: 1 / 2 force the skinny kernel / the MFMA GEMM in gpc_post_append_block (0: by k)
-    c->block_engine = value == 1 || value == 2 ? value : 0;
-  else if (n == "paths_engine")  // test hook: 1 / 2 force the fused kernel / the unfused composition in gpc_paths_eval (0: the default)
-    c->paths_engine = value == 1 || value == 2 ? value : 0;
-  else if (n == "paths_solve_engine")  // test hook: 2 runs the solve of gpc_paths_create on the MFMA GEMM (0 / 1: skinny kernel)
-    c->paths_solve_engine = value == 1 || value == 2 ? value : 0;
-  else {
-#ifdef GPC_EXPERIMENTS
-    if (int* slot = experiment_option(c, n))
-      *slot = clamp_experiment_option(n, value);
-    else
-#endif
-      FAIL(c, "gpc_set_option: unknown option");
-  }
+  const Option* o = find_option(name);
+  if (!o || !o->set) FAIL(c, "gpc_set_option: unknown option");
+  if (o->set(c, value)) return -1;
   ++g_alloc_epoch;  // cached launch graphs captured the old launch shapes
   return 0;
 }
 
 int gpc_get_option(gpc_ctx* c, const char* name, int* value) {
   if (!c || !name || !value) return -2;
-  const std::string n(name);
-  if (n == "groups") *value = c->groups;
-  else if (n == "small_blocks") *value = gpc::g_small_launch_blocks;
-  else if (n == "dual_launch") *value = gpc::g_dual_launch ? 1 : 0;
-  else if (n == "leaf") *value = gpc::g_leaf_version;
-  else if (n == "defer_min") *value = c->defer_min;
-  else if (n == "defer_reserve") *value = c->defer_reserve;
-  else if (n == "nll_block") *value = c->nll_block;
-  else if (n == "solves_beside_lauum") *value = c->solves_beside_lauum;
-  else if (n == "stable") *value = c->stable;
-  else if (n == "small_path") *value = c->small_path;
-  else if (n == "check_queues") *value = c->check_queues;
-  else if (n == "small_poll") *value = c->small_poll;
-  else if (n == "small_timing") *value = c->small_timing;
-  else if (n == "small_polled") *value = (int)(c->small_polled & 0x7fffffff);  // one-leaf calls completed by the polled word ...
-  else if (n == "small_synced") *value = (int)(c->small_synced & 0x7fffffff);  // ... and by a stream synchronisation
-  else if (n == "cov_fused") *value = (int)(c->cov_fused & 0x7fffffff);  // gpc_predict_cov calls reduced in the product's epilogue
-  else if (n == "quad_mix_gemms") *value = (int)(c->quad_mix_gemms & 0x7fffffff);  // MFMA GEMM launches inside gpc_quad_mix
-  else if (n == "block_engine") *value = c->block_engine;
-  else if (n == "block_engine_ran") *value = c->block_engine_ran;  // 1 / 2: what the last block append ran (0: none yet)
-  else if (n == "paths_engine") *value = c->paths_engine;
-  else if (n == "paths_engine_ran") *value = c->paths_engine_ran;  // 1 / 2: what the last gpc_paths_eval ran (0: none yet)
-  else if (n == "paths_solve_engine") *value = c->paths_solve_engine;
-  else if (n == "paths_solve_engine_ran") *value = c->paths_solve_engine_ran;  // 1 / 2: what the last gpc_paths_create ran
-  else if (n == "block_appended") *value = (int)(c->block_appended & 0x7fffffff);  // samples gpc_post_append_block appended ...
-  else if (n == "block_stale") *value = (int)(c->block_stale & 0x7fffffff);  // ... and left stale for gpc_post_recompute
-  else if (n == "experiments") {  // 1: this library is the experiments build (tests/ and tools/ ask before they use its options)
-#ifdef GPC_EXPERIMENTS
-    *value = 1;
-#else
-    *value = 0;
-#endif
-  } else {
-#ifdef GPC_EXPERIMENTS
-    if (int* slot = experiment_option(c, n))
-      *value = *slot;
-    else
-#endif
-      FAIL(c, "gpc_get_option: unknown option");
-  }
+  const Option* o = find_option(name);
+  if (!o || !o->get) FAIL(c, "gpc_get_option: unknown option");
+  *value = o->get(c);
   return 0;
 }
 

@@ -466,6 +466,14 @@ int gpc_debug_cov(gpc_ctx* ctx, int which, int kernel_id, int degree, int dtype,
 /* Debug: wrapping-sum hash of every 128 x 128 tile of one workspace matrix as the LAST call left it (which: 0 = A, 1 = W,
  * 2 = T; sample: position in the last chunk); out[(npad/128)^2].  Finds the tile where two schedules differ.          */
 int gpc_debug_workspace_hash(gpc_ctx* ctx, int dtype, int which, int sample, unsigned long long* out);
+
+/* Debug, HOST ONLY (no device needed): the samples per chunk every posterior consumer and evaluation works on when
+ * each sample needs `per` bytes of scratch beside `shared` bytes for the whole call and `budget` bytes may be used
+ * (the callers pass 80 % of what is free, or of GPC_MEM_BUDGET_MB).  min(S, (budget - shared) / per); when not even
+ * one sample fits: 0 (the caller refuses), or 1 with clamp_to_one (the caller runs one sample at a time anyway).
+ * -2 for S <= 0 or per = 0.                                                                                          */
+int gpc_debug_chunk_plan(int S, unsigned long long per, unsigned long long shared, unsigned long long budget,
+                         int clamp_to_one);
 /* ---- experiments build only (hipcc -DGPC_EXPERIMENTS -> lib/libgpcore_exp.so; NOT part of the product library) --------
  * Schedules that were built, measured and rejected (tile-level dataflow graph, independent pipelines,
  * rectangular / eight-wave tiles, right-looking panels) and their gpc_set_option names live there;

@@ -80,6 +80,45 @@ def test_size_envelope_entry_point_without_gpu():
             assert 3 * n * n * w <= 0.8 * total < 3 * (n + 128) * (n + 128) * w
 
 
+def test_chunk_plan_matches_the_parents_formulas():
+    """gpc_debug_chunk_plan (common.h: chunk_from_budget, the one planner of every consumer's sample chunks) against the
+    expressions the consumers carried before they shared it: 80 % of the budget (double product, truncated -- fed in as
+    the caller forms it), a refusal when one sample and the shared block do not fit, min(S, (budget - shared) // per),
+    and max(1, ...) for the callers that run one sample whatever the budget says."""
+    from gpyreg_amd import _lib
+
+    lib = _lib.load()
+
+    def before(S, per, shared, budget, clamp):
+        if clamp:
+            return max(1, min(S, (budget - shared) // per))
+        if budget < shared + per:
+            return 0
+        return min(S, (budget - shared) // per)
+
+    checked = refused = clamped = 0
+    for S in (1, 2, 7, 1024):
+        for per in (1 << 10, 3000, 96 << 10, (1 << 20) + 8, 3686400, 1 << 30, 4 << 30):
+            for shared in (0, 12345, 1 << 16):
+                for edge in (shared + per, shared + S * per):
+                    r0 = int(edge / 0.8)
+                    for raw in range(max(0, r0 - 3), r0 + 4):
+                        budget = int(float(raw) * 0.8)
+                        for clamp in (0, 1):
+                            want = before(S, per, shared, budget, clamp)
+                            assert lib.gpc_debug_chunk_plan(S, per, shared, budget, clamp) == want, \
+                                (S, per, shared, raw, budget, clamp)
+                            checked += 1
+                            refused += want == 0
+                            clamped += clamp and budget < shared + per
+                    products = {int(float(raw) * 0.8) for raw in range(max(0, r0 - 3), r0 + 4)}
+                    assert {edge - 1, edge, edge + 1} <= products  # just below, at and just above the threshold
+    assert checked > 2000 and refused > 100 and clamped > 100
+    # budgets far from the thresholds: nothing, and more than everything
+    assert lib.gpc_debug_chunk_plan(7, 1 << 20, 0, 0, 0) == 0 and lib.gpc_debug_chunk_plan(7, 1 << 20, 0, 0, 1) == 1
+    assert lib.gpc_debug_chunk_plan(7, 1 << 20, 1 << 16, 1 << 40, 0) == 7
+
+
 def test_assigning_data_attributes_marks_the_device_copy_stale():
     """gp.X = ..., gp.y = ... (the reference's tests assign them directly) must invalidate the
     resident copy; invalidate() covers in-place edits."""
