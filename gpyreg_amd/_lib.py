@@ -84,6 +84,7 @@ SIGNATURES = {
     "gpc_quad_grad": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpc_quad_cov": (C.c_int, [_vp, _dp, _dp, C.c_int, _dp, _dp]),
     "gpc_quad_mix": (C.c_int, [_vp, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int] + [_dp] * 10),
+    "gpc_cv": (C.c_int, [_vp, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp, _ip]),
     "gpc_last_timing": (C.c_int, [_vp, _dp, _dp]),
     "gpc_last_lauum_timing": (C.c_int, [_vp, _dp, _dp]),
     "gpc_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
@@ -739,6 +740,30 @@ class PostHandle:
                                         1 if compute_grad else 0, *[_ptr(v) for v in r.values()])
         self.ctx._check(rc, "gpc_quad_mix")
         return r
+
+    @_serial
+    def cv(self, folds=None):
+        """gpc_cv: leave-fold-out predictions from the resident posterior.  ``folds``: None (leave-one-out) or a
+        sequence of index arrays, each strictly ascending, pairwise disjoint.  Returns (dmu, s2, quad, logdet, info):
+        dmu and s2 (N, S), NaN at points in no fold; quad, logdet and info (F, S), or (N, S) for leave-one-out."""
+        N, S = self.N, self.S
+        dmu, s2 = np.empty((N, S)), np.empty((N, S))
+        if folds is None:
+            F, ptr, idx = 0, None, None
+        else:
+            F = len(folds)
+            if F == 0:
+                raise ValueError("cv: folds must not be an empty sequence")
+            ptr = np.zeros(F + 1, dtype=np.int32)
+            ptr[1:] = np.cumsum([len(f) for f in folds])
+            idx = np.ascontiguousarray(np.concatenate([np.asarray(f).ravel() for f in folds]), dtype=np.int32)
+        n_out = F if F else N
+        quad, logdet = np.empty((n_out, S)), np.empty((n_out, S))
+        info = np.empty((n_out, S), dtype=np.int32)
+        rc = self.ctx._lib.gpc_cv(self._h, F, _ptr(ptr), _ptr(idx), _ptr(dmu), _ptr(s2), _ptr(quad), _ptr(logdet),
+                                  _ptr(info))
+        self.ctx._check(rc, "gpc_cv")
+        return dmu, s2, quad, logdet, info
 
     @_serial
     def free(self):

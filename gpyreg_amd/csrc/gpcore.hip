@@ -23,6 +23,7 @@
 #include "block_append.h"
 #include "common.h"
 #include "covfun.h"
+#include "cv.h"
 #include "draw.h"
 #include "gemm.h"
 #include "leaf.h"
@@ -578,6 +579,8 @@ struct gpc_ctx {
   int paths_engine_ran = 0;  // the engine the last gpc_paths_eval ran (get-only)
   int paths_solve_engine = 0;      // test hook: the products of gpc_paths_create's solve (0 / 1: skinny kernel, 2: MFMA GEMM)
   int paths_solve_engine_ran = 0;  // the engine the last gpc_paths_create ran (get-only)
+  int cv_engine = 0;      // test hook: the engine of gpc_cv's fold Gram (0: cv.h's CV_DEFAULT_ENGINE, 1: fused gather + MFMA, 2: panels + library GEMM)
+  int cv_engine_ran = 0;  // the engine the last gpc_cv ran (get-only; 0: the leave-one-out pass, which has none)
   int retry_runs = 0;  // device pipelines spent on jitter retries by the last call (one per level)
 #ifdef GPC_EXPERIMENTS
   // ---- tile-level dataflow (dag.h).  Option "dag": 0 off, 1 wherever the plan supports it, -1 automatic (by what was
@@ -3926,6 +3929,218 @@ int append_block_check(gpc_post* po, int k, const char* fn) {
 }  // namespace
 
 
+// ---- cross-validation (cv.h; DESIGN.md "Cross-validation") --------------------------------------------------------
+namespace {
+
+// per-sample parameters of the kernels of cv.h (block_append.h's layout), uploaded into c->avec
+int cv_upload_par(gpc_post* po, double** d_par) {
+  gpc_ctx* c = po->ctx;
+  const int S = po->S;
+  std::vector<double> par((size_t)S * BA_STRIDE, 0.0);
+  for (int s = 0; s < S; ++s) {
+    par[(size_t)s * BA_STRIDE + BA_SL] = po->sp[(size_t)s * SP_STRIDE + SP_SL];
+    par[(size_t)s * BA_STRIDE + BA_LCH] = po->lchol[s] ? 1.0 : 0.0;
+    par[(size_t)s * BA_STRIDE + BA_PRE] = 1.0;
+  }
+  HIPCHK(c, c->avec.ensure((size_t)S * BA_STRIDE * 8));
+  // (pageable source: the copy is staged before the call returns)
+  HIPCHK(c, hipMemcpy(c->avec.p, par.data(), par.size() * 8, hipMemcpyHostToDevice));
+  *d_par = c->avec.as<double>();
+  return 0;
+}
+
+// Leave-one-out: cv_diag_kernel over the samples of a chunk, five planes of N_pad per sample and nothing else.
+// All outputs are N x S.
+template <typename T>
+int cv_loo_impl(gpc_post* po, double* dmu, double* s2, double* quad, double* logdet, int* info) {
+  gpc_ctx* c = po->ctx;
+  hipStream_t st = c->st;
+  const int S = po->S, N = po->N, npad = po->npad;
+  const long long sM = (long long)npad * npad;
+  c->cv_engine_ran = 0;
+  const size_t per = 5 * (size_t)npad * 8;
+  const int chunk = plan_chunk(c, S, per, 0, c->ks.bytes, (size_t)S * per <= c->ks.bytes, 0, false, [&](size_t budget) {
+    return "gpc_cv: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " + std::to_string(npad) +
+           ", F = 0, k_max = 1) exceeds the device memory budget (" + std::to_string(budget >> 10) + " KB)";
+  });
+  if (!chunk) return -2;
+  double* d_par = nullptr;
+  if (int rc = cv_upload_par(po, &d_par)) return rc;
+  HIPCHK(c, c->ks.ensure((size_t)chunk * per));
+  std::unique_ptr<double[]> spare;
+  c->pin.begin();
+  double* h = landing_block(c, (size_t)chunk * per, spare);
+  c->ms_total = c->ms_factor = 0;
+  CallTimer tm{c, true};
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    const size_t pl = (size_t)cnt * npad;
+    double* d = c->ks.as<double>();
+    HIPCHK(c, tm.start());
+    HIPCHK(c, tm.mark1());
+    hipLaunchKernelGGL((cv_diag_kernel<T>), dim3((N + CV_T - 1) / CV_T, cnt), dim3(256), 0, st,
+                       (const T*)(po->A.as<T>() + (size_t)s0 * sM), (const T*)(po->W.as<T>() + (size_t)s0 * sM), sM, npad, N,
+                       (const double*)(po->alpha.as<double>() + (size_t)s0 * npad),
+                       (const double*)(d_par + (size_t)s0 * BA_STRIDE), d, d + pl, d + 2 * pl, d + 3 * pl,
+                       reinterpret_cast<int*>(d + 4 * pl));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, tm.mark2());
+    HIPCHK(c, tm.stop());
+    HIPCHK(c, hipMemcpyAsync(h, d, 5 * pl * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    tm.accumulate();
+    scatter_plane(dmu, h, N, npad, S, s0, cnt);
+    scatter_plane(s2, h + pl, N, npad, S, s0, cnt);
+    if (quad) scatter_plane(quad, h + 2 * pl, N, npad, S, s0, cnt);
+    if (logdet) scatter_plane(logdet, h + 3 * pl, N, npad, S, s0, cnt);
+    if (info) {
+      const int* hi = reinterpret_cast<const int*>(h + 4 * pl);
+      for (int i = 0; i < N; ++i)
+        for (int q = 0; q < cnt; ++q) info[(size_t)i * S + s0 + q] = hi[(size_t)q * npad + i];
+    }
+  }
+  return 0;
+}
+
+// Folds of more than one point: Gram (or gather) -> one batched fp64 factorization of all (sample, fold) pairs of the
+// chunk -> epilogue.  fold_ptr / fold_idx have been validated.
+template <typename T>
+int cv_fold_impl(gpc_post* po, int F, const int* fold_ptr, const int* fold_idx, double* dmu, double* s2, double* quad,
+                 double* logdet, int* info) {
+  gpc_ctx* c = po->ctx;
+  hipStream_t st = c->st;
+  const int S = po->S, N = po->N, npad = po->npad;
+  const long long sM = (long long)npad * npad;
+  int kmax = 0;
+  for (int f = 0; f < F; ++f) kmax = std::max(kmax, fold_ptr[f + 1] - fold_ptr[f]);
+  const int kp = pad_tile(kmax), total = fold_ptr[F];
+  const int engine = c->cv_engine ? c->cv_engine : CV_DEFAULT_ENGINE;
+  c->cv_engine_ran = engine;
+  const size_t kk = (size_t)kp * kp;
+  // scratch of one sample: G, its inverse factor and the factorization's third slab for every fold, the vectors u, the
+  // two output planes, [quad | logdet | ld | info] per fold, and engine 2's gathered panels
+  const size_t per = (size_t)F * (3 * kk + kp) * 8 + (engine == 2 ? (size_t)F * npad * kp * 8 : 0) + 2 * (size_t)npad * 8 +
+                     (size_t)F * 32 + 64;
+  int chunk = plan_chunk(c, S, per, 0, c->ks.bytes, (size_t)S * per <= c->ks.bytes, 0, false, [&](size_t budget) {
+    return "gpc_cv: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " + std::to_string(npad) +
+           ", F = " + std::to_string(F) + ", k_max = " + std::to_string(kmax) + ") exceeds the device memory budget (" +
+           std::to_string(budget >> 10) + " KB)";
+  });
+  if (!chunk) return -2;
+  chunk = std::min(chunk, 65535 / F);  // (sample, fold) pairs are one grid dimension of the batched launches
+  double* d_par = nullptr;
+  if (int rc = cv_upload_par(po, &d_par)) return rc;
+  HIPCHK(c, c->rvec.ensure((size_t)(F + 1 + total) * sizeof(int)));
+  int* d_ptr = c->rvec.as<int>();
+  int* d_idx = d_ptr + F + 1;
+  HIPCHK(c, hipMemcpy(d_ptr, fold_ptr, (size_t)(F + 1) * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(d_idx, fold_idx, (size_t)total * sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(c, c->ks.ensure((size_t)chunk * per));
+  const size_t out_doubles = 2 * (size_t)chunk * npad + 4 * (size_t)chunk * F;
+  std::unique_ptr<double[]> spare;
+  c->pin.begin();
+  double* h = landing_block(c, out_doubles * 8, spare);
+  c->ms_total = c->ms_factor = 0;
+  CallTimer tm{c, true};
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0), np = cnt * F;
+    double* G = c->ks.as<double>();
+    double* Wf = G + (size_t)np * kk;
+    double* Tm = Wf + (size_t)np * kk;
+    double* uv = Tm + (size_t)np * kk;
+    double* o_dmu = uv + (size_t)np * kp;  // the block that is downloaded: [dmu | s2 | quad | logdet | ld | info]
+    double* o_s2 = o_dmu + (size_t)cnt * npad;
+    double* o_quad = o_s2 + (size_t)cnt * npad;
+    double* o_logdet = o_quad + np;
+    double* d_ld = o_logdet + np;
+    int* d_info = reinterpret_cast<int*>(d_ld + np);
+    double* panel = d_ld + 2 * (size_t)np;  // (engine 2; 8-byte aligned behind the ints)
+    HIPCHK(c, tm.start());
+    HIPCHK(c, hipMemsetAsync(G, 0, 3 * (size_t)np * kk * 8, st));
+    HIPCHK(c, hipMemsetAsync(o_dmu, 0xff, 2 * (size_t)cnt * npad * 8, st));  // NaN: points in no fold
+    HIPCHK(c, hipMemsetAsync(o_quad, 0, 4 * (size_t)np * 8, st));            // (ld and info start from zero)
+    const double* parc = d_par + (size_t)s0 * BA_STRIDE;
+    const double* alc = po->alpha.as<double>() + (size_t)s0 * npad;
+    HIPCHK(c, tm.mark1());
+    const int tk = kp / CV_T;
+    const int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+      double* Gr = G + (size_t)a * F * kk;
+      if (!lch) {
+        hipLaunchKernelGGL((cv_gather_low_kernel<T>), dim3(tk * (kp / 4), F, len), dim3(64, 4), 0, st,
+                           (const T*)(po->A.as<T>() + (size_t)(s0 + a) * sM), sM, npad, F, (const int*)d_ptr,
+                           (const int*)d_idx, kp, Gr);
+      } else if (engine == 1) {
+        hipLaunchKernelGGL((cv_gram_kernel<T>), dim3(tk * (tk + 1) / 2, F, len), dim3(256), 0, st,
+                           (const T*)(po->W.as<T>() + (size_t)(s0 + a) * sM), sM, npad, N, F, (const int*)d_ptr,
+                           (const int*)d_idx, kp, Gr);
+      } else {
+        double* pr = panel + (size_t)a * F * npad * kp;
+        for (int i = 0; i < len; ++i)  // (F blocks in z per launch)
+          hipLaunchKernelGGL((cv_panel_kernel<T>), dim3(kp / 64, npad / 4, F), dim3(64, 4), 0, st,
+                             (const T*)(po->W.as<T>() + (size_t)(s0 + a + i) * sM), sM, npad, N, F, (const int*)d_ptr,
+                             (const int*)d_idx, kp, pr + (size_t)i * F * npad * kp);
+        GemmArgs g;
+        g.A = pr, g.B = pr, g.C = Gr;
+        g.sA = g.sB = (long long)npad * kp, g.sC = (long long)kk;
+        g.lda = g.ldb = g.ldc = kp;
+        g.M = g.N = kp, g.K = npad;
+        g.alpha = 1.0, g.beta = 0;
+        g.klo = KLO_ZERO, g.khi = KHI_FULL, g.lower_only = 1;
+        HIPCHK(c, launch_gemm<double>(st, g, true, true, len * F));
+        hipLaunchKernelGGL(cv_pad_diag_kernel, dim3(F, len), dim3(256), 0, st, F, (const int*)d_ptr, kp, Gr);
+      }
+      HIPCHK(c, hipGetLastError());
+      return 0;
+    });
+    if (rc_runs) return rc_runs;
+    HIPCHK(c, tm.mark2());
+    // one batched factorization of every (sample, fold) operand: factor and inverse factor, no jitter
+    Factor<double> Fc;
+    Fc.st = st;
+    Fc.batch = np;
+    Fc.npad = kp;
+    Fc.A = G;
+    Fc.W = Wf;
+    Fc.Tm = Tm;
+    Fc.sA = Fc.sW = Fc.sT = (long long)kk;
+    Fc.logdet = d_ld;
+    Fc.info = d_info;
+    Fc.nvalid = kmax;
+    Fc.potrf_inv(0, kp, true, true);
+    HIPCHK(c, Fc.err);
+    HIPCHK(c, hipGetLastError());
+    hipLaunchKernelGGL(cv_fold_u_kernel, dim3(tk, F, cnt), dim3(256), 0, st, (const double*)Wf, kp, F, (const int*)d_ptr,
+                       (const int*)d_idx, alc, npad, uv);
+    hipLaunchKernelGGL(cv_fold_out_kernel, dim3(tk, F, cnt), dim3(256), 0, st, (const double*)Wf, kp, F, (const int*)d_ptr,
+                       (const int*)d_idx, (const double*)uv, parc, (const double*)d_ld, (const int*)d_info, npad, o_dmu,
+                       o_s2, o_quad, o_logdet);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, tm.stop());
+    const size_t nd = 2 * (size_t)cnt * npad + 4 * (size_t)np;
+    HIPCHK(c, hipMemcpyAsync(h, o_dmu, nd * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    tm.accumulate();
+    const double* hq = h + 2 * (size_t)cnt * npad;
+    const int* hi = reinterpret_cast<const int*>(hq + 3 * (size_t)np);
+    for (int i = 0; i < np; ++i)
+      if (hi[i] & LEAF_TIMEOUT) {
+        c->err = "gpc_cv: internal error: a leaf of the factorization timed out";
+        return -3;
+      }
+    scatter_plane(dmu, h, N, npad, S, s0, cnt);
+    scatter_plane(s2, h + (size_t)cnt * npad, N, npad, S, s0, cnt);
+    if (quad) scatter_plane(quad, hq, F, F, S, s0, cnt);
+    if (logdet) scatter_plane(logdet, hq + np, F, F, S, s0, cnt);
+    if (info)
+      for (int f = 0; f < F; ++f)
+        for (int q = 0; q < cnt; ++q) info[(size_t)f * S + s0 + q] = hi[(size_t)q * F + f];
+  }
+  return 0;
+}
+
+}  // namespace
+
+
 // ---- pathwise posterior samples (paths.h; DESIGN.md "Pathwise samples") -------------------------------------------
 namespace {
 
@@ -5272,6 +5487,65 @@ int gpc_quad_mix(gpc_post* po, const double* mu, const double* sigma, const doub
   return rc;
 }
 
+int gpc_cv(gpc_post* po, int F, const int* fold_ptr, const int* fold_idx, double* dmu, double* s2, double* quad,
+           double* logdet, int* info) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  const int N = po->N, S = po->S;
+  if (!dmu || !s2 || F < 0 || (F > 0 && (!fold_ptr || !fold_idx)) || (F == 0 && (fold_ptr || fold_idx)))
+    FAIL(c, "gpc_cv: bad arguments");
+  if (N < 2) FAIL(c, "gpc_cv: cross-validation needs at least two training points");
+  if (F > 65535) FAIL(c, "gpc_cv: at most 65535 folds per call, got " + std::to_string(F));
+  bool singletons = true;
+  if (F > 0) {
+    if (fold_ptr[0] != 0) FAIL(c, "gpc_cv: fold_ptr must start at 0");
+    std::vector<int> owner(N, -1);
+    for (int f = 0; f < F; ++f) {
+      const int lo = fold_ptr[f], k = fold_ptr[f + 1] - lo;
+      const std::string name = "gpc_cv: fold " + std::to_string(f);
+      if (k <= 0) FAIL(c, name + " is empty");
+      if (k >= N) FAIL(c, name + " holds all " + std::to_string(N) + " points: nothing is left to predict from");
+      singletons = singletons && k == 1;
+      for (int j = 0; j < k; ++j) {
+        const int i = fold_idx[lo + j];
+        if (i < 0 || i >= N)
+          FAIL(c, name + " has index " + std::to_string(i) + " out of range [0, " + std::to_string(N) + ")");
+        if (j > 0 && i <= fold_idx[lo + j - 1]) FAIL(c, name + " is unsorted: its indices must ascend strictly");
+        if (owner[i] >= 0)
+          FAIL(c, name + " overlaps fold " + std::to_string(owner[i]) + " at index " + std::to_string(i));
+        owner[i] = f;
+      }
+    }
+  }
+  if (int rc = require_factorized(po, "gpc_cv")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const bool f64 = po->dtype == GPC_F64;
+  if (F == 0) return f64 ? cv_loo_impl<double>(po, dmu, s2, quad, logdet, info) : cv_loo_impl<float>(po, dmu, s2, quad, logdet, info);
+  if (!singletons)
+    return f64 ? cv_fold_impl<double>(po, F, fold_ptr, fold_idx, dmu, s2, quad, logdet, info)
+               : cv_fold_impl<float>(po, F, fold_ptr, fold_idx, dmu, s2, quad, logdet, info);
+  // explicit singletons: the leave-one-out pass itself (the same bits), its per-point values picked per fold
+  const size_t ns = (size_t)N * S;
+  std::vector<double> tm_(ns), ts(ns), tq(ns), tl(ns);
+  std::vector<int> ti(ns);
+  if (int rc = f64 ? cv_loo_impl<double>(po, tm_.data(), ts.data(), tq.data(), tl.data(), ti.data())
+                   : cv_loo_impl<float>(po, tm_.data(), ts.data(), tq.data(), tl.data(), ti.data()))
+    return rc;
+  std::fill(dmu, dmu + ns, std::nan(""));
+  std::fill(s2, s2 + ns, std::nan(""));
+  for (int f = 0; f < F; ++f) {
+    const size_t i = (size_t)fold_idx[fold_ptr[f]];
+    for (int s = 0; s < S; ++s) {
+      dmu[i * S + s] = tm_[i * S + s];
+      s2[i * S + s] = ts[i * S + s];
+      if (quad) quad[(size_t)f * S + s] = tq[i * S + s];
+      if (logdet) logdet[(size_t)f * S + s] = tl[i * S + s];
+      if (info) info[(size_t)f * S + s] = ti[i * S + s];
+    }
+  }
+  return 0;
+}
+
 int gpc_last_timing(gpc_ctx* c, double* ms_total, double* ms_factor) {
   if (!c) return -2;
   if (ms_total) *ms_total = c->ms_total;
@@ -5329,6 +5603,8 @@ const Option OPTIONS[] = {
     {"paths_engine_ran", GPC_GET(c->paths_engine_ran), nullptr},
     {"paths_solve_engine", GPC_GET(c->paths_solve_engine), GPC_SET(c->paths_solve_engine = engine_choice(v))},  // the solve of gpc_paths_create: skinny kernel (0 / 1) / MFMA GEMM
     {"paths_solve_engine_ran", GPC_GET(c->paths_solve_engine_ran), nullptr},
+    {"cv_engine", GPC_GET(c->cv_engine), GPC_SET(c->cv_engine = engine_choice(v))},  // gpc_cv's fold Gram: fused gather + MFMA / gathered panels + library GEMM
+    {"cv_engine_ran", GPC_GET(c->cv_engine_ran), nullptr},
     {"block_appended", GPC_COUNTER(block_appended)},  // samples gpc_post_append_block appended ...
     {"block_stale", GPC_COUNTER(block_stale)},        // ... and left stale for gpc_post_recompute
     {"experiments", GPC_GET(IS_EXPERIMENTS_BUILD), nullptr},  // 1: this library is the experiments build (tests/ and tools/ ask before they use its options)

@@ -131,6 +131,46 @@ def _mix_samples(means, variances):
     return centre, total, between
 
 
+def _cv_folds(folds, N):
+    """``cv_predict``'s reading of ``folds``: None (leave-one-out) stays None, an int F becomes F contiguous blocks
+    (``np.array_split``), a sequence of index collections becomes a list of sorted int64 arrays, validated."""
+    if folds is None:
+        return None
+    if isinstance(folds, (int, np.integer)) and not isinstance(folds, (bool, np.bool_)):
+        F = int(folds)
+        if F < 2 or F > N:
+            raise ValueError(f"cv_predict: an integer folds must lie in [2, N = {N}], got {F}")
+        return list(np.array_split(np.arange(N, dtype=np.int64), F))
+    try:
+        seq = list(folds)
+    except TypeError:
+        raise ValueError(f"cv_predict: folds must be None, an int or a sequence of index arrays, got {folds!r}") from None
+    if not seq:
+        raise ValueError("cv_predict: folds is an empty sequence")
+    owner = np.full(N, -1, dtype=np.int64)
+    out = []
+    for f, idx in enumerate(seq):
+        a = np.asarray(idx)
+        if a.size == 0:
+            raise ValueError(f"cv_predict: fold {f} is empty")
+        if a.dtype.kind not in "iu":
+            raise ValueError(f"cv_predict: fold {f} must hold integer indices, got dtype {a.dtype}")
+        a = np.sort(a.ravel().astype(np.int64))
+        if a[0] < 0 or a[-1] >= N:
+            bad = a[0] if a[0] < 0 else a[-1]
+            raise ValueError(f"cv_predict: fold {f} has index {bad} out of range [0, {N})")
+        if np.any(a[1:] == a[:-1]):
+            raise ValueError(f"cv_predict: fold {f} repeats index {a[1:][a[1:] == a[:-1]][0]}")
+        if a.size >= N:
+            raise ValueError(f"cv_predict: fold {f} holds all {N} points: nothing is left to predict from")
+        clash = owner[a] >= 0
+        if clash.any():
+            raise ValueError(f"cv_predict: fold {f} overlaps fold {owner[a][clash][0]} at index {a[clash][0]}")
+        owner[a] = f
+        out.append(a)
+    return out
+
+
 def _mix_sample_grads(means, dmeans, dvariances):
     """Gradients of ``_mix_samples``' mixture moments.  means (M, S); dmeans, dvariances (M, D, S), the per-sample
     gradients with respect to the D inputs of each row: (dmean (M, D), dvariance (M, D)).  The spread term is
@@ -1361,6 +1401,77 @@ class GP:
                 lpd = -0.5 * (y_star - mu) ** 2 / noisy - 0.5 * np.log(2 * np.pi * noisy)
         if return_lpd:
             return mu, s2, lpd
+        return mu, s2
+
+    # ------------------------------------------------------------------ cross-validation
+    @_on_device
+    def cv_predict(self, folds=None, add_noise: bool = False, separate_samples: bool = False,
+                   return_lpd: bool = False):
+        """Leave-fold-out predictions of the training targets from the resident posteriors, the hyperparameters held
+        fixed (Rasmussen & Williams 5.4.2): what ``update`` on the data without a fold followed by ``predict`` at the
+        fold returns, without refitting anything (gpc_cv; no covariance is evaluated, so user-defined kernels and
+        posteriors grown by appends are served alike).
+
+        ``folds``: None = leave-one-out; an int F >= 2 = ``np.array_split(np.arange(N), F)``, contiguous blocks in the
+        order of the data (shuffle the data beforehand if a shuffle is wanted); otherwise a sequence of index arrays,
+        pairwise disjoint, which need not cover all points.
+
+        Returns ``(mu, s2)``, (N, 1) or with ``separate_samples`` (N, S), with ``predict``'s conventions: the latent
+        variance clamped at 0, the noisy one with ``add_noise``, the equal-weight mixture over hyperparameter samples.
+        Points in no fold are NaN.  With ``return_lpd`` also ``lpd`` (per point: the density of y_i under the noisy
+        predictive marginal, mixed as ``predict`` mixes it) and ``lpd_fold`` ((F, S), or (F, 1) = the log-mean-exp
+        over samples): the joint log density of each fold given the rest."""
+        import warnings
+
+        if self.y is None:
+            raise ValueError("cv_predict: the GP has no training data")
+        N = self.X.shape[0]
+        fl = _cv_folds(folds, N)
+        F = N if fl is None else len(fl)
+        s_N = self.posteriors.size
+        self._restore()
+        if self._post_handle is None and self._post_range is None:
+            raise ValueError("posteriors have been cleaned; call update() first")
+        self._ctx()
+        local_posts, _ = self._local_posteriors()
+        if not local_posts:
+            rows = np.zeros((2 * N + 3 * F, 0))
+        else:
+            rows = np.concatenate([np.asarray(r, dtype=float) for r in self._post_handle.cv(fl)], axis=0)
+        if self._post_range is not None:  # each rank has its block of samples: one all-gather
+            key = np.zeros(0) if fl is None else np.concatenate([np.r_[-1, f] for f in fl]).astype(float)
+            rows = self._gather_samples(rows, key)
+        dmu, s2n = rows[:N], rows[N:2 * N]
+        quad, logdet, info = rows[2 * N:2 * N + F], rows[2 * N + F:2 * N + 2 * F], rows[2 * N + 2 * F:]
+        bad = np.argwhere(info != 0)
+        if bad.size:
+            f, s = bad[0]
+            warnings.warn(f"cv_predict: the held-out block of fold {f} for hyperparameter sample {s} is not positive "
+                          f"definite in floating point ({bad.shape[0]} fold/sample pairs in all); its values are NaN",
+                          RuntimeWarning, stacklevel=2)
+        hyp = np.stack([p.hyp for p in self.posteriors])
+        sn2, _, _ = self._noise_values(hyp, False)
+        mult = np.array([1.0 if p.sn2_mult is None else float(p.sn2_mult) for p in self.posteriors])
+        noise = (np.broadcast_to(np.asarray(sn2, dtype=float).reshape(s_N, -1), (s_N, N)) * mult[:, None]).T
+        y = np.reshape(self.y, (-1, 1))
+        mu = y - dmu
+        y_s2 = s2n
+        s2 = y_s2 if add_noise else np.maximum(s2n - noise, 0)
+        lpd = lpd_fold = None
+        if return_lpd:
+            k = np.ones((F, 1)) if fl is None else np.array([[f.size] for f in fl], dtype=float)
+            lpd_fold = -0.5 * quad - 0.5 * logdet - 0.5 * k * np.log(2 * np.pi)
+            if separate_samples:
+                lpd = -0.5 * (y - mu) ** 2 / y_s2 - 0.5 * np.log(2 * np.pi * y_s2)
+        if not separate_samples:
+            mu, s2, between = _mix_samples(mu, s2)
+            if return_lpd:
+                noisy = s2 if add_noise else np.reshape(np.sum(y_s2, 1) / s_N + between, (-1, 1))
+                lpd = -0.5 * (y - mu) ** 2 / noisy - 0.5 * np.log(2 * np.pi * noisy)
+                top = np.max(lpd_fold, axis=1, keepdims=True)
+                lpd_fold = top + np.log(np.mean(np.exp(lpd_fold - top), axis=1, keepdims=True))
+        if return_lpd:
+            return mu, s2, lpd, lpd_fold
         return mu, s2
 
     @_on_device

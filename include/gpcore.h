@@ -390,6 +390,35 @@ int gpc_quad_mix(gpc_post* post, const double* mu, const double* sigma, const do
                  int compute_grad, double* zalpha, double* zbkzb, double* gw, double* zq, double* dza_dmu,
                  double* dza_dsigma, double* dzq_dmu, double* dzq_dsigma, double* dgw_dmu, double* dgw_dsigma);
 
+/* ---- cross-validation ------------------------------------------------------------
+ * Leave-fold-out predictive distributions of the training points themselves, from the resident posterior alone, the
+ * hyperparameters held fixed (Rasmussen & Williams 5.4.2): with P = (K + Sigma)^-1 the held-out set I given the rest
+ * has covariance C = (P_II)^-1 and mean y_I - C alpha_I.  No covariance or mean function is evaluated and no
+ * gpc_set_data state is read: the call serves posteriors from gpc_posterior_batch, from caller-provided K, and ones
+ * grown by gpc_post_append[_block] alike.
+ * fold_ptr holds F + 1 offsets into fold_idx; fold f is fold_idx[fold_ptr[f] .. fold_ptr[f+1]): indices in [0, N),
+ * strictly ascending, folds pairwise disjoint, none empty, at most N - 1 long; they need not cover all points.
+ * F == 0 with NULL arrays: every point its own fold (leave-one-out), one streaming pass over W; explicit folds that
+ * are all singletons take that same pass and give the same bits.
+ * Per sample s and fold f (sc = the fitted noise of an L_chol sample, 1 otherwise):
+ *   dmu[i*S + s]    = (C alpha_I)_j for i = I[j]          (the caller forms mu_i = y_i - dmu)
+ *   s2[i*S + s]     = C_jj, the variance of the noisy observation
+ *   quad[f*S + s]   = alpha_I^T C alpha_I,   logdet[f*S + s] = log det C
+ *   info[f*S + s]   = 0, or nonzero when the fold's operand (W[:, I]^T W[:, I], or -A[I, I]) was not positive definite
+ *                     in floating point: its outputs are NaN then, no jitter is applied.
+ * With F == 0 quad, logdet and info are N x S, one per point.  Points in no fold get NaN in dmu and s2.  quad, logdet and
+ * info may be NULL.  Everything after the load of W (or A) is fp64, for fp32 posteriors too; the operands of all folds
+ * and samples of a chunk are factored in one batched fp64 factorization padded to k_max rounded up to 128.  The
+ * numbers of (sample, fold) depend on the sample, the fold and the engine only: not on F, the other folds, the batch
+ * or the chunking (GPC_MEM_BUDGET_MB).  Test option "cv_engine": 1 = fused gather + MFMA Gram (default), 2 = gathered
+ * panels + the library GEMM (equal to rounding); get-only "cv_engine_ran" tells which one the last call ran (0: the
+ * leave-one-out pass).  gpc_last_timing: ms_total = the device section, ms_factor = the Gram or diagonal pass.
+ * Returns -2 with a message of its own for an index out of range, an unsorted fold, overlapping folds, an empty fold,
+ * a fold of all N points, a failed posterior, and (naming N_pad, F and k_max) when one sample's scratch does not fit
+ * the memory budget; -3 when a leaf of the factorization timed out. */
+int gpc_cv(gpc_post* post, int F, const int* fold_ptr, const int* fold_idx, double* dmu, double* s2, double* quad,
+           double* logdet, int* info);
+
 /* ---- instrumentation -------------------------------------------------------------
  * GPU time (ms, hipEvent on the library's stream) of the last gpc_nll_batch /
  * gpc_posterior_batch: whole device section, and the part spent in the MFMA GEMM
@@ -400,7 +429,8 @@ int gpc_last_timing(gpc_ctx* ctx, double* ms_total, double* ms_factor);
  * duration of its N^2 M product V = W Ks, the GEMM launch of gaussian_process.py:1752-1760; after
  * gpc_quad_grad: that of its products V = W z and Q = W^T V, ~0 without compute_var; after
  * gpc_predict_cov: ms_factor = its triangular products and the cross product, with the reduction;
- * after gpc_quad_mix: ms_factor = its solve, the triangular matrix-vector products, 0 without compute_var) */
+ * after gpc_quad_mix: ms_factor = its solve, the triangular matrix-vector products, 0 without compute_var;
+ * after gpc_cv: ms_factor = its Gram (or gather) launches, or the leave-one-out pass) */
 /* The dominant single kernel of the last gpc_nll_batch with gradient: the W^T W ("lauum")
  * launch of gemm_kernel<T, true, true, ...>.  ms = its duration (hipEvents on the stream it
  * was launched on; the slowest sample group), flops = its algorithmic flops
@@ -423,7 +453,7 @@ int gpc_last_lauum_timing(gpc_ctx* ctx, double* ms, double* flops);
  * "cov_fused" (get only): how many gpc_predict_cov calls formed their reduction in the product's epilogue.
  * "quad_mix_gemms" (get only): MFMA GEMM launches issued inside gpc_quad_mix over the life of the context (0 by design).
  * "paths_engine" / "paths_solve_engine" (test hooks) and "paths_engine_ran" / "paths_solve_engine_ran" (get only): see
- * gpc_paths_create / gpc_paths_eval. */
+ * gpc_paths_create / gpc_paths_eval.  "cv_engine" (test hook) and "cv_engine_ran" (get only): see gpc_cv. */
 int gpc_set_option(gpc_ctx* ctx, const char* name, int value);
 /* Current value of a tuning switch (so that a caller that changes one for a measurement can put it back). */
 int gpc_get_option(gpc_ctx* ctx, const char* name, int* value);
