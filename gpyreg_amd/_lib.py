@@ -105,6 +105,11 @@ SIGNATURES = {
     "gpc_debug_normals": (C.c_int, [_vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "gpc_debug_workspace_hash": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
     "gpc_debug_chunk_plan": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_int]),
+    "gpc_debug_gemm_queues": (C.c_int, [C.c_int] * 8 + [_ip] * 4),
+    "gpc_debug_gemm_form": (
+        C.c_int,
+        [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _dp, C.c_longlong, _dp, _dp, _ip, _ip],
+    ),
 }
 # declared under GPC_EXPERIMENTS in include/gpcore.h: present in the experiments build only (lib/libgpcore_exp.so, which
 # tests/ and tools/ select through GPYREG_AMD_LIB; the product library does not export them)
@@ -115,6 +120,35 @@ EXPERIMENTS_LIB_PATH = os.path.join(_HERE, "lib", "libgpcore_exp.so")
 
 # int (*gpc_dk_plane_fn)(void* user, int sample, int p, double* plane)
 DK_PLANE_FN = C.CFUNCTYPE(C.c_int, _vp, C.c_int, C.c_int, _dpp)
+
+
+class _GemmProductStruct(C.Structure):
+    """gpc_gemm_product of include/gpcore.h."""
+    _fields_ = ([(n, C.c_int) for n in ("M", "N", "K", "a_kmajor", "b_kmajor", "beta", "klo", "khi", "lower_only",
+                                        "lda", "ldb", "ldc")]
+                + [(n, C.c_longlong) for n in ("off_a", "off_b", "off_c", "s_a", "s_b", "s_c", "size_a", "size_b",
+                                               "size_c")]
+                + [("alpha", C.c_double), ("A", _vp), ("B", _vp), ("C", _vp)])
+
+
+class GemmProduct:
+    """One product of ``Context.debug_gemm_form`` (gpc_gemm_product): A, B, C are the WHOLE allocations as flat arrays;
+    sample b's operands start at element off_x + b * s_x with rows ld_x apart."""
+
+    def __init__(self, A, B, C, M, N, K, a_kmajor=0, b_kmajor=0, alpha=1.0, beta=0, klo=0, khi=0, lower_only=0,
+                 lda=None, ldb=None, ldc=None, off_a=0, off_b=0, off_c=0, s_a=0, s_b=0, s_c=0):
+        self.A, self.B, self.C = _f64(A).ravel(), _f64(B).ravel(), _f64(C).ravel()
+        self.M, self.N, self.K = int(M), int(N), int(K)
+        self.a_kmajor, self.b_kmajor = int(bool(a_kmajor)), int(bool(b_kmajor))
+        self.alpha, self.beta, self.klo, self.khi, self.lower_only = float(alpha), int(beta), klo, khi, int(bool(lower_only))
+        self.lda = int(lda if lda is not None else (M if a_kmajor else K))
+        self.ldb = int(ldb if ldb is not None else (N if b_kmajor else K))
+        self.ldc = int(ldc if ldc is not None else N)
+        self.off_a, self.off_b, self.off_c = int(off_a), int(off_b), int(off_c)
+        self.s_a, self.s_b, self.s_c = int(s_a), int(s_b), int(s_c)
+
+
+FORMS = {"plain": 0, "persist": 1, "persist_reserved": 2, "dual": 3, "colsq": 4, "wsq": 5}
 
 _lib = None
 _lock = threading.RLock()
@@ -419,6 +453,42 @@ class Context:
                                       _ptr(B), _ptr(Cm))
         self._check(rc, "gpc_debug_gemm")
         return Cm
+
+    @_serial
+    def debug_gemm_form(self, form, products, batch=1, tile=128, flags=None, block_slots=0, dtype=F64, ep_w=None,
+                        ep_sw=0, ep_alpha=None):
+        """gpc_debug_gemm_form: ``products`` (one GemmProduct, two for "dual") through the launch form ``form`` (a key
+        of FORMS) with ``flags`` in place of the GEMM flags and ``block_slots`` in place of the chip's block slots for
+        this call.  Returns None when the form is unavailable on this context ("persist_reserved" without a table of
+        reserved CUs), else a dict: C (the whole C allocation of every product after the launch; the inputs are not
+        modified), colsq ((batch, M / 128, N), the epilogue forms, else None), counters (the 8 queue counters)."""
+        prods = [products] if isinstance(products, GemmProduct) else list(products)
+        outs, structs = [], []
+        for p in prods:
+            Cout = p.C.copy()
+            outs.append(Cout)
+            structs.append(_GemmProductStruct(
+                p.M, p.N, p.K, p.a_kmajor, p.b_kmajor, p.beta, p.klo, p.khi, p.lower_only, p.lda, p.ldb, p.ldc,
+                p.off_a, p.off_b, p.off_c, p.s_a, p.s_b, p.s_c, p.A.size, p.B.size, Cout.size, p.alpha,
+                _ptr(p.A), _ptr(p.B), _ptr(Cout)))
+        code = FORMS[form]
+        p0 = prods[0]
+        colsq = np.empty((batch, p0.M // 128, p0.N)) if code >= 4 else None
+        w = al = None
+        if code == 5:
+            w, al = _f64(ep_w).ravel(), _f64(ep_alpha).ravel()
+            if w.size != (batch - 1) * ep_sw + p0.M or al.size != batch:
+                raise ValueError("debug_gemm_form: ep_w holds (batch - 1) * ep_sw + M weights, ep_alpha one factor per sample")
+        counters = np.zeros(8, dtype=np.int32)
+        avail = C.c_int(0)
+        rc = self._lib.gpc_debug_gemm_form(
+            self._h, dtype, code, int(tile), int(batch), -1 if flags is None else int(flags), int(block_slots),
+            C.addressof(structs[0]), C.addressof(structs[1]) if len(structs) > 1 else None, _ptr(w), int(ep_sw),
+            _ptr(al), _ptr(colsq), counters.ctypes.data, C.addressof(avail))
+        self._check(rc, "gpc_debug_gemm_form")
+        if not avail.value:
+            return None
+        return dict(C=outs, colsq=colsq, counters=counters)
 
     @_serial
     def debug_factor(self, A, want_inv=True, dtype=F64):
@@ -821,6 +891,28 @@ class Paths:
                 self.free()
         except Exception:
             pass
+
+
+def gemm_queues(ntiles, batch, flags, tiles_m=0, tiles_n=0, klo=0, khi=0, lower_only=0, want_tiles=False,
+                want_xcd=False):
+    """gpc_debug_gemm_queues (no device needed): (queues, totals, tiles, xcd).  queues: per tile queue of a persistent
+    launch the (tile, sample) pairs it hands out, in order (8 entries; the flat queue of a launch without flag 8 is
+    entry 0); totals: the 8 queue lengths as the kernel computes them; tiles: (ntiles, 2) array of the (ti, tj) of every position of the dispatch order, or None; xcd: (batch, ntiles, 2)
+    array of the item (bx, by) workgroup (bx, by) of a plain launch takes, or None."""
+    lib = load()
+    n = int(ntiles) * int(batch)
+    q_total = np.zeros(8, dtype=np.int32)
+    q_items = np.full((max(n, 1), 2), -1, dtype=np.int32)
+    tiles = np.full((ntiles, 2), -1, dtype=np.int32) if want_tiles else None
+    xcd = np.full((batch, ntiles, 2), -1, dtype=np.int32) if want_xcd else None
+    rc = lib.gpc_debug_gemm_queues(int(ntiles), int(batch), int(flags), int(tiles_m), int(tiles_n), int(klo), int(khi),
+                                   int(bool(lower_only)), q_total.ctypes.data, q_items.ctypes.data, _ptr(tiles),
+                                   _ptr(xcd))
+    if rc != 0:
+        raise RuntimeError(f"gpc_debug_gemm_queues failed (rc={rc})")
+    ends = np.concatenate([[0], np.cumsum(np.minimum(q_total, n))])
+    queues = [q_items[ends[q]:ends[q + 1]].copy() for q in range(8)]
+    return queues, q_total, tiles, xcd
 
 
 _contexts = {}

@@ -177,12 +177,62 @@ __device__ __forceinline__ T frag(const T* __restrict__ s, int r0, int kk, int l
     return s[(kk + (lane >> 4)) * ldp_of(BT) + r0 + (lane & 15)];
 }
 
-__device__ __forceinline__ void tri_tile(int tile, int& ti, int& tj) {
+// ---- index arithmetic shared by the kernels and the host (gpc_debug_gemm_queues enumerates it without a device; the
+// queues of gemm_persist_kernel are restated for the host below that kernel) ----
+__host__ __device__ __forceinline__ void tri_tile(int tile, int& ti, int& tj) {
   int i = (int)((sqrtf(8.f * (float)tile + 1.f) - 1.f) * 0.5f);
   while (i * (i + 1) / 2 > tile) --i;
   while ((i + 1) * (i + 2) / 2 <= tile) ++i;
   ti = i;
   tj = tile - i * (i + 1) / 2;
+}
+
+// gemm_tile's map from the position bx in the dispatch order to the tile (ti, tj).  Tiles differ in k-length when the
+// k-range is triangular, so the longest tiles go first (LPT) and the short ones fill the tail; the major index is
+// the one the k-range depends on, which also keeps consecutive blocks on one operand panel.  SQUARE: tile columns
+// as wide as the tile rows (false: the 128 x 64 tile, two tile columns per tile row).
+template <bool SQUARE = true>
+__host__ __device__ __forceinline__ void tile_of_bx(int klo, int khi, int lower_only, int tiles_m, int tiles_n, int bx,
+                                                    int& ti, int& tj) {
+  if (lower_only) {
+    if constexpr (SQUARE) {
+      tri_tile(bx, ti, tj);  // ti ascending: longest first for KLO_ROW (lauum), uniform for syrk
+    } else {
+      // tile row ti holds the columns 0 .. 2 ti + 1: ti (ti + 1) tiles come before it
+      int i = (int)((sqrtf(4.f * (float)bx + 1.f) - 1.f) * 0.5f);
+      while (i * (i + 1) > bx) --i;
+      while ((i + 1) * (i + 2) <= bx) ++i;
+      ti = i;
+      tj = bx - i * (i + 1);
+    }
+  } else if (khi == KHI_COL) {
+    tj = tiles_n - 1 - bx / tiles_m;
+    ti = bx % tiles_m;
+  } else if (klo == KLO_COL) {
+    tj = bx / tiles_m;
+    ti = bx % tiles_m;
+  } else if (khi == KHI_ROW) {
+    ti = tiles_m - 1 - bx / tiles_n;
+    tj = bx % tiles_n;
+  } else {
+    ti = bx / tiles_n;
+    tj = bx % tiles_n;
+  }
+}
+
+// XCD-aware work order of the plain launches (gemm_kernel, gemm_dual_kernel): workgroup L = by * gx + bx of a
+// (gx, gy) grid takes the item (bx, by) this returns.  Workgroups are dealt round-robin over the 8 XCDs in dispatch
+// order (x fastest), so workgroup L runs on XCD L % 8; XCD x gets the contiguous range [x total/8, (x+1) total/8) of
+// the (sample, tile) items: its blocks then work on the same one or two samples and share panels in its L2.  The
+// total % 8 items at the end keep their place.
+__host__ __device__ __forceinline__ void xcd_order(int gx, int gy, int& bx, int& by) {
+  const int total = gx * gy, per = total >> 3;
+  const int L = by * gx + bx;
+  if (L < (per << 3)) {
+    const int wk = (L & 7) * per + (L >> 3);
+    bx = wk % gx;
+    by = wk / gx;
+  }
 }
 
 // BT = block tile (128: 4 waves x 64x64; 64: 4 waves x 32x32, for launches too small to
@@ -226,36 +276,10 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
   const int t = threadIdx.x;
   const int lane = t & 63, w = t >> 6, wr = w / WCOLS, wc = w % WCOLS;
 
-  // Tile order = dispatch order.  Tiles differ in k-length when the k-range is
-  // triangular, so the longest tiles go first (LPT) and the short ones fill the tail;
-  // the major index is the one the k-range depends on, which also keeps consecutive
-  // blocks on one operand panel.
+  // Tile order = dispatch order (tile_of_bx: longest tiles first)
+  static_assert(BTN == BT || BT == 2 * BTN, "lower tiles of a rectangular launch: two tile columns per tile row");
   int ti, tj;
-  if (g.lower_only) {
-    if constexpr (BTN == BT) {
-      tri_tile(bx, ti, tj);  // ti ascending: longest first for KLO_ROW (lauum), uniform for syrk
-    } else {
-      static_assert(BT == 2 * BTN, "lower tiles of a rectangular launch: two tile columns per tile row");
-      // tile row ti holds the columns 0 .. 2 ti + 1: ti (ti + 1) tiles come before it
-      int i = (int)((sqrtf(4.f * (float)bx + 1.f) - 1.f) * 0.5f);
-      while (i * (i + 1) > bx) --i;
-      while ((i + 1) * (i + 2) <= bx) ++i;
-      ti = i;
-      tj = bx - i * (i + 1);
-    }
-  } else if (g.khi == KHI_COL) {
-    tj = g.tiles_n - 1 - bx / g.tiles_m;
-    ti = bx % g.tiles_m;
-  } else if (g.klo == KLO_COL) {
-    tj = bx / g.tiles_m;
-    ti = bx % g.tiles_m;
-  } else if (g.khi == KHI_ROW) {
-    ti = g.tiles_m - 1 - bx / g.tiles_n;
-    tj = bx % g.tiles_n;
-  } else {
-    ti = bx / g.tiles_n;
-    tj = bx % g.tiles_n;
-  }
+  tile_of_bx<BTN == BT>(g.klo, g.khi, g.lower_only, g.tiles_m, g.tiles_n, bx, ti, tj);
   const int m0 = ti * BT, n0 = tj * BTN;
   const int m128 = (m0 / TILE) * TILE, n128 = (n0 / TILE) * TILE;
   int k0 = g.klo == KLO_ROW ? m128 : (g.klo == KLO_COL ? n128 : 0);
@@ -566,16 +590,7 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_kernel(GemmArgs g) {
   if ((g.flags & 16) && gridDim.y >= 8) {
     // (with fewer than 8 samples a contiguous range is a piece of ONE sample's longest-first tile list: the
     // XCDs would get unequal work -- cfg4, one sample: -6.5 %)
-    // XCD-aware work order: workgroups are dealt round-robin over the 8 XCDs in dispatch order (x fastest), so
-    // workgroup L runs on XCD L % 8.  Give XCD x the contiguous range [x total/8, (x+1) total/8) of the
-    // (sample, tile) items: its blocks then work on the same one or two samples and share panels in its L2.
-    const int total = gridDim.x * gridDim.y, per = total >> 3;
-    const int L = blockIdx.y * gridDim.x + blockIdx.x;
-    if (L < (per << 3)) {
-      const int wk = (L & 7) * per + (L >> 3);
-      bx = wk % (int)gridDim.x;
-      by = wk / (int)gridDim.x;
-    }
+    xcd_order((int)gridDim.x, (int)gridDim.y, bx, by);
   }
   gemm_tile<T, AKM, BKM, BT, NW, 0, EPI, BTN>(g, bx, by, smem);
 }
@@ -587,15 +602,7 @@ template <typename T, bool A1, bool B1, bool A2, bool B2, int BT, int NW>
 __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_dual_kernel(GemmArgs g1, GemmArgs g2, int n1) {
   __shared__ __attribute__((aligned(16))) T smem[4 * opsz_of<T>(BT)];
   int bx = blockIdx.x, by = blockIdx.y;
-  if ((g1.flags & 16) && gridDim.y >= 8) {  // XCD-aware work order, as in gemm_kernel
-    const int total = gridDim.x * gridDim.y, per = total >> 3;
-    const int L = blockIdx.y * gridDim.x + blockIdx.x;
-    if (L < (per << 3)) {
-      const int wk = (L & 7) * per + (L >> 3);
-      bx = wk % (int)gridDim.x;
-      by = wk / (int)gridDim.x;
-    }
-  }
+  if ((g1.flags & 16) && gridDim.y >= 8) xcd_order((int)gridDim.x, (int)gridDim.y, bx, by);  // as in gemm_kernel
   if (bx < n1)
     gemm_tile<T, A1, B1, BT, NW>(g1, bx, by, smem);
   else
@@ -665,6 +672,42 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_persist_kernel(GemmArgs 
       gemm_tile<T, AKM, BKM, BT, NW, 0, EPI>(g, cls + tq * nclass, smp + NQ * sq, smem);
     }
   }
+}
+
+// The queue arithmetic of gemm_persist_kernel, RESTATED for the host (gpcore.hip: verify_queues, gpc_debug_gemm_queues).
+// The kernel above does not call these: with them its register allocation differed from the measured one (scalar and,
+// in two fp32 instances, vector spills), so its text stays as it is and tests/test_gpu_gemm_forms.py pins the two
+// together -- every queue counter of a launch against queue_total, every element of the result against a reference.
+// Queue q of the NQ XCD-affine queues (flags & 8): samples q, q + 8, ... when there are at least 8 samples; with fewer,
+// sample q % batch and every nclass-th tile of it starting at tile q / batch, nclass = 8 / batch.
+inline int queue_nclass(int batch) { return batch >= NQ ? 1 : NQ / batch; }
+// samples of queue q (0: the queue serves nothing), its first tile (cls) and its first sample (smp)
+inline int queue_of(int batch, int nclass, int q, int& cls, int& smp) {
+  int nsq;
+  cls = 0;
+  smp = q;
+  if (batch >= NQ) {
+    nsq = (batch - q + NQ - 1) / NQ;
+  } else {
+    if (q >= batch * nclass) return 0;
+    nsq = 1;
+    smp = q % batch;
+    cls = q / batch;
+  }
+  return nsq;
+}
+inline int queue_total(int ntiles, int nclass, int cls, int nsq) { return ((ntiles - cls + nclass - 1) / nclass) * nsq; }
+// item idx < total of a queue: sample-major, the tiles of a sample ascending
+inline void queue_item(int total, int nsq, int nclass, int cls, int smp, int idx, int& tile, int& sample) {
+  const int ntq = total / nsq;
+  const int sq = idx / ntq, tq = idx - sq * ntq;
+  tile = cls + tq * nclass;
+  sample = smp + NQ * sq;
+}
+// the one flat queue of a persistent launch without flags & 8: item idx < ntiles * batch
+inline void flat_queue_item(int batch, int idx, int& tile, int& sample) {
+  tile = idx / batch;
+  sample = idx % batch;
 }
 
 inline int g_persist_spare = 0;     // tunable: GPC_PERSIST_SPARE (block slots a persistent launch leaves free)

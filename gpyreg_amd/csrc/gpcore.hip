@@ -906,6 +906,11 @@ struct HostClock {
   }
 };
 
+// the table of CUs a deferred / split launch stays off (Pipe::reserve_tbl, gpc_debug_gemm_form)
+inline const unsigned short* ctx_reserve_tbl(const gpc_ctx* c) {
+  return (c->cu_map_ok && c->defer_reserve > 0) ? c->rsv_tbl.as<unsigned short>() : nullptr;
+}
+
 template <typename T>
 struct Pipe {
   gpc_ctx* c;
@@ -1454,9 +1459,7 @@ struct Pipe {
 
   // the table of CUs a deferred / split launch stays off, or nullptr when the device's CU numbering was not
   // recognised or no CU is to be reserved (the launches are then plain persistent ones)
-  const unsigned short* reserve_tbl() const {
-    return (c->cu_map_ok && c->defer_reserve > 0) ? c->rsv_tbl.as<unsigned short>() : nullptr;
-  }
+  const unsigned short* reserve_tbl() const { return ctx_reserve_tbl(c); }
   std::vector<typename Factor<T>::QueueCheck> qlog;  // debug option check_queues
 
   // check_queues: every tile queue of every persistent launch of the pipeline that just ran must have handed out all
@@ -1472,13 +1475,11 @@ struct Pipe {
       if (!affine) {
         drawn = std::min<long long>(v[0], (long long)q.ntiles * q.batch);
       } else {
-        const int nclass = q.batch >= NQ ? 1 : NQ / q.batch;
+        const int nclass = gpc::queue_nclass(q.batch);
         for (int k = 0; k < NQ; ++k) {
-          long long total;
-          if (q.batch >= NQ)
-            total = (long long)q.ntiles * ((q.batch - k + NQ - 1) / NQ);
-          else
-            total = k >= q.batch * nclass ? 0 : (q.ntiles - k / q.batch + nclass - 1) / nclass;
+          int cls, smp;
+          const int nsq = gpc::queue_of(q.batch, nclass, k, cls, smp);
+          const long long total = nsq > 0 ? gpc::queue_total(q.ntiles, nclass, cls, nsq) : 0;
           drawn += std::min<long long>(v[k], total);
         }
       }
@@ -3344,6 +3345,168 @@ int debug_gemm_impl(gpc_ctx* c, int M, int N, int K, int akm, int bkm, double al
   g.tiles_n = N / TILE;
   HIPCHK(c, launch_gemm<T>(c->st, g, akm != 0, bkm != 0, 1, (lower & 0x100) ? 64 : ((lower & 0x200) ? 128 : ((lower & 0x400) ? 12864 : 0))));  // (12864: experiments build)
   return download_as<T>(c, c->dbg3.as<T>(), C, (size_t)M * N);
+}
+
+// ---- gpc_debug_gemm_form: one product (two for the dual form) through a chosen launch form of gemm.h ----
+// device allocations of one hook call, freed when it returns (whatever the way out)
+struct HookMem {
+  std::vector<void*> ps;
+  ~HookMem() {
+    for (void* p : ps) (void)hipFree(p);
+  }
+  hipError_t get(void** p, size_t bytes) {
+    hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+    if (e == hipSuccess) ps.push_back(*p);
+    return e;
+  }
+};
+// the globals of gemm.h a hook call overrides, put back when it returns
+struct GemmGlobalsGuard {
+  const int flags = gpc::g_gemm_flags, slots = gpc::g_block_slots, spare = gpc::g_persist_spare;
+  ~GemmGlobalsGuard() {
+    gpc::g_gemm_flags = flags;
+    gpc::g_block_slots = slots;
+    gpc::g_persist_spare = spare;
+  }
+};
+
+// Every element the kernels may address lies inside the caller's allocations (the staging loads go through unbounded
+// buffer descriptors: nothing else stops a bad description).  vec: elements per 16-byte staging vector.
+const char* form_product_error(const gpc_gemm_product& p, int batch, int vec) {
+  constexpr long long CAP = 1ll << 27;  // elements per allocation: every 32-bit offset of the kernels stays far away
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0 || p.M % TILE || p.N % TILE || p.K % TILE) return "sizes must be multiples of 128";
+  if (p.lower_only && p.M != p.N) return "lower_only needs M == N";
+  if ((p.beta != 0 && p.beta != 1) || p.klo < 0 || p.klo > 2 || p.khi < 0 || p.khi > 2) return "beta is 0 or 1, klo and khi 0..2";
+  if (!p.A || !p.B || !p.C) return "A, B and C are required";
+  const long long ra = p.a_kmajor ? p.K : p.M, ca = p.a_kmajor ? p.M : p.K;
+  const long long rb = p.b_kmajor ? p.K : p.N, cb = p.b_kmajor ? p.N : p.K;
+  struct Op {
+    long long rows, cols, ld, off, stride, size;
+    bool staged;
+  } ops[3] = {{ra, ca, p.lda, p.off_a, p.s_a, p.size_a, true},
+              {rb, cb, p.ldb, p.off_b, p.s_b, p.size_b, true},
+              {p.M, p.N, p.ldc, p.off_c, p.s_c, p.size_c, false}};
+  for (const Op& o : ops) {
+    if (o.ld < o.cols || o.off < 0 || o.stride < 0 || o.size <= 0 || o.size > CAP || o.ld > CAP || o.stride > CAP)
+      return "leading dimension below the extent, or a negative / oversized offset, stride or allocation";
+    const long long span = (o.rows - 1) * o.ld + o.cols;
+    if (o.off + (batch - 1) * o.stride + span > o.size) return "an operand reaches past its allocation";
+    if (o.staged && (o.ld % vec || o.off % vec || o.stride % vec))
+      return "lda, ldb and the offsets and strides of A and B must be multiples of the 16-byte vector";
+    if (!o.staged && batch > 1 && o.stride < span) return "the C blocks of two samples overlap";
+  }
+  return nullptr;
+}
+
+template <typename T>
+int debug_gemm_form_impl(gpc_ctx* c, int form, int tile, int batch, int flags, int block_slots,
+                         const gpc_gemm_product* const* prods, int nprod, const double* ep_w, long long ep_sw,
+                         const double* ep_alpha, double* colsq, int* counters, int* available) {
+  HookMem mem;
+  GemmGlobalsGuard guard;
+  if (flags >= 0) gpc::g_gemm_flags = flags;
+  if (block_slots > 0) {
+    gpc::g_block_slots = block_slots;
+    gpc::g_persist_spare = 0;
+  }
+  const unsigned short* rsv = nullptr;
+  if (form == GPC_FORM_PERSIST_RESERVED) {
+    rsv = ctx_reserve_tbl(c);
+    if (!rsv) {
+      *available = 0;
+      return 0;
+    }
+  }
+  *available = 1;
+  GemmArgs g[2];
+  T* dC[2] = {nullptr, nullptr};
+  auto up = [&](const double* src, long long n, T** dst) -> int {
+    HIPCHK(c, mem.get(reinterpret_cast<void**>(dst), (size_t)n * sizeof(T)));
+    if constexpr (sizeof(T) == 8) {
+      HIPCHK(c, hipMemcpyAsync(*dst, src, (size_t)n * 8, hipMemcpyHostToDevice, c->st));
+      HIPCHK(c, hipStreamSynchronize(c->st));
+    } else {
+      std::vector<float> tmp((size_t)n);
+      for (long long i = 0; i < n; ++i) tmp[(size_t)i] = (float)src[i];
+      HIPCHK(c, hipMemcpyAsync(*dst, tmp.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->st));
+      HIPCHK(c, hipStreamSynchronize(c->st));
+    }
+    return 0;
+  };
+  for (int i = 0; i < nprod; ++i) {
+    const gpc_gemm_product& p = *prods[i];
+    T *dA = nullptr, *dB = nullptr;
+    if (up(p.A, p.size_a, &dA) || up(p.B, p.size_b, &dB) || up(p.C, p.size_c, &dC[i])) return -1;
+    GemmArgs& a = g[i];
+    a.A = dA + p.off_a;
+    a.B = dB + p.off_b;
+    a.C = dC[i] + p.off_c;
+    a.sA = p.s_a;
+    a.sB = p.s_b;
+    a.sC = p.s_c;
+    a.lda = p.lda;
+    a.ldb = p.ldb;
+    a.ldc = p.ldc;
+    a.M = p.M;
+    a.N = p.N;
+    a.K = p.K;
+    a.alpha = p.alpha;
+    a.beta = p.beta;
+    a.klo = p.klo;
+    a.khi = p.khi;
+    a.lower_only = p.lower_only ? 1 : 0;
+  }
+  int* ctr = nullptr;  // the hook's own CTR_STRIDE counters, zeroed
+  HIPCHK(c, mem.get(reinterpret_cast<void**>(&ctr), CTR_STRIDE * sizeof(int)));
+  HIPCHK(c, hipMemsetAsync(ctr, 0, CTR_STRIDE * sizeof(int), c->st));
+  const gpc_gemm_product& p0 = *prods[0];
+  const size_t ncolsq = (size_t)batch * (p0.M / TILE) * p0.N;
+  double* dcolsq = nullptr;
+  if (form == GPC_FORM_COLSQ || form == GPC_FORM_WSQ) {
+    HIPCHK(c, mem.get(reinterpret_cast<void**>(&dcolsq), ncolsq * sizeof(double)));
+    HIPCHK(c, hipMemsetAsync(dcolsq, 0xff, ncolsq * sizeof(double), c->st));  // NaN: an entry nobody wrote shows
+    g[0].colsq = dcolsq;
+  }
+  if (form == GPC_FORM_WSQ) {
+    double *dw = nullptr, *da = nullptr;
+    const size_t nw = (size_t)(batch - 1) * ep_sw + p0.M;
+    HIPCHK(c, mem.get(reinterpret_cast<void**>(&dw), nw * sizeof(double)));
+    HIPCHK(c, mem.get(reinterpret_cast<void**>(&da), (size_t)batch * sizeof(double)));
+    HIPCHK(c, hipMemcpyAsync(dw, ep_w, nw * sizeof(double), hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemcpyAsync(da, ep_alpha, (size_t)batch * sizeof(double), hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipStreamSynchronize(c->st));
+    g[0].ep_w = dw;
+    g[0].ep_sw = ep_sw;
+    g[0].ep_alpha = da;
+  }
+  const bool akm = p0.a_kmajor != 0, bkm = p0.b_kmajor != 0;
+  switch (form) {
+    case GPC_FORM_PLAIN:
+    case GPC_FORM_PERSIST:
+    case GPC_FORM_PERSIST_RESERVED: {
+      int* qc = form == GPC_FORM_PLAIN ? nullptr : ctr;
+      if (tile == 64)
+        HIPCHK(c, (launch_gemm_bt<T, 64, 4>(c->st, g[0], akm, bkm, batch, qc, rsv)));
+      else
+        HIPCHK(c, (launch_gemm_bt<T, 128, 4>(c->st, g[0], akm, bkm, batch, qc, rsv)));
+      break;
+    }
+    case GPC_FORM_DUAL:
+      HIPCHK(c, launch_gemm_dual_small<T>(c->st, g[0], g[1], batch));
+      break;
+    case GPC_FORM_COLSQ:
+      HIPCHK(c, launch_gemm_colsq<T>(c->st, g[0], batch, ctr));
+      break;
+    default:
+      HIPCHK(c, launch_gemm_wsq<T>(c->st, g[0], batch));
+      break;
+  }
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  for (int i = 0; i < nprod; ++i)
+    if (download_as<T>(c, dC[i], prods[i]->C, (size_t)prods[i]->size_c)) return -1;
+  if (dcolsq) HIPCHK(c, hipMemcpy(colsq, dcolsq, ncolsq * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(counters, ctr, NQ * sizeof(int), hipMemcpyDeviceToHost));
+  return 0;
 }
 
 template <typename T>
@@ -5771,6 +5934,75 @@ int gpc_debug_gemm(gpc_ctx* c, int dtype, int M, int N, int K, int a_kmajor, int
   return dtype == GPC_F64
              ? debug_gemm_impl<double>(c, M, N, K, a_kmajor, b_kmajor, alpha, beta, klo, khi, lower_only, A, B, C)
              : debug_gemm_impl<float>(c, M, N, K, a_kmajor, b_kmajor, alpha, beta, klo, khi, lower_only, A, B, C);
+}
+
+int gpc_debug_gemm_queues(int ntiles, int batch, int flags, int tiles_m, int tiles_n, int klo, int khi, int lower_only,
+                          int* q_total, int* q_items, int* tile_ij, int* xcd_items) {
+  if (ntiles <= 0 || batch <= 0 || !q_total || (long long)ntiles * batch > (1ll << 24)) return -2;
+  for (int q = 0; q < NQ; ++q) q_total[q] = 0;
+  int* out = q_items;
+  if (!(flags & 8)) {
+    q_total[0] = ntiles * batch;
+    for (int idx = 0; out && idx < q_total[0]; ++idx, out += 2) flat_queue_item(batch, idx, out[0], out[1]);
+  } else {
+    const int nclass = queue_nclass(batch);
+    for (int q = 0; q < NQ; ++q) {
+      int nsq, cls, smp;
+      nsq = queue_of(batch, nclass, q, cls, smp);
+      if (nsq <= 0) continue;
+      q_total[q] = queue_total(ntiles, nclass, cls, nsq);
+      for (int idx = 0; out && idx < q_total[q]; ++idx, out += 2) {
+        // (a queue that would hand out more than the launch holds must not write past the caller's 2 ntiles batch ints)
+        if (out - q_items >= 2ll * ntiles * batch) return -3;
+        queue_item(q_total[q], nsq, nclass, cls, smp, idx, out[0], out[1]);
+      }
+    }
+  }
+  if (tile_ij) {
+    if (tiles_m <= 0 || tiles_n <= 0 || klo < 0 || klo > 2 || khi < 0 || khi > 2) return -2;
+    if (ntiles != (lower_only ? tiles_m * (tiles_m + 1) / 2 : tiles_m * tiles_n)) return -2;
+    for (int bx = 0; bx < ntiles; ++bx) tile_of_bx(klo, khi, lower_only, tiles_m, tiles_n, bx, tile_ij[2 * bx], tile_ij[2 * bx + 1]);
+  }
+  if (xcd_items) {
+    for (int by = 0; by < batch; ++by)
+      for (int bx = 0; bx < ntiles; ++bx) {
+        int x = bx, y = by;
+        if ((flags & 16) && batch >= 8) xcd_order(ntiles, batch, x, y);
+        xcd_items[2 * (by * ntiles + bx)] = x;
+        xcd_items[2 * (by * ntiles + bx) + 1] = y;
+      }
+  }
+  return 0;
+}
+
+int gpc_debug_gemm_form(gpc_ctx* c, int dtype, int form, int tile, int batch, int flags, int block_slots,
+                        const gpc_gemm_product* p1, const gpc_gemm_product* p2, const double* ep_w, long long ep_sw,
+                        const double* ep_alpha, double* colsq, int* counters, int* available) {
+  if (!c) return -2;
+  if (!p1 || !counters || !available || batch <= 0 || batch > 64 || form < GPC_FORM_PLAIN || form > GPC_FORM_WSQ ||
+      (tile != 64 && tile != 128) || (dtype != GPC_F64 && dtype != GPC_F32) || flags > 31 || block_slots > 4096)
+    FAIL(c, "gpc_debug_gemm_form: bad arguments");
+  const int vec = dtype == GPC_F64 ? 2 : 4;
+  const gpc_gemm_product* prods[2] = {p1, p2};
+  const int nprod = form == GPC_FORM_DUAL ? 2 : 1;
+  if (nprod == 2 && !p2) FAIL(c, "gpc_debug_gemm_form: the dual form takes two products");
+  for (int i = 0; i < nprod; ++i)
+    if (const char* e = form_product_error(*prods[i], batch, vec)) {
+      c->err = std::string("gpc_debug_gemm_form: ") + e;
+      return -2;
+    }
+  if (form == GPC_FORM_DUAL && (p1->a_kmajor || p1->b_kmajor || p2->a_kmajor || !p2->b_kmajor))
+    FAIL(c, "gpc_debug_gemm_form: the dual launch is m-major x m-major beside m-major x k-major");
+  if (form == GPC_FORM_COLSQ && (p1->a_kmajor || !p1->b_kmajor || p1->lower_only || !colsq))
+    FAIL(c, "gpc_debug_gemm_form: colsq is m-major x k-major over all tiles and needs the colsq output");
+  if (form == GPC_FORM_WSQ && (!p1->a_kmajor || !p1->b_kmajor || p1->lower_only || !colsq || !ep_w || !ep_alpha ||
+                               (batch > 1 && ep_sw != 0 && ep_sw < p1->M) || ep_sw < 0 || ep_sw > (1ll << 27)))
+    FAIL(c, "gpc_debug_gemm_form: wsq is k-major x k-major over all tiles and needs colsq, ep_w, ep_alpha");
+  HIPCHK(c, hipSetDevice(c->device));
+  return dtype == GPC_F64 ? debug_gemm_form_impl<double>(c, form, tile, batch, flags, block_slots, prods, nprod, ep_w, ep_sw,
+                                                         ep_alpha, colsq, counters, available)
+                          : debug_gemm_form_impl<float>(c, form, tile, batch, flags, block_slots, prods, nprod, ep_w, ep_sw,
+                                                        ep_alpha, colsq, counters, available);
 }
 
 int gpc_debug_leaf(gpc_ctx* c, int dtype, const double* A, double* L, double* W, double* logdet, int* info) {

@@ -504,6 +504,63 @@ int gpc_debug_workspace_hash(gpc_ctx* ctx, int dtype, int which, int sample, uns
  * -2 for S <= 0 or per = 0.                                                                                          */
 int gpc_debug_chunk_plan(int S, unsigned long long per, unsigned long long shared, unsigned long long budget,
                          int clamp_to_one);
+/* Debug, HOST ONLY (no device needed): the index arithmetic of the GEMM launch forms (gemm.h) enumerated for one
+ * launch of `ntiles` tiles and `batch` samples -- tile_of_bx and xcd_order, which the kernels call themselves, and
+ * queue_of / queue_total / queue_item / flat_queue_item, the host's restatement of gemm_persist_kernel's queues.
+ *   q_total[8]              items of each tile queue of a persistent launch (flags & 8: the eight XCD-affine queues;
+ *                           otherwise the one flat queue in slot 0, the rest 0)
+ *   q_items[2 ntiles batch] optional: the (tile, sample) pairs the queues hand out, queue after queue in the order of
+ *                           their counters
+ *   tile_ij[2 ntiles]       optional: the tile (ti, tj) of every position bx of the dispatch order of a square-tile
+ *                           launch with tiles_m x tiles_n tiles and the k-range modes klo / khi / lower_only (ntiles
+ *                           must be what such a launch has)
+ *   xcd_items[2 ntiles batch] optional: the item (bx, by) that workgroup L = by * ntiles + bx of a plain (ntiles, batch)
+ *                           grid takes -- the XCD-aware order when flags & 16 and batch >= 8, else the identity
+ * Returns 0, -2 (bad arguments), -3 (the queues hold more than ntiles * batch items).                                */
+int gpc_debug_gemm_queues(int ntiles, int batch, int flags, int tiles_m, int tiles_n, int klo, int khi, int lower_only,
+                          int* q_total, int* q_items, int* tile_ij, int* xcd_items);
+
+/* One product of gpc_debug_gemm_form, as the kernels see it: C[b] (M x N, rows ldc apart, at element off_c + b s_c of
+ * an allocation of size_c elements) = beta C[b] + alpha op(A[b]) op(B[b]); A stored K x M when a_kmajor (else M x K)
+ * with rows lda apart at off_a + b s_a, B stored K x N when b_kmajor (else N x K).  Leading dimensions may exceed the
+ * extents, a stride may be 0 (an operand every sample shares); lda, ldb and the offsets and strides of A and B are
+ * multiples of the 16-byte vector (2 fp64 / 4 fp32 elements).  A, B, C: the WHOLE allocations (host, fp64; converted
+ * for an fp32 launch); C is overwritten with the whole allocation as the launch left it.                            */
+typedef struct gpc_gemm_product {
+  int M, N, K;
+  int a_kmajor, b_kmajor;
+  int beta, klo, khi, lower_only;
+  int lda, ldb, ldc;
+  long long off_a, off_b, off_c;
+  long long s_a, s_b, s_c;
+  long long size_a, size_b, size_c;
+  double alpha;
+  const double* A;
+  const double* B;
+  double* C;
+} gpc_gemm_product;
+enum { GPC_FORM_PLAIN = 0, GPC_FORM_PERSIST = 1, GPC_FORM_PERSIST_RESERVED = 2, GPC_FORM_DUAL = 3, GPC_FORM_COLSQ = 4,
+       GPC_FORM_WSQ = 5 };
+/* Test hook: one product through ONE launch form of gemm.h, by the launchers the product uses.  form:
+ *   PLAIN              launch_gemm_bt without counters: gemm_kernel (XCD-aware order with flags & 16 and batch >= 8)
+ *   PERSIST            launch_gemm_bt with counters: gemm_persist_kernel when the launch has more items than block
+ *                      slots (128-tiles; a 64-tile launch without a reservation is always plain), flat queue or, with
+ *                      flags & 8, the eight XCD-affine queues
+ *   PERSIST_RESERVED   the same behind cu_reserve_bail with the context's own table of reserved CUs; *available = 0
+ *                      and nothing is launched when the context has none
+ *   DUAL               launch_gemm_dual_small: p1 (m-major x m-major) and p2 (m-major x k-major) as 64-tiles in one grid
+ *   COLSQ              launch_gemm_colsq (EPI 1; m-major x k-major, 128-tiles, persistent as PERSIST): C is not stored,
+ *                      colsq[(b tiles_m + ti) N + col] = sum over the 128 rows of tile row ti of (alpha acc)^2
+ *   WSQ                launch_gemm_wsq (EPI 2; k-major x k-major, 128-tiles, plain): C is read, colsq[...] = sum over
+ *                      those rows of ep_w[b ep_sw + row] (C + ep_alpha[b] acc)^2; ep_w holds (batch - 1) ep_sw + M values
+ * tile: 64 or 128 (PLAIN, PERSIST, PERSIST_RESERVED).  flags >= 0 replaces the GEMM flags (bit 3: XCD-affine queues,
+ * bit 4: XCD-aware order) and block_slots > 0 the block slots of the chip (and clears persist_spare) for this call
+ * only.  The hook checks that every operand lies inside its allocation, allocates and zeroes its own counters, and
+ * returns the eight queue counters as the launch left them (all 0 after a plain launch).  colsq[batch (M / 128) N]
+ * (COLSQ, WSQ) is preset to NaN.                                                                                     */
+int gpc_debug_gemm_form(gpc_ctx* ctx, int dtype, int form, int tile, int batch, int flags, int block_slots,
+                        const gpc_gemm_product* p1, const gpc_gemm_product* p2, const double* ep_w, long long ep_sw,
+                        const double* ep_alpha, double* colsq, int* counters, int* available);
 /* ---- experiments build only (hipcc -DGPC_EXPERIMENTS -> lib/libgpcore_exp.so; NOT part of the product library) --------
  * Schedules that were built, measured and rejected (tile-level dataflow graph, independent pipelines,
  * rectangular / eight-wave tiles, right-looking panels) and their gpc_set_option names live there;
