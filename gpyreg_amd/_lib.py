@@ -67,6 +67,7 @@ SIGNATURES = {
     "gpc_post_free": (C.c_int, [_vp]),
     "gpc_predict": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "gpc_predict_grad": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpc_grad_post": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "gpc_post_append": (C.c_int, [_vp, _dp, _dp, C.c_double, _ip]),
     "gpc_post_recompute": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_post_append_K": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_double, _ip]),
@@ -102,6 +103,7 @@ SIGNATURES = {
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, C.c_int, C.c_int, _dp,
          C.c_int, _dp, _dp, _dp, _dp, _dp],
     ),
+    "gpc_debug_block_gram": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]),
     "gpc_debug_normals": (C.c_int, [_vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "gpc_debug_workspace_hash": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
     "gpc_debug_chunk_plan": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_int]),
@@ -508,8 +510,10 @@ class Context:
                   mat=None, vec=None):
         """gpc_debug_cov on one sample.  which = "build" | "front": A (npad, npad); "cross": Ks (npad, mpad) and the
         fused column sums Ks^T vec (mpad,); "trace": the cov_N + 1 sums and diag(Q) (npad,) for Q = mat / sl - vec vec^T.
+        "grad_operand": gpc_grad_post's operand, the panel rearranged to (npad, D + 1, mpad) (slot 0 = k, slot 1 + l =
+        dk/dx*_l) and its fused column sums against vec (D + 1, mpad).
         The last entry of the returned tuple is always the scaled inputs (npad, D) -- for "cross" the pair (Xs, Xss)."""
-        code = {"build": 0, "front": 1, "cross": 2, "trace": 3}[which]
+        code = {"build": 0, "front": 1, "cross": 2, "trace": 3, "grad_operand": 4}[which]
         X, hyp_cov = _f64(X), _f64(hyp_cov).ravel()
         N, D = X.shape
         npad = -(-N // 128) * 128
@@ -527,6 +531,8 @@ class Context:
             out0, out1 = np.empty((npad, npad)), None
         elif code == 2:
             out0, out1 = np.empty((npad, mpad)), np.empty(mpad)
+        elif code == 4:  # per block of 128 queries: [block][npad][D + 1][128] and [block][D + 1][128]
+            out0, out1 = np.empty((mpad // 128, npad, D + 1, 128)), np.empty((mpad // 128, D + 1, 128))
         else:
             out0, out1 = np.empty(self._lib.gpc_cov_count(kid, D) + 1), np.empty(npad)
         rc = self._lib.gpc_debug_cov(self._h, code, kid, degree, dtype, _ptr(hyp_cov), float(kscale), float(sl),
@@ -537,7 +543,25 @@ class Context:
             return out0, xs
         if code == 2:
             return out0, out1, (xs[:npad], xs[npad:])
+        if code == 4:
+            return (out0.transpose(1, 2, 0, 3).reshape(npad, D + 1, mpad),
+                    out1.transpose(1, 0, 2).reshape(D + 1, mpad), xs)
         return out0, out1, xs
+
+    @_serial
+    def debug_block_gram(self, Y, Z=None, dtype=F64, diag_only=False):
+        """gpc_debug_block_gram: Y, Z (n, Dp, M) panels (Z None: Z = Y).  Returns (M, Dp, Dp): [j, a, b] = [j, b, a] =
+        sum_i Y[i, a, j] Z[i, b, j] for a >= b, accumulated in fp64 from the values stored in ``dtype``; with
+        ``diag_only`` (M, Dp): sum_i Y[i, a, j] Z[i, a, j]."""
+        Y = _f64(Y)
+        Zc = None if Z is None else _f64(Z)
+        n, Dp, M = Y.shape
+        if Zc is not None and Zc.shape != Y.shape:
+            raise ValueError("debug_block_gram: Y and Z (n, Dp, M)")
+        out = np.empty((M, Dp) if diag_only else (M, Dp, Dp))
+        rc = self._lib.gpc_debug_block_gram(self._h, dtype, n, M, Dp, _ptr(Y), _ptr(Zc), int(bool(diag_only)), _ptr(out))
+        self._check(rc, "gpc_debug_block_gram")
+        return out
 
     @_serial
     def debug_normals(self, seed, stream, s, r, j0, count):
@@ -587,6 +611,20 @@ class PostHandle:
         rc = self.ctx._lib.gpc_predict_grad(self._h, _ptr(xs), M, _ptr(fmu), _ptr(fs2), _ptr(dfmu), _ptr(dfs2))
         self.ctx._check(rc, "gpc_predict_grad")
         return fmu, fs2, dfmu, dfs2
+
+    @_serial
+    def grad_post(self, x_star, diag_only=False):
+        """gpc_grad_post: the joint posterior of (f, grad f) at x_star (M, D) per sample.  Returns fmu (M, S), dfmu
+        (M, D, S) and cov (M, D + 1, D + 1, S) -- slot 0 = f, slot 1 + l = d/dx_l -- or, with ``diag_only``, its diagonal
+        (M, D + 1, S).  No clamp, no noise, no mean function."""
+        xs = _f64(x_star)
+        M, D = xs.shape
+        fmu = np.empty((M, self.S))
+        dfmu = np.empty((M, D, self.S))
+        cov = np.empty((M, D + 1, self.S) if diag_only else (M, D + 1, D + 1, self.S))
+        rc = self.ctx._lib.gpc_grad_post(self._h, _ptr(xs), M, int(bool(diag_only)), _ptr(fmu), _ptr(dfmu), _ptr(cov))
+        self.ctx._check(rc, "gpc_grad_post")
+        return fmu, dfmu, cov
 
     @_serial
     def predict_K(self, Ks, Kss=None, want_var=True):

@@ -26,6 +26,7 @@
 #include "cv.h"
 #include "draw.h"
 #include "gemm.h"
+#include "gradpost.h"
 #include "leaf.h"
 #include "lookahead.h"
 #include "paths.h"
@@ -488,6 +489,7 @@ struct gpc_ctx {
   static constexpr size_t LAND_BYTES = 64u << 10;
   unsigned long long land_seq = 0;
   unsigned long long small_polled = 0, small_synced = 0;  // statistics ("small_polled" / "small_synced")
+  unsigned long long grad_post_gram_us = 0;  // Gram passes of the last gpc_grad_post, device microseconds ("grad_post_gram_us")
   unsigned long long cov_fused = 0;  // gpc_predict_cov calls whose reduction ran in the product's epilogue ("cov_fused")
   unsigned long long quad_mix_gemms = 0;  // MFMA GEMM launches inside gpc_quad_mix ("quad_mix_gemms"; there should be none)
   int check_queues = 0;  // debug option: verify after every pipeline that the tile queues of its persistent launches were drained
@@ -3289,6 +3291,168 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
   return 0;
 }
 
+// gpc_grad_post: the joint posterior of (f, grad f) at every query, rhs_products' sibling (gradpost.h).  The queries are
+// worked on in blocks of GQB = 128 whatever the shape or the budget; per block and sample
+//   panel = [ k(X, x*) | dk/dx*_1 | ... | dk/dx*_D ]  (npad x (D + 1) 128, slot-major planes; the mean product fused in)
+//   L_chol:    V = W panel,   Gram = per query V_j^T V_j,         C_j = H - Gram / sl
+//   low noise: Z = L panel,   Gram = per query panel_j^T Z_j,     C_j = H + Gram
+// `diag`: the D + 1 variances only -- for L_chol samples the column sums of squares of V from the product's epilogue
+// (gemm.h: EPI = 1, V is never written), for the others the diagonal form of the Gram kernel.  The forms depend on
+// (npad, D, diag) alone, so a sample carries the same bits in any batch, chunk or run.  The budget decides the samples
+// per chunk only; a sample with one query block that does not fit is refused.
+// gpc_last_timing: the device sections of all (chunk, block) steps and, of these, the products with W (or L).
+struct GramClock {  // the Gram passes of a timed call, for the "grad_post_gram_us" counter
+  hipEvent_t e[2] = {nullptr, nullptr};
+  bool on;
+  explicit GramClock(bool on_) : on(on_) {
+    if (on && (hipEventCreate(&e[0]) != hipSuccess || hipEventCreate(&e[1]) != hipSuccess)) on = false;
+  }
+  ~GramClock() {
+    for (hipEvent_t x : e)
+      if (x) (void)hipEventDestroy(x);
+  }
+  hipError_t record(int i, hipStream_t st) { return on ? hipEventRecord(e[i], st) : hipSuccess; }
+  double elapsed_us() {
+    float ms = 0;
+    if (on) (void)hipEventElapsedTime(&ms, e[0], e[1]);
+    return 1e3 * ms;
+  }
+};
+
+template <typename T>
+int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* fmu, double* dfmu, double* cov) {
+  gpc_ctx* c = po->ctx;
+  const int S = po->S, N = po->N, D = po->D, npad = po->npad, Dp = D + 1, mb = GQB, ld = Dp * mb;
+  hipStream_t st = c->st;
+  const long long sP = (long long)npad * ld;
+  const int nt64 = npad / CT, tmr = npad / TILE, nseg = gram_segments(npad);
+  const size_t gper = (size_t)mb * Dp * (diag ? 1 : Dp);  // doubles of a sample's Gram result
+  const size_t per = 2 * (size_t)sP * sizeof(T) +
+                     ((size_t)nt64 * ld + (diag ? (size_t)tmr * ld : 0) + (nseg > 1 ? nseg : 0) * gper + gper + ld + 1 +
+                      (size_t)mb * D + (size_t)npad * D + SP_STRIDE + 2 * D) * 8;
+  const size_t held = c->ks.bytes + c->vb.bytes;
+  const bool fits = (size_t)S * per <= held && (size_t)S * sP * sizeof(T) <= std::min(c->ks.bytes, c->vb.bytes);
+  const int chunk = plan_chunk(c, S, per, 0, held, fits, 0, false, [&](size_t budget) {
+    return "gpc_grad_post: the scratch of one sample with one query block (" + std::to_string(per) + " bytes: N_pad = " +
+           std::to_string(npad) + ", D = " + std::to_string(D) + ", block = " + std::to_string(mb) +
+           " queries) exceeds the device memory budget (" + std::to_string(budget) + " bytes)";
+  });
+  if (!chunk) return -2;
+  HIPCHK(c, c->ks.ensure((size_t)chunk * sP * sizeof(T)));
+  HIPCHK(c, c->vb.ensure((size_t)chunk * sP * sizeof(T)));
+  HIPCHK(c, c->dbg2.ensure((size_t)chunk * nt64 * ld * 8));
+  if (diag) HIPCHK(c, c->dbg3.ensure((size_t)chunk * tmr * ld * 8));
+  if (nseg > 1) HIPCHK(c, c->gpart.ensure((size_t)chunk * nseg * gper * 8));
+  HIPCHK(c, c->gres.ensure((size_t)chunk * gper * 8));
+  HIPCHK(c, c->pout.ensure((size_t)chunk * ld * 8));
+  HIPCHK(c, c->daux.ensure((size_t)chunk * 8));
+  HIPCHK(c, c->xss.ensure(((size_t)chunk * mb + M) * D * 8));
+  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
+  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
+  HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
+  HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
+  T* const P = c->ks.as<T>();
+  T* const V = c->vb.as<T>();
+  double* const xsq = c->xss.as<double>();
+  double* const d_xa = xsq + (size_t)chunk * mb * D;
+  double* const d_mean = c->pout.as<double>();
+  double* const d_gram = c->gres.as<double>();
+  double* const d_f0 = c->daux.as<double>();
+  c->pin.begin();
+  c->pin.begin_gather();
+  CallTimer tm{c, CallTimer::wanted(c, npad)};
+  GramClock gc(tm.on);
+  HIPCHK(c, c->pin.up(d_xa, xstar, (size_t)M * D * 8, st));
+  std::vector<double> hmean((size_t)chunk * ld), hgram((size_t)chunk * gper), hf0(chunk);
+  ChunkConsts k;
+  if (int rc = k.init(po, chunk == S)) return rc;
+  c->ms_total = c->ms_factor = 0;
+  double gram_us = 0;
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    if (int rc = k.stage(s0, cnt, true)) return rc;
+    for (int q0 = 0; q0 < M; q0 += mb) {
+      const int mq = std::min(mb, M - q0);
+      HIPCHK(c, tm.start());
+      hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mb * D + 255) / 256), cnt), dim3(256), 0, st,
+                         (const double*)(d_xa + (size_t)q0 * D), mq, mb, D, k.mulb, k.divb, xsq);
+      GPC_COV_DISPATCH(grad_operand_tile_kernel, T, po->cd, dim3(mb / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
+                       (const double*)xsq, k.spb, k.mulb, k.divb, po->alpha.as<double>() + (size_t)s0 * npad, npad, N, npad,
+                       mq, mb, P, sP, c->dbg2.as<double>(), d_f0);
+      hipLaunchKernelGGL(colpart_reduce_kernel, dim3((ld + 255) / 256, cnt), dim3(256), 0, st,
+                         (const double*)c->dbg2.as<double>(), nt64, ld, d_mean);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, tm.mark1());
+      // the products of every run of equal L_chol, then (second pass) what reduces them
+      int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+        GemmArgs g = tri_product_args<T>(po, s0 + a, lch, P + (size_t)a * sP, V + (size_t)a * sP, sP, ld, ld);
+        if (diag && lch) {
+          int* qctr = c->tile_ctr.as<int>() + (size_t)gpc_ctx::MAXG * gpc_ctx::CTR_PER_GROUP;
+          HIPCHK(c, hipMemsetAsync(qctr, 0, CTR_STRIDE * sizeof(int), st));
+          g.colsq = c->dbg3.as<double>() + (size_t)a * tmr * ld;
+          HIPCHK(c, launch_gemm_colsq<T>(st, g, len, qctr));
+        } else {
+          HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
+        }
+        return 0;
+      });
+      if (rc_runs) return rc_runs;
+      HIPCHK(c, tm.mark2());
+      HIPCHK(c, gc.record(0, st));
+      rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+        if (diag && lch)  // [b][a * mb + j]: the panel's own column order
+          hipLaunchKernelGGL(colpart_reduce_kernel, dim3((ld + 255) / 256, len), dim3(256), 0, st,
+                             (const double*)(c->dbg3.as<double>() + (size_t)a * tmr * ld), tmr, ld, d_gram + (size_t)a * gper);
+        else
+          HIPCHK(c, launch_block_gram<T>(st, (lch ? V : P) + (size_t)a * sP, V + (size_t)a * sP, sP, npad, mb, Dp, len, diag,
+                                         nseg > 1 ? c->gpart.as<double>() + (size_t)a * nseg * gper : nullptr,
+                                         d_gram + (size_t)a * gper));
+        return 0;
+      });
+      if (rc_runs) return rc_runs;
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, gc.record(1, st));
+      HIPCHK(c, hipMemcpyAsync(hmean.data(), d_mean, (size_t)cnt * ld * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipMemcpyAsync(hgram.data(), d_gram, (size_t)cnt * gper * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipMemcpyAsync(hf0.data(), d_f0, (size_t)cnt * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, tm.stop());
+      HIPCHK(c, hipStreamSynchronize(st));
+      tm.accumulate();
+      gram_us += gc.elapsed_us();
+      // into the caller's layout: C = H - Gram / sl | H + Gram, H = diag(sf2, F0 c_1^2, ..., F0 c_D^2)
+      for (int i = 0; i < cnt; ++i) {
+        const int s = s0 + i;
+        const bool lch = po->lchol[s] != 0;
+        const double gs = lch ? -1.0 / po->sp[(size_t)s * SP_STRIDE + SP_SL] : 1.0;
+        std::vector<double> H(Dp);
+        H[0] = po->sp[(size_t)s * SP_STRIDE + SP_SF2];
+        for (int l = 0; l < D; ++l) {
+          const double cl = po->mul[(size_t)s * D + l] / po->dv[(size_t)s * D + l];
+          H[1 + l] = hf0[i] * cl * cl;
+        }
+        const double* mean = &hmean[(size_t)i * ld];
+        const double* gram = &hgram[(size_t)i * gper];
+        for (int jj = 0; jj < mq; ++jj) {
+          const size_t j = (size_t)q0 + jj;
+          fmu[j * S + s] = mean[jj];
+          for (int l = 0; l < D; ++l) dfmu[(j * D + l) * S + s] = mean[(size_t)(1 + l) * mb + jj];
+          if (diag) {
+            for (int a = 0; a < Dp; ++a)
+              cov[(j * Dp + a) * S + s] = H[a] + gs * (lch ? gram[(size_t)a * mb + jj] : gram[(size_t)jj * Dp + a]);
+          } else {
+            for (int a = 0; a < Dp; ++a)
+              for (int b = 0; b < Dp; ++b)
+                cov[((j * Dp + a) * Dp + b) * S + s] = (a == b ? H[a] : 0.0) + gs * gram[((size_t)jj * Dp + a) * Dp + b];
+          }
+        }
+      }
+    }
+  }
+  c->pin.finish();
+  c->grad_post_gram_us = (unsigned long long)gram_us;
+  return 0;
+}
+
 }  // namespace
 
 // test-hook helpers
@@ -3658,6 +3822,32 @@ int debug_cov_impl(gpc_ctx* c, int which, CovDesc cd, const double* hyp, double 
     if (download_as<T>(c, Ks, out0, (size_t)npad * mpad)) return -1;
     HIPCHK(c, hipMemcpyAsync(out1, mu, (size_t)mpad * 8, hipMemcpyDeviceToHost, st));
     if (xs_out) HIPCHK(c, hipMemcpyAsync(xs_out + (size_t)npad * D, xss, (size_t)mpad * D * 8, hipMemcpyDeviceToHost, st));
+  } else if (which == 4) {
+    // the derivative operand as gpc_grad_post launches it: one launch per block of GQB queries.  out0: the panels,
+    // [block][npad][(D + 1) GQB]; out1: the fused column sums against vec, [block][(D + 1) GQB]
+    const int mb = GQB, ld = (D + 1) * mb, nblk = (M + mb - 1) / mb;
+    const size_t psz = (size_t)npad * ld;
+    double* dXq = sd.get<double>((size_t)M * D);
+    double* xss = sd.get<double>((size_t)mb * D);
+    T* P = sd.get<T>(psz);
+    double* part = sd.get<double>((size_t)t64 * ld);
+    double* sums = sd.get<double>(ld);
+    double* f0 = sd.get<double>(1);
+    if (!dXq || !xss || !P || !part || !sums || !f0) FAIL(c, "gpc_debug_cov: out of device memory");
+    HIPCHK(c, hipMemcpyAsync(dXq, Xstar, (size_t)M * D * 8, hipMemcpyHostToDevice, st));
+    for (int q = 0; q < nblk; ++q) {
+      const int mq = std::min(mb, M - q * mb);
+      hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mb * D + 255) / 256), 1), dim3(256), 0, st,
+                         (const double*)(dXq + (size_t)q * mb * D), mq, mb, D, (const double*)dmul, (const double*)ddv, xss);
+      GPC_COV_DISPATCH(grad_operand_tile_kernel, T, cd, dim3(mb / CT, npad / CT, 1), dim3(256), 0, st, cd, (const double*)xs,
+                       (const double*)xss, (const double*)dsp, (const double*)dmul, (const double*)ddv, (const double*)dvv,
+                       npad, N, npad, mq, mb, P, (long long)psz, part, f0);
+      hipLaunchKernelGGL(colpart_reduce_kernel, dim3((ld + 255) / 256, 1), dim3(256), 0, st, (const double*)part, t64, ld, sums);
+      HIPCHK(c, hipGetLastError());
+      if (download_as<T>(c, P, out0 + (size_t)q * psz, psz)) return -1;
+      HIPCHK(c, hipMemcpyAsync(out1 + (size_t)q * ld, sums, (size_t)ld * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipStreamSynchronize(st));
+    }
   } else {
     std::vector<double> hT(msz, 0.0);
     for (int i = 0; i < N; ++i) std::copy(mat + (size_t)i * N, mat + (size_t)i * N + N, hT.begin() + (size_t)i * npad);
@@ -3686,6 +3876,39 @@ int debug_cov_impl(gpc_ctx* c, int which, CovDesc cd, const double* hyp, double 
   }
   if (xs_out) HIPCHK(c, hipMemcpyAsync(xs_out, xs, (size_t)npad * D * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
+  return 0;
+}
+}  // namespace
+
+// gpc_debug_block_gram: the block Gram kernel of gpc_grad_post on caller-provided panels
+namespace {
+template <typename T>
+int debug_block_gram_impl(gpc_ctx* c, int n, int M, int Dp, const double* Y, const double* Z, bool diag, double* out) {
+  hipStream_t st = c->st;
+  const int mb = pad_tile(M), ld = Dp * mb, nseg = gram_segments(n);
+  const size_t psz = (size_t)n * ld, gper = (size_t)mb * Dp * (diag ? 1 : Dp);
+  // the caller's n x (Dp M) planes into planes of width mb (zero padding), in the storage type
+  auto padded = [&](const double* src) {
+    std::vector<T> h(psz, (T)0);
+    for (int i = 0; i < n; ++i)
+      for (int a = 0; a < Dp; ++a)
+        for (int j = 0; j < M; ++j) h[(size_t)i * ld + (size_t)a * mb + j] = (T)src[((size_t)i * Dp + a) * M + j];
+    return h;
+  };
+  ScratchDev sd;
+  T* dY = sd.get<T>(psz);
+  T* dZ = Z ? sd.get<T>(psz) : dY;
+  double* part = sd.get<double>(nseg > 1 ? nseg * gper : 1);
+  double* res = sd.get<double>(gper);
+  if (!dY || !dZ || !part || !res) FAIL(c, "gpc_debug_block_gram: out of device memory");
+  const std::vector<T> hY = padded(Y), hZ = Z ? padded(Z) : std::vector<T>();
+  HIPCHK(c, hipMemcpy(dY, hY.data(), psz * sizeof(T), hipMemcpyHostToDevice));
+  if (Z) HIPCHK(c, hipMemcpy(dZ, hZ.data(), psz * sizeof(T), hipMemcpyHostToDevice));
+  HIPCHK(c, launch_block_gram<T>(st, dY, dZ, (long long)psz, n, mb, Dp, 1, diag, part, res));
+  std::vector<double> h(gper);
+  HIPCHK(c, hipMemcpyAsync(h.data(), res, gper * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  std::copy(h.begin(), h.begin() + (size_t)M * Dp * (diag ? 1 : Dp), out);
   return 0;
 }
 }  // namespace
@@ -5425,6 +5648,22 @@ int gpc_predict_grad(gpc_post* po, const double* xstar, int M, double* fmu, doub
                               : predict_impl<float>(po, xstar, M, fmu, fs2, dfmu, dfs2);
 }
 
+int gpc_grad_post(gpc_post* po, const double* xstar, int M, int diag_only, double* fmu, double* dfmu, double* cov) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!xstar || !fmu || !dfmu || !cov || M <= 0) FAIL(c, "gpc_grad_post: bad arguments");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_grad_post: this posterior was built from caller-provided K; a caller-provided kernel has no "
+            "derivative with respect to x*");
+  if ((po->cd.kind == K_MATERN || po->cd.kind == K_MATERN_ISO) && po->cd.degree == 1)
+    FAIL(c, "gpc_grad_post: the Matern kernel of degree 1 has no mean-square derivative (its gradient has infinite "
+            "prior variance)");
+  if (int rc = require_factorized(po, "gpc_grad_post")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? grad_post_impl<double>(po, xstar, M, diag_only != 0, fmu, dfmu, cov)
+                              : grad_post_impl<float>(po, xstar, M, diag_only != 0, fmu, dfmu, cov);
+}
+
 int gpc_draw(gpc_post* po, const double* xstar, int M, int R, unsigned long long seed, int s_offset,
              const double* noise_sd, double* f, double* tau) {
   if (!po) return -2;
@@ -5754,6 +5993,7 @@ const Option OPTIONS[] = {
     {"small_timing", GPC_GET(c->small_timing), GPC_SET(c->small_timing = v != 0)},  // 1: one-leaf evaluations record their timing events (gpc_last_timing is 0 for them otherwise)
     {"small_polled", GPC_COUNTER(small_polled)},  // one-leaf calls completed by the polled word ...
     {"small_synced", GPC_COUNTER(small_synced)},  // ... and by a stream synchronisation
+    {"grad_post_gram_us", GPC_COUNTER(grad_post_gram_us)},  // device time of the Gram passes of the last gpc_grad_post (timed calls only)
     {"cov_fused", GPC_COUNTER(cov_fused)},        // gpc_predict_cov calls reduced in the product's epilogue
     {"quad_mix_gemms", GPC_COUNTER(quad_mix_gemms)},  // MFMA GEMM launches inside gpc_quad_mix
     {"start_mult_log10", nullptr, GPC_SET(c->start_mult = std::pow(10.0, clamp_to(0, 9, v)))},  // test hook: first jitter multiplier 10^value
@@ -6022,10 +6262,11 @@ int gpc_debug_cov(gpc_ctx* c, int which, int kernel_id, int degree, int dtype, c
                   double sl, const double* dvec, const double* X, int N, int D, const double* Xstar, int M,
                   const double* mat, const double* vec, double* out0, double* out1, double* xs_out) {
   if (!c) return -2;
-  if (!valid_kernel(kernel_id, degree) || !hyp_cov || !X || N <= 0 || D <= 0 || !out0 || which < 0 || which > 3)
+  if (!valid_kernel(kernel_id, degree) || !hyp_cov || !X || N <= 0 || D <= 0 || !out0 || which < 0 || which > 4)
     FAIL(c, "gpc_debug_cov: bad arguments");
   if (which == 1 && N > TILE) FAIL(c, "gpc_debug_cov: the small front builds one 128 x 128 leaf (N <= 128)");
-  if (which == 2 && (!Xstar || M <= 0 || !vec || !out1)) FAIL(c, "gpc_debug_cov: cross needs X*, alpha and both outputs");
+  if ((which == 2 || which == 4) && (!Xstar || M <= 0 || !vec || !out1))
+    FAIL(c, "gpc_debug_cov: cross needs X*, alpha and both outputs");
   if (which == 3 && (!mat || !vec || !out1)) FAIL(c, "gpc_debug_cov: trace needs T, a and both outputs");
   HIPCHK(c, hipSetDevice(c->device));
   CovDesc cd;
@@ -6036,6 +6277,16 @@ int gpc_debug_cov(gpc_ctx* c, int which, int kernel_id, int degree, int dtype, c
   return dtype == GPC_F64
              ? debug_cov_impl<double>(c, which, cd, hyp_cov, kscale, sl, dvec, X, N, Xstar, M, mat, vec, out0, out1, xs_out)
              : debug_cov_impl<float>(c, which, cd, hyp_cov, kscale, sl, dvec, X, N, Xstar, M, mat, vec, out0, out1, xs_out);
+}
+
+int gpc_debug_block_gram(gpc_ctx* c, int dtype, int n, int M, int Dp, const double* Y, const double* Z, int diag_only,
+                         double* out) {
+  if (!c) return -2;
+  if (!Y || !out || n <= 0 || M <= 0 || Dp <= 0 || (dtype != GPC_F64 && dtype != GPC_F32))
+    FAIL(c, "gpc_debug_block_gram: bad arguments");
+  HIPCHK(c, hipSetDevice(c->device));
+  return dtype == GPC_F64 ? debug_block_gram_impl<double>(c, n, M, Dp, Y, Z, diag_only != 0, out)
+                          : debug_block_gram_impl<float>(c, n, M, Dp, Y, Z, diag_only != 0, out);
 }
 
 // Debug: a 64-bit hash (sum of the bit patterns, wrapping) of every 128 x 128 tile of one workspace matrix of the LAST call

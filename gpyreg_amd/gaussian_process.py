@@ -200,9 +200,9 @@ def _quad_gamma(mu, sigma, ell, ln_sf2):
     return np.exp(ln_sf2 + np.sum(np.log(ell)) - 0.5 * np.sum(np.log(t), 2) - 0.5 * np.sum(d**2 / t, 2))
 
 
-def _mean_grad_x(mean, hyp, X):
+def _mean_grad_x(mean, hyp, X, who="predict_grad"):
     """d m(x) / dx (M, D) of a stock mean function under the mean hyperparameters ``hyp``; exact types only (a
-    subclass may compute anything): other mean objects raise NotImplementedError."""
+    subclass may compute anything): other mean objects raise NotImplementedError (``who``: the method named there)."""
     from .mean_functions import ConstantMean, NegativeQuadratic, ZeroMean
 
     if type(mean) in (ZeroMean, ConstantMean):
@@ -210,8 +210,8 @@ def _mean_grad_x(mean, hyp, X):
     if type(mean) is NegativeQuadratic:
         D = X.shape[1]
         return -(X - hyp[1:1 + D]) / np.exp(2 * hyp[1 + D:1 + 2 * D])
-    raise NotImplementedError(f"predict_grad: the mean function {mean!r} is user-defined; its gradient with "
-                              "respect to x_star is unknown")
+    raise NotImplementedError(f"{who}: the mean function {mean!r} ({type(mean).__name__}) is user-defined; its "
+                              "gradient with respect to x_star is unknown")
 
 
 class PosteriorPaths:
@@ -1553,6 +1553,79 @@ class GP:
             dmu, ds2 = _mix_sample_grads(mu, dmu, ds2)
             mu, s2, _ = _mix_samples(mu, s2)
         return mu, s2, dmu, ds2
+
+    @_on_device
+    def gradient_posterior(self, x_star, cov: str = "full", with_value: bool = False,
+                           separate_samples: bool = False):
+        """The posterior distribution of the gradient of the latent function at ``x_star``: (dmu, dcov).
+
+        dmu (M, D) is the posterior mean of grad f (``predict_grad``'s dmu, the stock mean functions' gradient
+        included); dcov (M, D, D) its posterior covariance, entry [j, l, k] = Cov(df/dx_l, df/dx_k) at x_star[j], or
+        with ``cov="diag"`` the variances (M, D) alone (cheaper: no Gram matrix is formed).  With ``with_value`` f
+        itself is prepended as slot 0: shapes (M, D + 1) and (M, D + 1, D + 1) (or (M, D + 1)), slot 0 holding
+        ``predict``'s latent mean and variance and [j, 0, 1 + l] = Cov(f, df/dx_l) = half of ``predict_grad``'s variance
+        gradient before its clamp.  Nothing is clamped or projected: a joint covariance must stay consistent, so each
+        per-sample matrix is returned as computed (symmetric to the bit; in floating point its smallest eigenvalue
+        may be a rounding error below 0 where the posterior is nearly certain).  With ``separate_samples`` a trailing
+        axis S holds the hyperparameter samples; otherwise the moments of their equal-weight mixture are returned: the
+        mean of the means, and the mean of the covariances plus the between-sample covariance of the mean vectors
+        (divisor S - 1, ``predict``'s convention; one sample is returned as it is).  E[(df/dx_l)^2] = dmu_l^2 + dcov_ll.
+
+        With data the operand, the solves and the per-query Gram matrices run on the device (gpc_grad_post); a GP
+        without data returns the prior (the mean function's gradient and the diagonal prior block) from the host.
+        Built-in covariance functions and stock mean functions only (NotImplementedError otherwise); the Matern kernel
+        of degree 1 has no mean-square derivative and is refused.  Under sharding each rank computes its samples and
+        the results are gathered: the same values as one process."""
+        from . import _gradpost as _gpm
+
+        if cov not in ("full", "diag"):
+            raise ValueError(f"gradient_posterior: cov must be 'full' or 'diag', got {cov!r}")
+        diag = cov == "diag"
+        x_star, _, _ = self._convert_shapes(x_star, None, None)
+        if not self._builtin:
+            raise NotImplementedError(f"gradient_posterior: the covariance function {self.covariance!r} is "
+                                      "user-defined; it has no derivative with respect to x_star")
+        kid, degree = self._kid()
+        _gpm.check_kind(kid, degree)
+        s_N = self.posteriors.size
+        M, D = x_star.shape
+        P = D + 1
+        cov_N, noise_N, mean_N = self._counts()
+        hyps = [self.posteriors[s].hyp for s in range(s_N)]
+        mean = np.empty((M, P, s_N))
+        for s, h in enumerate(hyps):
+            hm = h[cov_N + noise_N:cov_N + noise_N + mean_N]
+            mean[:, 1:, s] = _mean_grad_x(self.mean, hm, x_star, "gradient_posterior")
+            mean[:, 0, s] = np.reshape(self.mean.compute(hm, x_star), (-1,))
+        if self.y is None:  # no data: the prior
+            Hd = np.stack([_gpm.prior_block(kid, degree, h[:cov_N], D) for h in hyps], axis=1)  # (P, S)
+            C = np.broadcast_to(Hd[None], (M, P, s_N)).copy()
+            if not diag:
+                C = np.einsum("mas,ab->mabs", C, np.eye(P))
+        else:
+            self._restore()
+            if self._post_handle is None and self._post_range is None:
+                raise ValueError("posteriors have been cleaned; call update() first")
+            self._ctx()
+            local_posts, _ = self._local_posteriors()
+            csz = P if diag else P * P
+            if not local_posts:
+                rows = np.zeros((M * (P + csz), 0))
+            else:
+                fmu, dfmu, fc = self._post_handle.grad_post(x_star, diag)
+                k = fmu.shape[1]
+                rows = np.concatenate([fmu, dfmu.reshape(M * D, k), fc.reshape(M * csz, k)], axis=0)
+            if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
+                rows = self._gather_samples(rows, x_star, np.array([float(diag)]))
+            mean[:, 0, :] += rows[:M]
+            mean[:, 1:, :] += rows[M:M + M * D].reshape(M, D, -1)
+            C = rows[M + M * D:].reshape((M, P, -1) if diag else (M, P, P, -1))
+        if not with_value:
+            mean = mean[:, 1:]
+            C = C[:, 1:] if diag else C[:, 1:, 1:]
+        if separate_samples:
+            return mean, C
+        return _gpm.mix_diag(mean, C) if diag else _gpm.mix(mean, C)
 
     @_on_device
     def predict_full(self, x_star, y_star=None, s2_star=None, add_noise: bool = False):

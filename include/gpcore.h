@@ -158,6 +158,25 @@ int gpc_predict(gpc_post* post, const double* xstar, int M, double* fmu, double*
 int gpc_predict_grad(gpc_post* post, const double* xstar, int M, double* fmu, double* fs2, double* dfmu,
                      double* dfs2);
 
+/* ---- GP.gradient_posterior: the joint posterior of (f(x*), grad f(x*)) per sample ----------------------
+ * With B_j = [ k(X, x*_j) | G_j ], G_j[i, l] = dk(x*_j, X_i) / dx*_jl = -c_l F_ij (xs*_jl - xs_il) (F, c_l, xs of
+ * gpc_predict_grad; a pair at distance 0 contributes 0 to G) and the prior block H = diag(kss, F0 c_1^2, ..., F0 c_D^2),
+ * F0 = F at distance 0 (stationary kernels: the value / derivative cross terms vanish at coincident points):
+ *   fmu[j*S + s]            = B_j^T alpha, slot 0                         (as gpc_predict)
+ *   dfmu[(j*D + l)*S + s]   = B_j^T alpha, slot 1 + l                     (as gpc_predict_grad)
+ *   cov[((j*(D+1) + a)*(D+1) + b)*S + s] = C_j[a, b],   slot 0 = f, slot 1 + l = d/dx_l,
+ *     C_j = H - V_j^T V_j / sl, V_j = W B_j (L_chol samples)   |   C_j = H + B_j^T (L B_j) (L = -inv)
+ *   diag_only != 0:  cov[(j*(D+1) + a)*S + s] = C_j[a, a] only (no Gram matrix is formed for L_chol samples)
+ * C_j[0, 0] is gpc_predict's fs2, C_j[0, 1 + l] half of gpc_predict_grad's dfs2.  The full matrix is symmetric to the
+ * bit (the lower triangle is computed and mirrored) and returned as computed: no clamp, no projection to PSD, no
+ * noise, no mean function -- those are the caller's.  The queries are worked on in blocks of 128 whatever the memory
+ * budget (GPC_MEM_BUDGET_MB), which decides the samples per chunk only: a sample's results do not depend on it.
+ * Returns -2 with a message of its own for: bad arguments; a posterior from caller-provided K; the Matern kernel of
+ * degree 1 (ARD or isotropic: no mean-square derivative, F0 is infinite); a posterior that holds a failed
+ * factorization; one sample with one query block exceeding the budget (the message names N_pad, D, the block size and
+ * the bytes).  gpc_last_timing: ms_total = the device sections, ms_factor = the products with W (or L).               */
+int gpc_grad_post(gpc_post* post, const double* xstar, int M, int diag_only, double* fmu, double* dfmu, double* cov);
+
 /* ---- GP.draw_functions: joint posterior draws, n_draws per sample (extends gaussian_process.py:2241-2329) ----
  * For every sample s of the posterior (global index s_offset + s), draw r < R and query point j < M:
  *   f[(j*R + r)*S + s] = fmu_js + (L_s z_{s,r})_j  (+ noise_sd[j*S + s] z'_{s,r,j})
@@ -487,11 +506,22 @@ int gpc_debug_factor(gpc_ctx* ctx, int dtype, int n, const double* A, double* L,
  *   2  cross_tile_kernel:   out0[npad x mpad] = K(X, Xstar[M x D]), out1[mpad] = the fused column sums Ks^T vec[N]
  *   3  trace_kernel + the reduction of its partials: Q = mat / sl - vec vec^T over the lower triangle of mat[N x N]
  *      (stored in `dtype`): out0[cov_N + 1] = sum_ij w_ij Q_ij dK_ij/dtheta_p, last slot trace(Q); out1[npad] = diag(Q)
+ *   4  grad_operand_tile_kernel (gpc_grad_post's operand), one launch per block of 128 queries as the product path
+ *      launches it: out0[block][npad][(D + 1) 128] = the panels, slot-major planes (column a 128 + j: slot a of query j
+ *      of the block; slot 0 = k, slot 1 + l = dk/dx*_l), zero padding; out1[block][(D + 1) 128] = the fused column sums
+ *      against vec[N]
  * xs_out (optional): the scaled inputs, npad x D (which = 2: followed by the mpad x D of Xstar).                        */
 int gpc_debug_cov(gpc_ctx* ctx, int which, int kernel_id, int degree, int dtype, const double* hyp_cov,
                   double kscale, double sl, const double* dvec, const double* X, int N, int D,
                   const double* Xstar, int M, const double* mat, const double* vec, double* out0,
                   double* out1, double* xs_out);
+
+/* gpc_grad_post's block Gram kernel on caller-provided panels Y, Z: n rows x (Dp planes of M queries), row major
+ * ([i][a][j]), stored in `dtype` and padded to the pipeline's plane width.  Z = NULL: Z = Y.  out[j][a][b] = out[j][b][a]
+ * = sum_i Y[i][a][j] Z[i][b][j] for a >= b (the lower triangle, mirrored), accumulated in fp64 in an order fixed by n alone;
+ * diag_only != 0: out[j][a] = sum_i Y[i][a][j] Z[i][a][j].                                                            */
+int gpc_debug_block_gram(gpc_ctx* ctx, int dtype, int n, int M, int Dp, const double* Y, const double* Z, int diag_only,
+                         double* out);
 
 /* Debug: wrapping-sum hash of every 128 x 128 tile of one workspace matrix as the LAST call left it (which: 0 = A, 1 = W,
  * 2 = T; sample: position in the last chunk); out[(npad/128)^2].  Finds the tile where two schedules differ.          */
