@@ -68,6 +68,7 @@ SIGNATURES = {
     "gpc_predict": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "gpc_predict_grad": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "gpc_grad_post": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "gpc_predict_hess": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpc_post_append": (C.c_int, [_vp, _dp, _dp, C.c_double, _ip]),
     "gpc_post_recompute": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_post_append_K": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_double, _ip]),
@@ -104,6 +105,8 @@ SIGNATURES = {
          C.c_int, _dp, _dp, _dp, _dp, _dp],
     ),
     "gpc_debug_block_gram": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]),
+    "gpc_debug_hess_contract": (
+        C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "gpc_debug_normals": (C.c_int, [_vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "gpc_debug_workspace_hash": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
     "gpc_debug_chunk_plan": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_int]),
@@ -564,6 +567,25 @@ class Context:
         return out
 
     @_serial
+    def debug_hess_contract(self, kernel_id, degree, hyp_cov, X, x_star, alpha, Q=None, dtype=F64):
+        """gpc_debug_hess_contract: the contraction kernel of gpc_predict_hess on the weights alpha (N,) and, optionally,
+        a dense Q (N, M) stored in ``dtype``.  Returns (out_alpha, out_q), each (M, 1 + D (D + 1) / 2): column 0 =
+        sum_i w F, column 1 + a (a + 1) / 2 + b = sum_i w G d_a d_b for a >= b; out_q is None without Q."""
+        X, xs, hyp, al = _f64(X), _f64(x_star), _f64(hyp_cov), _f64(alpha).ravel()
+        N, D = X.shape
+        M = xs.shape[0]
+        Qc = None if Q is None else _f64(Q)
+        if xs.shape[1] != D or al.size != N or (Qc is not None and Qc.shape != (N, M)):
+            raise ValueError("debug_hess_contract: X (N, D), x_star (M, D), alpha (N,), Q (N, M)")
+        npl = 1 + D * (D + 1) // 2
+        out_a = np.empty((M, npl))
+        out_q = None if Qc is None else np.empty((M, npl))
+        rc = self._lib.gpc_debug_hess_contract(self._h, kernel_id, degree, dtype, _ptr(hyp), _ptr(X), N, D, _ptr(xs), M,
+                                               _ptr(al), _ptr(Qc), _ptr(out_a), _ptr(out_q))
+        self._check(rc, "gpc_debug_hess_contract")
+        return out_a, out_q
+
+    @_serial
     def debug_normals(self, seed, stream, s, r, j0, count):
         """gpc_debug_normals: the device's z of rows j0 .. j0 + count - 1 of (seed, stream, sample s, draw r)."""
         out = np.empty(count)
@@ -625,6 +647,23 @@ class PostHandle:
         rc = self.ctx._lib.gpc_grad_post(self._h, _ptr(xs), M, int(bool(diag_only)), _ptr(fmu), _ptr(dfmu), _ptr(cov))
         self.ctx._check(rc, "gpc_grad_post")
         return fmu, dfmu, cov
+
+    @_serial
+    def predict_hess(self, x_star, compute_var=True):
+        """gpc_predict_hess: fmu, fs2 (M, S), dfmu, dfs2 (M, D, S) as predict_grad, and the Hessians hmu, hs2
+        (M, D, D, S) of the mean and the variance with respect to x_star, symmetric to the bit.  Without
+        ``compute_var`` the three variance entries are None and no product is launched."""
+        xs = _f64(x_star)
+        M, D = xs.shape
+        S = self.S
+        fmu, dfmu, hmu = np.empty((M, S)), np.empty((M, D, S)), np.empty((M, D, D, S))
+        fs2 = np.empty((M, S)) if compute_var else None
+        dfs2 = np.empty((M, D, S)) if compute_var else None
+        hs2 = np.empty((M, D, D, S)) if compute_var else None
+        rc = self.ctx._lib.gpc_predict_hess(self._h, _ptr(xs), M, int(bool(compute_var)), _ptr(fmu), _ptr(fs2), _ptr(dfmu),
+                                            _ptr(dfs2), _ptr(hmu), _ptr(hs2))
+        self.ctx._check(rc, "gpc_predict_hess")
+        return fmu, fs2, dfmu, dfs2, hmu, hs2
 
     @_serial
     def predict_K(self, Ks, Kss=None, want_var=True):

@@ -192,6 +192,39 @@ __device__ __forceinline__ PairVal pair_eval_t(double r2, double sf2, double rqa
   return o;
 }
 
+// The second radial factor G = -2 dF/d(r2) next to F (hess.h): d^2 K / dxs_a dxs_b = G d_a d_b - F delta_ab.  A sibling
+// of pair_eval_t, which stays as it is: F is taken from it (the same bits as every other kernel's), and G repeats
+// its subexpressions (sqrt_fast, the exponential, the reciprocal), which the compiler shares after inlining.
+//   SE: K    Matern 3: e / t    Matern 5: e / 3    RQ: (alpha + 1) / alpha F / m    (e = sf2 exp(-t), t = sqrt(r2))
+// Matern 3 has G = +inf at r2 = 0 (G d_a d_b -> 0 there: the caller drops the term); Matern 1 has no second derivative
+// and gets G = 0.
+struct PairFG {
+  double F, G;
+};
+template <int KIND, int DEG>
+__device__ __forceinline__ PairFG pair_eval_fg_t(double r2, double sf2, double rqa, const ExpC& ex) {
+  const PairVal pv = pair_eval_t<KIND, DEG>(r2, sf2, rqa, ex);
+  PairFG o;
+  o.F = pv.F;
+  if constexpr (KIND == K_SE || KIND == K_SE_ISO) {
+    o.G = pv.K;
+  } else if constexpr (KIND == K_MATERN || KIND == K_MATERN_ISO) {
+    const double t = sqrt_fast(r2);
+    if constexpr (DEG == 3) {
+      o.G = pv.F / t;
+    } else if constexpr (DEG == 5) {
+      constexpr double third = 1.0 / 3.0;
+      o.G = (sf2 * ex(-t)) * third;
+    } else {
+      o.G = 0.0;
+    }
+  } else {
+    const double Mv = fma(r2, 0.5 / rqa, 1.0);
+    o.G = ((rqa + 1.0) / rqa) * (pv.F * rcp_fast(Mv));
+  }
+  return o;
+}
+
 // squared distances of the 4 x 4 pairs of one thread (rows ty + 16a of tile i, rows tx + 16c of tile j),
 // dimensions summed in ascending order; leaves the LAST staged chunk of dimensions in xi / xj
 __device__ __forceinline__ void tile_r2_ab(double (&r2)[4][4], double (*xi)[DCH + 1], double (*xj)[DCH + 1],

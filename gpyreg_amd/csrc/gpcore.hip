@@ -27,6 +27,7 @@
 #include "draw.h"
 #include "gemm.h"
 #include "gradpost.h"
+#include "hess.h"
 #include "leaf.h"
 #include "lookahead.h"
 #include "paths.h"
@@ -490,6 +491,7 @@ struct gpc_ctx {
   unsigned long long land_seq = 0;
   unsigned long long small_polled = 0, small_synced = 0;  // statistics ("small_polled" / "small_synced")
   unsigned long long grad_post_gram_us = 0;  // Gram passes of the last gpc_grad_post, device microseconds ("grad_post_gram_us")
+  unsigned long long hess_contract_us = 0;  // contraction passes of the last gpc_predict_hess, device microseconds ("hess_contract_us")
   unsigned long long cov_fused = 0;  // gpc_predict_cov calls whose reduction ran in the product's epilogue ("cov_fused")
   unsigned long long quad_mix_gemms = 0;  // MFMA GEMM launches inside gpc_quad_mix ("quad_mix_gemms"; there should be none)
   int check_queues = 0;  // debug option: verify after every pipeline that the tile queues of its persistent launches were drained
@@ -3453,6 +3455,183 @@ int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* 
   return 0;
 }
 
+// gpc_predict_hess: the Hessians of the predictive mean and variance with respect to x*, gpc_grad_post's sibling
+// (hess.h).  Per block of GQB = 128 queries and sample, with the variance:
+//   panel = [ k | dk/dx*_1 .. dk/dx*_D ]  (grad_operand_tile_kernel; (fmu, dfmu) = panel^T alpha fused in)
+//   L_chol:    V = W panel, Gram = V_j^T V_j,      Q = W^T V[slot 0] / sl     fs2 = sf2 - Gram_00 / sl
+//   low noise: Z = L panel, Gram = panel_j^T Z_j,  Q = -Z[slot 0]             fs2 = sf2 + Gram_00
+//   dfs2_a = 2 gs Gram_0a,  P_ab = -gs Gram_ab  (gs = -1 / sl | 1),  the contraction with the weights (alpha | Q)
+//   Hmu = c c^T o (S_G[alpha] - I S_F[alpha]),   Hs2 = -2 (P + c c^T o (S_G[Q] - I S_F[Q]))
+// Without the variance no product is launched: the operand kernel (for fmu, dfmu: the same bits as with it) and the
+// contraction with the weights alpha alone.  Every form depends on (npad, D, compute_var) alone.
+template <typename T>
+int hess_impl(gpc_post* po, const double* xstar, int M, bool var, double* fmu, double* fs2, double* dfmu, double* dfs2,
+              double* hmu, double* hs2) {
+  gpc_ctx* c = po->ctx;
+  const int S = po->S, N = po->N, D = po->D, npad = po->npad, Dp = D + 1, mb = GQB, ld = Dp * mb;
+  hipStream_t st = c->st;
+  const long long sP = (long long)npad * ld, sQ = (long long)npad * mb;
+  const int nt64 = npad / CT, nseg = gram_segments(npad);
+  const int npl = hess_planes(D), nset = var ? 2 : 1;
+  const size_t gper = var ? (size_t)mb * Dp * Dp : 0;   // doubles of a sample's Gram result
+  const size_t hper = (size_t)nset * npl * mb;          // ... of its reduced Hessian sums
+  const size_t per = ((var ? 2 : 1) * (size_t)sP + (var ? (size_t)sQ : 0)) * sizeof(T) +
+                     ((size_t)nt64 * ld + (size_t)nt64 * hper + hper + (nseg > 1 ? nseg : 0) * gper + gper + ld + 1 +
+                      (size_t)mb * D + (size_t)npad * D + SP_STRIDE + 2 * D) * 8;
+  const size_t held = c->ks.bytes + c->vb.bytes + c->qb.bytes + c->dbg3.bytes;
+  const bool fits = (size_t)S * per <= held && (size_t)S * sP * sizeof(T) <= c->ks.bytes &&
+                    (!var || ((size_t)S * sP * sizeof(T) <= c->vb.bytes && (size_t)S * sQ * sizeof(T) <= c->qb.bytes)) &&
+                    (size_t)S * nt64 * hper * 8 <= c->dbg3.bytes;
+  const int chunk = plan_chunk(c, S, per, 0, held, fits, 0, false, [&](size_t budget) {
+    return "gpc_predict_hess: the scratch of one sample with one query block (" + std::to_string(per) +
+           " bytes: N_pad = " + std::to_string(npad) + ", D = " + std::to_string(D) + ", block = " + std::to_string(mb) +
+           " queries) exceeds the device memory budget (" + std::to_string(budget) + " bytes)";
+  });
+  if (!chunk) return -2;
+  HIPCHK(c, c->ks.ensure((size_t)chunk * sP * sizeof(T)));
+  if (var) {
+    HIPCHK(c, c->vb.ensure((size_t)chunk * sP * sizeof(T)));
+    HIPCHK(c, c->qb.ensure((size_t)chunk * sQ * sizeof(T)));
+    if (nseg > 1) HIPCHK(c, c->gpart.ensure((size_t)chunk * nseg * gper * 8));
+    HIPCHK(c, c->gres.ensure((size_t)chunk * gper * 8));
+  }
+  HIPCHK(c, c->dbg2.ensure((size_t)chunk * nt64 * ld * 8));
+  HIPCHK(c, c->dbg3.ensure((size_t)chunk * nt64 * hper * 8));
+  HIPCHK(c, c->qcon.ensure((size_t)chunk * hper * 8));
+  HIPCHK(c, c->pout.ensure((size_t)chunk * ld * 8));
+  HIPCHK(c, c->daux.ensure((size_t)chunk * 8));
+  HIPCHK(c, c->xss.ensure(((size_t)chunk * mb + M) * D * 8));
+  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
+  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
+  HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
+  HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
+  T* const P = c->ks.as<T>();
+  T* const V = c->vb.as<T>();
+  T* const Q = c->qb.as<T>();
+  double* const xsq = c->xss.as<double>();
+  double* const d_xa = xsq + (size_t)chunk * mb * D;
+  double* const d_mean = c->pout.as<double>();
+  double* const d_gram = c->gres.as<double>();
+  double* const d_hpart = c->dbg3.as<double>();
+  double* const d_hsum = c->qcon.as<double>();
+  c->pin.begin();
+  c->pin.begin_gather();
+  CallTimer tm{c, CallTimer::wanted(c, npad)};
+  GramClock hc(tm.on);  // the contraction passes, for the "hess_contract_us" counter
+  double contract_us = 0;
+  HIPCHK(c, c->pin.up(d_xa, xstar, (size_t)M * D * 8, st));
+  std::vector<double> hmean((size_t)chunk * ld), hgram((size_t)chunk * gper), hsum((size_t)chunk * hper), cs(D),
+      Ha((size_t)D * D), Hq((size_t)D * D);
+  ChunkConsts k;
+  if (int rc = k.init(po, chunk == S)) return rc;
+  c->ms_total = c->ms_factor = 0;
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    if (int rc = k.stage(s0, cnt, true)) return rc;
+    for (int q0 = 0; q0 < M; q0 += mb) {
+      const int mq = std::min(mb, M - q0);
+      const double* alpha = po->alpha.as<double>() + (size_t)s0 * npad;
+      HIPCHK(c, tm.start());
+      hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mb * D + 255) / 256), cnt), dim3(256), 0, st,
+                         (const double*)(d_xa + (size_t)q0 * D), mq, mb, D, k.mulb, k.divb, xsq);
+      GPC_COV_DISPATCH(grad_operand_tile_kernel, T, po->cd, dim3(mb / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
+                       (const double*)xsq, k.spb, k.mulb, k.divb, alpha, npad, N, npad, mq, mb, P, sP,
+                       c->dbg2.as<double>(), c->daux.as<double>());
+      hipLaunchKernelGGL(colpart_reduce_kernel, dim3((ld + 255) / 256, cnt), dim3(256), 0, st,
+                         (const double*)c->dbg2.as<double>(), nt64, ld, d_mean);
+      HIPCHK(c, hipGetLastError());
+      if (var) {
+        HIPCHK(c, tm.mark1());
+        // the products of every run of equal L_chol: V = W panel | Z = L panel, then Q from slot 0 alone
+        int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+          GemmArgs g = tri_product_args<T>(po, s0 + a, lch, P + (size_t)a * sP, V + (size_t)a * sP, sP, ld, ld);
+          HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
+          if (lch) {  // Q = W^T V[slot 0]: W^T upper triangular, k from the tile row's diagonal block on
+            GemmArgs q = g;
+            q.B = V + (size_t)a * sP;
+            q.C = Q + (size_t)a * sQ;
+            q.sC = sQ;
+            q.ldc = mb;
+            q.N = mb;
+            q.klo = KLO_ROW;
+            q.khi = KHI_FULL;
+            HIPCHK(c, launch_gemm<T>(st, q, true, true, len));
+          }
+          return 0;
+        });
+        if (rc_runs) return rc_runs;
+        HIPCHK(c, tm.mark2());
+        rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+          HIPCHK(c, launch_block_gram<T>(st, (lch ? V : P) + (size_t)a * sP, V + (size_t)a * sP, sP, npad, mb, Dp, len, false,
+                                         nseg > 1 ? c->gpart.as<double>() + (size_t)a * nseg * gper : nullptr,
+                                         d_gram + (size_t)a * gper));
+          return 0;
+        });
+        if (rc_runs) return rc_runs;
+        HIPCHK(c, hc.record(0, st));
+        rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+          GPC_COV_DISPATCH(hess_tile_kernel, T, po->cd, dim3(mb / CT, npad / CT, len), dim3(256), 0, st, po->cd,
+                           k.xsb + (size_t)a * npad * D, (const double*)(xsq + (size_t)a * mb * D),
+                           k.spb + (size_t)a * SP_STRIDE, alpha + (size_t)a * npad, npad,
+                           (const T*)(lch ? Q + (size_t)a * sQ : V + (size_t)a * sP), lch ? sQ : sP, lch ? mb : ld,
+                           lch ? 1 : 0, N, npad, mq, mb, d_hpart + (size_t)a * nt64 * hper);
+          return 0;
+        });
+        if (rc_runs) return rc_runs;
+      } else {
+        HIPCHK(c, hc.record(0, st));
+        GPC_COV_DISPATCH(hess_tile_mean_kernel, T, po->cd, dim3(mb / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
+                         (const double*)xsq, k.spb, alpha, npad, N, npad, mq, mb, d_hpart);
+      }
+      hipLaunchKernelGGL(colpart_reduce_kernel, dim3((unsigned)((hper + 255) / 256), cnt), dim3(256), 0, st,
+                         (const double*)d_hpart, nt64, (int)hper, d_hsum);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hc.record(1, st));
+      HIPCHK(c, hipMemcpyAsync(hmean.data(), d_mean, (size_t)cnt * ld * 8, hipMemcpyDeviceToHost, st));
+      if (var) HIPCHK(c, hipMemcpyAsync(hgram.data(), d_gram, (size_t)cnt * gper * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipMemcpyAsync(hsum.data(), d_hsum, (size_t)cnt * hper * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, tm.stop());
+      HIPCHK(c, hipStreamSynchronize(st));
+      if (var) tm.accumulate();
+      else if (tm.on) {  // no product: the whole device section, nothing in it a product's
+        float t03 = 0;
+        (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
+        c->ms_total += t03;
+      }
+      contract_us += hc.elapsed_us();
+      // into the caller's layout, once per query: c_a c_b, the delta_ab term, the mirror, the variance's -2 (P + .)
+      for (int i = 0; i < cnt; ++i) {
+        const int s = s0 + i;
+        const bool lch = po->lchol[s] != 0;
+        const double gs = lch ? -1.0 / po->sp[(size_t)s * SP_STRIDE + SP_SL] : 1.0;
+        const double sf2 = po->sp[(size_t)s * SP_STRIDE + SP_SF2];
+        for (int l = 0; l < D; ++l) cs[l] = po->mul[(size_t)s * D + l] / po->dv[(size_t)s * D + l];
+        const double* mean = &hmean[(size_t)i * ld];
+        const double* gram = var ? &hgram[(size_t)i * gper] : nullptr;
+        const double* sums = &hsum[(size_t)i * hper];
+        for (int jj = 0; jj < mq; ++jj) {
+          const size_t j = (size_t)q0 + jj;
+          fmu[j * S + s] = mean[jj];
+          for (int l = 0; l < D; ++l) dfmu[(j * D + l) * S + s] = mean[(size_t)(1 + l) * mb + jj];
+          hess_assemble(sums, mb, jj, D, cs.data(), Ha.data());
+          for (int e = 0; e < D * D; ++e) hmu[(j * D * D + e) * S + s] = Ha[e];
+          if (!var) continue;
+          const double* gj = gram + (size_t)jj * Dp * Dp;
+          fs2[j * S + s] = sf2 + gs * gj[0];
+          for (int l = 0; l < D; ++l) dfs2[(j * D + l) * S + s] = 2.0 * gs * gj[(size_t)(1 + l) * Dp];
+          hess_assemble(sums + (size_t)npl * mb, mb, jj, D, cs.data(), Hq.data());
+          for (int a = 0; a < D; ++a)
+            for (int b = 0; b < D; ++b)
+              hs2[((j * D + a) * D + b) * S + s] = -2.0 * (-gs * gj[(size_t)(1 + a) * Dp + 1 + b] + Hq[(size_t)a * D + b]);
+        }
+      }
+    }
+  }
+  c->pin.finish();
+  c->hess_contract_us = (unsigned long long)contract_us;
+  return 0;
+}
+
 }  // namespace
 
 // test-hook helpers
@@ -3909,6 +4088,78 @@ int debug_block_gram_impl(gpc_ctx* c, int n, int M, int Dp, const double* Y, con
   HIPCHK(c, hipMemcpyAsync(h.data(), res, gper * 8, hipMemcpyDeviceToHost, st));
   HIPCHK(c, hipStreamSynchronize(st));
   std::copy(h.begin(), h.begin() + (size_t)M * Dp * (diag ? 1 : Dp), out);
+  return 0;
+}
+}  // namespace
+
+// gpc_debug_hess_contract: the Hessian contraction of gpc_predict_hess (hess.h) on caller-provided weights, one launch
+// per block of GQB queries as the product path; Q (optional): dense N x M, taken with factor 1
+namespace {
+template <typename T>
+int debug_hess_impl(gpc_ctx* c, CovDesc cd, const double* hyp, const double* X, int N, const double* Xstar, int M,
+                    const double* alpha, const double* Qd, double* out_a, double* out_q) {
+  hipStream_t st = c->st;
+  const int D = cd.D, npad = pad_tile(N), mb = GQB, nt64 = npad / CT, npl = hess_planes(D), nset = Qd ? 2 : 1;
+  const size_t hper = (size_t)nset * npl * mb;
+  std::vector<double> mul(D), dv(D), sp(SP_STRIDE, 0.0), hal(npad, 0.0);
+  double sf2 = 0.0, rqa = 1.0;
+  scaling_of(cd.kind, cd.degree, D, hyp, mul.data(), dv.data(), &sf2, &rqa);
+  sp[SP_SF2] = sf2;
+  sp[SP_RQA] = rqa;
+  sp[SP_KSCALE] = 1.0;
+  sp[SP_SL] = 1.0;  // (with lch = 1: Q is taken as it is)
+  std::copy(alpha, alpha + N, hal.begin());
+  ScratchDev sd;
+  double* dX = sd.get<double>((size_t)N * D);
+  double* dXq = sd.get<double>((size_t)M * D);
+  double* dmul = sd.get<double>(D);
+  double* ddv = sd.get<double>(D);
+  double* dsp = sd.get<double>(SP_STRIDE);
+  double* dal = sd.get<double>(npad);
+  double* xs = sd.get<double>((size_t)npad * D);
+  double* xss = sd.get<double>((size_t)mb * D);
+  T* dQ = sd.get<T>((size_t)npad * mb);
+  double* part = sd.get<double>((size_t)nt64 * hper);
+  double* sums = sd.get<double>(hper);
+  if (!dX || !dXq || !dmul || !ddv || !dsp || !dal || !xs || !xss || !dQ || !part || !sums)
+    FAIL(c, "gpc_debug_hess_contract: out of device memory");
+  HIPCHK(c, hipMemcpy(dX, X, (size_t)N * D * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dXq, Xstar, (size_t)M * D * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dmul, mul.data(), (size_t)D * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(ddv, dv.data(), (size_t)D * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dsp, sp.data(), SP_STRIDE * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dal, hal.data(), (size_t)npad * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)npad * D + 255) / 256), 1), dim3(256), 0, st,
+                     (const double*)dX, N, npad, D, (const double*)dmul, (const double*)ddv, xs);
+  std::vector<T> hQ((size_t)npad * mb);
+  std::vector<double> h(hper);
+  for (int q0 = 0; q0 < M; q0 += mb) {
+    const int mq = std::min(mb, M - q0);
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mb * D + 255) / 256), 1), dim3(256), 0, st,
+                       (const double*)(dXq + (size_t)q0 * D), mq, mb, D, (const double*)dmul, (const double*)ddv, xss);
+    if (Qd) {
+      std::fill(hQ.begin(), hQ.end(), (T)0);
+      for (int i = 0; i < N; ++i)
+        for (int jj = 0; jj < mq; ++jj) hQ[(size_t)i * mb + jj] = (T)Qd[(size_t)i * M + q0 + jj];
+      HIPCHK(c, hipMemcpy(dQ, hQ.data(), hQ.size() * sizeof(T), hipMemcpyHostToDevice));
+      GPC_COV_DISPATCH(hess_tile_kernel, T, cd, dim3(mb / CT, npad / CT, 1), dim3(256), 0, st, cd, (const double*)xs,
+                       (const double*)xss, (const double*)dsp, (const double*)dal, npad, (const T*)dQ,
+                       (long long)npad * mb, mb, 1, N, npad, mq, mb, part);
+    } else {
+      GPC_COV_DISPATCH(hess_tile_mean_kernel, T, cd, dim3(mb / CT, npad / CT, 1), dim3(256), 0, st, cd, (const double*)xs,
+                       (const double*)xss, (const double*)dsp, (const double*)dal, npad, N, npad, mq, mb, part);
+    }
+    hipLaunchKernelGGL(colpart_reduce_kernel, dim3((unsigned)((hper + 255) / 256), 1), dim3(256), 0, st,
+                       (const double*)part, nt64, (int)hper, sums);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h.data(), sums, hper * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (int jj = 0; jj < mq; ++jj)
+      for (int p = 0; p < npl; ++p) {
+        out_a[(size_t)(q0 + jj) * npl + p] = h[(size_t)p * mb + jj];
+        if (Qd) out_q[(size_t)(q0 + jj) * npl + p] = h[(size_t)(npl + p) * mb + jj];
+      }
+  }
   return 0;
 }
 }  // namespace
@@ -5664,6 +5915,24 @@ int gpc_grad_post(gpc_post* po, const double* xstar, int M, int diag_only, doubl
                               : grad_post_impl<float>(po, xstar, M, diag_only != 0, fmu, dfmu, cov);
 }
 
+int gpc_predict_hess(gpc_post* po, const double* xstar, int M, int compute_var, double* fmu, double* fs2, double* dfmu,
+                     double* dfs2, double* hmu, double* hs2) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  const bool var = compute_var != 0;
+  if (!xstar || !fmu || !dfmu || !hmu || (var && (!fs2 || !dfs2 || !hs2)) || M <= 0)
+    FAIL(c, "gpc_predict_hess: bad arguments");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_predict_hess: this posterior was built from caller-provided K; a caller-provided kernel has no "
+            "derivative with respect to x*");
+  if ((po->cd.kind == K_MATERN || po->cd.kind == K_MATERN_ISO) && po->cd.degree == 1)
+    FAIL(c, "gpc_predict_hess: the Matern kernel of degree 1 has no second derivative with respect to x*");
+  if (int rc = require_factorized(po, "gpc_predict_hess")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? hess_impl<double>(po, xstar, M, var, fmu, fs2, dfmu, dfs2, hmu, hs2)
+                              : hess_impl<float>(po, xstar, M, var, fmu, fs2, dfmu, dfs2, hmu, hs2);
+}
+
 int gpc_draw(gpc_post* po, const double* xstar, int M, int R, unsigned long long seed, int s_offset,
              const double* noise_sd, double* f, double* tau) {
   if (!po) return -2;
@@ -5993,6 +6262,7 @@ const Option OPTIONS[] = {
     {"small_timing", GPC_GET(c->small_timing), GPC_SET(c->small_timing = v != 0)},  // 1: one-leaf evaluations record their timing events (gpc_last_timing is 0 for them otherwise)
     {"small_polled", GPC_COUNTER(small_polled)},  // one-leaf calls completed by the polled word ...
     {"small_synced", GPC_COUNTER(small_synced)},  // ... and by a stream synchronisation
+    {"hess_contract_us", GPC_COUNTER(hess_contract_us)},  // device time of the contraction passes (kernel + reduction) of the last gpc_predict_hess (timed calls only)
     {"grad_post_gram_us", GPC_COUNTER(grad_post_gram_us)},  // device time of the Gram passes of the last gpc_grad_post (timed calls only)
     {"cov_fused", GPC_COUNTER(cov_fused)},        // gpc_predict_cov calls reduced in the product's epilogue
     {"quad_mix_gemms", GPC_COUNTER(quad_mix_gemms)},  // MFMA GEMM launches inside gpc_quad_mix
@@ -6287,6 +6557,25 @@ int gpc_debug_block_gram(gpc_ctx* c, int dtype, int n, int M, int Dp, const doub
   HIPCHK(c, hipSetDevice(c->device));
   return dtype == GPC_F64 ? debug_block_gram_impl<double>(c, n, M, Dp, Y, Z, diag_only != 0, out)
                           : debug_block_gram_impl<float>(c, n, M, Dp, Y, Z, diag_only != 0, out);
+}
+
+int gpc_debug_hess_contract(gpc_ctx* c, int kernel_id, int degree, int dtype, const double* hyp_cov, const double* X, int N,
+                            int D, const double* xstar, int M, const double* alpha, const double* Q, double* out_alpha,
+                            double* out_q) {
+  if (!c) return -2;
+  if (!valid_kernel(kernel_id, degree) || !hyp_cov || !X || N <= 0 || D <= 0 || !xstar || M <= 0 || !alpha || !out_alpha ||
+      (Q && !out_q) || (dtype != GPC_F64 && dtype != GPC_F32))
+    FAIL(c, "gpc_debug_hess_contract: bad arguments");
+  if ((kernel_id == K_MATERN || kernel_id == K_MATERN_ISO) && degree == 1)
+    FAIL(c, "gpc_debug_hess_contract: the Matern kernel of degree 1 has no second derivative with respect to x*");
+  HIPCHK(c, hipSetDevice(c->device));
+  CovDesc cd;
+  cd.kind = kernel_id;
+  cd.degree = degree;
+  cd.D = D;
+  cd.cov_N = cov_count_of(kernel_id, D);
+  return dtype == GPC_F64 ? debug_hess_impl<double>(c, cd, hyp_cov, X, N, xstar, M, alpha, Q, out_alpha, out_q)
+                          : debug_hess_impl<float>(c, cd, hyp_cov, X, N, xstar, M, alpha, Q, out_alpha, out_q);
 }
 
 // Debug: a 64-bit hash (sum of the bit patterns, wrapping) of every 128 x 128 tile of one workspace matrix of the LAST call

@@ -1628,6 +1628,90 @@ class GP:
         return _gpm.mix_diag(mean, C) if diag else _gpm.mix(mean, C)
 
     @_on_device
+    def predict_hess(self, x_star, compute_var: bool = True, separate_samples: bool = False):
+        """``predict_grad``'s (mu, s2, dmu, ds2) at ``x_star`` and the Hessians of the predictive mean and variance
+        with respect to ``x_star``: (mu, s2, dmu, ds2, Hmu, Hs2), shapes (M,), (M,), (M, D), (M, D), (M, D, D),
+        (M, D, D); ``separate_samples`` adds a trailing axis S.  Entry [j, a, b] is the second derivative with respect
+        to x_star[j, a] and x_star[j, b]; every matrix is symmetric to the bit.  With ``compute_var=False`` the three
+        variance entries are None and no product with the factors is launched (the mean Hessian is one pass over the
+        pairs).
+
+        mu, s2, dmu, ds2 follow ``predict_grad``'s conventions (no noise): the stock mean functions, the clamp
+        s2 = max(s2, 0), a zero variance gradient where the clamp holds -- and there Hs2 is 0 as well.  Without
+        ``separate_samples`` the moments of the equal-weight mixture are differentiated (``predict``'s convention,
+        spread with divisor S - 1): Hmu is the mean of the per-sample Hessians, Hs2 the mean of theirs plus
+        2 / (S - 1) sum_s [(dmu_s - dmu)(dmu_s - dmu)^T + (mu_s - mu)(Hmu_s - Hmu)].
+
+        With data everything but the mean function runs on the device (gpc_predict_hess); a GP without data returns
+        the prior: the mean function's Hessian and Hs2 = 0.  Built-in covariance functions and stock mean functions
+        only (NotImplementedError otherwise); the Matern kernel of degree 1 has no second derivative and is refused.
+        Under sharding each rank computes its samples and the results are gathered: the same values as one process."""
+        from . import _hess as _hm
+
+        x_star, _, _ = self._convert_shapes(x_star, None, None)
+        if not self._builtin:
+            raise NotImplementedError(f"predict_hess: the covariance function {self.covariance!r} is user-defined; it "
+                                      "has no derivative with respect to x_star")
+        kid, degree = self._kid()
+        _hm.check_kind(kid, degree)
+        var = bool(compute_var)
+        s_N = self.posteriors.size
+        M, D = x_star.shape
+        cov_N, noise_N, mean_N = self._counts()
+        hyps = [self.posteriors[s].hyp for s in range(s_N)]
+        h_mean = [h[cov_N + noise_N:cov_N + noise_N + mean_N] for h in hyps]
+        dmu = np.stack([_mean_grad_x(self.mean, hm, x_star, "predict_hess") for hm in h_mean], axis=2)
+        Hmu = np.stack([_hm.mean_hess(self.mean, hm, x_star) for hm in h_mean], axis=3)
+        mu = np.stack([np.reshape(self.mean.compute(hm, x_star), (-1,)) for hm in h_mean], axis=1)
+        s2 = ds2 = Hs2 = None
+        if self.y is None:  # no data: the prior, whose variance is constant for stationary kernels
+            if var:
+                s2 = np.stack([self.covariance.compute(h[0:cov_N], x_star, compute_diag=True)[:, 0] for h in hyps], axis=1)
+                ds2, Hs2 = np.zeros((M, D, s_N)), np.zeros((M, D, D, s_N))
+        else:
+            self._restore()
+            if self._post_handle is None and self._post_range is None:
+                raise ValueError("posteriors have been cleaned; call update() first")
+            self._ctx()
+            local_posts, _ = self._local_posteriors()
+            nd, ndd = M * D, M * D * D
+            per = (M + nd + ndd) * (2 if var else 1)
+            if not local_posts:
+                rows = np.zeros((per, 0))
+            else:
+                fmu, fs2, dfmu, dfs2, hmu, hs2 = self._post_handle.predict_hess(x_star, var)
+                k = fmu.shape[1]
+                parts = [fmu, dfmu.reshape(nd, k), hmu.reshape(ndd, k)]
+                if var:
+                    parts += [fs2, dfs2.reshape(nd, k), hs2.reshape(ndd, k)]
+                rows = np.concatenate(parts, axis=0)
+            if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
+                rows = self._gather_samples(rows, x_star, np.array([float(var)]))
+            mu = mu + rows[:M]
+            dmu = dmu + rows[M:M + nd].reshape(M, D, -1)
+            Hmu = Hmu + rows[M + nd:M + nd + ndd].reshape(M, D, D, -1)
+            if var:
+                o = M + nd + ndd
+                s2 = rows[o:o + M]
+                ds2 = rows[o + M:o + M + nd].reshape(M, D, -1)
+                Hs2 = rows[o + M + nd:].reshape(M, D, D, -1)
+        if var:
+            # the clamp of predict, s2 = max(s2, 0): neither gradient nor curvature where it holds s2 at 0
+            held = s2 <= 0
+            s2 = np.maximum(s2, 0)
+            ds2 = np.where(held[:, None, :], 0.0, ds2)
+            Hs2 = np.where(held[:, None, None, :], 0.0, Hs2)
+        if separate_samples:
+            return mu, s2, dmu, ds2, Hmu, Hs2
+        Hmu_m, Hs2_m = _hm.mix(mu, dmu, Hmu, Hs2)
+        if var:
+            dmu_m, ds2_m = _mix_sample_grads(mu, dmu, ds2)
+        else:
+            dmu_m, ds2_m = np.sum(dmu, 2) / s_N, None
+        mu_m, s2_m, _ = _mix_samples(mu, s2)
+        return np.reshape(mu_m, (-1,)), None if s2_m is None else np.reshape(s2_m, (-1,)), dmu_m, ds2_m, Hmu_m, Hs2_m
+
+    @_on_device
     def predict_full(self, x_star, y_star=None, s2_star=None, add_noise: bool = False):
         """Posterior mean and FULL covariance per hyperparameter sample (reference :1561-1661):
         mu (M, S), cov (M, M, S).  K**, Ks, V = L^-T Ks and K** - V^T V are device products."""

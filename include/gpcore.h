@@ -177,6 +177,27 @@ int gpc_predict_grad(gpc_post* post, const double* xstar, int M, double* fmu, do
  * the bytes).  gpc_last_timing: ms_total = the device sections, ms_factor = the products with W (or L).               */
 int gpc_grad_post(gpc_post* post, const double* xstar, int M, int diag_only, double* fmu, double* dfmu, double* cov);
 
+/* ---- GP.predict_hess: Hessians of the predictive mean and variance with respect to x*, per sample ------------------
+ * With d = xs*_j - xs_i, r2 = |d|^2, F and c_l of gpc_predict_grad and the second radial factor G = -2 dF/d(r2)
+ * (SE: K; Matern 3: e / t; Matern 5: e / 3, e = sf2 exp(-t), t = sqrt(r2); RQ: (alpha + 1) / alpha F / m),
+ *   d^2 k / dx*_a dx*_b = c_a c_b (G d_a d_b - F delta_ab),
+ *   hmu[((j*D + a)*D + b)*S + s] = c_a c_b ( sum_i alpha_i G_ij d_a d_b - delta_ab sum_i alpha_i F_ij )
+ *   hs2[((j*D + a)*D + b)*S + s] = -2 ( P_j[a, b] + c_a c_b ( sum_i Q_ij G_ij d_a d_b - delta_ab sum_i Q_ij F_ij ) )
+ *   P_j[a, b] = (d_a k*)^T (K + Sigma)^-1 (d_b k*): the derivative block of gpc_grad_post's Gram matrix,
+ * Q = (K + Sigma)^-1 k* as gpc_predict_grad forms it.  A pair at r2 = 0 contributes 0 to the G term (its limit, also
+ * where G is infinite) and its full F(0) to the diagonal term.  fmu, fs2, dfmu, dfs2 are laid out as gpc_predict_grad's
+ * and come from the operand panel and the Gram matrix of gpc_grad_post (they agree with gpc_predict_grad's to
+ * rounding, not to the bit).  Every matrix is symmetric to the bit (the lower triangle is computed and mirrored);
+ * results are unclamped, without noise or mean function.  Queries are worked on in blocks of 128 whatever the memory
+ * budget, which decides the samples per chunk only: a sample's results do not depend on it.
+ * compute_var == 0: no product with W or L is launched; fs2, dfs2, hs2 may be NULL and are not written; fmu, dfmu and
+ * hmu carry the same bits as with the variance; gpc_last_timing's ms_factor is 0.
+ * Returns -2 with a message of its own for: bad arguments; a posterior from caller-provided K; the Matern kernel of
+ * degree 1 (no second derivative); a posterior that holds a failed factorization; one sample with one query block
+ * exceeding the budget (the message names N_pad, D, the block size and the bytes).                                   */
+int gpc_predict_hess(gpc_post* post, const double* xstar, int M, int compute_var, double* fmu, double* fs2, double* dfmu,
+                     double* dfs2, double* hmu, double* hs2);
+
 /* ---- GP.draw_functions: joint posterior draws, n_draws per sample (extends gaussian_process.py:2241-2329) ----
  * For every sample s of the posterior (global index s_offset + s), draw r < R and query point j < M:
  *   f[(j*R + r)*S + s] = fmu_js + (L_s z_{s,r})_j  (+ noise_sd[j*S + s] z'_{s,r,j})
@@ -522,6 +543,14 @@ int gpc_debug_cov(gpc_ctx* ctx, int which, int kernel_id, int degree, int dtype,
  * diag_only != 0: out[j][a] = sum_i Y[i][a][j] Z[i][a][j].                                                            */
 int gpc_debug_block_gram(gpc_ctx* ctx, int dtype, int n, int M, int Dp, const double* Y, const double* Z, int diag_only,
                          double* out);
+
+/* gpc_predict_hess's contraction kernel on caller-provided weights, one launch per block of 128 queries as the product
+ * path launches it (inputs scaled from hyp_cov as in gpc_debug_cov; Q stored in `dtype`).  With P = 1 + D (D + 1) / 2:
+ *   out_alpha[j][0] = sum_i alpha_i F_ij,   out_alpha[j][1 + a (a + 1) / 2 + b] = sum_i alpha_i G_ij d_a d_b  (a >= b)
+ *   out_q[j][.]     = the same with the weights Q[i][j] (dense N x M; optional: NULL runs the kernel of the mean alone)  */
+int gpc_debug_hess_contract(gpc_ctx* ctx, int kernel_id, int degree, int dtype, const double* hyp_cov, const double* X,
+                            int N, int D, const double* xstar, int M, const double* alpha, const double* Q,
+                            double* out_alpha, double* out_q);
 
 /* Debug: wrapping-sum hash of every 128 x 128 tile of one workspace matrix as the LAST call left it (which: 0 = A, 1 = W,
  * 2 = T; sample: position in the last chunk); out[(npad/128)^2].  Finds the tile where two schedules differ.          */
