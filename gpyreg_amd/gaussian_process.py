@@ -214,6 +214,17 @@ def _mean_grad_x(mean, hyp, X, who="predict_grad"):
                               "gradient with respect to x_star is unknown")
 
 
+def _mean_hyp(hyp, counts):
+    """The mean function's hyperparameters in a sample's vector (or in the rows of a batch); counts = GP._counts()."""
+    cov_N, noise_N, mean_N = counts
+    return hyp[..., cov_N + noise_N:cov_N + noise_N + mean_N]
+
+
+def _sn2_mult(post):
+    """A posterior record's noise multiplier; 1 for a record that never had one (no data, or cleaned)."""
+    return 1 if post.sn2_mult is None else post.sn2_mult
+
+
 class PosteriorPaths:
     """``GP.sample_paths``' result: ``n_paths`` sampled posterior FUNCTIONS per hyperparameter sample, evaluable --
     with their gradient -- at any points, any number of times (``_paths`` has the formulas).  ``paths(x_star)`` returns
@@ -239,9 +250,9 @@ class PosteriorPaths:
         if x_star.ndim != 2 or x_star.shape[1] != self._D:
             raise ValueError(f"x_star must be (M, {self._D}), got {x_star.shape}")
         M, D, R = x_star.shape[0], self._D, self.n_paths
-        cov_N, noise_N, mean_N = self._counts
+        cov_N = self._counts[0]
         S = len(self._hyps)
-        h_mean = [h[cov_N + noise_N:cov_N + noise_N + mean_N] for h in self._hyps]
+        h_mean = [_mean_hyp(h, self._counts) for h in self._hyps]
         dm = [_mean_grad_x(self._mean, h, x_star) for h in h_mean] if compute_grad else None
         if self._host is not None:  # a GP without data: prior paths (v = 0) on the host
             f = np.empty((M, R, S))
@@ -466,9 +477,10 @@ class GP:
         object with the reference's protocol is called once per sample through its own ``compute``."""
         from .mean_functions import ConstantMean, NegativeQuadratic, ZeroMean
 
-        cov_N, noise_N, mean_N = self._counts()
+        counts = self._counts()
+        mean_N = counts[2]
         S, N = hyp.shape[0], self.X.shape[0]
-        h_mean = hyp[:, cov_N + noise_N:cov_N + noise_N + mean_N]
+        h_mean = _mean_hyp(hyp, counts)
         dm = None
         if type(self.mean) in (ZeroMean, ConstantMean, NegativeQuadratic):
             m = self.mean.values(h_mean, self.X, grad)
@@ -1107,14 +1119,14 @@ class GP:
         a user-defined object -- it supplies its own, like the reference's rank-one path does whatever the object is
         (gaussian_process.py:771-772).  One new row: scalars per sample (``append`` / ``append_K``); k rows: k-vectors
         and, for an object, Ks (S, n, k) and Kss (S, k, k) (``append_block`` / ``append_block_K``)."""
-        cov_N, noise_N, mean_N = self._counts()
+        cov_N, noise_N, _ = counts = self._counts()
         k = X_new.shape[0]
         one = k == 1
         m_star, sn2_star, Ks, kss = [], [], [], []
         for p in local_posts:
             h = p.hyp
             sn2_star.append(float(self.noise.compute(h[cov_N:cov_N + noise_N], X_new, y_new, 0)))
-            m_new = np.ravel(self.mean.compute(h[cov_N + noise_N:cov_N + noise_N + mean_N], X_new))
+            m_new = np.ravel(self.mean.compute(_mean_hyp(h, counts), X_new))
             m_star.append(float(m_new[0]) if one else np.array(m_new, dtype=float))
             if not self._builtin:
                 cross = np.asarray(self.covariance.compute(h[0:cov_N], self.X, X_new), dtype=float)
@@ -1244,6 +1256,47 @@ class GP:
                                   _sh.fingerprint(*args))
         return full.T.copy()
 
+    def _require_posteriors(self):
+        """Every posterior consumer's first step: rebuild a copied GP's device posteriors, refuse a cleaned GP."""
+        self._restore()
+        if self._post_handle is None and self._post_range is None:
+            raise ValueError("posteriors have been cleaned; call update() first")
+
+    def _device_rows(self, call, layout, *key):
+        """The per-sample row protocol of every posterior consumer: {name: array, all S samples on the last axis}.
+
+        ``layout``: the ordered (name, shape) pairs of what the consumer computes per sample, shape without the
+        sample axis -- (), (M,), (M, D), (M, D, D) ...; an output that a flag switches off is simply not listed.
+        ``call(handle, local_posts, lo)`` runs only on a rank that holds samples and returns the arrays in the
+        layout's order, sample axis last, for this rank's samples (global indices lo, lo + 1, ...); per-sample
+        fix-ups of the local block belong inside it.  A rank without a sample contributes shape + (0,) zeros.
+        Unsharded, what ``call`` returned is handed on as it is.  Sharded, the fields are stacked to (R, k) rows,
+        exchanged in ONE all-gather and split again by the layout; ``key`` holds the arguments every rank must have
+        passed identically (``ShardError`` otherwise)."""
+        self._require_posteriors()
+        self._ctx()
+        local_posts, lo = self._local_posteriors()
+        names = [n for n, _ in layout]
+        if local_posts:
+            fields = call(self._post_handle, local_posts, lo)
+        else:
+            fields = [np.zeros(tuple(shape) + (0,)) for _, shape in layout]
+        if len(fields) != len(layout):
+            raise ValueError(f"_device_rows: the call returned {len(fields)} arrays for the {len(layout)} of {names}")
+        if self._post_range is None:
+            return dict(zip(names, fields))
+        k = len(local_posts)
+        heights = [math.prod(shape) for _, shape in layout]
+        rows = np.concatenate([np.reshape(f, (h, k)) for f, h in zip(fields, heights)], axis=0)
+        rows = self._gather_samples(rows, *key)
+        S, ends = rows.shape[1], np.cumsum(heights)
+        return {n: rows[e - h:e].reshape(tuple(shape) + (S,)) for (n, shape), h, e in zip(layout, heights, ends)}
+
+    def _noise_star(self, post, x_star, y_star, s2_star):
+        """A sample's predictive noise at ``x_star``: the noise function's value times the record's multiplier."""
+        cov_N, noise_N, _ = self._counts()
+        return self.noise.compute(post.hyp[cov_N:cov_N + noise_N], x_star, y_star, s2_star) * _sn2_mult(post)
+
     def _drop_handle(self):
         self._rebuild = False
         if self._post_handle is not None:
@@ -1341,38 +1394,30 @@ class GP:
         x_star, y_star, s2_star = self._convert_shapes(x_star, y_star, s2_star)
         s_N = self.posteriors.size
         N_star, D = x_star.shape
-        cov_N, noise_N, mean_N = self._counts()
+        cov_N, _, _ = counts = self._counts()
         if return_lpd and y_star is None:
             raise ValueError("Cannot calculate log predictive density without y_star.")
 
         mu = np.zeros((N_star, s_N))
         s2 = np.zeros((N_star, s_N))
         if self.y is not None:
-            self._restore()
-            if self._post_handle is None and self._post_range is None:
-                raise ValueError("posteriors have been cleaned; call update() first")
-            self._ctx()
-            local_posts, _ = self._local_posteriors()
-            if not local_posts:
-                fmu = fs2 = np.zeros((N_star, 0))
-            elif self._builtin:
-                fmu, fs2 = self._post_handle.predict(x_star)
-            else:  # user-defined kernel: its own cross covariances, the solves on the device
+            def call(handle, local_posts, lo):
+                if self._builtin:
+                    return handle.predict(x_star)
+                # user-defined kernel: its own cross covariances, the solves on the device
                 Ks = np.stack([self.covariance.compute(p.hyp[0:cov_N], self.X, x_star) for p in local_posts])
                 kss = np.stack([self.covariance.compute(p.hyp[0:cov_N], x_star, compute_diag=True)[:, 0]
                                 for p in local_posts], axis=1)
-                fmu, fq, _ = self._post_handle.predict_K(Ks)
-                fs2 = kss + fq
-            if self._post_range is not None:  # each rank predicted its block of samples: one all-gather
-                both = self._gather_samples(np.concatenate([fmu, fs2], axis=0), x_star)
-                fmu, fs2 = both[:N_star], both[N_star:]
+                fmu, fq, _ = handle.predict_K(Ks)
+                return fmu, kss + fq
+
+            fmu, fs2 = self._device_rows(call, [("fmu", (N_star,)), ("fs2", (N_star,))], x_star).values()
         y_s2 = np.zeros((N_star, s_N)) if (return_lpd or add_noise) else None
         lpd = np.zeros((N_star, s_N)) if (return_lpd and separate_samples) else None
 
         for s in range(s_N):
             hyp = self.posteriors[s].hyp
-            m_star = np.reshape(
-                self.mean.compute(hyp[cov_N + noise_N:cov_N + noise_N + mean_N], x_star), (-1,))
+            m_star = np.reshape(self.mean.compute(_mean_hyp(hyp, counts), x_star), (-1,))
             if self.y is not None:
                 mu[:, s] = m_star + fmu[:, s]
                 s2[:, s] = fs2[:, s]
@@ -1381,11 +1426,7 @@ class GP:
                 s2[:, s] = self.covariance.compute(hyp[0:cov_N], x_star, compute_diag=True)[:, 0]
             s2[:, s] = np.maximum(s2[:, s], 0)  # :1770
             if return_lpd or add_noise:
-                sn2_mult = self.posteriors[s].sn2_mult
-                if sn2_mult is None:
-                    sn2_mult = 1
-                sn2_star = self.noise.compute(hyp[cov_N:cov_N + noise_N], x_star, y_star, s2_star)
-                y_s2[:, s:s + 1] = s2[:, s:s + 1] + sn2_star * sn2_mult
+                y_s2[:, s:s + 1] = s2[:, s:s + 1] + self._noise_star(self.posteriors[s], x_star, y_star, s2_star)
             if return_lpd and separate_samples:
                 lpd[:, s:s + 1] = -0.5 * (y_star - mu[:, s:s + 1]) ** 2 / y_s2[:, s:s + 1] \
                     - 0.5 * np.log(2 * np.pi * y_s2[:, s:s + 1])
@@ -1429,20 +1470,10 @@ class GP:
         fl = _cv_folds(folds, N)
         F = N if fl is None else len(fl)
         s_N = self.posteriors.size
-        self._restore()
-        if self._post_handle is None and self._post_range is None:
-            raise ValueError("posteriors have been cleaned; call update() first")
-        self._ctx()
-        local_posts, _ = self._local_posteriors()
-        if not local_posts:
-            rows = np.zeros((2 * N + 3 * F, 0))
-        else:
-            rows = np.concatenate([np.asarray(r, dtype=float) for r in self._post_handle.cv(fl)], axis=0)
-        if self._post_range is not None:  # each rank has its block of samples: one all-gather
-            key = np.zeros(0) if fl is None else np.concatenate([np.r_[-1, f] for f in fl]).astype(float)
-            rows = self._gather_samples(rows, key)
-        dmu, s2n = rows[:N], rows[N:2 * N]
-        quad, logdet, info = rows[2 * N:2 * N + F], rows[2 * N + F:2 * N + 2 * F], rows[2 * N + 2 * F:]
+        key = np.zeros(0) if fl is None else np.concatenate([np.r_[-1, f] for f in fl]).astype(float)
+        dmu, s2n, quad, logdet, info = self._device_rows(
+            lambda handle, local_posts, lo: [np.asarray(a, dtype=float) for a in handle.cv(fl)],
+            [("dmu", (N,)), ("s2n", (N,)), ("quad", (F,)), ("logdet", (F,)), ("info", (F,))], key).values()
         bad = np.argwhere(info != 0)
         if bad.size:
             f, s = bad[0]
@@ -1451,7 +1482,7 @@ class GP:
                           RuntimeWarning, stacklevel=2)
         hyp = np.stack([p.hyp for p in self.posteriors])
         sn2, _, _ = self._noise_values(hyp, False)
-        mult = np.array([1.0 if p.sn2_mult is None else float(p.sn2_mult) for p in self.posteriors])
+        mult = np.array([float(_sn2_mult(p)) for p in self.posteriors])
         noise = (np.broadcast_to(np.asarray(sn2, dtype=float).reshape(s_N, -1), (s_N, N)) * mult[:, None]).T
         y = np.reshape(self.y, (-1, 1))
         mu = y - dmu
@@ -1496,40 +1527,23 @@ class GP:
                                       "needs noise that does not depend on x_star")
         s_N = self.posteriors.size
         N_star, D = x_star.shape
-        cov_N, noise_N, mean_N = self._counts()
+        cov_N, _, _ = counts = self._counts()
         hyps = [self.posteriors[s].hyp for s in range(s_N)]
-        dm = np.stack([_mean_grad_x(self.mean, h[cov_N + noise_N:cov_N + noise_N + mean_N], x_star) for h in hyps],
-                      axis=2)
+        dm = np.stack([_mean_grad_x(self.mean, _mean_hyp(h, counts), x_star) for h in hyps], axis=2)
 
         mu = np.zeros((N_star, s_N))
         s2 = np.zeros((N_star, s_N))
         dmu, ds2 = dm, np.zeros((N_star, D, s_N))
         if self.y is not None:
-            self._restore()
-            if self._post_handle is None and self._post_range is None:
-                raise ValueError("posteriors have been cleaned; call update() first")
-            self._ctx()
-            local_posts, _ = self._local_posteriors()
-            if not local_posts:
-                fmu = fs2 = np.zeros((N_star, 0))
-                dfmu = dfs2 = np.zeros((N_star, D, 0))
-            else:
-                fmu, fs2, dfmu, dfs2 = self._post_handle.predict_grad(x_star)
-            if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
-                k = fmu.shape[1]
-                rows = np.concatenate([fmu, fs2, dfmu.reshape(N_star * D, k), dfs2.reshape(N_star * D, k)], axis=0)
-                rows = self._gather_samples(rows, x_star)
-                nd = N_star * D
-                fmu, fs2 = rows[:N_star], rows[N_star:2 * N_star]
-                dfmu = rows[2 * N_star:2 * N_star + nd].reshape(N_star, D, -1)
-                dfs2 = rows[2 * N_star + nd:].reshape(N_star, D, -1)
+            fmu, fs2, dfmu, dfs2 = self._device_rows(
+                lambda handle, local_posts, lo: handle.predict_grad(x_star),
+                [("fmu", (N_star,)), ("fs2", (N_star,)), ("dfmu", (N_star, D)), ("dfs2", (N_star, D))], x_star).values()
             dmu = dm + dfmu
             ds2 = dfs2
         y_s2 = np.zeros((N_star, s_N)) if add_noise else None
         for s in range(s_N):
             hyp = hyps[s]
-            m_star = np.reshape(
-                self.mean.compute(hyp[cov_N + noise_N:cov_N + noise_N + mean_N], x_star), (-1,))
+            m_star = np.reshape(self.mean.compute(_mean_hyp(hyp, counts), x_star), (-1,))
             if self.y is not None:
                 mu[:, s] = m_star + fmu[:, s]
                 s2[:, s] = fs2[:, s]
@@ -1538,11 +1552,7 @@ class GP:
                 s2[:, s] = self.covariance.compute(hyp[0:cov_N], x_star, compute_diag=True)[:, 0]
             s2[:, s] = np.maximum(s2[:, s], 0)
             if add_noise:
-                sn2_mult = self.posteriors[s].sn2_mult
-                if sn2_mult is None:
-                    sn2_mult = 1
-                sn2_star = self.noise.compute(hyp[cov_N:cov_N + noise_N], x_star, y_star, s2_star)
-                y_s2[:, s:s + 1] = s2[:, s:s + 1] + sn2_star * sn2_mult
+                y_s2[:, s:s + 1] = s2[:, s:s + 1] + self._noise_star(self.posteriors[s], x_star, y_star, s2_star)
 
         # the clamp of predict, s2 = max(s2, 0): no variance gradient where it holds s2 at 0 (s2 <= 0 before it; at
         # s2 = 0 exactly the one-sided derivatives differ, and 0 is the one that keeps the floor)
@@ -1590,11 +1600,11 @@ class GP:
         s_N = self.posteriors.size
         M, D = x_star.shape
         P = D + 1
-        cov_N, noise_N, mean_N = self._counts()
+        cov_N, _, _ = counts = self._counts()
         hyps = [self.posteriors[s].hyp for s in range(s_N)]
         mean = np.empty((M, P, s_N))
         for s, h in enumerate(hyps):
-            hm = h[cov_N + noise_N:cov_N + noise_N + mean_N]
+            hm = _mean_hyp(h, counts)
             mean[:, 1:, s] = _mean_grad_x(self.mean, hm, x_star, "gradient_posterior")
             mean[:, 0, s] = np.reshape(self.mean.compute(hm, x_star), (-1,))
         if self.y is None:  # no data: the prior
@@ -1603,23 +1613,12 @@ class GP:
             if not diag:
                 C = np.einsum("mas,ab->mabs", C, np.eye(P))
         else:
-            self._restore()
-            if self._post_handle is None and self._post_range is None:
-                raise ValueError("posteriors have been cleaned; call update() first")
-            self._ctx()
-            local_posts, _ = self._local_posteriors()
-            csz = P if diag else P * P
-            if not local_posts:
-                rows = np.zeros((M * (P + csz), 0))
-            else:
-                fmu, dfmu, fc = self._post_handle.grad_post(x_star, diag)
-                k = fmu.shape[1]
-                rows = np.concatenate([fmu, dfmu.reshape(M * D, k), fc.reshape(M * csz, k)], axis=0)
-            if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
-                rows = self._gather_samples(rows, x_star, np.array([float(diag)]))
-            mean[:, 0, :] += rows[:M]
-            mean[:, 1:, :] += rows[M:M + M * D].reshape(M, D, -1)
-            C = rows[M + M * D:].reshape((M, P, -1) if diag else (M, P, P, -1))
+            fmu, dfmu, C = self._device_rows(
+                lambda handle, local_posts, lo: handle.grad_post(x_star, diag),
+                [("fmu", (M,)), ("dfmu", (M, D)), ("cov", (M, P) if diag else (M, P, P))],
+                x_star, np.array([float(diag)])).values()
+            mean[:, 0, :] += fmu
+            mean[:, 1:, :] += dfmu
         if not with_value:
             mean = mean[:, 1:]
             C = C[:, 1:] if diag else C[:, 1:, 1:]
@@ -1657,9 +1656,9 @@ class GP:
         var = bool(compute_var)
         s_N = self.posteriors.size
         M, D = x_star.shape
-        cov_N, noise_N, mean_N = self._counts()
+        cov_N, _, _ = counts = self._counts()
         hyps = [self.posteriors[s].hyp for s in range(s_N)]
-        h_mean = [h[cov_N + noise_N:cov_N + noise_N + mean_N] for h in hyps]
+        h_mean = [_mean_hyp(h, counts) for h in hyps]
         dmu = np.stack([_mean_grad_x(self.mean, hm, x_star, "predict_hess") for hm in h_mean], axis=2)
         Hmu = np.stack([_hm.mean_hess(self.mean, hm, x_star) for hm in h_mean], axis=3)
         mu = np.stack([np.reshape(self.mean.compute(hm, x_star), (-1,)) for hm in h_mean], axis=1)
@@ -1669,32 +1668,17 @@ class GP:
                 s2 = np.stack([self.covariance.compute(h[0:cov_N], x_star, compute_diag=True)[:, 0] for h in hyps], axis=1)
                 ds2, Hs2 = np.zeros((M, D, s_N)), np.zeros((M, D, D, s_N))
         else:
-            self._restore()
-            if self._post_handle is None and self._post_range is None:
-                raise ValueError("posteriors have been cleaned; call update() first")
-            self._ctx()
-            local_posts, _ = self._local_posteriors()
-            nd, ndd = M * D, M * D * D
-            per = (M + nd + ndd) * (2 if var else 1)
-            if not local_posts:
-                rows = np.zeros((per, 0))
-            else:
-                fmu, fs2, dfmu, dfs2, hmu, hs2 = self._post_handle.predict_hess(x_star, var)
-                k = fmu.shape[1]
-                parts = [fmu, dfmu.reshape(nd, k), hmu.reshape(ndd, k)]
-                if var:
-                    parts += [fs2, dfs2.reshape(nd, k), hs2.reshape(ndd, k)]
-                rows = np.concatenate(parts, axis=0)
-            if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
-                rows = self._gather_samples(rows, x_star, np.array([float(var)]))
-            mu = mu + rows[:M]
-            dmu = dmu + rows[M:M + nd].reshape(M, D, -1)
-            Hmu = Hmu + rows[M + nd:M + nd + ndd].reshape(M, D, D, -1)
+            def call(handle, local_posts, lo):
+                fmu, fs2, dfmu, dfs2, hmu, hs2 = handle.predict_hess(x_star, var)
+                return [fmu, dfmu, hmu] + ([fs2, dfs2, hs2] if var else [])
+
+            layout = [("fmu", (M,)), ("dfmu", (M, D)), ("hmu", (M, D, D))]
             if var:
-                o = M + nd + ndd
-                s2 = rows[o:o + M]
-                ds2 = rows[o + M:o + M + nd].reshape(M, D, -1)
-                Hs2 = rows[o + M + nd:].reshape(M, D, D, -1)
+                layout += [("fs2", (M,)), ("dfs2", (M, D)), ("hs2", (M, D, D))]
+            r = self._device_rows(call, layout, x_star, np.array([float(var)]))
+            mu, dmu, Hmu = mu + r["fmu"], dmu + r["dfmu"], Hmu + r["hmu"]
+            if var:
+                s2, ds2, Hs2 = r["fs2"], r["dfs2"], r["hs2"]
         if var:
             # the clamp of predict, s2 = max(s2, 0): neither gradient nor curvature where it holds s2 at 0
             held = s2 <= 0
@@ -1718,44 +1702,33 @@ class GP:
         x_star, y_star, s2_star = self._convert_shapes(x_star, y_star, s2_star)
         s_N = self.posteriors.size
         N_star, _ = x_star.shape
-        cov_N, noise_N, mean_N = self._counts()
+        cov_N, _, _ = counts = self._counts()
         mu = np.zeros((N_star, s_N))
         cov = np.zeros((s_N, N_star, N_star))
         if self.y is not None:
-            self._restore()
-            if self._post_handle is None and self._post_range is None:
-                raise ValueError("posteriors have been cleaned; call update() first")
-            self._ctx()
-            local_posts, _ = self._local_posteriors()
-            if not local_posts:
-                fmu, fcov = np.zeros((N_star, 0)), np.zeros((0, N_star, N_star))
-            elif self._builtin:
-                fmu, fcov = self._post_handle.predict_full(x_star)
-            else:
-                Ks = np.stack([self.covariance.compute(p.hyp[0:cov_N], self.X, x_star) for p in local_posts])
-                Kss = np.stack([self.covariance.compute(p.hyp[0:cov_N], x_star) for p in local_posts])
-                fmu, _, fcov = self._post_handle.predict_K(Ks, Kss, want_var=False)
-            if self._post_range is not None:
-                both = self._gather_samples(np.concatenate([fmu, fcov.reshape(fcov.shape[0], N_star * N_star).T], axis=0), x_star)
-                fmu, fcov = both[:N_star], both[N_star:].T.reshape(-1, N_star, N_star)
+            def call(handle, local_posts, lo):
+                if self._builtin:
+                    fmu, fcov = handle.predict_full(x_star)
+                else:
+                    Ks = np.stack([self.covariance.compute(p.hyp[0:cov_N], self.X, x_star) for p in local_posts])
+                    Kss = np.stack([self.covariance.compute(p.hyp[0:cov_N], x_star) for p in local_posts])
+                    fmu, _, fcov = handle.predict_K(Ks, Kss, want_var=False)
+                return fmu, fcov.transpose(1, 2, 0)  # (the device's covariances are sample-first)
+
+            fmu, fcov = self._device_rows(call, [("fmu", (N_star,)), ("fcov", (N_star, N_star))], x_star).values()
         for s in range(s_N):
             hyp = self.posteriors[s].hyp
-            m_star = np.reshape(
-                self.mean.compute(hyp[cov_N + noise_N:cov_N + noise_N + mean_N], x_star), (-1,))
+            m_star = np.reshape(self.mean.compute(_mean_hyp(hyp, counts), x_star), (-1,))
             if self.y is None:  # no data: the prior
                 mu[:, s] = m_star
                 C = self.covariance.compute(hyp[0:cov_N], x_star)
             else:
                 mu[:, s] = m_star + fmu[:, s]
-                C = fcov[s]
+                C = fcov[:, :, s]
             C = (C + C.T) / 2  # :1647
             cov[s, :, :] = C
-            if add_noise:
-                sn2_mult = self.posteriors[s].sn2_mult
-                if sn2_mult is None:
-                    sn2_mult = 1
-                sn2_star = self.noise.compute(hyp[cov_N:cov_N + noise_N], x_star, y_star, s2_star)
-                cov[s, :, :] += np.dot(np.eye(N_star), sn2_star) * sn2_mult  # :1659, verbatim semantics
+            if add_noise:  # :1659, verbatim semantics
+                cov[s, :, :] += np.dot(np.eye(N_star), self._noise_star(self.posteriors[s], x_star, y_star, s2_star))
         return mu, cov.transpose(1, 2, 0)
 
     def predict_cov(self, x_a, x_b):
@@ -1806,7 +1779,7 @@ class GP:
         x_ref, _, _ = self._convert_shapes(x_ref, None, None)
         s_N = self.posteriors.size
         Mc, Mr = x_cand.shape[0], x_ref.shape[0]
-        cov_N, noise_N, _ = self._counts()
+        cov_N = self._counts()[0]
         if weights is None:
             w = np.full(Mr, 1.0 / Mr)
         else:
@@ -1827,11 +1800,8 @@ class GP:
         else:
             _, wsq, fs2 = self._cov_on_device(x_ref, x_cand, w)
         den = np.empty((Mc, s_N))
-        for s in range(s_N):
-            post = self.posteriors[s]
-            sn2_mult = 1 if post.sn2_mult is None else post.sn2_mult
-            sn2 = self.noise.compute(post.hyp[cov_N:cov_N + noise_N], x_cand, y_cand, s2_cand)
-            den[:, s:s + 1] = np.maximum(fs2[:, s:s + 1], 0) + sn2 * sn2_mult
+        for s, post in enumerate(self.posteriors):
+            den[:, s:s + 1] = np.maximum(fs2[:, s:s + 1], 0) + self._noise_star(post, x_cand, y_cand, s2_cand)
         red = np.where(den > 0, wsq / np.where(den > 0, den, 1.0), 0.0)
         if not separate_samples:
             red = np.reshape(np.sum(red, 1) / s_N, (-1, 1))
@@ -1842,24 +1812,16 @@ class GP:
         """The device part of ``predict_cov`` (weights None: (cov (Ma, Mb, S), None, None)) and ``lookahead_variance``
         ((None, wsq (Mb, S), fs2 of x_b (Mb, S))), gathered over the ranks when sharded."""
         Ma, Mb = x_a.shape[0], x_b.shape[0]
-        self._restore()
-        if self._post_handle is None and self._post_range is None:
-            raise ValueError("posteriors have been cleaned; call update() first")
-        self._ctx()
-        local_posts, lo = self._local_posteriors()
-        k = len(local_posts)
         want_cov = weights is None
-        if not local_posts:
-            rows = np.zeros((Ma * Mb if want_cov else 2 * Mb, 0))
-        else:
-            w = weights[:, lo:lo + k] if (weights is not None and weights.ndim == 2) else weights
-            cov, wsq, fs2 = self._post_handle.predict_cov(x_a, x_b, w, want_cov=want_cov, want_fs2=not want_cov)
-            rows = cov.reshape(k, Ma * Mb).T if want_cov else np.concatenate([wsq, fs2], axis=0)
-        if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
-            rows = self._gather_samples(rows, x_a, x_b, np.zeros(0) if weights is None else weights)
-        if want_cov:
-            return rows.reshape(Ma, Mb, -1), None, None
-        return None, rows[:Mb], rows[Mb:]
+
+        def call(handle, local_posts, lo):
+            w = weights[:, lo:lo + len(local_posts)] if (weights is not None and weights.ndim == 2) else weights
+            cov, wsq, fs2 = handle.predict_cov(x_a, x_b, w, want_cov=want_cov, want_fs2=not want_cov)
+            return [cov.transpose(1, 2, 0)] if want_cov else [wsq, fs2]  # (the device's covariance is sample-first)
+
+        r = self._device_rows(call, [("cov", (Ma, Mb))] if want_cov else [("wsq", (Mb,)), ("fs2", (Mb,))],
+                              x_a, x_b, np.zeros(0) if weights is None else weights)
+        return r.get("cov"), r.get("wsq"), r.get("fs2")
 
     def random_function(self, X_star, add_noise: bool = False):
         """One function drawn from the GP at ``X_star`` (reference :2241-2329): a hyperparameter sample is picked
@@ -1881,8 +1843,7 @@ class GP:
         cov_N, noise_N, _ = self._counts()
         post = self.posteriors[s]
         sn2 = self.noise.compute(post.hyp[cov_N:cov_N + noise_N], X_star, None, None)
-        mult = getattr(post, "sn2_mult", None)
-        return f_star + np.sqrt(sn2 * (1 if mult is None else mult)) * np.random.standard_normal(size=f_mu.shape)
+        return f_star + np.sqrt(sn2 * _sn2_mult(post)) * np.random.standard_normal(size=f_mu.shape)
 
     def draw_functions(self, x_star, n_draws: int = 1, add_noise: bool = False, seed: int = 0, y_star=None,
                        s2_star=None, return_jitter: bool = False):
@@ -1911,16 +1872,15 @@ class GP:
         x_star, y_star, s2_star = self._convert_shapes(x_star, y_star, s2_star)
         s_N = self.posteriors.size
         M = x_star.shape[0]
-        cov_N, noise_N, mean_N = self._counts()
+        cov_N, noise_N, _ = counts = self._counts()
         hyps = [self.posteriors[s].hyp for s in range(s_N)]
         nsd = None
         if add_noise:
             nsd = np.empty((M, s_N))
             for s in range(s_N):
-                mult = self.posteriors[s].sn2_mult
                 sn2 = np.asarray(self.noise.compute(hyps[s][cov_N:cov_N + noise_N], x_star, y_star, s2_star), float)
                 sn2 = np.broadcast_to(sn2.reshape(-1) if sn2.size == M else sn2.reshape(-1)[:1], (M,))
-                nsd[:, s] = np.sqrt(sn2 * (1 if mult is None else mult))
+                nsd[:, s] = np.sqrt(sn2 * _sn2_mult(self.posteriors[s]))
 
         if self.y is not None:
             f, tau = self._draw_on_device(x_star, n_draws, seed, nsd)
@@ -1935,7 +1895,7 @@ class GP:
                 if add_noise:
                     f[:, :, s] += nsd[:, s:s + 1] * _philox.normals_block(seed, 1, M, n_draws, [s])[:, :, 0]
         for s in range(s_N):
-            m_star = np.reshape(self.mean.compute(hyps[s][cov_N + noise_N:cov_N + noise_N + mean_N], x_star), (-1,))
+            m_star = np.reshape(self.mean.compute(_mean_hyp(hyps[s], counts), x_star), (-1,))
             f[:, :, s] += m_star[:, None]
         return (f, tau) if return_jitter else f
 
@@ -1943,23 +1903,12 @@ class GP:
     def _draw_on_device(self, x_star, n_draws, seed, nsd):
         """draw_functions' posterior part: (f (M, n_draws, S) without the mean function, tau (S,)), gathered over the
         ranks when sharded (each rank draws its block of samples under their global indices)."""
-        M = x_star.shape[0]
-        self._restore()
-        if self._post_handle is None and self._post_range is None:
-            raise ValueError("posteriors have been cleaned; call update() first")
-        self._ctx()
-        local_posts, lo = self._local_posteriors()
-        if not local_posts:
-            f, tau = np.zeros((M, n_draws, 0)), np.zeros(0)
-        else:
-            k = len(local_posts)
-            f, tau = self._post_handle.draw(x_star, n_draws, seed, lo, None if nsd is None else nsd[:, lo:lo + k])
-        if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
-            k = f.shape[2]
-            rows = np.concatenate([f.reshape(M * n_draws, k), tau.reshape(1, k)], axis=0)
-            rows = self._gather_samples(rows, x_star, n_draws, seed, nsd is not None)
-            f, tau = rows[:M * n_draws].reshape(M, n_draws, -1), rows[M * n_draws].copy()
-        return f, tau
+        def call(handle, local_posts, lo):
+            return handle.draw(x_star, n_draws, seed, lo, None if nsd is None else nsd[:, lo:lo + len(local_posts)])
+
+        r = self._device_rows(call, [("f", (x_star.shape[0], n_draws)), ("tau", ())],
+                              x_star, n_draws, seed, nsd is not None)
+        return r["f"], r["tau"]
 
     def sample_paths(self, n_paths: int = 1, n_features: int = 1024, seed: int = 0):
         """``n_paths`` sampled posterior functions per hyperparameter sample, as a ``PosteriorPaths`` object that
@@ -2002,10 +1951,9 @@ class GP:
 
     @_on_device
     def _paths_on_device(self, n_paths, n_features, seed):
-        """sample_paths' device part: (the ``_lib.Paths`` handle of this rank's samples or None, the shard range)."""
-        self._restore()
-        if self._post_handle is None and self._post_range is None:
-            raise ValueError("posteriors have been cleaned; call update() first")
+        """sample_paths' device part: (the ``_lib.Paths`` handle of this rank's samples or None, the shard range).
+        Nothing is exchanged here (``PosteriorPaths`` gathers what it evaluates), so no ``_device_rows``."""
+        self._require_posteriors()
         self._ctx()
         local_posts, lo = self._local_posteriors()
         if not local_posts:
@@ -2013,7 +1961,7 @@ class GP:
         pv = self._plugin_values(np.stack([p.hyp for p in local_posts]), False)
         N = self.X.shape[0]
         ym = np.reshape(self.y, (1, -1)) - pv["m"]
-        mult = np.array([1.0 if p.sn2_mult is None else float(p.sn2_mult) for p in local_posts])
+        mult = np.array([float(_sn2_mult(p)) for p in local_posts])
         nsd = np.sqrt(np.broadcast_to(pv["sn2"], (len(local_posts), N)) * mult[:, None]).T
         return self._post_handle.paths(n_paths, n_features, seed, lo, ym, nsd), self._post_range
 
@@ -2095,45 +2043,40 @@ class GP:
         cov_N, noise_N, _ = self._counts()
         mu, sigma = _quad_measures(mu, sigma, D)
         N_star = mu.shape[0]
-        self._restore()
-        if self._post_handle is None and self._post_range is None:
-            raise ValueError("posteriors have been cleaned; call update() first")
-        self._ctx()
+        self._require_posteriors()
+        self._ctx()  # (before the probe below, as ever: a GP without targets is refused first)
         quirks = self.reference_quirks
         iso = cov_N == 2 and D != 1
         if quirks:  # the reference evaluates exp(2 hyp[cov_N]) for every sample, variance or not: without a noise
             for p in self.posteriors:  # hyperparameter that is a mean hyperparameter, or an IndexError (:1921)
                 np.exp(2 * p.hyp[cov_N])
-        if self._post_handle is None:
-            za, zkz = np.zeros((N_star, 0)), (np.zeros((N_star, 0)) if compute_var else None)
-        elif quirks and iso:
-            # the reference reads hyp[0:D] as length scales and hyp[D] as the output scale whatever the kernel
-            # (:1898-1903): with an isotropic kernel's two hyperparameters that is [ell, sf, ...] taken for D length
-            # scales.  Its kernel-mean vectors z, built here on the host from that reading, against the device's factors.
-            local, _ = self._local_posteriors()
-            Z = np.empty((len(local), N, N_star))
-            for k, p in enumerate(local):
-                tau = np.sqrt(sigma**2 + np.exp(p.hyp[0:D])**2)
-                lnnf = 2 * p.hyp[D] + np.sum(p.hyp[0:D]) - np.sum(np.log(tau), 1)
-                d2 = np.zeros((N_star, N))
-                for i in range(D):
-                    d2 += ((mu[:, i] - np.reshape(self.X[:, i], (-1, 1))).T / tau[:, i:i + 1]) ** 2
-                Z[k] = np.exp(np.reshape(lnnf, (-1, 1)) - 0.5 * d2).T
-            za, fq, _ = self._post_handle.predict_K(Z, want_var=compute_var)
-            zkz = None if fq is None else -fq  # fq = -z (K + Sigma)^-1 z^T (the variance term of predict)
-        else:
-            za, zkz = self._post_handle.quad(mu, sigma, compute_var)
-        if quirks and compute_var and self._post_handle is not None:
-            # the factor was scaled by sl = min(sn2) sn2_mult, the reference divides by exp(2 hyp[cov_N]) sn2_mult
-            # (:1921-1922, :1953-1958): the same thing only when the noise model is its constant term
-            local, _ = self._local_posteriors()
-            for k, p in enumerate(local):
-                if p.L_chol:
-                    sl = 1.0 / float(np.ravel(p.sW)[0]) ** 2
-                    zkz[:, k] *= sl / (np.exp(2 * p.hyp[cov_N]) * p.sn2_mult)
-        if self._post_range is not None:
-            both = self._gather_samples(np.concatenate([za, zkz], axis=0) if compute_var else za, mu, sigma)
-            za, zkz = both[:N_star], (both[N_star:] if compute_var else None)
+
+        def call(handle, local_posts, lo):
+            if quirks and iso:
+                # the reference reads hyp[0:D] as length scales and hyp[D] as the output scale whatever the kernel
+                # (:1898-1903): with an isotropic kernel's two hyperparameters that is [ell, sf, ...] taken for D length
+                # scales.  Its kernel-mean vectors z, built here on the host from that reading, against the device's
+                # factors.
+                Z = np.empty((len(local_posts), N, N_star))
+                for k, p in enumerate(local_posts):
+                    tau = np.sqrt(sigma**2 + np.exp(p.hyp[0:D])**2)
+                    lnnf = 2 * p.hyp[D] + np.sum(p.hyp[0:D]) - np.sum(np.log(tau), 1)
+                    d2 = np.zeros((N_star, N))
+                    for i in range(D):
+                        d2 += ((mu[:, i] - np.reshape(self.X[:, i], (-1, 1))).T / tau[:, i:i + 1]) ** 2
+                    Z[k] = np.exp(np.reshape(lnnf, (-1, 1)) - 0.5 * d2).T
+                za, fq, _ = handle.predict_K(Z, want_var=compute_var)
+                zkz = None if fq is None else -fq  # fq = -z (K + Sigma)^-1 z^T (the variance term of predict)
+            else:
+                za, zkz = handle.quad(mu, sigma, compute_var)
+            if not compute_var:
+                return [za]
+            if quirks:
+                zkz *= self._quad_solve_scales(local_posts, cov_N)
+            return za, zkz
+
+        r = self._device_rows(call, [("za", (N_star,))] + ([("zkz", (N_star,))] if compute_var else []), mu, sigma)
+        za, zkz = r["za"], r.get("zkz")
         quadratic = isinstance(self.mean, NegativeQuadratic)
         F = np.zeros((N_star, N_s))
         F_var = np.zeros((N_star, N_s)) if compute_var else None
@@ -2182,9 +2125,7 @@ class GP:
         N_star = mu.shape[0]
         if mu.shape[1] != D:
             raise ValueError(f"quad_grad: the measures have {mu.shape[1]} dimensions, the GP {D}")
-        self._restore()
-        if self._post_handle is None and self._post_range is None:
-            raise ValueError("posteriors have been cleaned; call update() first")
+        self._require_posteriors()
         quirks = self.reference_quirks
         iso = cov_N == 2 and D != 1
         if quirks:
@@ -2193,35 +2134,24 @@ class GP:
             if iso:
                 raise NotImplementedError("quad_grad: under reference_quirks, quad builds an isotropic kernel's z on the "
                                           "host from a misread of its hyperparameters (D > 1); it has no device gradient")
-        self._ctx()
-        if self._post_handle is None:  # a rank without local samples
-            za, zkz = np.zeros((N_star, 0)), np.zeros((N_star, 0))
-            dza_mu = dza_sg = dzkz_mu = dzkz_sg = np.zeros((N_star, D, 0))
-        else:
-            za, zkz, dza_mu, dza_sg, dzkz_mu, dzkz_sg = self._post_handle.quad_grad(mu, sigma, compute_var)
-        if quirks and compute_var and self._post_handle is not None:  # quad's rescaling of the variance term
-            local, _ = self._local_posteriors()
-            for k, p in enumerate(local):
-                if p.L_chol:
-                    sl = 1.0 / float(np.ravel(p.sW)[0]) ** 2
-                    scale = sl / (np.exp(2 * p.hyp[cov_N]) * p.sn2_mult)
-                    zkz[:, k] *= scale
-                    dzkz_mu[:, :, k] *= scale
-                    dzkz_sg[:, :, k] *= scale
-        if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
-            k = za.shape[1]
-            planes = (dza_mu, dza_sg, dzkz_mu, dzkz_sg) if compute_var else (dza_mu, dza_sg)
-            rows = [za, zkz] if compute_var else [za]
-            rows = self._gather_samples(np.concatenate(rows + [g.reshape(N_star * D, k) for g in planes], axis=0),
-                                        mu, sigma)
-            za, rows = rows[:N_star], rows[N_star:]
-            if compute_var:
-                zkz, rows = rows[:N_star], rows[N_star:]
-            nd = N_star * D
-            planes = [rows[q * nd:(q + 1) * nd].reshape(N_star, D, -1) for q in range(len(planes))]
-            dza_mu, dza_sg = planes[:2]
-            if compute_var:
-                dzkz_mu, dzkz_sg = planes[2:]
+
+        def call(handle, local_posts, lo):
+            za, zkz, dza_mu, dza_sg, dzkz_mu, dzkz_sg = handle.quad_grad(mu, sigma, compute_var)
+            if not compute_var:
+                return za, dza_mu, dza_sg
+            if quirks:  # quad's rescaling of the variance term
+                scale = self._quad_solve_scales(local_posts, cov_N)
+                zkz *= scale
+                dzkz_mu *= scale
+                dzkz_sg *= scale
+            return za, dza_mu, dza_sg, zkz, dzkz_mu, dzkz_sg
+
+        layout = [("za", (N_star,)), ("dza_mu", (N_star, D)), ("dza_sg", (N_star, D))]
+        if compute_var:
+            layout += [("zkz", (N_star,)), ("dzkz_mu", (N_star, D)), ("dzkz_sg", (N_star, D))]
+        r = self._device_rows(call, layout, mu, sigma)
+        za, dza_mu, dza_sg = r["za"], r["dza_mu"], r["dza_sg"]
+        zkz, dzkz_mu, dzkz_sg = r.get("zkz"), r.get("dzkz_mu"), r.get("dzkz_sg")
         quadratic = isinstance(self.mean, NegativeQuadratic)
         F = np.zeros((N_star, N_s))
         F_var = np.zeros((N_star, N_s)) if compute_var else None
@@ -2274,9 +2204,7 @@ class GP:
         mu, sigma = _quad_measures(mu, sigma, D)
         if mu.shape[1] != D:
             raise ValueError(f"{name}: the measures have {mu.shape[1]} dimensions, the GP {D}")
-        self._restore()
-        if self._post_handle is None and self._post_range is None:
-            raise ValueError("posteriors have been cleaned; call update() first")
+        self._require_posteriors()
         iso = cov_N == 2 and D != 1
         if self.reference_quirks:
             for p in self.posteriors:  # (as quad: an IndexError without a noise hyperparameter)
@@ -2286,13 +2214,13 @@ class GP:
                                           "host from a misread of its hyperparameters (D > 1); it has no device form")
         return mu, sigma, D, np.size(self.posteriors), cov_N, noise_N, iso
 
-    def _quad_solve_scales(self, cov_N):
+    def _quad_solve_scales(self, local_posts, cov_N):
         """``quad``'s ``reference_quirks`` rescaling of the solve term, per local sample (1 where it does not apply): the
-        factor was scaled by sl = min(sn2) sn2_mult, the reference divides by exp(2 hyp[cov_N]) sn2_mult."""
-        local, _ = self._local_posteriors()
-        scale = np.ones(len(local))
+        factor was scaled by sl = min(sn2) sn2_mult, the reference divides by exp(2 hyp[cov_N]) sn2_mult (:1921-1922,
+        :1953-1958): the same thing only when the noise model is its constant term."""
+        scale = np.ones(len(local_posts))
         if self.reference_quirks:
-            for k, p in enumerate(local):
+            for k, p in enumerate(local_posts):
                 if p.L_chol:
                     sl = 1.0 / float(np.ravel(p.sW)[0]) ** 2
                     scale[k] = sl / (np.exp(2 * p.hyp[cov_N]) * p.sn2_mult)
@@ -2323,20 +2251,18 @@ class GP:
         ``quad_grad`` refuses."""
         mu, sigma, D, N_s, cov_N, noise_N, iso = self._quad_mixture_prepare("quad_cov", mu, sigma)
         M = mu.shape[0]
-        self._ctx()
-        if self._post_handle is None:  # a rank without local samples
-            za, C = np.zeros((M, 0)), np.zeros((0, M, M))
-        else:
-            za, C = self._post_handle.quad_cov(mu, sigma)
-            for k, sc in enumerate(self._quad_solve_scales(cov_N)):
+
+        def call(handle, local_posts, lo):
+            za, C = handle.quad_cov(mu, sigma)
+            for k, sc in enumerate(self._quad_solve_scales(local_posts, cov_N)):
                 if sc != 1.0:  # quirks: Gamma - sc (Gamma - C)
-                    hyp = self._local_posteriors()[0][k].hyp
+                    hyp = local_posts[k].hyp
                     G = _quad_gamma(mu, sigma, np.exp(hyp[0:D]), 2 * hyp[D])
                     C[k] = G - sc * (G - C[k])
-        rows = np.concatenate([za, C.reshape(C.shape[0], M * M).T], axis=0)
-        if self._post_range is not None:  # one all-gather of the stacked rows
-            rows = self._gather_samples(rows, mu, sigma)
-        za, C = rows[:M], rows[M:].reshape(M, M, N_s)
+            return za, C.transpose(1, 2, 0)  # (the device's covariances are sample-first)
+
+        za, C = self._device_rows(call, [("za", (M,)), ("C", (M, M))], mu, sigma).values()
+        C = np.ascontiguousarray(C)  # (samples innermost, whatever the sharding: the sums below run in one order)
         C = 0.5 * (C + C.transpose(1, 0, 2))
         F = np.stack([za[:, s] + self._quad_mean_terms(s, mu, sigma, cov_N, noise_N)[0] for s in range(N_s)], 1)
         if separate_samples:
@@ -2370,36 +2296,26 @@ class GP:
             raise ValueError(f"quad_mixture: {M} measures but {w.size} weights")
         if not np.all(np.isfinite(w)):
             raise ValueError("quad_mixture: the weights must be finite")
-        self._ctx()
         var, grad = bool(compute_var), bool(compute_grad)
-        # the device's rows, one block (R, S_local): za | gw | zq | zbkzb | the planes
-        names = ["za"] + (["gw", "zq", "zbkzb"] if var else [])
-        planes = (["dza_dmu", "dza_dsigma"] if grad else []) + \
-                 (["dzq_dmu", "dzq_dsigma", "dgw_dmu", "dgw_dsigma"] if var and grad else [])
-        height = {n: (1 if n == "zbkzb" else M) for n in names}
-        height.update({n: M * D for n in planes})
-        if self._post_handle is None:  # a rank without local samples
-            d = {n: np.zeros((height[n], 0)) for n in names + planes}
-        else:
-            d = self._post_handle.quad_mix(mu, sigma, w, var, grad)
-            scale = self._quad_solve_scales(cov_N)
+        layout = [("za", (M,))] + ([("gw", (M,)), ("zq", (M,)), ("zbkzb", ())] if var else [])
+        if grad:
+            layout += [(n, (M, D)) for n in ["dza_dmu", "dza_dsigma"] +
+                       (["dzq_dmu", "dzq_dsigma", "dgw_dmu", "dgw_dsigma"] if var else [])]
+
+        def call(handle, local_posts, lo):
+            d = handle.quad_mix(mu, sigma, w, var, grad)
+            scale = self._quad_solve_scales(local_posts, cov_N)
             if var and np.any(scale != 1.0):  # quad's rescaling of the solve term
                 for n in ("zbkzb", "zq", "dzq_dmu", "dzq_dsigma"):
                     if d[n] is not None:
                         d[n] = d[n] * scale
-        if self._post_range is not None:  # each rank has its block of samples: one all-gather of the stacked rows
-            rows = np.concatenate([np.reshape(d[n], (height[n], -1)) for n in names + planes], axis=0)
-            rows = self._gather_samples(rows, mu, sigma, w)
-            at = 0
-            for n in names + planes:
-                d[n] = rows[at:at + height[n]]
-                at += height[n]
-        for n in planes:
-            d[n] = np.reshape(d[n], (M, D, N_s))
+            return [d[n] for n, _ in layout]
+
+        d = self._device_rows(call, layout, mu, sigma, w)
         # the host terms, for all samples at once; the two dot products with w run per sample on contiguous rows, so
         # that their order of summation -- a sample's bits -- does not depend on the batch
         terms = [self._quad_mean_terms(s, mu, sigma, cov_N, noise_N) for s in range(N_s)]
-        F = np.reshape(d["za"], (M, N_s)) + np.stack([t[0] for t in terms], 1)
+        F = d["za"] + np.stack([t[0] for t in terms], 1)
         dot_w = lambda A: np.array([w @ row for row in np.ascontiguousarray(A.T)])
         E, V = dot_w(F)[None, :], None
         dE = dV = None
@@ -2412,8 +2328,8 @@ class GP:
             if not var:
                 dV = [np.zeros_like(g) for g in dE]
         if var:
-            gw, zq = np.reshape(d["gw"], (M, N_s)), np.reshape(d["zq"], (M, N_s))
-            raw = dot_w(gw) - np.reshape(d["zbkzb"], -1)
+            gw, zq = d["gw"], d["zq"]
+            raw = dot_w(gw) - d["zbkzb"]
             V = np.maximum(np.spacing(1), raw)[None, :]
             if grad:  # the clamp: no variance gradient where it holds V
                 free = raw > np.spacing(1)

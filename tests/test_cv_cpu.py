@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 from scipy.linalg import cholesky, solve_triangular
 
-from test_quad_grad_cpu import _NoDevice, _counts, _se_gp, solve_posterior
+from gp_stubs import _NoDevice, _se_gp
+from test_quad_grad_cpu import _counts, solve_posterior
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RTOL = 1e-8  # the project's fp64 parity bound

@@ -3,11 +3,11 @@ the host terms) against 5-point differences of a NumPy restatement of GP.quad, o
 gradients with quad's shapes; the refusals that come before any device work.  test_gpu_quad_grad.py compares the device
 against the same restatement."""
 
-import threading
-
 import numpy as np
 import pytest
 from scipy.linalg import solve_triangular
+
+from gp_stubs import _NoDevice, _se_gp
 
 
 def _counts(model, D):
@@ -200,21 +200,6 @@ def test_mixture_gradients_with_quad_shapes():
         fs = five_point(lambda g: _mix_samples(*quad_numpy(model, posts, X, mu, g))[k], sigma, h)[:, :, 0]
         assert np.abs(gm[k] - fm).max() <= 1e-8 * np.abs(fm).max()
         assert np.abs(gs[k] - fs).max() <= 1e-8 * np.abs(fs).max()
-
-
-class _NoDevice:
-    """Stands in for the device context: the refusals below must come before any device work."""
-
-    lock = threading.RLock()
-
-
-def _se_gp(D=2, iso=False, quirks=False, mean=None):
-    import gpyreg_amd as gpr
-
-    cov = gpr.isotropic_covariance_functions.SquaredExponentialIsotropic() if iso else \
-        gpr.covariance_functions.SquaredExponential()
-    return gpr.GP(D, cov, mean or gpr.mean_functions.ConstantMean(),
-                  gpr.noise_functions.GaussianNoise(constant_add=True), reference_quirks=quirks)
 
 
 def test_refusals_before_device_work(monkeypatch):

@@ -4,7 +4,8 @@
 
 The library documents fixed reduction orders and no atomics, so two builds that launch the same kernels in the same order
 print the same lines; a refactor of the host code is checked by diffing the output of the build before against the build
-after (tools/build_ref.sh builds the former).  Public Python API only, seeded data, the smallest shapes that reach each
+after (tools/build_ref.sh builds the former); a refactor of the Python side by running this file from a checkout of the
+commit before and from the tree (it imports the package of the tree it lies in) on one library.  Public Python API only, seeded data, the smallest shapes that reach each
 branch: D = 3 and S = 4 hyperparameter samples whose noise is high, low, low, high (low: below the 1e-6 at which the
 posterior stores -(K + Sigma)^-1 instead of the Cholesky factor), i.e. runs of 1, 2, 1 samples; N = 200 (N_pad 256),
 M = 70 (M_pad 128).  Every call runs once with all samples in one chunk and once under a GPC_MEM_BUDGET_MB picked from
@@ -177,6 +178,31 @@ def consumers(dtype):
     both("quad_mixture with variance and gradient", dtype,
          lambda: gp.quad_mixture(mu, sigma, wm, compute_var=True, compute_grad=True, separate_samples=True), mix,
          (2 * ss + mpad + 2 * M * D + M) * 8)
+    # gradient_posterior and predict_hess: the bytes per sample of grad_post_impl and hess_impl (one block of 128 queries,
+    # D + 1 slots; the Gram matrix in one segment below N_pad = 1024)
+    qb, dp, nt64 = 128, D + 1, npad // 64
+    ld, vecs = dp * qb, qb * D + npad * D + 4 + 2 * D
+    for cov in ("full", "diag"):
+        gper = qb * dp * (1 if cov == "diag" else dp)
+        per = 2 * npad * ld * w + (nt64 * ld + (npad // 128 * ld if cov == "diag" else 0) + gper + ld + 1 + vecs) * 8
+        for val in (False, True):
+            both(f"gradient_posterior {cov}" + (" with value" if val else ""), dtype,
+                 lambda: gp.gradient_posterior(xq, cov=cov, with_value=val, separate_samples=True), per)
+    for var in (True, False):
+        gper, hper = (qb * dp * dp if var else 0), (2 if var else 1) * (1 + D * (D + 1) // 2) * qb
+        per = ((2 * npad * ld + npad * qb) if var else npad * ld) * w + \
+            (nt64 * ld + nt64 * hper + hper + gper + ld + 1 + vecs) * 8
+        both("predict_hess" + ("" if var else " without variance"), dtype,
+             lambda: gp.predict_hess(xq, compute_var=var, separate_samples=True), per)
+    # cv_predict: the leave-one-out pass (five vectors per sample: one megabyte holds every sample), and three scattered
+    # folds of 5, 9 and 3 points -- cv_fold_impl's three k_pad x k_pad slabs and one vector per fold, two output planes
+    both("cv_predict leave-one-out", dtype, lambda: gp.cv_predict(None, separate_samples=True, return_lpd=True),
+         5 * npad * 8)
+    order = np.random.default_rng(9).permutation(N)
+    folds = [np.sort(order[:5]), np.sort(order[5:14]), np.sort(order[14:17])]
+    per = len(folds) * (3 * pad(9) ** 2 + pad(9)) * 8 + 2 * npad * 8 + len(folds) * 32 + 64
+    both("cv_predict scattered folds", dtype, lambda: gp.cv_predict(folds, separate_samples=True), per)
+    both("cv_predict scattered folds with lpd", dtype, lambda: gp.cv_predict(folds, return_lpd=True), per)
     # sample_paths: creation under both solve engines, evaluation with gradients under both engines
     kq, kp = pad(R_PATHS, 16), pad(R_PATHS)
     try:
