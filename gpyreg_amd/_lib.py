@@ -69,6 +69,7 @@ SIGNATURES = {
     "gpc_predict_grad": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "gpc_grad_post": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "gpc_predict_hess": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "gpc_nll_hess": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
     "gpc_post_append": (C.c_int, [_vp, _dp, _dp, C.c_double, _ip]),
     "gpc_post_recompute": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_post_append_K": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_double, _ip]),
@@ -107,6 +108,10 @@ SIGNATURES = {
     "gpc_debug_block_gram": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]),
     "gpc_debug_hess_contract": (
         C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpc_debug_nll_plane": (
+        C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "gpc_debug_nll_d2": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
+    "gpc_debug_nll_gram": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp]),
     "gpc_debug_normals": (C.c_int, [_vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "gpc_debug_workspace_hash": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
     "gpc_debug_chunk_plan": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_int]),
@@ -586,6 +591,50 @@ class Context:
         return out_a, out_q
 
     @_serial
+    def debug_nll_plane(self, kernel_id, degree, hyp_cov, X, p, alpha, Q=None):
+        """gpc_debug_nll_plane: the plane kernel of gpc_nll_hess for covariance hyperparameter ``p`` with weights alpha
+        (N,) and a dense symmetric Q (N, N) (None: zeros).  Returns (plane (N, N), u (N,), g (2,))."""
+        X, hyp, al = _f64(X), _f64(hyp_cov), _f64(alpha).ravel()
+        N, D = X.shape
+        Qc = None if Q is None else _f64(Q)
+        if al.size != N or (Qc is not None and Qc.shape != (N, N)):
+            raise ValueError("debug_nll_plane: X (N, D), alpha (N,), Q (N, N)")
+        plane, u, g = np.empty((N, N)), np.empty(N), np.empty(2)
+        rc = self._lib.gpc_debug_nll_plane(self._h, kernel_id, degree, _ptr(hyp), _ptr(X), N, D, int(p), _ptr(al), _ptr(Qc),
+                                           _ptr(plane), _ptr(u), _ptr(g))
+        self._check(rc, "gpc_debug_nll_plane")
+        return plane, u, g
+
+    @_serial
+    def debug_nll_d2(self, kernel_id, degree, hyp_cov, X, alpha, Q):
+        """gpc_debug_nll_d2: the second-derivative contraction of gpc_nll_hess (ARD families) with weights
+        Q - alpha alpha^T over the lower triangle.  Returns (D (D + 1) / 2,): entry a (a + 1) / 2 + b, a >= b."""
+        X, hyp, al, Qc = _f64(X), _f64(hyp_cov), _f64(alpha).ravel(), _f64(Q)
+        N, D = X.shape
+        if al.size != N or Qc.shape != (N, N):
+            raise ValueError("debug_nll_d2: X (N, D), alpha (N,), Q (N, N)")
+        out = np.empty(D * (D + 1) // 2)
+        rc = self._lib.gpc_debug_nll_d2(self._h, kernel_id, degree, _ptr(hyp), _ptr(X), N, D, _ptr(al), _ptr(Qc), _ptr(out))
+        self._check(rc, "gpc_debug_nll_d2")
+        return out
+
+    @_serial
+    def debug_nll_gram(self, planes, out=None):
+        """gpc_debug_nll_gram: the Gram pass of gpc_nll_hess on planes (P, npad, npad).  Returns (or fills ``out``, a
+        C-contiguous view of P (P + 1) / 2 doubles) entry p (p + 1) / 2 + q = sum_ab planes[p][a][b] planes[q][b][a]."""
+        pl = _f64(planes)
+        P, npad, n2 = pl.shape
+        if npad != n2:
+            raise ValueError("debug_nll_gram: planes (P, npad, npad)")
+        if out is None:
+            out = np.empty(P * (P + 1) // 2)
+        if out.dtype != np.float64 or out.size != P * (P + 1) // 2:
+            raise ValueError("debug_nll_gram: out holds P (P + 1) / 2 doubles")
+        rc = self._lib.gpc_debug_nll_gram(self._h, npad, P, _ptr(pl), _ptr(out))
+        self._check(rc, "gpc_debug_nll_gram")
+        return out
+
+    @_serial
     def debug_normals(self, seed, stream, s, r, j0, count):
         """gpc_debug_normals: the device's z of rows j0 .. j0 + count - 1 of (seed, stream, sample s, draw r)."""
         out = np.empty(count)
@@ -664,6 +713,26 @@ class PostHandle:
                                             _ptr(dfs2), _ptr(hmu), _ptr(hs2))
         self.ctx._check(rc, "gpc_predict_hess")
         return fmu, fs2, dfmu, dfs2, hmu, hs2
+
+    @_serial
+    def nll_hess(self, cov_N, dm=None, dsn2=None):
+        """gpc_nll_hess: ``cov_N`` covariance hyperparameters (gpc_cov_count of the posterior's kernel); dm (S, N, mean_N) | None, dsn2 (S, 1 | N, noise_N) | None (without the jitter multiplier).
+        Returns H (S, P, P) without the plugins' second-derivative terms, dnlz (S, P), alpha (S, N) and
+        diagq = diag(Q - alpha alpha^T) (S, N)."""
+        S, N = self.S, self.N
+        dm_c = None if dm is None or dm.shape[2] == 0 else _f64(dm)
+        ds_c = None if dsn2 is None or dsn2.shape[2] == 0 else _f64(dsn2)
+        mean_N = 0 if dm_c is None else dm_c.shape[2]
+        noise_N = 0 if ds_c is None else ds_c.shape[2]
+        rows = 1 if ds_c is None else ds_c.shape[1]
+        if (dm_c is not None and dm_c.shape[:2] != (S, N)) or (ds_c is not None and (ds_c.shape[0] != S or rows not in (1, N))):
+            raise ValueError("nll_hess: dm (S, N, mean_N); dsn2 (S, 1 or N, noise_N)")
+        P = int(cov_N) + noise_N + mean_N
+        H, g, al, dq = np.empty((S, P, P)), np.empty((S, P)), np.empty((S, N)), np.empty((S, N))
+        rc = self.ctx._lib.gpc_nll_hess(self._h, _ptr(dm_c), mean_N, _ptr(ds_c), rows, noise_N, _ptr(H), _ptr(g), _ptr(al),
+                                        _ptr(dq))
+        self.ctx._check(rc, "gpc_nll_hess")
+        return H, g, al, dq
 
     @_serial
     def predict_K(self, Ks, Kss=None, want_var=True):

@@ -28,6 +28,7 @@
 #include "gemm.h"
 #include "gradpost.h"
 #include "hess.h"
+#include "nll_hess.h"
 #include "leaf.h"
 #include "lookahead.h"
 #include "paths.h"
@@ -492,6 +493,7 @@ struct gpc_ctx {
   unsigned long long small_polled = 0, small_synced = 0;  // statistics ("small_polled" / "small_synced")
   unsigned long long grad_post_gram_us = 0;  // Gram passes of the last gpc_grad_post, device microseconds ("grad_post_gram_us")
   unsigned long long hess_contract_us = 0;  // contraction passes of the last gpc_predict_hess, device microseconds ("hess_contract_us")
+  unsigned long long nll_hess_gram_us = 0, nll_hess_contract_us = 0;  // Gram pass / second-derivative contraction of the last gpc_nll_hess, device microseconds
   unsigned long long cov_fused = 0;  // gpc_predict_cov calls whose reduction ran in the product's epilogue ("cov_fused")
   unsigned long long quad_mix_gemms = 0;  // MFMA GEMM launches inside gpc_quad_mix ("quad_mix_gemms"; there should be none)
   int check_queues = 0;  // debug option: verify after every pipeline that the tile queues of its persistent launches were drained
@@ -519,6 +521,7 @@ struct gpc_ctx {
   DevBuf qb, gpart, gres;        // predict_grad / quad_grad: Q = W^T V, per-tile partials, the gradients
   DevBuf qcon;                   // quad_grad: the measures' constants (quad.h: quad_grad_prep_kernel)
   DevBuf qmix;                   // quad_mix: the whole scratch of a chunk, carved up in quad_mix_impl
+  DevBuf nhs;                    // nll_hess: the whole scratch of a chunk, carved up in nll_hess_impl (NhScratch)
   DevBuf zb, fb, dout, daux;     // draw: Z, F = L Z, the draws, [logdet | info | noise sd] (the factor: mA mW mT)
   DevBuf dbg1, dbg2, dbg3;       // debug hooks / fetch staging
   PinBuf pin;                    // pinned staging for host<->device transfers (see PinBuf)
@@ -3632,6 +3635,278 @@ int hess_impl(gpc_post* po, const double* xstar, int M, bool var, double* fmu, d
   return 0;
 }
 
+// ---- gpc_nll_hess: the Hessian of the negative log marginal likelihood (nll_hess.h) -----------------------------------
+// The plane of covariance hyperparameter p: what it differentiates and, for an ARD lengthscale, its dimension
+inline void nh_plane_of(const CovDesc& cd, int p, int* mode, int* dim) {
+  *dim = 0;
+  if (cov_is_iso(cd.kind)) {
+    *mode = p == 0 ? NH_LS : NH_SF;
+  } else if (p < cd.D) {
+    *mode = NH_LS;
+    *dim = p;
+  } else {
+    *mode = p == cd.D ? NH_SF : NH_SHAPE;
+  }
+}
+
+// Device buffers of a chunk of `cnt` samples, carved from one allocation (all doubles; vectors are [plane][sample][npad])
+struct NhScratch {
+  int npad = 0, ppl = 0, cov_N = 0, noise_N = 0, mean_N = 0, nt = 0, ntl = 0, npairs = 0, nd2 = 0;
+  double *Q, *B, *Op, *X, *Y, *E, *diagq, *upart, *gpart, *gsum, *grpart, *grsum, *d2part, *d2sum;
+  // doubles of one sample's share
+  static size_t per_sample(int npad, int cov_N, int noise_N, int mean_N, int nd2) {
+    const size_t n2 = (size_t)npad * npad, ppl = cov_N + noise_N, nt = npad / CT, ntl = nt * (nt + 1) / 2;
+    return (ppl + 2) * n2 + (2 * (ppl + mean_N) + noise_N + 1 + nt) * (size_t)npad + nt * nt * 2 + 2 * (size_t)cov_N +
+           (nt * nt + 1) * (ppl * (ppl + 1) / 2) + (ntl + 1) * (size_t)nd2;
+  }
+  void carve(double* p, int cnt, int npad_, int cov_N_, int noise_N_, int mean_N_, int nd2_) {
+    npad = npad_, cov_N = cov_N_, noise_N = noise_N_, mean_N = mean_N_, nd2 = nd2_;
+    ppl = cov_N + noise_N, nt = npad / CT, ntl = nt * (nt + 1) / 2, npairs = ppl * (ppl + 1) / 2;
+    const size_t n2 = (size_t)npad * npad, c = cnt;
+    auto take = [&](size_t n) {
+      double* r = p;
+      p += n;
+      return r;
+    };
+    Q = take(c * n2);
+    B = take(c * ppl * n2);
+    Op = take(c * n2);
+    X = take(c * (ppl + mean_N) * npad);
+    Y = take(c * (ppl + mean_N) * npad);
+    E = take(c * noise_N * npad);
+    diagq = take(c * npad);
+    upart = take(c * nt * npad);
+    gpart = take(c * nt * nt * 2);
+    gsum = take(c * cov_N * 2);
+    grpart = take(c * nt * nt * npairs);
+    grsum = take(c * npairs);
+    d2part = take(c * ntl * nd2);
+    d2sum = take(c * nd2);
+  }
+};
+
+// One covariance plane of `cnt` samples: the operand into Op, u into X[p], the two sums into gsum[p]
+int nh_launch_plane(gpc_ctx* c, const CovDesc& cd, const NhScratch& z, int cnt, int p, const double* xs, const double* sp,
+                    const double* alpha, int N) {
+  hipStream_t st = c->st;
+  const int npad = z.npad;
+  const long long n2 = (long long)npad * npad;
+  int mode, dim;
+  nh_plane_of(cd, p, &mode, &dim);
+  GPC_COV_DISPATCH(nh_plane_kernel, double, cd, dim3(z.nt, z.nt, cnt), dim3(256), 0, st, cd, xs, sp, alpha, N, npad, mode, dim,
+                   (const double*)z.Q, n2, z.Op, n2, z.upart, z.gpart);
+  hipLaunchKernelGGL(colpart_reduce_kernel, dim3((npad + 255) / 256, cnt), dim3(256), 0, st, (const double*)z.upart, z.nt,
+                     npad, z.X + (size_t)p * cnt * npad);
+  hipLaunchKernelGGL(reduce_parts_kernel, dim3(2, cnt), dim3(256), 0, st, (const double*)z.gpart, z.nt * z.nt, 2,
+                     z.gsum + (size_t)p * cnt * 2);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// tr(B_p B_q), p >= q, of `cnt` samples into grsum[b][pair]
+int nh_launch_gram(gpc_ctx* c, const NhScratch& z, int cnt) {
+  const long long n2 = (long long)z.npad * z.npad;
+  hipLaunchKernelGGL(nh_gram_kernel, dim3(z.nt * z.nt, z.ppl, cnt), dim3(256), 0, c->st, (const double*)z.B, n2, z.ppl * n2,
+                     z.npad, z.ppl, z.grpart);
+  hipLaunchKernelGGL(reduce_parts_kernel, dim3(z.npairs, cnt), dim3(256), 0, c->st, (const double*)z.grpart, z.nt * z.nt,
+                     z.npairs, z.grsum);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// sum Qm G d_a^2 d_b^2 of `cnt` samples (ARD families) into d2sum[b][pair]
+int nh_launch_d2(gpc_ctx* c, const CovDesc& cd, const NhScratch& z, int cnt, const double* xs, const double* sp,
+                 const double* alpha, int N) {
+  const long long n2 = (long long)z.npad * z.npad;
+  const size_t shm = 4 * (size_t)(((z.nd2 + 3) & ~3) + 4) * sizeof(double);
+  GPC_COV_DISPATCH(nh_d2_kernel, double, cd, dim3(z.ntl, cnt), dim3(256), shm, c->st, cd, xs, sp, alpha, N, z.npad,
+                   (const double*)z.Q, n2, z.d2part, z.ntl);
+  hipLaunchKernelGGL(reduce_parts_kernel, dim3(z.nd2, cnt), dim3(256), 0, c->st, (const double*)z.d2part, z.ntl, z.nd2,
+                     z.d2sum);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// <Qm, d2_pq K> for two covariance hyperparameters p >= q from a sample's sums: g[2 p] = <Qm, d_p K>, g[2 p + 1] the
+// plane's second sum, sg the ARD contraction (nll_hess.h: the table in the header)
+inline double nh_second(const CovDesc& cd, int p, int q, const double* g, int gstride, const double* sg) {
+  auto g1 = [&](int h) { return g[(size_t)h * gstride]; };
+  auto g2 = [&](int h) { return g[(size_t)h * gstride + 1]; };
+  if (cov_is_iso(cd.kind)) {
+    if (p == 0) return g2(0) - 2.0 * g1(0);
+    return q == 0 ? 2.0 * g1(0) : 2.0 * g1(1);
+  }
+  const int D = cd.D;
+  if (p < D) return sg[p * (p + 1) / 2 + q] - (p == q ? 2.0 * g1(p) : 0.0);
+  if (p == D) return q < D ? 2.0 * g1(q) : 2.0 * g1(D);
+  if (q < D) return g2(q);             // shape x lengthscale
+  return q == D ? 2.0 * g1(D + 1) : g2(D + 1);  // shape x sf | shape x shape
+}
+
+int nll_hess_impl(gpc_post* po, const double* dm, int mean_N, const double* dsn2, int dsn2_rows, int noise_N, double* H,
+                  double* dnlz, double* alpha_out, double* diagq_out) {
+  gpc_ctx* c = po->ctx;
+  const int S = po->S, N = po->N, npad = po->npad, cov_N = po->cd.cov_N;
+  const int ppl = cov_N + noise_N, P = ppl + mean_N, nvec = ppl + mean_N;
+  const bool ard = !cov_is_iso(po->cd.kind);
+  const int nd2 = ard ? nh_pairs(po->D) : 0;
+  hipStream_t st = c->st;
+  const long long n2 = (long long)npad * npad, sM = n2;
+  const size_t per = NhScratch::per_sample(npad, cov_N, noise_N, mean_N, nd2) * 8;
+  const size_t held = c->nhs.bytes;
+  const int chunk = plan_chunk(c, S, per, 0, held, (size_t)S * per <= held, 0, false, [&](size_t budget) {
+    return "gpc_nll_hess: the scratch of one sample (" + std::to_string(per) + " bytes: N_pad = " + std::to_string(npad) +
+           ", planes = " + std::to_string(ppl) + ": Q, one B per plane and one operand) exceeds the device memory budget (" +
+           std::to_string(budget) + " bytes)";
+  });
+  if (!chunk) return -2;
+  HIPCHK(c, c->nhs.ensure((size_t)chunk * per));
+  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * po->D * 8));
+  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
+  HIPCHK(c, c->mulb.ensure((size_t)chunk * po->D * 8));
+  HIPCHK(c, c->divb.ensure((size_t)chunk * po->D * 8));
+  NhScratch z;
+  z.carve(c->nhs.as<double>(), chunk, npad, cov_N, noise_N, mean_N, nd2);
+  CallTimer tm{c, CallTimer::wanted(c, npad)};
+  GramClock gc(tm.on), cc(tm.on);
+  double gram_us = 0, contract_us = 0;
+  ChunkConsts k;
+  if (int rc = k.init(po, chunk == S)) return rc;
+  c->ms_total = c->ms_factor = 0;
+  const size_t vlen = (size_t)chunk * npad;
+  std::vector<double> hx((size_t)(mean_N + noise_N) * vlen), hX((size_t)ppl * vlen), hY((size_t)nvec * vlen), hal(vlen),
+      hdq(vlen), hgr((size_t)chunk * z.npairs), hg((size_t)cov_N * chunk * 2), hd2((size_t)chunk * nd2), uw((size_t)ppl * ppl);
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    z.carve(c->nhs.as<double>(), cnt, npad, cov_N, noise_N, mean_N, nd2);
+    if (int rc = k.stage(s0, cnt, true)) return rc;
+    const double* alpha = po->alpha.as<double>() + (size_t)s0 * npad;
+    // the mean planes d_k m (rows of X after the u's) and the noise planes' e = mult d sn2, zero in the padding
+    std::fill(hx.begin(), hx.end(), 0.0);
+    double* hdm = hx.data();
+    double* he = hx.data() + (size_t)mean_N * cnt * npad;
+    for (int i = 0; i < cnt; ++i) {
+      const int s = s0 + i;
+      for (int kk = 0; kk < mean_N; ++kk)
+        for (int a = 0; a < N; ++a) hdm[((size_t)kk * cnt + i) * npad + a] = dm[((size_t)s * N + a) * mean_N + kk];
+      for (int nz = 0; nz < noise_N; ++nz)
+        for (int a = 0; a < N; ++a)
+          he[((size_t)nz * cnt + i) * npad + a] =
+              po->mult[s] * dsn2[((size_t)s * dsn2_rows + (dsn2_rows == 1 ? 0 : a)) * noise_N + nz];
+    }
+    if (mean_N)
+      HIPCHK(c, hipMemcpyAsync(z.X + (size_t)ppl * cnt * npad, hdm, (size_t)mean_N * cnt * npad * 8, hipMemcpyHostToDevice, st));
+    if (noise_N) HIPCHK(c, hipMemcpyAsync(z.E, he, (size_t)noise_N * cnt * npad * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, tm.start());
+    // a. Q of every sample: W^T W / sl (L_chol; the lower tiles land in the operand buffer) | -A
+    int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+      const double* src = po->A.as<double>() + (size_t)(s0 + a) * sM;
+      if (lch) {
+        Factor<double> F;
+        F.st = st;
+        F.batch = len;
+        F.npad = npad;
+        F.A = po->A.as<double>() + (size_t)(s0 + a) * sM;
+        F.W = po->W.as<double>() + (size_t)(s0 + a) * sM;
+        F.Tm = z.Op + (size_t)a * n2;
+        F.sA = F.sW = sM;
+        F.sT = n2;
+        F.lauum(F.Tm, n2);
+        HIPCHK(c, F.err);
+        src = F.Tm;
+      }
+      hipLaunchKernelGGL(nh_form_q_kernel, dim3((unsigned)(n2 / 256), len), dim3(256), 0, st, src, n2, npad,
+                         k.spb + (size_t)a * SP_STRIDE, lch ? 1 : 0, alpha + (size_t)a * npad, N, npad, z.Q + (size_t)a * n2,
+                         n2, z.diagq + (size_t)a * npad);
+      HIPCHK(c, hipGetLastError());
+      return 0;
+    });
+    if (rc_runs) return rc_runs;
+    HIPCHK(c, tm.mark1());
+    // b, c. the covariance planes: operand, then B_p = Q d_p K on the plain batched GEMM
+    for (int p = 0; p < cov_N; ++p) {
+      if (int rc = nh_launch_plane(c, po->cd, z, cnt, p, k.xsb, k.spb, alpha, N)) return rc;
+      GemmArgs g;
+      g.A = z.Q, g.B = z.Op, g.C = z.B + (size_t)p * n2;
+      g.sA = n2, g.sB = n2, g.sC = (long long)ppl * n2;
+      g.lda = g.ldb = g.ldc = npad;
+      g.M = g.N = g.K = npad;
+      g.alpha = 1.0, g.beta = 0;
+      g.klo = KLO_ZERO, g.khi = KHI_FULL, g.lower_only = 0;
+      g.tiles_n = npad / TILE;
+      HIPCHK(c, launch_gemm<double>(st, g, false, true, cnt));
+    }
+    HIPCHK(c, tm.mark2());
+    for (int nz = 0; nz < noise_N; ++nz) {  // (a batch of planes cov_N + nz: sample stride ppl n2)
+      hipLaunchKernelGGL(nh_noise_plane_kernel, dim3((unsigned)(n2 / 256), cnt), dim3(256), 0, st, (const double*)z.Q, n2,
+                         (const double*)(z.E + (size_t)nz * cnt * npad), alpha, npad, z.B + (size_t)(cov_N + nz) * n2,
+                         (long long)ppl * n2, z.X + (size_t)(cov_N + nz) * cnt * npad);
+    }
+    // f. w_p = Q u_p and v_k = Q d_k m
+    hipLaunchKernelGGL(nh_matvec_kernel, dim3(npad / 4, nvec, cnt), dim3(256), 0, st, (const double*)z.Q, n2, npad,
+                       (const double*)z.X, z.Y);
+    HIPCHK(c, hipGetLastError());
+    // d. the Gram pass, e. the second-derivative contraction
+    HIPCHK(c, gc.record(0, st));
+    if (int rc = nh_launch_gram(c, z, cnt)) return rc;
+    HIPCHK(c, gc.record(1, st));
+    HIPCHK(c, cc.record(0, st));
+    if (ard)
+      if (int rc = nh_launch_d2(c, po->cd, z, cnt, k.xsb, k.spb, alpha, N)) return rc;
+    HIPCHK(c, cc.record(1, st));
+    HIPCHK(c, tm.stop());
+    HIPCHK(c, hipMemcpyAsync(hX.data(), z.X, (size_t)ppl * cnt * npad * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hY.data(), z.Y, (size_t)nvec * cnt * npad * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hal.data(), alpha, (size_t)cnt * npad * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hdq.data(), z.diagq, (size_t)cnt * npad * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hgr.data(), z.grsum, (size_t)cnt * z.npairs * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hg.data(), z.gsum, (size_t)cov_N * cnt * 2 * 8, hipMemcpyDeviceToHost, st));
+    if (nd2) HIPCHK(c, hipMemcpyAsync(hd2.data(), z.d2sum, (size_t)cnt * nd2 * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    tm.accumulate();
+    gram_us += gc.elapsed_us();
+    contract_us += cc.elapsed_us();
+    // the small dot products and the assembly: the lower triangle, mirrored
+    for (int i = 0; i < cnt; ++i) {
+      const int s = s0 + i;
+      const double* al = &hal[(size_t)i * npad];
+      const double* dq = &hdq[(size_t)i * npad];
+      auto uvec = [&](int p) { return &hX[((size_t)p * cnt + i) * npad]; };
+      auto yvec = [&](int v) { return &hY[((size_t)v * cnt + i) * npad]; };
+      auto dmv = [&](int kk) { return &hdm[((size_t)kk * cnt + i) * npad]; };
+      auto dot = [&](const double* x, const double* y) {
+        double t = 0.0;
+        for (int a = 0; a < N; ++a) t = std::fma(x[a], y[a], t);
+        return t;
+      };
+      double* Hs = H + (size_t)s * P * P;
+      double* gs = dnlz + (size_t)s * P;
+      const double* g = &hg[(size_t)i * 2];  // sample i's pair of plane p at g[p * cnt * 2]
+      const int gstride = cnt * 2;
+      for (int p = 0; p < ppl; ++p) {
+        const double g1 = p < cov_N ? g[(size_t)p * gstride] : dot(dq, &he[((size_t)(p - cov_N) * cnt + i) * npad]);
+        gs[p] = 0.5 * g1;
+        for (int q = 0; q <= p; ++q) {
+          const double second = p < cov_N ? nh_second(po->cd, p, q, g, gstride, &hd2[(size_t)i * nd2]) : 0.0;
+          const double v = -0.5 * hgr[(size_t)i * z.npairs + p * (p + 1) / 2 + q] + dot(uvec(p), yvec(q)) + 0.5 * second;
+          Hs[(size_t)p * P + q] = Hs[(size_t)q * P + p] = v;
+        }
+      }
+      for (int kk = 0; kk < mean_N; ++kk) {
+        const int r = ppl + kk;
+        gs[r] = -dot(al, dmv(kk));
+        for (int p = 0; p < ppl; ++p) Hs[(size_t)r * P + p] = Hs[(size_t)p * P + r] = dot(yvec(p), dmv(kk));
+        for (int l = 0; l <= kk; ++l) Hs[(size_t)r * P + ppl + l] = Hs[(size_t)(ppl + l) * P + r] = dot(dmv(kk), yvec(ppl + l));
+      }
+      std::copy(al, al + N, alpha_out + (size_t)s * N);
+      std::copy(dq, dq + N, diagq_out + (size_t)s * N);
+    }
+  }
+  c->nll_hess_gram_us = (unsigned long long)gram_us;
+  c->nll_hess_contract_us = (unsigned long long)contract_us;
+  return 0;
+}
+
 }  // namespace
 
 // test-hook helpers
@@ -5427,7 +5702,7 @@ void gpc_destroy(gpc_ctx* c) {
   DevBuf* bufs[] = {&c->dX,   &c->dY,  &c->mA,    &c->mW,  &c->mT,   &c->xs,   &c->spb,  &c->mulb, &c->divb,
                     &c->dvec, &c->rvec,  &c->zvec, &c->avec, &c->scal, &c->parts, &c->gout, &c->diagq,
                     &c->dmb,  &c->dsn2b, &c->mg,  &c->ng,   &c->ks,   &c->vb,   &c->xss,  &c->pout, &c->kss,
-                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->qmix, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
+                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->qmix, &c->nhs, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
   for (auto& g : c->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (DevBuf* b : bufs) b->release();
@@ -5933,6 +6208,32 @@ int gpc_predict_hess(gpc_post* po, const double* xstar, int M, int compute_var, 
                               : hess_impl<float>(po, xstar, M, var, fmu, fs2, dfmu, dfs2, hmu, hs2);
 }
 
+int gpc_nll_hess(gpc_post* po, const double* dm, int mean_N, const double* dsn2, int dsn2_rows, int noise_N, double* H,
+                 double* dnlz, double* alpha, double* diagq) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!H || !dnlz || !alpha || !diagq || mean_N < 0 || noise_N < 0 || (mean_N > 0 && !dm) || (noise_N > 0 && !dsn2) ||
+      (noise_N > 0 && dsn2_rows != 1 && dsn2_rows != po->N))
+    FAIL(c, "gpc_nll_hess: bad arguments (H, dnlz, alpha, diagq are required; dm with mean_N > 0; dsn2 with noise_N > 0 "
+            "and dsn2_rows 1 or N)");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_nll_hess: this posterior was built from caller-provided K; a caller-provided kernel has no second "
+            "derivative with respect to its hyperparameters");
+  if (po->dtype != GPC_F64) FAIL(c, "gpc_nll_hess: the Hessian is fp64 only; this posterior is stored in fp32");
+  if ((po->cd.kind == K_MATERN || po->cd.kind == K_MATERN_ISO) && po->cd.degree == 1)
+    FAIL(c, "gpc_nll_hess: the Matern kernel of degree 1 has no second radial factor (and an infinite first one on the "
+            "diagonal)");
+  if (po->cd.cov_N + noise_N > NH_MAXP)
+    FAIL(c, "gpc_nll_hess: " + std::to_string(po->cd.cov_N + noise_N) + " covariance and noise hyperparameters; the Gram "
+            "pass takes at most " + std::to_string(NH_MAXP));
+  if (!cov_is_iso(po->cd.kind) && nh_pairs(po->D) > NH_D2_MAX)
+    FAIL(c, "gpc_nll_hess: D = " + std::to_string(po->D) + " has " + std::to_string(nh_pairs(po->D)) +
+            " lengthscale pairs; the contraction holds at most " + std::to_string(NH_D2_MAX));
+  if (int rc = require_factorized(po, "gpc_nll_hess")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return nll_hess_impl(po, dm, mean_N, dsn2, dsn2_rows, noise_N, H, dnlz, alpha, diagq);
+}
+
 int gpc_draw(gpc_post* po, const double* xstar, int M, int R, unsigned long long seed, int s_offset,
              const double* noise_sd, double* f, double* tau) {
   if (!po) return -2;
@@ -6263,6 +6564,8 @@ const Option OPTIONS[] = {
     {"small_polled", GPC_COUNTER(small_polled)},  // one-leaf calls completed by the polled word ...
     {"small_synced", GPC_COUNTER(small_synced)},  // ... and by a stream synchronisation
     {"hess_contract_us", GPC_COUNTER(hess_contract_us)},  // device time of the contraction passes (kernel + reduction) of the last gpc_predict_hess (timed calls only)
+    {"nll_hess_gram_us", GPC_COUNTER(nll_hess_gram_us)},  // device time of the Gram pass (kernel + reduction) of the last gpc_nll_hess (timed calls only)
+    {"nll_hess_contract_us", GPC_COUNTER(nll_hess_contract_us)},  // ... of its second-derivative contraction (ARD families; 0 for the isotropic ones)
     {"grad_post_gram_us", GPC_COUNTER(grad_post_gram_us)},  // device time of the Gram passes of the last gpc_grad_post (timed calls only)
     {"cov_fused", GPC_COUNTER(cov_fused)},        // gpc_predict_cov calls reduced in the product's epilogue
     {"quad_mix_gemms", GPC_COUNTER(quad_mix_gemms)},  // MFMA GEMM launches inside gpc_quad_mix
@@ -6576,6 +6879,107 @@ int gpc_debug_hess_contract(gpc_ctx* c, int kernel_id, int degree, int dtype, co
   cd.cov_N = cov_count_of(kernel_id, D);
   return dtype == GPC_F64 ? debug_hess_impl<double>(c, cd, hyp_cov, X, N, xstar, M, alpha, Q, out_alpha, out_q)
                           : debug_hess_impl<float>(c, cd, hyp_cov, X, N, xstar, M, alpha, Q, out_alpha, out_q);
+}
+
+// gpc_debug_nll_plane / gpc_debug_nll_d2: the plane kernel and the second-derivative contraction of gpc_nll_hess
+// (nll_hess.h) on one sample with caller-given alpha and dense symmetric Q (null: zeros), launched as the call launches
+// them; gpc_debug_nll_gram: its Gram pass on caller-given planes.
+namespace {
+struct NhHookSample {
+  ScratchDev sd;
+  NhScratch z;
+  CovDesc cd;
+  int N = 0, npad = 0;
+  double *xs = nullptr, *sp = nullptr, *al = nullptr;
+  int init(gpc_ctx* c, const char* fn, int kernel_id, int degree, const double* hyp, const double* X, int N_, int D,
+           const double* alpha, const double* Qd) {
+    cd.kind = kernel_id, cd.degree = degree, cd.D = D, cd.cov_N = cov_count_of(kernel_id, D);
+    N = N_, npad = pad_tile(N);
+    const int nd2 = cov_is_iso(kernel_id) ? 0 : nh_pairs(D);
+    std::vector<double> mul(D), dv(D), hsp(SP_STRIDE, 0.0), hal(npad, 0.0), hq((size_t)npad * npad, 0.0);
+    double sf2 = 0.0, rqa = 1.0;
+    scaling_of(kernel_id, degree, D, hyp, mul.data(), dv.data(), &sf2, &rqa);
+    hsp[SP_SF2] = sf2, hsp[SP_RQA] = rqa, hsp[SP_KSCALE] = 1.0, hsp[SP_SL] = 1.0;
+    std::copy(alpha, alpha + N, hal.begin());
+    if (Qd)
+      for (int i = 0; i < N; ++i) std::copy(Qd + (size_t)i * N, Qd + (size_t)(i + 1) * N, hq.begin() + (size_t)i * npad);
+    double* dX = sd.get<double>((size_t)N * D);
+    double* dmul = sd.get<double>(D);
+    double* ddv = sd.get<double>(D);
+    sp = sd.get<double>(SP_STRIDE);
+    al = sd.get<double>(npad);
+    xs = sd.get<double>((size_t)npad * D);
+    double* blk = sd.get<double>(NhScratch::per_sample(npad, cd.cov_N, 0, 0, nd2));
+    if (!dX || !dmul || !ddv || !sp || !al || !xs || !blk) FAIL(c, std::string(fn) + ": out of device memory");
+    z.carve(blk, 1, npad, cd.cov_N, 0, 0, nd2);
+    HIPCHK(c, hipMemcpy(dX, X, (size_t)N * D * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(dmul, mul.data(), (size_t)D * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(ddv, dv.data(), (size_t)D * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(sp, hsp.data(), SP_STRIDE * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(al, hal.data(), (size_t)npad * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(z.Q, hq.data(), hq.size() * 8, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)npad * D + 255) / 256), 1), dim3(256), 0, c->st,
+                       (const double*)dX, N, npad, D, (const double*)dmul, (const double*)ddv, xs);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  }
+};
+bool nh_hook_kernel_ok(int kernel_id, int degree) {
+  return valid_kernel(kernel_id, degree) && !((kernel_id == K_MATERN || kernel_id == K_MATERN_ISO) && degree == 1);
+}
+}  // namespace
+
+int gpc_debug_nll_plane(gpc_ctx* c, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D, int p,
+                        const double* alpha, const double* Q, double* plane, double* u, double* g) {
+  if (!c) return -2;
+  if (!nh_hook_kernel_ok(kernel_id, degree) || !hyp_cov || !X || N <= 0 || D <= 0 || !alpha || !plane || !u || !g || p < 0 ||
+      p >= cov_count_of(kernel_id, D))
+    FAIL(c, "gpc_debug_nll_plane: bad arguments (Matern 1 has no Hessian; p < cov_N)");
+  HIPCHK(c, hipSetDevice(c->device));
+  NhHookSample h;
+  if (int rc = h.init(c, "gpc_debug_nll_plane", kernel_id, degree, hyp_cov, X, N, D, alpha, Q)) return rc;
+  if (int rc = nh_launch_plane(c, h.cd, h.z, 1, p, h.xs, h.sp, h.al, N)) return rc;
+  const int npad = h.npad;
+  std::vector<double> hp((size_t)npad * npad), hu(npad);
+  HIPCHK(c, hipMemcpyAsync(hp.data(), h.z.Op, hp.size() * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(c, hipMemcpyAsync(hu.data(), h.z.X + (size_t)p * npad, (size_t)npad * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(c, hipMemcpyAsync(g, h.z.gsum + (size_t)p * 2, 16, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  for (int i = 0; i < N; ++i) std::copy(hp.begin() + (size_t)i * npad, hp.begin() + (size_t)i * npad + N, plane + (size_t)i * N);
+  std::copy(hu.begin(), hu.begin() + N, u);
+  return 0;
+}
+
+int gpc_debug_nll_d2(gpc_ctx* c, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                     const double* alpha, const double* Q, double* out) {
+  if (!c) return -2;
+  if (!nh_hook_kernel_ok(kernel_id, degree) || cov_is_iso(kernel_id) || !hyp_cov || !X || N <= 0 || D <= 0 ||
+      nh_pairs(D) > NH_D2_MAX || !alpha || !Q || !out)
+    FAIL(c, "gpc_debug_nll_d2: bad arguments (ARD families only; Matern 1 has no Hessian)");
+  HIPCHK(c, hipSetDevice(c->device));
+  NhHookSample h;
+  if (int rc = h.init(c, "gpc_debug_nll_d2", kernel_id, degree, hyp_cov, X, N, D, alpha, Q)) return rc;
+  if (int rc = nh_launch_d2(c, h.cd, h.z, 1, h.xs, h.sp, h.al, N)) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, h.z.d2sum, (size_t)nh_pairs(D) * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  return 0;
+}
+
+int gpc_debug_nll_gram(gpc_ctx* c, int npad, int P, const double* planes, double* out) {
+  if (!c) return -2;
+  if (npad <= 0 || npad % CT || npad > 4096 || P <= 0 || P > NH_MAXP || !planes || !out)
+    FAIL(c, "gpc_debug_nll_gram: bad arguments (npad a multiple of 64 up to 4096, 1 <= P <= 128)");
+  HIPCHK(c, hipSetDevice(c->device));
+  ScratchDev sd;
+  NhScratch z;
+  double* blk = sd.get<double>(NhScratch::per_sample(npad, P, 0, 0, 0));
+  if (!blk) FAIL(c, "gpc_debug_nll_gram: out of device memory");
+  z.carve(blk, 1, npad, P, 0, 0, 0);
+  HIPCHK(c, hipMemcpy(z.B, planes, (size_t)P * npad * npad * 8, hipMemcpyHostToDevice));
+  if (int rc = nh_launch_gram(c, z, 1)) return rc;
+  HIPCHK(c, hipMemcpyAsync(out, z.grsum, (size_t)z.npairs * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  return 0;
 }
 
 // Debug: a 64-bit hash (sum of the bit patterns, wrapping) of every 128 x 128 tile of one workspace matrix of the LAST call

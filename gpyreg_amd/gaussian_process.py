@@ -970,6 +970,148 @@ class GP:
             return -r[0], -r[1]
         return -r
 
+    # ------------------------------------------------------------------ curvature of the objective
+    def _nll_hess_check(self, who):
+        """The refusals of the marginal-likelihood Hessian that need no device."""
+        from . import _nllhess as _nh
+        from .mean_functions import ConstantMean, NegativeQuadratic, ZeroMean
+        from .noise_functions import GaussianNoise
+
+        if not self._builtin:
+            raise NotImplementedError(f"{who}: the covariance function {self.covariance!r} is user-defined; its second "
+                                      "derivatives with respect to the hyperparameters are unknown")
+        if self.dtype != "f64":
+            raise NotImplementedError(f"{who}: the Hessian is computed in fp64 only; this GP's dtype is {self.dtype!r}")
+        _nh.check_kind(*self._kid(), who=who)
+        if type(self.noise) is not GaussianNoise:
+            raise NotImplementedError(f"{who}: the noise function {self.noise!r} ({type(self.noise).__name__}) is "
+                                      "user-defined; its second derivatives with respect to the hyperparameters are unknown")
+        if type(self.mean) not in (ZeroMean, ConstantMean, NegativeQuadratic):
+            raise NotImplementedError(f"{who}: the mean function {self.mean!r} ({type(self.mean).__name__}) is "
+                                      "user-defined; its second derivatives with respect to the hyperparameters are unknown")
+
+    def nll_hess_batch(self, hyp=None):
+        """Negative log marginal likelihood, its gradient and its HESSIAN with respect to the hyperparameters for many
+        hyperparameter vectors: ``hyp`` (S, hyp_N) -> nlZ (S,), dnlZ (S, hyp_N), H (S, hyp_N, hyp_N), ordered
+        [cov | noise | mean] as ``nll_batch``'s gradient.  Every H[s] is symmetric to the bit.
+
+        ``hyp=None`` uses the resident posteriors (appended points included); otherwise temporary posteriors are built
+        for ``hyp`` and freed.  The closed form (``_nllhess``) runs on the device (gpc_nll_hess) at each sample's own
+        jitter multiplier, held fixed; the second derivatives of the noise and mean functions are added here.  dnlZ
+        comes from the same sums and equals ``nll_batch``'s to rounding.
+
+        Built-in covariance functions, the stock ``GaussianNoise`` and the stock mean functions in float64 only
+        (NotImplementedError otherwise, naming the reason); the Matern kernel of degree 1 has no second derivative.
+        Under a process group the call is NOT sharded: it runs on the calling rank alone, whatever the others do, and
+        exchanges nothing (resident posteriors that are sharded are rebuilt locally as temporaries)."""
+        self._nll_hess_check("nll_hess_batch")
+        return self._nll_hess_local(hyp)
+
+    @_on_device
+    def _nll_hess_local(self, hyp):
+        """``nll_hess_batch`` after its refusals: this rank's device call and the plugin terms."""
+        from . import _nllhess as _nh
+
+        cov_N, noise_N, mean_N = counts = self._counts()
+        resident = hyp is None
+        if resident:
+            self._require_posteriors()
+            hyp = np.stack([p.hyp for p in self.posteriors])
+            resident = self._post_range is None and self._post_handle is not None
+        hyp = np.atleast_2d(np.asarray(hyp, dtype=float))
+        if hyp.shape[1] != cov_N + noise_N + mean_N:
+            raise ValueError("Input hyperparameter array is the wrong shape!")
+        S = hyp.shape[0]
+        ctx = self._ctx()
+        pv = self._plugin_values(hyp, True)
+        kid, deg = self._kid()
+        if resident:
+            handle = self._post_handle
+            mult = np.array([float(_sn2_mult(p)) for p in self.posteriors])
+        else:
+            handle, mult, _, info = ctx.posterior_batch(kid, deg, _DTYPES[self.dtype], hyp[:, :cov_N], pv["m"], pv["sn2"],
+                                                        pv["vec"])
+            if np.any(info != 0):
+                handle.free()
+                raise LinAlgError("Singular matrix for L Cholesky decomposition")
+        try:
+            H, g, alpha, diagq = handle.nll_hess(cov_N, pv["dm"], pv["dsn2"])
+        finally:
+            if not resident:
+                handle.free()
+        for s in range(S):
+            if noise_N:
+                d2 = _nh.noise_d2(self.noise, hyp[s, cov_N:cov_N + noise_N], self.X, self.y, self.s2)
+                H[s, cov_N:cov_N + noise_N, cov_N:cov_N + noise_N] += 0.5 * mult[s] * np.einsum(
+                    "a,anm->nm", diagq[s], np.broadcast_to(d2, (diagq.shape[1],) + d2.shape[1:]))
+            if mean_N:
+                d2 = _nh.mean_d2(self.mean, _mean_hyp(hyp[s], counts), self.X)
+                H[s, cov_N + noise_N:, cov_N + noise_N:] -= np.einsum("a,akl->kl", alpha[s], d2)
+        nlz, _, info = self._nll_batch_local(hyp, False, counts)
+        if np.any(info != 0):
+            raise LinAlgError("Singular matrix for L Cholesky decomposition")
+        return nlz, g, H
+
+    def log_posterior_hess(self, hyp):
+        """Value, gradient and Hessian of ``log_posterior`` at ONE hyperparameter vector (array or dict), the prior
+        terms included (the four prior families are products over the dimensions: a diagonal), in ``log_posterior``'s
+        sign convention.  A fixed dimension (lower bound = upper bound) carries NaN, as in the gradient."""
+        from . import _nllhess as _nh
+
+        if isinstance(hyp, dict):
+            hyp = self.hyperparameters_from_dict(hyp)[0]
+        hyp = np.asarray(hyp, dtype=float).ravel()
+        nlz, g, H = self.nll_hess_batch(hyp[None, :])
+        val, grad, hess = -float(nlz[0]), -g[0], -H[0]
+        if self.no_prior is not True:
+            lp, dlp = self.__compute_log_priors(hyp, True)
+            d2 = _nh.prior_d2(hyp, self.hyper_priors, self.lower_bounds, self.upper_bounds)
+            val, grad = val + lp, grad + dlp
+            hess[np.diag_indices_from(hess)] += d2
+        return val, grad, hess
+
+    def laplace_approximation(self, hyp=None, free=None):
+        """The Laplace approximation of the hyperparameter posterior at ``hyp`` (default: the first resident sample,
+        e.g. the MAP that ``fit`` left): a dict with
+
+            mean          ``hyp``
+            hess          the Hessian of the NEGATIVE log posterior over the free coordinates
+            cov           its inverse, or None
+            is_pd         whether ``hess`` is positive definite (a Cholesky factorization succeeds)
+            log_evidence  log p(y) ~ log posterior(hyp) + k/2 log 2 pi - 1/2 log det hess, k free coordinates; None
+                          when ``hess`` is not positive definite
+            free          the indices of the free coordinates
+
+        ``free``: indices (or a boolean mask) of the coordinates the Gaussian lives on; by default all that are not
+        fixed by the bounds.  ``hyp`` is taken as it is -- the caller vouches that it is a mode.  Nothing is repaired:
+        when the Hessian is not positive definite (a ridge, a saddle, a point that is no mode), ``cov`` is None and
+        ``is_pd`` False."""
+        if hyp is None:
+            self._require_posteriors()
+            hyp = self.posteriors[0].hyp
+        if isinstance(hyp, dict):
+            hyp = self.hyperparameters_from_dict(hyp)[0]
+        hyp = np.asarray(hyp, dtype=float).ravel().copy()
+        val, _, hess = self.log_posterior_hess(hyp)
+        if free is None:
+            lb, ub = self.lower_bounds, self.upper_bounds
+            fixed = np.zeros(hyp.size, bool) if lb is None or ub is None else np.asarray(lb) == np.asarray(ub)
+            free = np.flatnonzero(~fixed)
+        else:
+            free = np.asarray(free)
+            free = np.flatnonzero(free) if free.dtype == bool else free.astype(int)
+        A = -hess[np.ix_(free, free)]
+        out = dict(mean=hyp, hess=A, cov=None, is_pd=False, log_evidence=None, free=free)
+        if free.size and np.all(np.isfinite(A)):
+            try:
+                L = np.linalg.cholesky(A)
+            except LinAlgError:
+                return out
+            Li = np.linalg.solve(L, np.eye(free.size))
+            out.update(cov=Li.T @ Li, is_pd=True,
+                       log_evidence=val + 0.5 * free.size * np.log(2 * np.pi) - np.sum(np.log(np.diag(L))))
+        return out
+
     # ------------------------------------------------------------------ hyperparameters
     def get_hyperparameters(self, as_array: bool = False):
         """Reference :516-552."""

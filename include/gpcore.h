@@ -198,6 +198,37 @@ int gpc_grad_post(gpc_post* post, const double* xstar, int M, int diag_only, dou
 int gpc_predict_hess(gpc_post* post, const double* xstar, int M, int compute_var, double* fmu, double* fs2, double* dfmu,
                      double* dfs2, double* hmu, double* hs2);
 
+/* ---- GP.nll_hess_batch: the Hessian of the negative log marginal likelihood with respect to the hyperparameters ------
+ * Per sample of the posterior, at the posterior's own jitter multiplier `mult` (held fixed), with
+ * Sigma = K + mult diag(sn2), Q = Sigma^-1, alpha = Q (y - m), Qm = Q - alpha alpha^T, hyperparameters ordered
+ * [cov | noise | mean] as gpc_nll_batch's dnlz, P = cov_N + noise_N + mean_N.  Every covariance and noise
+ * hyperparameter p is a plane d_p Sigma (lengthscale a: F o d_a^2 on the scaled inputs, isotropic: F o r2; log sf: 2 K;
+ * RQ shape: Ka; noise n: mult diag(dsn2_n));  B_p = Q d_p Sigma, u_p = d_p Sigma alpha, w_p = Q u_p, v_k = Q d_k m:
+ *   H[s][p][q] = -1/2 tr(B_p B_q) + u_p . w_q + 1/2 <Qm, d2_pq K>       planes p, q
+ *   H[s][p][k] =  w_p . d_k m                                            plane p, mean k
+ *   H[s][k][l] =  d_k m . v_l                                            mean k, l
+ * d2_pq K on log scales as gpyreg_amd/csrc/nll_hess.h lists them (G = -2 dF/d(r2) of gpc_predict_hess; a pair at
+ * r2 = 0 contributes nothing to a lengthscale term).  H EXCLUDES the two terms that need second derivatives of the
+ * plugins: 1/2 mult sum_a diagq[a] d2 sn2_a (noise x noise) and -alpha . d2 m (mean x mean); the call returns
+ * alpha (S x N) and diagq = diag(Qm) (S x N) for the caller to add them.  dnlz (S x P) is the gradient from the same
+ * sums: gpc_nll_batch's to rounding, not to the bit.  H is symmetric to the bit (lower triangle computed, mirrored).
+ *   dm   S x N x mean_N (may be NULL with mean_N = 0);  dsn2  S x dsn2_rows x noise_N, dsn2_rows = 1 (one noise value)
+ *   or N (per point), WITHOUT the multiplier.
+ * Device work per sample: Q formed once (W^T W / sl for L_chol samples, -L for the low-noise ones: one path after
+ * that); per covariance hyperparameter one dense plane (u and the sums <Qm, .> fused in) and one plain fp64 GEMM
+ * B_p = Q d_p K -- the log sf plane included, because the posterior does not keep sn2; the noise planes are column
+ * scalings of Q; a streaming Gram pass for tr(B_p B_q); for the ARD families the contraction sum Qm G d_a^2 d_b^2; the
+ * dot products of the downloaded vectors and the assembly on the host.  Every reduction's order is fixed by the shape:
+ * a sample's results are the same bits whatever the batch, the other samples or the chunking (GPC_MEM_BUDGET_MB).
+ * Scratch per sample: (cov_N + noise_N + 2) N_pad^2 doubles (Q, the B planes, one operand) and vectors.
+ * gpc_last_timing: ms_total = the device sections, ms_factor = the planes and their products; options
+ * "nll_hess_gram_us" / "nll_hess_contract_us": the Gram pass and the contraction of the last call.
+ * Returns -2 with a message of its own for: bad arguments; a posterior from caller-provided K; an fp32 posterior (the
+ * Hessian is fp64 only); the Matern kernel of degree 1 (no second radial factor G); more than 128 planes or more than
+ * 860 lengthscale pairs; a failed factorization; one sample's scratch exceeding the budget (N_pad, planes, bytes). */
+int gpc_nll_hess(gpc_post* post, const double* dm, int mean_N, const double* dsn2, int dsn2_rows, int noise_N, double* H,
+                 double* dnlz, double* alpha, double* diagq);
+
 /* ---- GP.draw_functions: joint posterior draws, n_draws per sample (extends gaussian_process.py:2241-2329) ----
  * For every sample s of the posterior (global index s_offset + s), draw r < R and query point j < M:
  *   f[(j*R + r)*S + s] = fmu_js + (L_s z_{s,r})_j  (+ noise_sd[j*S + s] z'_{s,r,j})
@@ -551,6 +582,23 @@ int gpc_debug_block_gram(gpc_ctx* ctx, int dtype, int n, int M, int Dp, const do
 int gpc_debug_hess_contract(gpc_ctx* ctx, int kernel_id, int degree, int dtype, const double* hyp_cov, const double* X,
                             int N, int D, const double* xstar, int M, const double* alpha, const double* Q,
                             double* out_alpha, double* out_q);
+
+/* gpc_nll_hess's plane kernel on one sample, launched as the call launches it (inputs scaled from hyp_cov as in
+ * gpc_debug_cov): covariance hyperparameter p < cov_N, weights alpha[N] and a dense symmetric Q[N x N] (NULL: zeros).
+ *   plane[N x N] = d K / d theta_p;   u[N] = plane alpha;   g[0] = <Q - alpha alpha^T, plane>;
+ *   g[1] = <Q - alpha alpha^T, second>, second = G r2^2 (isotropic lengthscale) | dF/dlog(alpha) d_p^2 (RQ lengthscale)
+ *          | dKa/dlog(alpha) (RQ shape) | 0                                                                              */
+int gpc_debug_nll_plane(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                        int p, const double* alpha, const double* Q, double* plane, double* u, double* g);
+
+/* gpc_nll_hess's second-derivative contraction (ARD families) on caller-given weights: over the lower triangle,
+ *   out[a (a + 1) / 2 + b] = sum_ij w_ij (Q_ij - alpha_i alpha_j) G_ij d_a^2 d_b^2,  a >= b,  w = 1 on the diagonal, else 2 */
+int gpc_debug_nll_d2(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                     const double* alpha, const double* Q, double* out);
+
+/* gpc_nll_hess's Gram pass on caller-given planes[P][npad][npad] (npad a multiple of 64, at most 4096; P <= 128):
+ *   out[p (p + 1) / 2 + q] = sum_ab planes[p][a][b] planes[q][b][a],  q <= p  (P (P + 1) / 2 values, nothing beyond)   */
+int gpc_debug_nll_gram(gpc_ctx* ctx, int npad, int P, const double* planes, double* out);
 
 /* Debug: wrapping-sum hash of every 128 x 128 tile of one workspace matrix as the LAST call left it (which: 0 = A, 1 = W,
  * 2 = T; sample: position in the last chunk); out[(npad/128)^2].  Finds the tile where two schedules differ.          */
