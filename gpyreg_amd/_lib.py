@@ -70,6 +70,8 @@ SIGNATURES = {
     "gpc_grad_post": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "gpc_predict_hess": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpc_nll_hess": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpc_predict_hyp_grad": (
+        C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "gpc_post_append": (C.c_int, [_vp, _dp, _dp, C.c_double, _ip]),
     "gpc_post_recompute": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_post_append_K": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_double, _ip]),
@@ -108,6 +110,8 @@ SIGNATURES = {
     "gpc_debug_block_gram": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]),
     "gpc_debug_hess_contract": (
         C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpc_debug_hyp_cross": (
+        C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_int, _dp, _dp]),
     "gpc_debug_nll_plane": (
         C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "gpc_debug_nll_d2": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
@@ -591,6 +595,26 @@ class Context:
         return out_a, out_q
 
     @_serial
+    def debug_hyp_cross(self, kernel_id, degree, hyp_cov, X, x_star, alpha, W, Q=None):
+        """gpc_debug_hyp_cross: the fused cross pass of gpc_predict_hyp_grad on the weights alpha (N,), the weight
+        vectors W (P, N), P >= cov_N, and, optionally, a dense Q (N, M); without Q the mean-only kernel runs.  Returns
+        (B (M, P) = sum_i k W[p], A (M, cov_N) = sum_i d_c k alpha, C (M, cov_N) = sum_i d_c k Q | None); the log sf
+        column holds k itself, not 2 k."""
+        X, xs, hyp, al, Wc = _f64(X), _f64(x_star), _f64(hyp_cov), _f64(alpha).ravel(), _f64(W)
+        N, D = X.shape
+        M = xs.shape[0]
+        Qc = None if Q is None else _f64(Q)
+        if xs.shape[1] != D or al.size != N or Wc.ndim != 2 or Wc.shape[1] != N or (Qc is not None and Qc.shape != (N, M)):
+            raise ValueError("debug_hyp_cross: X (N, D), x_star (M, D), alpha (N,), W (P, N), Q (N, M)")
+        P = Wc.shape[0]
+        cov_N = self._lib.gpc_cov_count(kernel_id, D)
+        out = np.empty((M, P + cov_N * (1 if Qc is None else 2)))
+        rc = self._lib.gpc_debug_hyp_cross(self._h, kernel_id, degree, _ptr(hyp), _ptr(X), N, D, _ptr(xs), M, _ptr(al),
+                                           _ptr(Wc), P, _ptr(Qc), _ptr(out))
+        self._check(rc, "gpc_debug_hyp_cross")
+        return out[:, :P], out[:, P:P + cov_N], (None if Qc is None else out[:, P + cov_N:])
+
+    @_serial
     def debug_nll_plane(self, kernel_id, degree, hyp_cov, X, p, alpha, Q=None):
         """gpc_debug_nll_plane: the plane kernel of gpc_nll_hess for covariance hyperparameter ``p`` with weights alpha
         (N,) and a dense symmetric Q (N, N) (None: zeros).  Returns (plane (N, N), u (N,), g (2,))."""
@@ -733,6 +757,33 @@ class PostHandle:
                                         _ptr(dq))
         self.ctx._check(rc, "gpc_nll_hess")
         return H, g, al, dq
+
+    @_serial
+    def predict_hyp_grad(self, x_star, cov_N, sn2, dsn2=None, dm=None, compute_var=True):
+        """gpc_predict_hyp_grad: ``cov_N`` covariance hyperparameters (gpc_cov_count of the posterior's kernel); sn2 (S, 1 | N), dsn2 (S, 1 | N, noise_N) | None (both without the jitter multiplier),
+        dm (S, N, mean_N) | None.  Returns fmu, fs2 (M, S) and dfmu, dfs2 (M, P, S), P = cov_N + noise_N + mean_N, the
+        latent prediction (no mean function, unclamped) and its derivatives.  Without ``compute_var`` fs2 and dfs2 are
+        None and no product is launched."""
+        xs = _f64(x_star)
+        M = xs.shape[0]
+        S, N = self.S, self.N
+        sn2_c = _f64(sn2).reshape(S, -1)
+        rows = sn2_c.shape[1]
+        dm_c = None if dm is None or dm.shape[2] == 0 else _f64(dm)
+        ds_c = None if dsn2 is None or dsn2.shape[2] == 0 else _f64(dsn2)
+        mean_N = 0 if dm_c is None else dm_c.shape[2]
+        noise_N = 0 if ds_c is None else ds_c.shape[2]
+        if rows not in (1, N) or (dm_c is not None and dm_c.shape[:2] != (S, N)) or \
+                (ds_c is not None and ds_c.shape[:2] != (S, rows)):
+            raise ValueError("predict_hyp_grad: sn2 (S, 1 or N); dsn2 (S, 1 or N, noise_N) with sn2's rows; dm (S, N, mean_N)")
+        P = int(cov_N) + noise_N + mean_N
+        fmu, dfmu = np.empty((M, S)), np.empty((M, P, S))
+        fs2 = np.empty((M, S)) if compute_var else None
+        dfs2 = np.empty((M, P, S)) if compute_var else None
+        rc = self.ctx._lib.gpc_predict_hyp_grad(self._h, _ptr(xs), M, int(bool(compute_var)), _ptr(sn2_c), _ptr(ds_c), rows,
+                                                noise_N, _ptr(dm_c), mean_N, _ptr(fmu), _ptr(fs2), _ptr(dfmu), _ptr(dfs2))
+        self.ctx._check(rc, "gpc_predict_hyp_grad")
+        return fmu, fs2, dfmu, dfs2
 
     @_serial
     def predict_K(self, Ks, Kss=None, want_var=True):

@@ -28,6 +28,7 @@
 #include "gemm.h"
 #include "gradpost.h"
 #include "hess.h"
+#include "hypgrad.h"
 #include "nll_hess.h"
 #include "leaf.h"
 #include "lookahead.h"
@@ -522,6 +523,7 @@ struct gpc_ctx {
   DevBuf qcon;                   // quad_grad: the measures' constants (quad.h: quad_grad_prep_kernel)
   DevBuf qmix;                   // quad_mix: the whole scratch of a chunk, carved up in quad_mix_impl
   DevBuf nhs;                    // nll_hess: the whole scratch of a chunk, carved up in nll_hess_impl (NhScratch)
+  DevBuf hgs;                    // predict_hyp_grad: the whole scratch of a chunk, carved up in hyp_grad_impl (HgScratch)
   DevBuf zb, fb, dout, daux;     // draw: Z, F = L Z, the draws, [logdet | info | noise sd] (the factor: mA mW mT)
   DevBuf dbg1, dbg2, dbg3;       // debug hooks / fetch staging
   PinBuf pin;                    // pinned staging for host<->device transfers (see PinBuf)
@@ -3907,6 +3909,289 @@ int nll_hess_impl(gpc_post* po, const double* dm, int mean_N, const double* dsn2
   return 0;
 }
 
+// ---- gpc_predict_hyp_grad: derivatives of the latent prediction with respect to the hyperparameters (hypgrad.h) --------
+// The covariance hyperparameters that are planes (a lengthscale or the RQ shape: everything but log sf), in order
+inline std::vector<int> hg_plane_cols(const CovDesc& cd) {
+  std::vector<int> cols;
+  for (int p = 0; p < cd.cov_N; ++p) {
+    int mode, dim;
+    nh_plane_of(cd, p, &mode, &dim);
+    if (mode != NH_SF) cols.push_back(p);
+  }
+  return cols;
+}
+
+// Device buffers of a chunk of `cnt` samples and one super-block of `msb` queries, carved from one allocation (all
+// doubles; vectors are [vector][sample][npad], panels [sample][npad][msb])
+struct HgScratch {
+  double *Op, *KP, *VP, *Qa, *X, *Y, *Vn, *tmp, *tpart, *upart, *mupart, *cpart, *csum, *dpart, *dsum, *xss, *qs;
+  // doubles of one sample's share
+  static size_t per_sample(int npad, int D, int P, int nvv, int ngp, int msb, bool var, int nout) {
+    const size_t n2 = (size_t)npad * npad, nt = npad / CT, nch = npad / TRC, np = npad, mm = msb;
+    size_t d = (2 * (size_t)P + 1 + nch + nt) * np + (nt + 1) * (size_t)nout * mm + mm * D + 1;
+    if (var) d += n2 + 3 * np * mm + (size_t)nvv * np + nt * mm + nt * (1 + (size_t)nvv) * mm + ((size_t)ngp + nvv) * mm;
+    return d;
+  }
+  void carve(double* p, int cnt, int npad, int D, int P, int nvv, int ngp, int msb, bool var, int nout) {
+    const size_t n2 = (size_t)npad * npad, nt = npad / CT, nch = npad / TRC, np = npad, mm = msb, c = cnt;
+    auto take = [&](size_t n) {
+      double* r = p;
+      p += n;
+      return r;
+    };
+    Op = take(var ? c * n2 : 0);
+    KP = take(var ? c * np * mm : 0);
+    VP = take(var ? c * np * mm : 0);
+    Qa = take(var ? c * np * mm : 0);
+    dpart = take(var ? c * nt * (1 + (size_t)nvv) * mm : 0);
+    dsum = take(var ? c * ((size_t)ngp + nvv) * mm : 0);
+    mupart = take(var ? c * nt * mm : 0);
+    Vn = take(var ? c * (size_t)nvv * np : 0);
+    X = take(c * P * np);
+    Y = take(c * P * np);
+    tmp = take(c * np);
+    tpart = take(c * nch * np);
+    upart = take(c * nt * np);
+    cpart = take(c * nt * nout * mm);
+    csum = take(c * nout * mm);
+    xss = take(c * mm * D);
+    qs = take(c);
+  }
+};
+
+// Per chunk of samples and super-block of queries (all of the call's queries unless the budget says otherwise), with
+// the variance:
+//   panel K* = k(X, x*) (cross_tile_kernel),  Qs = W^T (W K*) (L_chol; q = Qs / sl) | L K* (low noise; q = -Qs)
+//   per plane (lengthscale, RQ shape): d_p K dense with u_p = d_p K alpha fused in (hg_plane_kernel),
+//     T = d_p K Qs on the plain fp64 GEMM, q_j^T d_p K q_j by hg_coldot_kernel (the first plane's pass also leaves the
+//     weighted column sums of squares sum_i v_i q_ij^2)
+//   w_p = Q u_p for all P vectors: two triangular matrix-vector products (L_chol) | one symmetric (low noise)
+//   the fused cross pass (hg_cross_kernel) and the assembly on the host.
+// Without the variance: the planes' u_p alone (nothing dense), the same weights, hg_cross_mean_kernel -- no product
+// with W, no GEMM; fmu and dfmu are the same instructions on the same operands.  The planes are rebuilt per super-block.
+// gpc_last_timing: the device sections and, of these, the interval of the products with W and the planes' build, GEMM
+// and column dots.
+int hyp_grad_impl(gpc_post* po, const double* xstar, int M, bool var, const double* sn2, const double* dsn2, int rows,
+                  int noise_N, const double* dm, int mean_N, double* fmu, double* fs2, double* dfmu, double* dfs2) {
+  gpc_ctx* c = po->ctx;
+  const int S = po->S, N = po->N, D = po->D, npad = po->npad, cov_N = po->cd.cov_N;
+  const int P = cov_N + noise_N + mean_N, sfc = hg_sf_col(po->cd);
+  const std::vector<int> gcols = hg_plane_cols(po->cd);
+  const int ngp = (int)gcols.size(), nvv = rows == 1 ? 1 : 1 + noise_N;
+  const int nout = hg_cross_sums(P, cov_N, var), nt = npad / CT, nch = npad / TRC;
+  hipStream_t st = c->st;
+  const long long n2 = (long long)npad * npad, sM = n2;
+  // the super-block: all queries, halved until one sample fits
+  int msb = pad_tile(M), chunk = 0;
+  size_t per = 0;
+  for (;;) {
+    per = HgScratch::per_sample(npad, D, P, nvv, ngp, msb, var, nout) * 8;
+    const size_t held = c->hgs.bytes;
+    const int blk = msb;
+    chunk = plan_chunk(c, S, per, 0, held, (size_t)S * per <= held, 0, false, [&](size_t budget) {
+      return "gpc_predict_hyp_grad: the scratch of one sample with one query block (" + std::to_string(per) +
+             " bytes: N_pad = " + std::to_string(npad) + ", planes = " + std::to_string(ngp) + ", block = " +
+             std::to_string(blk) + " queries) exceeds the device memory budget (" + std::to_string(budget) + " bytes)";
+    });
+    if (chunk || msb == TILE) break;
+    msb = pad_tile(msb / 2);
+  }
+  if (!chunk) return -2;
+  const long long sK = (long long)npad * msb;
+  HIPCHK(c, c->hgs.ensure((size_t)chunk * per));
+  HIPCHK(c, c->xss.ensure((size_t)M * D * 8));
+  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
+  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
+  HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
+  HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
+  double* const d_xa = c->xss.as<double>();
+  HgScratch z;
+  CallTimer tm{c, CallTimer::wanted(c, npad)};
+  HIPCHK(c, hipMemcpyAsync(d_xa, xstar, (size_t)M * D * 8, hipMemcpyHostToDevice, st));
+  ChunkConsts k;
+  if (int rc = k.init(po, chunk == S)) return rc;
+  c->ms_total = c->ms_factor = 0;
+  const size_t vlen = (size_t)chunk * npad;
+  const size_t dper = ((size_t)ngp + nvv) * msb;  // doubles of a sample's quadratic-form sums
+  std::vector<double> hX((size_t)P * vlen), hV(var ? (size_t)nvv * vlen : 0), hqs(chunk), hc((size_t)chunk * nout * msb),
+      hd(var ? (size_t)chunk * dper : 0);
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    z.carve(c->hgs.as<double>(), cnt, npad, D, P, nvv, ngp, msb, var, nout);
+    if (int rc = k.stage(s0, cnt, true)) return rc;
+    const double* alpha = po->alpha.as<double>() + (size_t)s0 * npad;
+    // what the weights start from, zero in the padding: mult sn2 (log sf), mult d_n sn2 (noise n), d_k m (mean k); the
+    // planes' rows are written on the device.  For the column dots: sn2 and d_n sn2 per point
+    std::fill(hX.begin(), hX.end(), 0.0);
+    std::fill(hV.begin(), hV.end(), 0.0);
+    for (int i = 0; i < cnt; ++i) {
+      const int s = s0 + i;
+      const double mult = po->mult[s];
+      hqs[i] = po->lchol[s] ? 1.0 / po->sp[(size_t)s * SP_STRIDE + SP_SL] : -1.0;
+      for (int a = 0; a < N; ++a) {
+        const size_t r = (size_t)s * rows + (rows == 1 ? 0 : a);
+        hX[((size_t)sfc * cnt + i) * npad + a] = mult * sn2[r];
+        for (int nz = 0; nz < noise_N; ++nz) hX[((size_t)(cov_N + nz) * cnt + i) * npad + a] = mult * dsn2[r * noise_N + nz];
+        for (int kk = 0; kk < mean_N; ++kk)
+          hX[((size_t)(cov_N + noise_N + kk) * cnt + i) * npad + a] = dm[((size_t)s * N + a) * mean_N + kk];
+        if (var && rows != 1) {
+          hV[(size_t)i * npad + a] = sn2[r];
+          for (int nz = 0; nz < noise_N; ++nz) hV[((size_t)(1 + nz) * cnt + i) * npad + a] = dsn2[r * noise_N + nz];
+        }
+      }
+    }
+    if (var && rows != 1) HIPCHK(c, hipMemcpyAsync(z.Vn, hV.data(), (size_t)nvv * cnt * npad * 8, hipMemcpyHostToDevice, st));
+    if (var) HIPCHK(c, hipMemcpyAsync(z.qs, hqs.data(), (size_t)cnt * 8, hipMemcpyHostToDevice, st));
+    for (int b0 = 0; b0 < M; b0 += msb) {
+      const int mq = std::min(msb, M - b0);
+      HIPCHK(c, hipMemcpyAsync(z.X + (size_t)sfc * cnt * npad, &hX[(size_t)sfc * cnt * npad], (size_t)cnt * npad * 8,
+                               hipMemcpyHostToDevice, st));
+      if (P > cov_N)
+        HIPCHK(c, hipMemcpyAsync(z.X + (size_t)cov_N * cnt * npad, &hX[(size_t)cov_N * cnt * npad],
+                                 (size_t)(P - cov_N) * cnt * npad * 8, hipMemcpyHostToDevice, st));
+      HIPCHK(c, tm.start());
+      hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)msb * D + 255) / 256), cnt), dim3(256), 0, st,
+                         (const double*)(d_xa + (size_t)b0 * D), mq, msb, D, k.mulb, k.divb, z.xss);
+      if (var) {
+        GPC_COV_DISPATCH(cross_tile_kernel, double, po->cd, dim3(msb / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
+                         (const double*)z.xss, k.spb, alpha, npad, N, npad, mq, msb, z.KP, sK, z.mupart);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, tm.mark1());
+        // the products of every run of equal L_chol: Qs = W^T (W K*) | L K*
+        const int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+          GemmArgs g = tri_product_args<double>(po, s0 + a, lch, z.KP + (size_t)a * sK, (lch ? z.VP : z.Qa) + (size_t)a * sK,
+                                                sK, msb, msb);
+          HIPCHK(c, launch_gemm<double>(st, g, false, true, len));
+          if (lch) {  // W^T upper triangular: k from the tile row's diagonal block on
+            GemmArgs q = g;
+            q.B = z.VP + (size_t)a * sK;
+            q.C = z.Qa + (size_t)a * sK;
+            q.klo = KLO_ROW;
+            q.khi = KHI_FULL;
+            HIPCHK(c, launch_gemm<double>(st, q, true, true, len));
+          }
+          return 0;
+        });
+        if (rc_runs) return rc_runs;
+      }
+      // the planes: u_p and, with the variance, the quadratic forms through T = d_p K Qs (T overlays the panel K*)
+      for (int gi = 0; gi < ngp; ++gi) {
+        const int p = gcols[gi];
+        int mode, dim;
+        nh_plane_of(po->cd, p, &mode, &dim);
+        GPC_COV_DISPATCH(hg_plane_kernel, double, po->cd, dim3(nt, nt, cnt), dim3(256), 0, st, po->cd, k.xsb, k.spb, alpha, N,
+                         npad, mode, dim, var ? z.Op : (double*)nullptr, n2, z.upart);
+        hipLaunchKernelGGL(colpart_reduce_kernel, dim3((npad + 255) / 256, cnt), dim3(256), 0, st, (const double*)z.upart, nt,
+                           npad, z.X + (size_t)p * cnt * npad);
+        HIPCHK(c, hipGetLastError());
+        if (!var) continue;
+        GemmArgs g;
+        g.A = z.Op, g.B = z.Qa, g.C = z.KP;
+        g.sA = n2, g.sB = g.sC = sK;
+        g.lda = npad, g.ldb = g.ldc = msb;
+        g.M = npad, g.N = msb, g.K = npad;
+        g.alpha = 1.0, g.beta = 0;
+        g.klo = KLO_ZERO, g.khi = KHI_FULL, g.lower_only = 0;
+        g.tiles_n = msb / TILE;
+        HIPCHK(c, launch_gemm<double>(st, g, false, true, cnt));
+        const int nv = gi == 0 ? nvv : 0;  // the first plane's pass also takes the weighted sums of squares
+        hipLaunchKernelGGL(hg_coldot_kernel, dim3(msb / TILE, nt, cnt), dim3(256), 0, st, (const double*)z.Qa, sK,
+                           (const double*)z.KP, sK, msb, (const double*)(rows == 1 ? nullptr : z.Vn), nv, N, npad, z.dpart);
+        double* const dst = gi == 0 ? z.dsum : z.dsum + (size_t)cnt * (1 + nvv) * msb + (size_t)(gi - 1) * cnt * msb;
+        hipLaunchKernelGGL(colpart_reduce_kernel, dim3((unsigned)(((size_t)(1 + nv) * msb + 255) / 256), cnt), dim3(256), 0, st,
+                           (const double*)z.dpart, nt, (1 + nv) * msb, dst);
+        HIPCHK(c, hipGetLastError());
+      }
+      if (var) HIPCHK(c, tm.mark2());
+      // the weights: e o alpha, then w = Q x for all P vectors, then log sf's 2 alpha - 2 (.)
+      hipLaunchKernelGGL(hg_mul_alpha_kernel, dim3((npad + 255) / 256, 1, cnt), dim3(256), 0, st,
+                         z.X + (size_t)sfc * cnt * npad, alpha, npad);
+      if (noise_N)
+        hipLaunchKernelGGL(hg_mul_alpha_kernel, dim3((npad + 255) / 256, noise_N, cnt), dim3(256), 0, st,
+                           z.X + (size_t)cov_N * cnt * npad, alpha, npad);
+      for (int p = 0; p < P; ++p) {
+        const double* xp = z.X + (size_t)p * cnt * npad;
+        double* const yp = z.Y + (size_t)p * cnt * npad;
+        const int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+          if (lch) {
+            const double* W = po->W.as<double>() + (size_t)(s0 + a) * sM;
+            hipLaunchKernelGGL((trmv_kernel<double>), dim3(npad / 4, len), dim3(256), 0, st, W, sM, npad, xp + (size_t)a * npad,
+                               npad, z.tmp + (size_t)a * npad, 0);
+            hipLaunchKernelGGL((trmv_t_part_kernel<double, 8>), dim3((npad + 64 * MM<double>::VEC - 1) / (64 * MM<double>::VEC), nch, len),
+                               dim3(256), 0, st, W, sM, npad, (const double*)(z.tmp + (size_t)a * npad), npad,
+                               z.tpart + (size_t)a * nch * npad, (double*)nullptr);
+            hipLaunchKernelGGL(trmv_t_sum_kernel, dim3(npad / 128, len), dim3(128), 0, st,
+                               (const double*)(z.tpart + (size_t)a * nch * npad), npad, k.spb + (size_t)a * SP_STRIDE,
+                               (int)SP_STRIDE, (int)SP_SL, yp + (size_t)a * npad);
+          } else {  // y = 0 - L x (L = -(K + Sigma)^-1, full symmetric)
+            HIPCHK(c, hipMemsetAsync(yp + (size_t)a * npad, 0, (size_t)len * npad * 8, st));
+            hipLaunchKernelGGL((gemv_sub_kernel<double>), dim3(npad / 4, len), dim3(256), 0, st,
+                               (const double*)(po->A.as<double>() + (size_t)(s0 + a) * sM), sM, npad, xp + (size_t)a * npad,
+                               yp + (size_t)a * npad, npad, 0, 0, npad);
+          }
+          return 0;
+        });
+        if (rc_runs) return rc_runs;
+      }
+      hipLaunchKernelGGL(hg_sf_weight_kernel, dim3((npad + 255) / 256, cnt), dim3(256), 0, st,
+                         z.Y + (size_t)sfc * cnt * npad, alpha, npad);
+      HIPCHK(c, hipGetLastError());
+      // the fused cross pass
+      if (var)
+        GPC_COV_DISPATCH(hg_cross_kernel, double, po->cd, dim3(msb / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
+                         (const double*)z.xss, k.spb, alpha, (const double*)z.Y, P, (const double*)z.Qa, sK, msb,
+                         (const double*)z.qs, N, npad, mq, msb, z.cpart);
+      else
+        GPC_COV_DISPATCH(hg_cross_mean_kernel, double, po->cd, dim3(msb / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
+                         (const double*)z.xss, k.spb, alpha, (const double*)z.Y, P, N, npad, mq, msb, z.cpart);
+      hipLaunchKernelGGL(colpart_reduce_kernel, dim3((unsigned)(((size_t)nout * msb + 255) / 256), cnt), dim3(256), 0, st,
+                         (const double*)z.cpart, nt, nout * msb, z.csum);
+      HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipMemcpyAsync(hc.data(), z.csum, (size_t)cnt * nout * msb * 8, hipMemcpyDeviceToHost, st));
+      if (var) HIPCHK(c, hipMemcpyAsync(hd.data(), z.dsum, (size_t)cnt * dper * 8, hipMemcpyDeviceToHost, st));
+      HIPCHK(c, tm.stop());
+      HIPCHK(c, hipStreamSynchronize(st));
+      if (var) tm.accumulate();
+      else if (tm.on) {  // no product: the whole device section, nothing in it a product's
+        float t03 = 0;
+        (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
+        c->ms_total += t03;
+      }
+      // into the caller's layout
+      for (int i = 0; i < cnt; ++i) {
+        const int s = s0 + i;
+        const double mult = po->mult[s], qs2 = hqs[i] * hqs[i], sf2 = po->sp[(size_t)s * SP_STRIDE + SP_SF2];
+        const double* cs = &hc[(size_t)i * nout * msb];
+        const double* d0 = var ? &hd[(size_t)i * (1 + nvv) * msb] : nullptr;
+        for (int jj = 0; jj < mq; ++jj) {
+          const size_t j = (size_t)b0 + jj;
+          auto Bs = [&](int p) { return cs[(size_t)p * msb + jj]; };
+          auto As = [&](int cc) { return cs[(size_t)(P + cc) * msb + jj]; };
+          auto Cs = [&](int cc) { return cs[(size_t)(P + cov_N + cc) * msb + jj]; };
+          fmu[j * S + s] = As(sfc);
+          for (int p = 0; p < P; ++p)
+            dfmu[(j * P + p) * S + s] = p < cov_N ? (p == sfc ? 2.0 * As(p) : As(p)) - Bs(p) : -Bs(p);
+          if (!var) continue;
+          const double f2 = sf2 - Cs(sfc);
+          fs2[j * S + s] = f2;
+          auto vsum = [&](int v) { return d0[(size_t)(1 + v) * msb + jj]; };
+          for (int gi = 0; gi < ngp; ++gi) {
+            const double quad = gi == 0 ? d0[jj] : hd[(size_t)cnt * (1 + nvv) * msb + ((size_t)(gi - 1) * cnt + i) * msb + jj];
+            dfs2[(j * P + gcols[gi]) * S + s] = -2.0 * Cs(gcols[gi]) + qs2 * quad;
+          }
+          const double sq = rows == 1 ? sn2[s] * vsum(0) : vsum(0);
+          dfs2[(j * P + sfc) * S + s] = 2.0 * f2 - 2.0 * mult * qs2 * sq;
+          for (int nz = 0; nz < noise_N; ++nz)
+            dfs2[(j * P + cov_N + nz) * S + s] =
+                mult * qs2 * (rows == 1 ? dsn2[(size_t)s * noise_N + nz] * vsum(0) : vsum(1 + nz));
+          for (int kk = 0; kk < mean_N; ++kk) dfs2[(j * P + cov_N + noise_N + kk) * S + s] = 0.0;
+        }
+      }
+    }
+  }
+  return 0;
+}
+
 }  // namespace
 
 // test-hook helpers
@@ -4435,6 +4720,75 @@ int debug_hess_impl(gpc_ctx* c, CovDesc cd, const double* hyp, const double* X, 
         if (Qd) out_q[(size_t)(q0 + jj) * npl + p] = h[(size_t)(npl + p) * mb + jj];
       }
   }
+  return 0;
+}
+}  // namespace
+
+// gpc_debug_hyp_cross: the fused cross pass of gpc_predict_hyp_grad (hypgrad.h) on caller-provided weights, one launch
+// over all queries; Q (optional): dense N x M, taken with factor 1; without it the mean-only kernel runs
+namespace {
+int debug_hyp_cross_impl(gpc_ctx* c, CovDesc cd, const double* hyp, const double* X, int N, const double* Xstar, int M,
+                         const double* alpha, const double* Wv, int P, const double* Qd, double* out) {
+  hipStream_t st = c->st;
+  const int D = cd.D, npad = pad_tile(N), mpad = pad_tile(M), nt = npad / CT;
+  const int nout = hg_cross_sums(P, cd.cov_N, Qd != nullptr);
+  std::vector<double> mul(D), dv(D), sp(SP_STRIDE, 0.0), hal(npad, 0.0), hW((size_t)P * npad, 0.0);
+  double sf2 = 0.0, rqa = 1.0;
+  scaling_of(cd.kind, cd.degree, D, hyp, mul.data(), dv.data(), &sf2, &rqa);
+  sp[SP_SF2] = sf2;
+  sp[SP_RQA] = rqa;
+  sp[SP_KSCALE] = 1.0;
+  sp[SP_SL] = 1.0;
+  std::copy(alpha, alpha + N, hal.begin());
+  for (int p = 0; p < P; ++p) std::copy(Wv + (size_t)p * N, Wv + (size_t)(p + 1) * N, hW.begin() + (size_t)p * npad);
+  ScratchDev sd;
+  double* dX = sd.get<double>((size_t)N * D);
+  double* dXq = sd.get<double>((size_t)M * D);
+  double* dmul = sd.get<double>(D);
+  double* ddv = sd.get<double>(D);
+  double* dsp = sd.get<double>(SP_STRIDE);
+  double* dal = sd.get<double>(npad);
+  double* dW = sd.get<double>((size_t)P * npad);
+  double* xs = sd.get<double>((size_t)npad * D);
+  double* xss = sd.get<double>((size_t)mpad * D);
+  double* dQ = sd.get<double>((size_t)npad * mpad);
+  double* dqs = sd.get<double>(1);
+  double* part = sd.get<double>((size_t)nt * nout * mpad);
+  double* sums = sd.get<double>((size_t)nout * mpad);
+  if (!dX || !dXq || !dmul || !ddv || !dsp || !dal || !dW || !xs || !xss || !dQ || !dqs || !part || !sums)
+    FAIL(c, "gpc_debug_hyp_cross: out of device memory");
+  const double one = 1.0;
+  HIPCHK(c, hipMemcpy(dX, X, (size_t)N * D * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dXq, Xstar, (size_t)M * D * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dmul, mul.data(), (size_t)D * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(ddv, dv.data(), (size_t)D * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dsp, sp.data(), SP_STRIDE * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dal, hal.data(), (size_t)npad * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dW, hW.data(), hW.size() * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dqs, &one, 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)npad * D + 255) / 256), 1), dim3(256), 0, st,
+                     (const double*)dX, N, npad, D, (const double*)dmul, (const double*)ddv, xs);
+  hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mpad * D + 255) / 256), 1), dim3(256), 0, st,
+                     (const double*)dXq, M, mpad, D, (const double*)dmul, (const double*)ddv, xss);
+  if (Qd) {
+    std::vector<double> hQ((size_t)npad * mpad, 0.0);
+    for (int i = 0; i < N; ++i) std::copy(Qd + (size_t)i * M, Qd + (size_t)(i + 1) * M, hQ.begin() + (size_t)i * mpad);
+    HIPCHK(c, hipMemcpy(dQ, hQ.data(), hQ.size() * 8, hipMemcpyHostToDevice));
+    GPC_COV_DISPATCH(hg_cross_kernel, double, cd, dim3(mpad / CT, npad / CT, 1), dim3(256), 0, st, cd, (const double*)xs,
+                     (const double*)xss, (const double*)dsp, (const double*)dal, (const double*)dW, P, (const double*)dQ,
+                     (long long)npad * mpad, mpad, (const double*)dqs, N, npad, M, mpad, part);
+  } else {
+    GPC_COV_DISPATCH(hg_cross_mean_kernel, double, cd, dim3(mpad / CT, npad / CT, 1), dim3(256), 0, st, cd, (const double*)xs,
+                     (const double*)xss, (const double*)dsp, (const double*)dal, (const double*)dW, P, N, npad, M, mpad, part);
+  }
+  hipLaunchKernelGGL(colpart_reduce_kernel, dim3((unsigned)(((size_t)nout * mpad + 255) / 256), 1), dim3(256), 0, st,
+                     (const double*)part, nt, nout * mpad, sums);
+  HIPCHK(c, hipGetLastError());
+  std::vector<double> h((size_t)nout * mpad);
+  HIPCHK(c, hipMemcpyAsync(h.data(), sums, h.size() * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  for (int j = 0; j < M; ++j)
+    for (int o = 0; o < nout; ++o) out[(size_t)j * nout + o] = h[(size_t)o * mpad + j];
   return 0;
 }
 }  // namespace
@@ -5702,7 +6056,7 @@ void gpc_destroy(gpc_ctx* c) {
   DevBuf* bufs[] = {&c->dX,   &c->dY,  &c->mA,    &c->mW,  &c->mT,   &c->xs,   &c->spb,  &c->mulb, &c->divb,
                     &c->dvec, &c->rvec,  &c->zvec, &c->avec, &c->scal, &c->parts, &c->gout, &c->diagq,
                     &c->dmb,  &c->dsn2b, &c->mg,  &c->ng,   &c->ks,   &c->vb,   &c->xss,  &c->pout, &c->kss,
-                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->qmix, &c->nhs, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
+                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->qmix, &c->nhs, &c->hgs, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
   for (auto& g : c->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (DevBuf* b : bufs) b->release();
@@ -6232,6 +6586,29 @@ int gpc_nll_hess(gpc_post* po, const double* dm, int mean_N, const double* dsn2,
   if (int rc = require_factorized(po, "gpc_nll_hess")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   return nll_hess_impl(po, dm, mean_N, dsn2, dsn2_rows, noise_N, H, dnlz, alpha, diagq);
+}
+
+int gpc_predict_hyp_grad(gpc_post* po, const double* xstar, int M, int compute_var, const double* sn2, const double* dsn2,
+                         int noise_rows, int noise_N, const double* dm, int mean_N, double* fmu, double* fs2, double* dfmu,
+                         double* dfs2) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  const bool var = compute_var != 0;
+  if (!xstar || M <= 0 || !sn2 || !fmu || !dfmu || (var && (!fs2 || !dfs2)) || noise_N < 0 || mean_N < 0 ||
+      (noise_N > 0 && !dsn2) || (mean_N > 0 && !dm) || (noise_rows != 1 && noise_rows != po->N))
+    FAIL(c, "gpc_predict_hyp_grad: bad arguments (xstar, sn2, fmu, dfmu are required, fs2 and dfs2 with compute_var; dsn2 "
+            "with noise_N > 0; dm with mean_N > 0; noise_rows 1 or N)");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_predict_hyp_grad: this posterior was built from caller-provided K; a caller-provided kernel has no "
+            "derivative with respect to its hyperparameters");
+  if (po->dtype != GPC_F64)
+    FAIL(c, "gpc_predict_hyp_grad: the hyperparameter gradients are fp64 only; this posterior is stored in fp32");
+  if ((po->cd.kind == K_MATERN || po->cd.kind == K_MATERN_ISO) && po->cd.degree == 1)
+    FAIL(c, "gpc_predict_hyp_grad: the Matern kernel of degree 1 has an infinite radial factor on the diagonal; its "
+            "lengthscale planes are not formed");
+  if (int rc = require_factorized(po, "gpc_predict_hyp_grad")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return hyp_grad_impl(po, xstar, M, var, sn2, dsn2, noise_rows, noise_N, dm, mean_N, fmu, fs2, dfmu, dfs2);
 }
 
 int gpc_draw(gpc_post* po, const double* xstar, int M, int R, unsigned long long seed, int s_offset,
@@ -6879,6 +7256,25 @@ int gpc_debug_hess_contract(gpc_ctx* c, int kernel_id, int degree, int dtype, co
   cd.cov_N = cov_count_of(kernel_id, D);
   return dtype == GPC_F64 ? debug_hess_impl<double>(c, cd, hyp_cov, X, N, xstar, M, alpha, Q, out_alpha, out_q)
                           : debug_hess_impl<float>(c, cd, hyp_cov, X, N, xstar, M, alpha, Q, out_alpha, out_q);
+}
+
+int gpc_debug_hyp_cross(gpc_ctx* c, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                        const double* xstar, int M, const double* alpha, const double* W, int P, const double* Q,
+                        double* out) {
+  if (!c) return -2;
+  if (!valid_kernel(kernel_id, degree) || !hyp_cov || !X || N <= 0 || D <= 0 || !xstar || M <= 0 || !alpha || !W || P <= 0 ||
+      !out)
+    FAIL(c, "gpc_debug_hyp_cross: bad arguments");
+  if ((kernel_id == K_MATERN || kernel_id == K_MATERN_ISO) && degree == 1)
+    FAIL(c, "gpc_debug_hyp_cross: the Matern kernel of degree 1 has an infinite radial factor on the diagonal");
+  HIPCHK(c, hipSetDevice(c->device));
+  CovDesc cd;
+  cd.kind = kernel_id;
+  cd.degree = degree;
+  cd.D = D;
+  cd.cov_N = cov_count_of(kernel_id, D);
+  if (P < cd.cov_N) FAIL(c, "gpc_debug_hyp_cross: P must cover the covariance hyperparameters");
+  return debug_hyp_cross_impl(c, cd, hyp_cov, X, N, xstar, M, alpha, W, P, Q, out);
 }
 
 // gpc_debug_nll_plane / gpc_debug_nll_d2: the plane kernel and the second-derivative contraction of gpc_nll_hess

@@ -1837,6 +1837,122 @@ class GP:
         mu_m, s2_m, _ = _mix_samples(mu, s2)
         return np.reshape(mu_m, (-1,)), None if s2_m is None else np.reshape(s2_m, (-1,)), dmu_m, ds2_m, Hmu_m, Hs2_m
 
+    def _hyp_grad_check(self, who):
+        """The refusals of the hyperparameter gradients of predictions that need no device."""
+        from . import _hypgrad as _hg
+        from .mean_functions import ConstantMean, NegativeQuadratic, ZeroMean
+        from .noise_functions import GaussianNoise
+
+        if not self._builtin:
+            raise NotImplementedError(f"{who}: the covariance function {self.covariance!r} is user-defined; its "
+                                      "derivatives with respect to the hyperparameters are not on the device")
+        if self.dtype != "f64":
+            raise NotImplementedError(f"{who}: the hyperparameter gradients are computed in fp64 only; this GP's dtype is "
+                                      f"{self.dtype!r}")
+        _hg.check_kind(*self._kid(), who=who)
+        if type(self.noise) is not GaussianNoise:
+            raise NotImplementedError(f"{who}: the noise function {self.noise!r} ({type(self.noise).__name__}) is "
+                                      "user-defined; its derivatives at x_star are unknown")
+        if type(self.mean) not in (ZeroMean, ConstantMean, NegativeQuadratic):
+            raise NotImplementedError(f"{who}: the mean function {self.mean!r} ({type(self.mean).__name__}) is "
+                                      "user-defined; its derivatives at x_star are unknown")
+
+    def predict_hyp_grad(self, x_star, compute_var: bool = True, add_noise: bool = False, s2_star=None):
+        """The prediction at ``x_star`` under every resident hyperparameter sample and its derivatives with respect to
+        that sample's own hyperparameters: (mu, s2, dmu, ds2), mu and s2 (M, S), dmu and ds2 (M, hyp_N, S), entry
+        [j, p, s] the derivative of sample s's prediction at x_star[j] with respect to its hyperparameter p, ordered
+        [cov | noise | mean] on the scales ``nll_batch`` differentiates on.  Always per sample: every sample has its
+        own theta, so no mixture is formed.  With ``compute_var=False`` s2 and ds2 are None and no product with the
+        factors is launched; mu and dmu carry the same bits.
+
+        The derivatives hold each sample's jitter multiplier fixed, as ``nll_hess_batch`` does.  The mean function and
+        d m(x_star) / d theta_mean are added here; with ``add_noise`` so are mult sn2(x_star) (``s2_star``: the
+        provided noise at x_star) and its derivatives in the noise columns.  ``predict_grad``'s conventions: the clamp
+        s2 = max(s2, 0) on the latent variance, and a zero variance gradient where it holds.
+
+        Everything but the plugins runs on the device (gpc_predict_hyp_grad; ``_hypgrad`` has the closed form).
+        Built-in covariance functions, the stock ``GaussianNoise`` and the stock mean functions in float64 only
+        (NotImplementedError otherwise, naming the reason); the Matern kernel of degree 1 is refused.  Under sharding
+        each rank computes its samples and the results are gathered: the same values as one process."""
+        self._hyp_grad_check("predict_hyp_grad")
+        return self._predict_hyp_grad_local(x_star, compute_var, add_noise, s2_star)
+
+    @_on_device
+    def _predict_hyp_grad_local(self, x_star, compute_var, add_noise, s2_star):
+        """``predict_hyp_grad`` after its refusals: the device call and the plugin terms."""
+        x_star, _, s2_star = self._convert_shapes(x_star, None, s2_star)
+        if self.y is None:
+            raise ValueError("predict_hyp_grad: the GP holds no data; the prior's derivatives are the plugins' own")
+        var = bool(compute_var)
+        if add_noise and not var:
+            raise ValueError("predict_hyp_grad: add_noise needs compute_var")
+        self._require_posteriors()
+        s_N = self.posteriors.size
+        M = x_star.shape[0]
+        cov_N, noise_N, mean_N = counts = self._counts()
+        P = cov_N + noise_N + mean_N
+        hyp = np.stack([p.hyp for p in self.posteriors])
+        pv = self._plugin_values(hyp, True)
+
+        def call(handle, local_posts, lo):
+            sl = slice(lo, lo + len(local_posts))
+            fmu, fs2, dfmu, dfs2 = handle.predict_hyp_grad(
+                x_star, cov_N, pv["sn2"][sl], None if pv["dsn2"] is None else pv["dsn2"][sl],
+                None if pv["dm"] is None else pv["dm"][sl], var)
+            return [fmu, dfmu] + ([fs2, dfs2] if var else [])
+
+        layout = [("fmu", (M,)), ("dfmu", (M, P))] + ([("fs2", (M,)), ("dfs2", (M, P))] if var else [])
+        r = self._device_rows(call, layout, x_star, np.array([float(var)]))
+        mu, dmu = r["fmu"].copy(), r["dfmu"].copy()
+        h_mean = _mean_hyp(hyp, counts)
+        m_star = self.mean.values(h_mean, x_star, mean_N > 0)
+        if mean_N > 0:
+            m_star, dm_star = m_star
+            dmu[:, cov_N + noise_N:, :] += np.transpose(dm_star, (1, 2, 0))
+        mu += np.transpose(m_star)
+        if not var:
+            return mu, None, dmu, None
+        s2, ds2 = r["fs2"], r["dfs2"]
+        # the clamp of predict, s2 = max(s2, 0): no gradient where it holds s2 at 0
+        held = s2 <= 0
+        s2 = np.maximum(s2, 0)
+        ds2 = np.where(held[:, None, :], 0.0, ds2)
+        if add_noise:
+            mult = np.array([float(_sn2_mult(p)) for p in self.posteriors])
+            ns, dns = self.noise.values(hyp[:, cov_N:cov_N + noise_N], x_star, None, s2_star, True)
+            s2 = s2 + np.transpose(np.broadcast_to(ns, (s_N, M)) * mult[:, None])
+            if noise_N:
+                dns = np.broadcast_to(dns, (s_N, M, noise_N)) * mult[:, None, None]
+                ds2[:, cov_N:cov_N + noise_N, :] += np.transpose(dns, (1, 2, 0))
+        return mu, s2, dmu, ds2
+
+    def predict_laplace(self, x_star, laplace=None, add_noise: bool = False):
+        """The prediction at the first resident hyperparameter sample theta-hat (e.g. the MAP that ``fit`` left) with the
+        hyperparameter uncertainty of a Laplace approximation carried into it: a dict with
+
+            mu, s2     the prediction at theta-hat (M,), ``predict_hyp_grad``'s
+            var_mu     g_mu^T Sigma g_mu, g_mu = d mu / d theta restricted to ``laplace["free"]``
+            var_s2     g_s2^T Sigma g_s2, the same for the variance
+            s2_total   s2 + var_mu
+
+        ``laplace``: what ``laplace_approximation`` returned (default: ``self.laplace_approximation()``); its ``cov``
+        is Sigma, on the coordinates ``free``.  This is the FIRST-ORDER delta method: Var_theta[mu*] ~ g^T Sigma g, the
+        variance of the linearisation of mu*(theta) about theta-hat under N(theta-hat, Sigma).  ``var_s2`` is returned
+        so that callers can assemble a marginal-GP variance of their choice; no paper's constants are built in.  When
+        ``laplace["cov"]`` is None (``is_pd`` False: the Hessian at theta-hat is not positive definite) a ValueError
+        is raised; nothing is repaired."""
+        from . import _hypgrad as _hg
+
+        if laplace is None:
+            laplace = self.laplace_approximation()
+        if laplace["cov"] is None:
+            raise ValueError("predict_laplace: the Laplace approximation has no covariance (is_pd is False: the Hessian "
+                             "of the negative log posterior is not positive definite at this point)")
+        mu, s2, dmu, ds2 = self.predict_hyp_grad(x_star, True, add_noise)
+        var_mu = _hg.delta_variance(dmu[:, :, 0], laplace["cov"], laplace["free"])
+        var_s2 = _hg.delta_variance(ds2[:, :, 0], laplace["cov"], laplace["free"])
+        return dict(mu=mu[:, 0], s2=s2[:, 0], var_mu=var_mu, var_s2=var_s2, s2_total=s2[:, 0] + var_mu)
+
     @_on_device
     def predict_full(self, x_star, y_star=None, s2_star=None, add_noise: bool = False):
         """Posterior mean and FULL covariance per hyperparameter sample (reference :1561-1661):

@@ -229,6 +229,39 @@ int gpc_predict_hess(gpc_post* post, const double* xstar, int M, int compute_var
 int gpc_nll_hess(gpc_post* post, const double* dm, int mean_N, const double* dsn2, int dsn2_rows, int noise_N, double* H,
                  double* dnlz, double* alpha, double* diagq);
 
+/* ---- GP.predict_hyp_grad: derivatives of the latent prediction with respect to the hyperparameters, per sample -------
+ * Sigma = K + mult diag(sn2) at each sample's own jitter multiplier, held fixed; Q = Sigma^-1, alpha = Q (y - m); for
+ * query j: k_j = k(X, x*_j), q_j = Q k_j, fmu_j = k_j . alpha, fs2_j = k** - k_j . q_j.  Hyperparameters ordered
+ * [cov | noise | mean] on the scales gpc_nll_batch differentiates on, P = cov_N + noise_N + mean_N.  With the weight
+ * vectors  w_p = Q (d_p K alpha) (lengthscale, RQ shape) | 2 alpha - 2 mult Q (sn2 o alpha) (log sf) |
+ * mult Q (dsn2_n o alpha) (noise n) | Q d_k m (mean k)  and the cross planes d_p k_ij = F d_a^2 (isotropic: F r2) |
+ * 2 k | Ka of gpc_nll_hess (a pair at r2 = 0 contributes nothing to a lengthscale term):
+ *   dfmu[(j*P + p)*S + s] = sum_i d_p k_ij alpha_i - sum_i k_ij w_p,i        (first sum: covariance p only)
+ *   dfs2[(j*P + p)*S + s] = -2 sum_i d_p k_ij q_ij + q_j^T (d_p K) q_j       lengthscale, RQ shape
+ *                         = 2 fs2_j - 2 mult sum_i sn2_i q_ij^2              log sf
+ *                         = mult sum_i dsn2_n,i q_ij^2                       noise n;      0 for a mean hyperparameter
+ * fmu, fs2 are laid out as gpc_predict's (M x S, [j*S + s]).  Results are unclamped, without noise at x* and without
+ * a mean function (the caller adds d_k m(x*_j) to the mean columns of dfmu).
+ *   sn2   S x noise_rows,  dsn2  S x noise_rows x noise_N (may be NULL with noise_N = 0), both WITHOUT the multiplier;
+ *   noise_rows = 1 (one noise value) or N (per point);  dm  S x N x mean_N (may be NULL with mean_N = 0).
+ * Device work per sample: the panel Q k* for all queries of a super-block (two products with W for L_chol samples, one
+ * with L otherwise); per lengthscale / shape plane the dense d_p K (u_p = d_p K alpha fused in), one plain fp64 GEMM
+ * T = d_p K (Q k*) and a streaming column dot for q_j^T d_p K q_j (the first plane's pass also takes the weighted
+ * column sums of squares); w_p by triangular matrix-vector products; one fused pass over (training point, query)
+ * tiles for every other sum.  No atomics: a sample's results are the same bits whatever the batch, the other samples
+ * or the chunking (GPC_MEM_BUDGET_MB).  The budget decides the samples per chunk and, when the panels of all queries
+ * do not fit, the queries per super-block (a multiple of 128; the planes are rebuilt per super-block).
+ * compute_var == 0: no product with W or L and no GEMM is launched; fs2, dfs2 may be NULL and are not written; fmu and
+ * dfmu carry the same bits as with the variance; gpc_last_timing's ms_factor is 0.
+ * gpc_last_timing: ms_total = the device sections, ms_factor = the products with W (or L) and the planes (build, GEMM,
+ * column dots).
+ * Returns -2 with a message of its own for: bad arguments; a posterior from caller-provided K; an fp32 posterior (fp64
+ * only); the Matern kernel of degree 1 (F infinite on the diagonal); a failed factorization; one sample with one block
+ * of 128 queries exceeding the budget (the message names N_pad, the planes, the block and the bytes).                 */
+int gpc_predict_hyp_grad(gpc_post* post, const double* xstar, int M, int compute_var, const double* sn2, const double* dsn2,
+                         int noise_rows, int noise_N, const double* dm, int mean_N, double* fmu, double* fs2, double* dfmu,
+                         double* dfs2);
+
 /* ---- GP.draw_functions: joint posterior draws, n_draws per sample (extends gaussian_process.py:2241-2329) ----
  * For every sample s of the posterior (global index s_offset + s), draw r < R and query point j < M:
  *   f[(j*R + r)*S + s] = fmu_js + (L_s z_{s,r})_j  (+ noise_sd[j*S + s] z'_{s,r,j})
@@ -582,6 +615,17 @@ int gpc_debug_block_gram(gpc_ctx* ctx, int dtype, int n, int M, int Dp, const do
 int gpc_debug_hess_contract(gpc_ctx* ctx, int kernel_id, int degree, int dtype, const double* hyp_cov, const double* X,
                             int N, int D, const double* xstar, int M, const double* alpha, const double* Q,
                             double* out_alpha, double* out_q);
+
+/* gpc_predict_hyp_grad's fused cross pass on caller-provided weights, one launch over all queries (inputs scaled from
+ * hyp_cov as in gpc_debug_cov): alpha[N], W[P x N] the weight vectors (P >= cov_N), Q dense N x M taken with factor 1
+ * (optional: NULL runs the kernel of the mean alone, which leaves the C sums out).  out[j][.], rows of P + cov_N (+ cov_N):
+ *   out[j][p]             = sum_i k_ij W[p][i]                                             p < P
+ *   out[j][P + c]         = sum_i d_c k_ij alpha_i                                         c < cov_N
+ *   out[j][P + cov_N + c] = sum_i d_c k_ij Q[i][j]                                         c < cov_N  (with Q)
+ * d_c k = F d_a^2 (lengthscale a; isotropic F r2) | k itself for log sf (the caller doubles it) | Ka (RQ shape).     */
+int gpc_debug_hyp_cross(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                        const double* xstar, int M, const double* alpha, const double* W, int P, const double* Q,
+                        double* out);
 
 /* gpc_nll_hess's plane kernel on one sample, launched as the call launches it (inputs scaled from hyp_cov as in
  * gpc_debug_cov): covariance hyperparameter p < cov_N, weights alpha[N] and a dense symmetric Q[N x N] (NULL: zeros).
