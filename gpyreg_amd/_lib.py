@@ -20,6 +20,7 @@ K_SE, K_MATERN, K_RQ, K_SE_ISO, K_MATERN_ISO = range(5)
 F64, F32 = 0, 1
 KLO_ZERO, KLO_ROW, KLO_COL = 0, 1, 2
 KHI_FULL, KHI_ROW, KHI_COL = 0, 1, 2
+CV_LOSSES = {"lpd": 0, "mse": 1}  # the loss of gpc_cv_grad
 
 # Array arguments are declared void* and passed as the integer address of the NumPy buffer: `a.ctypes.data_as(POINTER(..))`
 # costs ~2 us per argument, the address ~1 us, and an evaluation has a dozen of them -- a visible share of a 90 us call.
@@ -70,6 +71,7 @@ SIGNATURES = {
     "gpc_grad_post": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "gpc_predict_hess": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpc_nll_hess": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpc_cv_grad": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpc_predict_hyp_grad": (
         C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
     "gpc_post_append": (C.c_int, [_vp, _dp, _dp, C.c_double, _ip]),
@@ -116,6 +118,8 @@ SIGNATURES = {
         C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "gpc_debug_nll_d2": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "gpc_debug_nll_gram": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp]),
+    "gpc_debug_cv_trace": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "gpc_debug_cv_weights": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "gpc_debug_normals": (C.c_int, [_vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "gpc_debug_workspace_hash": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
     "gpc_debug_chunk_plan": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_int]),
@@ -659,6 +663,34 @@ class Context:
         return out
 
     @_serial
+    def debug_cv_trace(self, kernel_id, degree, hyp_cov, X, M, alpha, beta):
+        """gpc_debug_cv_trace: the contraction of gpc_cv_grad alone, with the weight
+        G = M - (beta alpha^T + alpha beta^T) / 2 over the lower triangle (M (N, N) is read from its lower triangle).
+        Returns (gsum (cov_N,) = <d_p K, G>, diagG (N,))."""
+        X, hyp, Mc, al, be = _f64(X), _f64(hyp_cov), _f64(M), _f64(alpha).ravel(), _f64(beta).ravel()
+        N, D = X.shape
+        if al.size != N or be.size != N or Mc.shape != (N, N):
+            raise ValueError("debug_cv_trace: X (N, D), M (N, N), alpha (N,), beta (N,)")
+        gsum, dg = np.empty(self._lib.gpc_cov_count(kernel_id, D)), np.empty(N)
+        rc = self._lib.gpc_debug_cv_trace(self._h, kernel_id, degree, _ptr(hyp), _ptr(X), N, D, _ptr(Mc), _ptr(al), _ptr(be),
+                                          _ptr(gsum), _ptr(dg))
+        self._check(rc, "gpc_debug_cv_trace")
+        return gsum, dg
+
+    @_serial
+    def debug_cv_weights(self, loss, alpha, q, weights=None):
+        """gpc_debug_cv_weights: the per-point kernel of gpc_cv_grad; ``loss`` 0 = lpd, 1 = mse.  Returns (c (N,), b (N,))."""
+        al, qc = _f64(alpha).ravel(), _f64(q).ravel()
+        wc = None if weights is None else _f64(weights).ravel()
+        N = al.size
+        if qc.size != N or (wc is not None and wc.size != N):
+            raise ValueError("debug_cv_weights: alpha (N,), q (N,), weights (N,) | None")
+        cw, b = np.empty(N), np.empty(N)
+        rc = self._lib.gpc_debug_cv_weights(self._h, N, int(loss), _ptr(al), _ptr(qc), _ptr(wc), _ptr(cw), _ptr(b))
+        self._check(rc, "gpc_debug_cv_weights")
+        return cw, b
+
+    @_serial
     def debug_normals(self, seed, stream, s, r, j0, count):
         """gpc_debug_normals: the device's z of rows j0 .. j0 + count - 1 of (seed, stream, sample s, draw r)."""
         out = np.empty(count)
@@ -757,6 +789,24 @@ class PostHandle:
                                         _ptr(dq))
         self.ctx._check(rc, "gpc_nll_hess")
         return H, g, al, dq
+
+    @_serial
+    def cv_grad(self, cov_N, loss="lpd", weights=None):
+        """gpc_cv_grad: ``cov_N`` covariance hyperparameters (gpc_cov_count of the posterior's kernel); ``loss`` "lpd" or
+        "mse"; weights (N,) | None.  Returns the six arrays gsum (S, cov_N) = <d_p K, G>, diagG (S, N) = diag(G), beta,
+        alpha, q = diag(Q) and c (S, N each) of the leave-one-out objective (``_cvgrad`` has the formulas)."""
+        S, N = self.S, self.N
+        if loss not in CV_LOSSES:
+            raise ValueError(f"cv_grad: loss must be one of {sorted(CV_LOSSES)}, got {loss!r}")
+        wc = None if weights is None else _f64(weights).ravel()
+        if wc is not None and wc.size != N:
+            raise ValueError("cv_grad: weights (N,)")
+        gsum = np.empty((S, int(cov_N)))
+        dg, be, al, q, cw = (np.empty((S, N)) for _ in range(5))
+        rc = self.ctx._lib.gpc_cv_grad(self._h, CV_LOSSES[loss], _ptr(wc), _ptr(gsum), _ptr(dg), _ptr(be), _ptr(al),
+                                       _ptr(q), _ptr(cw))
+        self.ctx._check(rc, "gpc_cv_grad")
+        return gsum, dg, be, al, q, cw
 
     @_serial
     def predict_hyp_grad(self, x_star, cov_N, sn2, dsn2=None, dm=None, compute_var=True):

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "covfun.h"
 #include "cv.h"
+#include "cvgrad.h"
 #include "draw.h"
 #include "gemm.h"
 #include "gradpost.h"
@@ -495,6 +496,7 @@ struct gpc_ctx {
   unsigned long long grad_post_gram_us = 0;  // Gram passes of the last gpc_grad_post, device microseconds ("grad_post_gram_us")
   unsigned long long hess_contract_us = 0;  // contraction passes of the last gpc_predict_hess, device microseconds ("hess_contract_us")
   unsigned long long nll_hess_gram_us = 0, nll_hess_contract_us = 0;  // Gram pass / second-derivative contraction of the last gpc_nll_hess, device microseconds
+  unsigned long long cv_grad_trace_us = 0;  // contraction pass of the last gpc_cv_grad, device microseconds ("cv_grad_trace_us")
   unsigned long long cov_fused = 0;  // gpc_predict_cov calls whose reduction ran in the product's epilogue ("cov_fused")
   unsigned long long quad_mix_gemms = 0;  // MFMA GEMM launches inside gpc_quad_mix ("quad_mix_gemms"; there should be none)
   int check_queues = 0;  // debug option: verify after every pipeline that the tile queues of its persistent launches were drained
@@ -3909,6 +3911,163 @@ int nll_hess_impl(gpc_post* po, const double* dm, int mean_N, const double* dsn2
   return 0;
 }
 
+// ---- gpc_cv_grad: the leave-one-out objective's weight matrix and its contraction (cvgrad.h) ---------------------------
+// Device buffers of a chunk of `cnt` samples, carved from one allocation (all doubles; vectors are [sample][npad])
+struct CvgScratch {
+  double *Q, *QC, *M, *diagq, *u, *b, *part, *out;
+  // the block that is downloaded, in order: gsum [cnt][cov_N] | diagG | beta | q | cw, [cnt][npad] each
+  double *gsum, *diagG, *beta, *q, *cw;
+  static size_t out_doubles(int cnt, int npad, int cov_N) { return (size_t)cnt * (cov_N + 4 * (size_t)npad); }
+  // doubles of one sample's share
+  static size_t per_sample(int npad, int cov_N) {
+    const size_t n2 = (size_t)npad * npad, nt = npad / CT, ntl = nt * (nt + 1) / 2;
+    return 3 * n2 + 7 * (size_t)npad + (ntl + 1) * (size_t)cov_N;
+  }
+  void carve(double* p, int cnt, int npad, int cov_N) {
+    const size_t n2 = (size_t)npad * npad, nt = npad / CT, ntl = nt * (nt + 1) / 2, c = cnt;
+    auto take = [&](size_t n) {
+      double* r = p;
+      p += n;
+      return r;
+    };
+    Q = take(c * n2);
+    QC = take(c * n2);
+    M = take(c * n2);
+    diagq = take(c * npad);
+    u = take(c * npad);
+    b = take(c * npad);
+    part = take(c * ntl * cov_N);
+    out = gsum = take(c * cov_N);
+    diagG = take(c * npad);
+    beta = take(c * npad);
+    q = take(c * npad);
+    cw = take(c * npad);
+  }
+};
+
+// <d_p K, G> of `cnt` samples into gsum[b][p], diag(G) into diagG: the contraction and the sum of its per-tile partials
+int cvg_launch_trace(gpc_ctx* c, const CovDesc& cd, int cnt, int N, int npad, const double* xs, const double* sp,
+                     const double* alpha, const double* beta, const double* M, double* part, double* gsum, double* diagG) {
+  const int nt = npad / CT, ntl = nt * (nt + 1) / 2, P = cd.cov_N;
+  const size_t shm = 4 * (size_t)(((P + 3) & ~3) + 4) * sizeof(double);
+  GPC_COV_DISPATCH(cvg_trace_kernel, double, cd, dim3(ntl, cnt), dim3(256), shm, c->st, cd, xs, sp, alpha, beta, N, npad, M,
+                   (long long)npad * npad, part, ntl, diagG);
+  hipLaunchKernelGGL(reduce_parts_kernel, dim3(P, cnt), dim3(256), 0, c->st, (const double*)part, ntl, P, gsum);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+int cv_grad_impl(gpc_post* po, int loss, const double* weights, double* gsum_out, double* diagG_out, double* beta_out,
+                 double* alpha_out, double* q_out, double* c_out) {
+  gpc_ctx* c = po->ctx;
+  const int S = po->S, N = po->N, npad = po->npad, cov_N = po->cd.cov_N;
+  hipStream_t st = c->st;
+  const long long n2 = (long long)npad * npad, sM = n2;
+  const size_t per = CvgScratch::per_sample(npad, cov_N) * 8, shared = (size_t)npad * 8;
+  const size_t held = c->nhs.bytes;
+  const int chunk = plan_chunk(c, S, per, shared, held, shared + (size_t)S * per <= held, 0, false, [&](size_t budget) {
+    return "gpc_cv_grad: the scratch of one sample (" + std::to_string(per) + " bytes: N_pad = " + std::to_string(npad) +
+           ": Q, Q diag(c) and their product) exceeds the device memory budget (" + std::to_string(budget) + " bytes)";
+  });
+  if (!chunk) return -2;
+  HIPCHK(c, c->nhs.ensure(shared + (size_t)chunk * per));
+  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * po->D * 8));
+  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
+  HIPCHK(c, c->mulb.ensure((size_t)chunk * po->D * 8));
+  HIPCHK(c, c->divb.ensure((size_t)chunk * po->D * 8));
+  double* d_omega = c->nhs.as<double>();  // the weights, shared by the samples, ahead of the chunk's scratch
+  std::vector<double> hw(npad, 0.0);
+  for (int i = 0; i < N; ++i) hw[i] = weights ? weights[i] : 1.0;
+  HIPCHK(c, hipMemcpyAsync(d_omega, hw.data(), (size_t)npad * 8, hipMemcpyHostToDevice, st));
+  CvgScratch z;
+  CallTimer tm{c, CallTimer::wanted(c, npad)};
+  GramClock tc(tm.on);
+  double trace_us = 0;
+  ChunkConsts k;
+  if (int rc = k.init(po, chunk == S)) return rc;
+  c->ms_total = c->ms_factor = 0;
+  const size_t vlen = (size_t)chunk * npad;
+  std::vector<double> ho(CvgScratch::out_doubles(chunk, npad, cov_N)), hal(vlen);
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    z.carve(c->nhs.as<double>() + npad, cnt, npad, cov_N);
+    if (int rc = k.stage(s0, cnt, true)) return rc;
+    const double* alpha = po->alpha.as<double>() + (size_t)s0 * npad;
+    HIPCHK(c, tm.start());
+    HIPCHK(c, tm.mark1());
+    // a. Q of every sample: W^T W / sl (L_chol; the lower tiles land in M's buffer, overwritten in d) | -A
+    int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+      const double* src = po->A.as<double>() + (size_t)(s0 + a) * sM;
+      if (lch) {
+        Factor<double> F;
+        F.st = st;
+        F.batch = len;
+        F.npad = npad;
+        F.A = po->A.as<double>() + (size_t)(s0 + a) * sM;
+        F.W = po->W.as<double>() + (size_t)(s0 + a) * sM;
+        F.Tm = z.M + (size_t)a * n2;
+        F.sA = F.sW = sM;
+        F.sT = n2;
+        F.lauum(F.Tm, n2);
+        HIPCHK(c, F.err);
+        src = F.Tm;
+      }
+      hipLaunchKernelGGL(nh_form_q_kernel, dim3((unsigned)(n2 / 256), len), dim3(256), 0, st, src, n2, npad,
+                         k.spb + (size_t)a * SP_STRIDE, lch ? 1 : 0, alpha + (size_t)a * npad, N, npad, z.Q + (size_t)a * n2,
+                         n2, z.diagq + (size_t)a * npad);
+      HIPCHK(c, hipGetLastError());
+      return 0;
+    });
+    if (rc_runs) return rc_runs;
+    // b. c and b per point, beta = Q b
+    hipLaunchKernelGGL(cvg_weights_kernel, dim3((npad + 255) / 256, cnt), dim3(256), 0, st, alpha, (const double*)z.Q, n2,
+                       npad + 1, (const double*)d_omega, N, npad, loss, z.q, z.cw, z.b);
+    hipLaunchKernelGGL(nh_matvec_kernel, dim3(npad / 4, 1, cnt), dim3(256), 0, st, (const double*)z.Q, n2, npad,
+                       (const double*)z.b, z.beta);
+    // c. QC = Q diag(c): the noise planes' column scaling
+    hipLaunchKernelGGL(nh_noise_plane_kernel, dim3((unsigned)(n2 / 256), cnt), dim3(256), 0, st, (const double*)z.Q, n2,
+                       (const double*)z.cw, alpha, npad, z.QC, n2, z.u);
+    HIPCHK(c, hipGetLastError());
+    // d. M = QC Q^T, the lower tiles only (Q is symmetric to the bit: its rows serve as the k-major operand)
+    {
+      GemmArgs g;
+      g.A = z.QC, g.B = z.Q, g.C = z.M;
+      g.sA = g.sB = g.sC = n2;
+      g.lda = g.ldb = g.ldc = npad;
+      g.M = g.N = g.K = npad;
+      g.alpha = 1.0, g.beta = 0;
+      g.klo = KLO_ZERO, g.khi = KHI_FULL, g.lower_only = 1;
+      HIPCHK(c, launch_gemm<double>(st, g, false, true, cnt));
+    }
+    HIPCHK(c, tm.mark2());
+    // e. the contraction <d_p K, G>
+    HIPCHK(c, tc.record(0, st));
+    if (int rc = cvg_launch_trace(c, po->cd, cnt, N, npad, k.xsb, k.spb, alpha, z.beta, z.M, z.part, z.gsum, z.diagG)) return rc;
+    HIPCHK(c, tc.record(1, st));
+    HIPCHK(c, tm.stop());
+    // f. the sums and the vectors; the value and the noise and mean columns are the caller's
+    HIPCHK(c, hipMemcpyAsync(ho.data(), z.out, CvgScratch::out_doubles(cnt, npad, cov_N) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(hal.data(), alpha, (size_t)cnt * npad * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    tm.accumulate();
+    trace_us += tc.elapsed_us();
+    const double* hg = ho.data();
+    const double* hv = hg + (size_t)cnt * cov_N;  // diagG | beta | q | cw, cnt x npad each
+    const size_t pl = (size_t)cnt * npad;
+    for (int i = 0; i < cnt; ++i) {
+      const size_t s = s0 + i, o = (size_t)i * npad;
+      std::copy(hg + (size_t)i * cov_N, hg + (size_t)(i + 1) * cov_N, gsum_out + s * cov_N);
+      std::copy(hv + o, hv + o + N, diagG_out + s * N);
+      std::copy(hv + pl + o, hv + pl + o + N, beta_out + s * N);
+      std::copy(hv + 2 * pl + o, hv + 2 * pl + o + N, q_out + s * N);
+      std::copy(hv + 3 * pl + o, hv + 3 * pl + o + N, c_out + s * N);
+      std::copy(hal.begin() + o, hal.begin() + o + N, alpha_out + s * N);
+    }
+  }
+  c->cv_grad_trace_us = (unsigned long long)trace_us;
+  return 0;
+}
+
 // ---- gpc_predict_hyp_grad: derivatives of the latent prediction with respect to the hyperparameters (hypgrad.h) --------
 // The covariance hyperparameters that are planes (a lengthscale or the RQ shape: everything but log sf), in order
 inline std::vector<int> hg_plane_cols(const CovDesc& cd) {
@@ -6588,6 +6747,26 @@ int gpc_nll_hess(gpc_post* po, const double* dm, int mean_N, const double* dsn2,
   return nll_hess_impl(po, dm, mean_N, dsn2, dsn2_rows, noise_N, H, dnlz, alpha, diagq);
 }
 
+int gpc_cv_grad(gpc_post* po, int loss, const double* weights, double* gsum, double* diagG, double* beta, double* alpha,
+                double* q, double* cw) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if ((loss != CVG_LPD && loss != CVG_MSE) || !gsum || !diagG || !beta || !alpha || !q || !cw)
+    FAIL(c, "gpc_cv_grad: bad arguments (loss 0 = lpd or 1 = mse; the six outputs are required)");
+  if (weights)
+    for (int i = 0; i < po->N; ++i)
+      if (!(weights[i] >= 0.0) || !std::isfinite(weights[i])) FAIL(c, "gpc_cv_grad: the weights must be finite and >= 0");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_cv_grad: this posterior was built from caller-provided K; a caller-provided kernel has no derivative "
+            "with respect to its hyperparameters");
+  if (po->dtype != GPC_F64) FAIL(c, "gpc_cv_grad: the cross-validation gradient is fp64 only; this posterior is stored in fp32");
+  if ((po->cd.kind == K_MATERN || po->cd.kind == K_MATERN_ISO) && po->cd.degree == 1)
+    FAIL(c, "gpc_cv_grad: the Matern kernel of degree 1 has an infinite radial factor on the diagonal");
+  if (int rc = require_factorized(po, "gpc_cv_grad")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return cv_grad_impl(po, loss, weights, gsum, diagG, beta, alpha, q, cw);
+}
+
 int gpc_predict_hyp_grad(gpc_post* po, const double* xstar, int M, int compute_var, const double* sn2, const double* dsn2,
                          int noise_rows, int noise_N, const double* dm, int mean_N, double* fmu, double* fs2, double* dfmu,
                          double* dfs2) {
@@ -6943,6 +7122,7 @@ const Option OPTIONS[] = {
     {"hess_contract_us", GPC_COUNTER(hess_contract_us)},  // device time of the contraction passes (kernel + reduction) of the last gpc_predict_hess (timed calls only)
     {"nll_hess_gram_us", GPC_COUNTER(nll_hess_gram_us)},  // device time of the Gram pass (kernel + reduction) of the last gpc_nll_hess (timed calls only)
     {"nll_hess_contract_us", GPC_COUNTER(nll_hess_contract_us)},  // ... of its second-derivative contraction (ARD families; 0 for the isotropic ones)
+    {"cv_grad_trace_us", GPC_COUNTER(cv_grad_trace_us)},  // device time of the contraction pass (kernel + reduction) of the last gpc_cv_grad (timed calls only)
     {"grad_post_gram_us", GPC_COUNTER(grad_post_gram_us)},  // device time of the Gram passes of the last gpc_grad_post (timed calls only)
     {"cov_fused", GPC_COUNTER(cov_fused)},        // gpc_predict_cov calls reduced in the product's epilogue
     {"quad_mix_gemms", GPC_COUNTER(quad_mix_gemms)},  // MFMA GEMM launches inside gpc_quad_mix
@@ -7375,6 +7555,60 @@ int gpc_debug_nll_gram(gpc_ctx* c, int npad, int P, const double* planes, double
   if (int rc = nh_launch_gram(c, z, 1)) return rc;
   HIPCHK(c, hipMemcpyAsync(out, z.grsum, (size_t)z.npairs * 8, hipMemcpyDeviceToHost, c->st));
   HIPCHK(c, hipStreamSynchronize(c->st));
+  return 0;
+}
+
+// gpc_debug_cv_trace: the contraction of gpc_cv_grad (cvgrad.h) alone on one sample with caller-given lower-triangular M
+// and the vectors alpha, beta, launched as the call launches it; gpc_debug_cv_weights: its per-point kernel.
+int gpc_debug_cv_trace(gpc_ctx* c, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                       const double* M, const double* alpha, const double* beta, double* gsum, double* diagG) {
+  if (!c) return -2;
+  if (!nh_hook_kernel_ok(kernel_id, degree) || !hyp_cov || !X || N <= 0 || D <= 0 || !M || !alpha || !beta || !gsum || !diagG)
+    FAIL(c, "gpc_debug_cv_trace: bad arguments (the Matern kernel of degree 1 is not served)");
+  HIPCHK(c, hipSetDevice(c->device));
+  NhHookSample h;
+  if (int rc = h.init(c, "gpc_debug_cv_trace", kernel_id, degree, hyp_cov, X, N, D, alpha, M)) return rc;  // (M in Q's place)
+  const int npad = h.npad, nt = npad / CT, ntl = nt * (nt + 1) / 2, P = h.cd.cov_N;
+  std::vector<double> hb(npad, 0.0), hd(npad);
+  std::copy(beta, beta + N, hb.begin());
+  double* be = h.sd.get<double>(npad);
+  double* part = h.sd.get<double>((size_t)ntl * P);
+  double* sum = h.sd.get<double>(P);
+  double* dg = h.sd.get<double>(npad);
+  if (!be || !part || !sum || !dg) FAIL(c, "gpc_debug_cv_trace: out of device memory");
+  HIPCHK(c, hipMemcpy(be, hb.data(), (size_t)npad * 8, hipMemcpyHostToDevice));
+  if (int rc = cvg_launch_trace(c, h.cd, 1, N, npad, h.xs, h.sp, h.al, be, h.z.Q, part, sum, dg)) return rc;
+  HIPCHK(c, hipMemcpyAsync(gsum, sum, (size_t)P * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(c, hipMemcpyAsync(hd.data(), dg, (size_t)npad * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  std::copy(hd.begin(), hd.begin() + N, diagG);
+  return 0;
+}
+
+int gpc_debug_cv_weights(gpc_ctx* c, int N, int loss, const double* alpha, const double* q, const double* weights,
+                         double* cw, double* b) {
+  if (!c) return -2;
+  if (N <= 0 || (loss != CVG_LPD && loss != CVG_MSE) || !alpha || !q || !cw || !b)
+    FAIL(c, "gpc_debug_cv_weights: bad arguments (loss 0 = lpd or 1 = mse)");
+  HIPCHK(c, hipSetDevice(c->device));
+  const int npad = pad_tile(N);
+  std::vector<double> hin(3 * (size_t)npad, 0.0), hout(3 * (size_t)npad);
+  std::copy(alpha, alpha + N, hin.begin());
+  std::copy(q, q + N, hin.begin() + npad);
+  for (int i = 0; i < N; ++i) hin[2 * (size_t)npad + i] = weights ? weights[i] : 1.0;
+  ScratchDev sd;
+  double* din = sd.get<double>(3 * (size_t)npad);
+  double* dout = sd.get<double>(3 * (size_t)npad);
+  if (!din || !dout) FAIL(c, "gpc_debug_cv_weights: out of device memory");
+  HIPCHK(c, hipMemcpy(din, hin.data(), hin.size() * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(cvg_weights_kernel, dim3((npad + 255) / 256, 1), dim3(256), 0, c->st, (const double*)din,
+                     (const double*)(din + npad), 0ll, 1, (const double*)(din + 2 * (size_t)npad), N, npad, loss, dout,
+                     dout + npad, dout + 2 * (size_t)npad);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(hout.data(), dout, hout.size() * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  std::copy(hout.begin() + npad, hout.begin() + npad + N, cw);
+  std::copy(hout.begin() + 2 * (size_t)npad, hout.begin() + 2 * (size_t)npad + N, b);
   return 0;
 }
 

@@ -1112,6 +1112,109 @@ class GP:
                        log_evidence=val + 0.5 * free.size * np.log(2 * np.pi) - np.sum(np.log(np.diag(L))))
         return out
 
+    # ------------------------------------------------------------------ cross-validation objective
+    def _cv_grad_check(self, who, loss="lpd", weights=None):
+        """The refusals of the cross-validation objective that need no device.  Returns ``weights`` as a float64
+        vector (None stays None)."""
+        from . import _cvgrad as _cg
+        from .mean_functions import ConstantMean, NegativeQuadratic, ZeroMean
+        from .noise_functions import GaussianNoise
+
+        if not self._builtin:
+            raise NotImplementedError(f"{who}: the covariance function {self.covariance!r} is user-defined; its "
+                                      "derivatives with respect to the hyperparameters are not available on the device")
+        if self.dtype != "f64":
+            raise NotImplementedError(f"{who}: the cross-validation objective is computed in fp64 only; this GP's dtype "
+                                      f"is {self.dtype!r}")
+        _cg.check_kind(*self._kid(), who=who)
+        if type(self.noise) is not GaussianNoise:
+            raise NotImplementedError(f"{who}: the noise function {self.noise!r} ({type(self.noise).__name__}) is "
+                                      "user-defined; only the stock GaussianNoise is served")
+        if type(self.mean) not in (ZeroMean, ConstantMean, NegativeQuadratic):
+            raise NotImplementedError(f"{who}: the mean function {self.mean!r} ({type(self.mean).__name__}) is "
+                                      "user-defined; only the stock mean functions are served")
+        _cg.check_loss(loss, who)
+        return _cg.check_weights(weights, None if self.X is None else self.X.shape[0], who)
+
+    def cv_nll_batch(self, hyp=None, compute_grad: bool = True, loss: str = "lpd", weights=None):
+        """The leave-one-out cross-validation objective and its gradient with respect to the hyperparameters for many
+        hyperparameter vectors: ``hyp`` (S, hyp_N) -> L (S,), dL (S, hyp_N) | None, ordered [cov | noise | mean] as
+        ``nll_batch``'s gradient.
+
+        ``loss="lpd"``: L is the NEGATIVE leave-one-out log predictive density (Rasmussen & Williams 5.4.2; the negated
+        sum of ``cv_predict(return_lpd=True)``'s single-point folds); ``loss="mse"``: the sum of squared leave-one-out
+        residuals.  ``weights`` (N,), finite and >= 0, weighs the points (default 1).
+
+        ``hyp=None`` uses the resident posteriors (appended points included); otherwise temporary posteriors are built
+        for ``hyp`` and freed (LinAlgError when a factorization fails).  The closed form (``_cvgrad``) runs on the
+        device (gpc_cv_grad) at each sample's own jitter multiplier, held fixed: all derivatives collapse onto one
+        weight matrix, so value and gradient cost one N^3 product and one contraction pass whatever hyp_N is.  Without
+        ``compute_grad`` the value comes from the leave-one-out pass of ``cv_predict`` (gpc_cv) and no product is
+        launched; the two values agree to rounding, not to the bit.
+
+        Built-in covariance functions, the stock ``GaussianNoise`` and the stock mean functions in float64 only
+        (NotImplementedError otherwise, naming the reason); the Matern kernel of degree 1 is refused.  Under a process
+        group the call is NOT sharded: it runs on the calling rank alone, whatever the others do, and exchanges nothing
+        (resident posteriors that are sharded are rebuilt locally as temporaries)."""
+        weights = self._cv_grad_check("cv_nll_batch", loss, weights)
+        return self._cv_nll_local(hyp, compute_grad, loss, weights)
+
+    @_on_device
+    def _cv_nll_local(self, hyp, compute_grad, loss, weights):
+        """``cv_nll_batch`` after its refusals: this rank's device call and the plugin columns."""
+        from . import _cvgrad as _cg
+
+        cov_N, noise_N, mean_N = self._counts()
+        resident = hyp is None
+        if resident:
+            self._require_posteriors()
+            hyp = np.stack([p.hyp for p in self.posteriors])
+            resident = self._post_range is None and self._post_handle is not None
+        hyp = np.atleast_2d(np.asarray(hyp, dtype=float))
+        if hyp.shape[1] != cov_N + noise_N + mean_N:
+            raise ValueError("Input hyperparameter array is the wrong shape!")
+        S = hyp.shape[0]
+        ctx = self._ctx()
+        pv = self._plugin_values(hyp, bool(compute_grad))
+        kid, deg = self._kid()
+        if resident:
+            handle = self._post_handle
+            mult = np.array([float(_sn2_mult(p)) for p in self.posteriors])
+        else:
+            handle, mult, _, info = ctx.posterior_batch(kid, deg, _DTYPES[self.dtype], hyp[:, :cov_N], pv["m"], pv["sn2"],
+                                                        pv["vec"])
+            if np.any(info != 0):
+                handle.free()
+                raise LinAlgError("Singular matrix for L Cholesky decomposition")
+        try:
+            if not compute_grad:
+                dmu, s2, _, _, info = handle.cv(None)  # (N, S): alpha / q and 1 / q
+                if np.any(info != 0):
+                    raise LinAlgError("cv_nll_batch: a leave-one-out variance is not positive in floating point")
+                return _cg.loo_value((dmu / s2).T, (1 / s2).T, loss, weights), None
+            gsum, diagG, beta, alpha, q, _ = handle.cv_grad(cov_N, loss, weights)
+        finally:
+            if not resident:
+                handle.free()
+        L = _cg.loo_value(alpha, q, loss, weights)
+        dL = np.empty((S, hyp.shape[1]))
+        for s in range(S):
+            dL[s] = _cg.assemble(gsum[s], diagG[s], beta[s], mult[s], None if pv["dsn2"] is None else pv["dsn2"][s],
+                                 None if pv["dm"] is None else pv["dm"][s])
+        return L, dL
+
+    def log_pseudo_likelihood(self, hyp, compute_grad: bool = False):
+        """The leave-one-out log pseudo-likelihood (Rasmussen & Williams 5.4.2), the sum over the points of the log
+        density of y_i under its leave-one-out prediction, at ONE hyperparameter vector (array or dict), in
+        ``log_likelihood``'s sign convention: -L of ``cv_nll_batch(loss="lpd")``.  With ``compute_grad`` the pair
+        (lpl, dlpl); negated, an objective for ``scipy.optimize``."""
+        if isinstance(hyp, dict):
+            hyp = self.hyperparameters_from_dict(hyp)[0]
+        L, dL = self.cv_nll_batch(np.asarray(hyp, dtype=float).ravel()[None, :], compute_grad)
+        if compute_grad:
+            return -float(L[0]), -dL[0]
+        return -float(L[0])
+
     # ------------------------------------------------------------------ hyperparameters
     def get_hyperparameters(self, as_array: bool = False):
         """Reference :516-552."""

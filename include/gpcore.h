@@ -229,6 +229,34 @@ int gpc_predict_hess(gpc_post* post, const double* xstar, int M, int compute_var
 int gpc_nll_hess(gpc_post* post, const double* dm, int mean_N, const double* dsn2, int dsn2_rows, int noise_N, double* H,
                  double* dnlz, double* alpha, double* diagq);
 
+/* ---- GP.cv_nll_batch: the leave-one-out cross-validation objective's gradient with respect to the hyperparameters ----
+ * Per sample of the posterior, at the posterior's own jitter multiplier `mult` (held fixed), with
+ * Sigma = K + mult diag(sn2), Q = Sigma^-1, alpha = Q (y - m), q_i = Q_ii: leaving point i out predicts y_i with mean
+ * y_i - alpha_i / q_i and variance 1 / q_i.  With weights w_i >= 0 (NULL: ones; one vector of N for all samples):
+ *   loss 0 ("lpd"):  L = -sum_i w_i (1/2 log q_i - alpha_i^2 / (2 q_i) - 1/2 log 2 pi)
+ *                    c_i = w_i (1 + alpha_i^2 / q_i) / (2 q_i)         b_i = w_i alpha_i / q_i
+ *   loss 1 ("mse"):  L =  sum_i w_i (alpha_i / q_i)^2
+ *                    c_i = 2 w_i alpha_i^2 / q_i^3                     b_i = 2 w_i alpha_i / q_i^2
+ *   beta = Q b,   G = Q diag(c) Q - 1/2 (beta alpha^T + alpha beta^T)   (symmetric)
+ *   dL / d theta_p = <d_p K, G>   covariance hyperparameter p (planes F o d_a^2 | F o r2 | 2 K | Ka as gpc_nll_hess; a
+ *                                 pair at r2 = 0 contributes nothing to a lengthscale term)
+ *                  = mult sum_i G_ii d_n sn2_i  (noise n)      = -beta . d_k m  (mean k)
+ * The call returns what needs the device: gsum (S x cov_N) = <d_p K, G>, diagG (S x N) = diag(G), beta, alpha, q and
+ * c (S x N each).  The value L and the noise and mean columns are O(N P) and the caller's.
+ * Device work per sample: Q formed once (W^T W / sl for L_chol samples, -L for the low-noise ones: one path after
+ * that); c, b per point and beta = Q b; the column scaling Q diag(c); ONE plain fp64 GEMM over the lower tiles,
+ * M = (Q diag(c)) Q; one contraction pass over the lower 64 x 64 tiles, the marginal likelihood's gradient pass with the
+ * weight G in place of Q - alpha alpha^T.  No plane d_p K is formed: the cost does not depend on cov_N.  No atomics: a
+ * sample's results are the same bits whatever the batch, the other samples or the chunking (GPC_MEM_BUDGET_MB).
+ * Scratch per sample: 3 N_pad^2 doubles (Q, Q diag(c), M) and vectors.
+ * gpc_last_timing: ms_total = the device sections, ms_factor = everything up to and including the product; option
+ * "cv_grad_trace_us": the contraction pass of the last call.
+ * Returns -2 with a message of its own for: bad arguments (weights negative or not finite among them); a posterior from
+ * caller-provided K; an fp32 posterior (fp64 only); the Matern kernel of degree 1 (F infinite on the diagonal); a failed
+ * factorization; one sample's scratch exceeding the budget (N_pad, bytes).                                              */
+int gpc_cv_grad(gpc_post* post, int loss, const double* weights, double* gsum, double* diagG, double* beta, double* alpha,
+                double* q, double* c);
+
 /* ---- GP.predict_hyp_grad: derivatives of the latent prediction with respect to the hyperparameters, per sample -------
  * Sigma = K + mult diag(sn2) at each sample's own jitter multiplier, held fixed; Q = Sigma^-1, alpha = Q (y - m); for
  * query j: k_j = k(X, x*_j), q_j = Q k_j, fmu_j = k_j . alpha, fs2_j = k** - k_j . q_j.  Hyperparameters ordered
@@ -643,6 +671,17 @@ int gpc_debug_nll_d2(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_
 /* gpc_nll_hess's Gram pass on caller-given planes[P][npad][npad] (npad a multiple of 64, at most 4096; P <= 128):
  *   out[p (p + 1) / 2 + q] = sum_ab planes[p][a][b] planes[q][b][a],  q <= p  (P (P + 1) / 2 values, nothing beyond)   */
 int gpc_debug_nll_gram(gpc_ctx* ctx, int npad, int P, const double* planes, double* out);
+
+/* gpc_cv_grad's contraction alone on one sample, launched as the call launches it (inputs scaled from hyp_cov as in
+ * gpc_debug_cov): M[N x N] read from its lower triangle, alpha[N], beta[N];  G_ij = M_ij - (beta_i alpha_j + alpha_i beta_j) / 2:
+ *   gsum[p] = sum over i >= j of w_ij G_ij d_p K_ij,  p < cov_N,  w = 1 on the diagonal, else 2;   diagG[i] = G_ii       */
+int gpc_debug_cv_trace(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                       const double* M, const double* alpha, const double* beta, double* gsum, double* diagG);
+
+/* gpc_cv_grad's per-point kernel: c[N] and b[N] of `loss` (0 = lpd, 1 = mse) from alpha[N], q[N] and weights[N] (NULL:
+ * ones), the formulas of gpc_cv_grad.                                                                                   */
+int gpc_debug_cv_weights(gpc_ctx* ctx, int N, int loss, const double* alpha, const double* q, const double* weights,
+                         double* c, double* b);
 
 /* Debug: wrapping-sum hash of every 128 x 128 tile of one workspace matrix as the LAST call left it (which: 0 = A, 1 = W,
  * 2 = T; sample: position in the last chunk); out[(npad/128)^2].  Finds the tile where two schedules differ.          */

@@ -203,6 +203,13 @@ def consumers(dtype):
     per = len(folds) * (3 * pad(9) ** 2 + pad(9)) * 8 + 2 * npad * 8 + len(folds) * 32 + 64
     both("cv_predict scattered folds", dtype, lambda: gp.cv_predict(folds, separate_samples=True), per)
     both("cv_predict scattered folds with lpd", dtype, lambda: gp.cv_predict(folds, return_lpd=True), per)
+    # cv_nll_batch on the resident posteriors (fp64 only): Q, Q diag(c) and their product, seven vectors, the per-tile
+    # partials of the contraction; the weights are shared by the samples
+    if dtype == "f64" and hasattr(gp, "cv_nll_batch"):
+        ntl = gnt * (gnt + 1) // 2
+        per = (3 * npad * npad + 7 * npad + (ntl + 1) * (D + 1)) * 8
+        for loss in ("lpd", "mse"):
+            both(f"cv_nll_batch {loss}", dtype, lambda: gp.cv_nll_batch(loss=loss, weights=wm.repeat(3)[:N]), per, npad * 8)
     # sample_paths: creation under both solve engines, evaluation with gradients under both engines
     kq, kp = pad(R_PATHS, 16), pad(R_PATHS)
     try:
