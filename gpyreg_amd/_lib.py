@@ -109,6 +109,7 @@ SIGNATURES = {
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, C.c_int, C.c_int, _dp,
          C.c_int, _dp, _dp, _dp, _dp, _dp],
     ),
+    "gpc_debug_blas1": (C.c_int, [_vp, C.c_int, C.c_int, _ip, _vp, _vp, _vp, _vp]),
     "gpc_debug_block_gram": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp]),
     "gpc_debug_hess_contract": (
         C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp]),
@@ -165,6 +166,13 @@ class GemmProduct:
         self.off_a, self.off_b, self.off_c = int(off_a), int(off_b), int(off_c)
         self.s_a, self.s_b, self.s_c = int(s_a), int(s_b), int(s_c)
 
+
+# `which` of gpc_debug_blas1 (include/gpcore.h), and the guard after each of its result buffers
+BLAS1 = {name: code for code, name in enumerate((
+    "trmv", "trmv_low", "gemv_sub", "trmv_t_part", "trmv_t_part_low", "trmv_t_sum", "dot", "mat_t_vec", "grad_tail",
+    "colsum_prod", "colsum_vec", "diagq", "trace_plane", "extract", "neg_sym", "pad_load", "pad_rect", "load_K",
+    "rect_copy", "grow_copy", "append_row", "append_low"))}
+BLAS1_GUARD = 128
 
 FORMS = {"plain": 0, "persist": 1, "persist_reserved": 2, "dual": 3, "colsq": 4, "wsq": 5}
 
@@ -563,6 +571,30 @@ class Context:
             return (out0.transpose(1, 2, 0, 3).reshape(npad, D + 1, mpad),
                     out1.transpose(1, 0, 2).reshape(D + 1, mpad), xs)
         return out0, out1, xs
+
+    @_serial
+    def debug_blas1(self, which, ip, ins, out_sizes, dtype=F64):
+        """gpc_debug_blas1: one launch of the blas1.h kernel ``which`` (a key of ``BLAS1``) with the int parameters ``ip``
+        on the operands ``ins`` (at most six arrays, None: absent; uploaded whole) -- the table in include/gpcore.h gives
+        both per kernel.  ``out_sizes``: the element count of every result (0: a buffer that is its guard alone).
+        Returns one flat array per result, ``size + BLAS1_GUARD`` long: the buffer as the launch left it, then its
+        guard."""
+        if len(ins) > 6 or len(out_sizes) > 3:
+            raise ValueError("debug_blas1: at most six operands and three results")
+        ipa = np.zeros(8, dtype=np.int32)
+        ipa[:len(ip)] = ip
+        arrs = [None if a is None else _f64(a).ravel() for a in ins]
+        arrs += [None] * (6 - len(arrs))
+        sizes = [int(n) for n in out_sizes]
+        outs = [np.empty(n + BLAS1_GUARD) for n in sizes] + [None] * (3 - len(sizes))
+        in_p = (C.c_void_p * 6)(*[_ptr(a) for a in arrs])
+        in_n = (C.c_longlong * 6)(*[0 if a is None else a.size for a in arrs])
+        out_p = (C.c_void_p * 3)(*[_ptr(o) for o in outs])
+        out_n = (C.c_longlong * 3)(*(sizes + [0] * (3 - len(sizes))))
+        rc = self._lib.gpc_debug_blas1(self._h, BLAS1[which], dtype, _ptr(ipa), C.addressof(in_p), C.addressof(in_n),
+                                       C.addressof(out_p), C.addressof(out_n))
+        self._check(rc, "gpc_debug_blas1")
+        return [o for o in outs if o is not None]
 
     @_serial
     def debug_block_gram(self, Y, Z=None, dtype=F64, diag_only=False):

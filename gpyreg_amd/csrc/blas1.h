@@ -9,7 +9,8 @@ namespace gpc {
 
 // z[b][i] = sum_{k<=i} W[b][i][k] * r[b][k].   One wave per row, 4 rows per block.
 // The diagonal tile of W is zero above the diagonal, so the row is read up to the end
-// of its 128-wide diagonal tile without masking.   grid = (npad/4, batch)
+// of its 128-wide diagonal tile without masking: r must be FINITE over the whole tile, the entries past the row and
+// the padding included (0 * NaN is NaN), and their values do not matter.   grid = (npad/4, batch)
 // With row0 > 0 the product is restricted to the diagonal block starting at row0
 // (rows row0 + blockIdx.x*4 + wave, columns >= row0): the blocked forward solve.
 template <typename T>
@@ -120,6 +121,7 @@ __global__ __launch_bounds__(256) void gemv_sub_kernel(const T* __restrict__ A_a
 // W^T z in two deterministic passes.  Pass 1: part[b][ch][k] = sum over the rows of chunk ch
 // (TRC rows, only rows >= the diagonal tile of column k) of W[b][i][k] * z[b][i];
 // grid = (npad/64, npad/TRC, batch).  Pass 2: out[b][k] = scale[b] * sum_ch part (fixed order).
+// (The diagonal tile is read whole, its zeros above the diagonal too: z must be finite everywhere, as r for trmv_kernel.)
 constexpr int TRC = 128;  // = TILE, so every padded size is a whole number of chunks
 // Each lane owns VEC adjacent columns (one 16-byte load per row), each wave every fourth row of the chunk,
 // eight loads in flight per lane.   grid = (npad / (64 * VEC), npad / TRC, batch)

@@ -6104,6 +6104,364 @@ int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const dou
 }
 }  // namespace
 
+// gpc_debug_blas1: ONE launch of one blas1.h kernel, with the grid and block of the production call named at each case,
+// on buffers that live for this call only (ScratchDev frees them): nothing of the context's workspace is touched, so
+// what a kernel reads outside its contract is what the caller put there, and what it writes outside shows in the result.
+namespace {
+constexpr long long B1_GUARD = 128;  // elements after every result buffer (include/gpcore.h)
+struct Blas1Call {
+  const double* const* in;
+  const long long* in_n;
+  double* const* out;
+  const long long* out_n;
+  ScratchDev sd;
+  void* dev[3] = {nullptr, nullptr, nullptr};
+  bool ok = true;  // false: out of device memory, or a copy failed
+
+  // operand k, uploaded whole as U: a plain cast of the caller's doubles (a NaN stays a NaN)
+  template <typename U>
+  const U* up(int k) {
+    if (!in[k] || in_n[k] <= 0) return nullptr;
+    const size_t n = (size_t)in_n[k];
+    U* d = sd.get<U>(n);
+    std::vector<U> h(in[k], in[k] + n);
+    if (!d || hipMemcpy(d, h.data(), n * sizeof(U), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+    return d;
+  }
+  // result k as U: out_n[k] quiet NaNs -- or, for a kernel that works in place, operand `from` -- and the NaN guard
+  template <typename U>
+  U* res(int k, int from = -1) {
+    if (!out[k] || out_n[k] < 0) return nullptr;  // (out_n[k] = 0: the guard alone)
+    const size_t n = (size_t)out_n[k];
+    std::vector<U> h(n + B1_GUARD, std::numeric_limits<U>::quiet_NaN());
+    if (from >= 0)
+      for (size_t i = 0; i < n; ++i) h[i] = (U)in[from][i];
+    U* d = sd.get<U>(h.size());
+    if (!d || hipMemcpy(d, h.data(), h.size() * sizeof(U), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+    dev[k] = d;
+    return d;
+  }
+  // the whole of result k, guard included, back to the caller
+  template <typename U>
+  bool down(int k) {
+    if (!dev[k]) return true;
+    std::vector<U> h((size_t)(out_n[k] + B1_GUARD));
+    if (hipMemcpy(h.data(), dev[k], h.size() * sizeof(U), hipMemcpyDeviceToHost) != hipSuccess) return false;
+    std::copy(h.begin(), h.end(), out[k]);
+    return true;
+  }
+};
+
+#define B1_REQ(cond) \
+  if (!(cond)) FAIL(c, "gpc_debug_blas1: the arguments must satisfy " #cond)
+
+template <typename T>
+int debug_blas1_impl(gpc_ctx* c, int which, const int* ip, const double* const* in, const long long* in_n,
+                     double* const* out, const long long* out_n) {
+  constexpr int VEC = MM<T>::VEC;
+  hipStream_t st = c->st;
+  Blas1Call q{in, in_n, out, out_n};
+  auto has_in = [&](int k, long long n) { return in[k] != nullptr && in_n[k] >= n; };
+  auto has_out = [&](int k, long long n) { return out[k] != nullptr && out_n[k] == n; };
+  // entries [first, first + count) of every row of `stride` of operand k: the vector a triangular product multiplies
+  // with the exact zeros of W above the diagonal, which it reads unmasked (blas1.h: trmv_kernel)
+  auto finite = [&](int k, long long batch, long long stride, long long first, long long count) {
+    for (long long b = 0; b < batch; ++b)
+      for (long long i = first; i < first + count; ++i)
+        if (!std::isfinite(in[k][b * stride + i])) return false;
+    return true;
+  };
+  const dim3 blk(64, 4);
+  int nT = 0;  // the first nT results are stored as T
+  // (every case: the argument check that keeps the launch inside the buffers, the buffers, the launch)
+  switch (which) {
+    case 0:    // trmv_kernel: plan.h:424 (forward_solve; :331 and :401 launch it with the same grid)
+    case 1: {  // trmv_low_kernel: plan.h:421
+      const long long npad = ip[0], batch = ip[1];
+      const int row0 = which == 0 ? ip[2] : 0, rows = which == 0 ? ip[3] : (int)npad;
+      B1_REQ(npad > 0 && npad % TILE == 0 && batch > 0 && row0 >= 0 && row0 % TILE == 0 && rows > 0 && rows % 16 == 0 &&
+             row0 + rows <= npad);
+      B1_REQ(has_in(0, batch * npad * npad) && has_in(1, batch * npad) && has_out(0, batch * npad));
+      B1_REQ(finite(1, batch, npad, row0, rows));
+      const T* W = q.up<T>(0);
+      const double* r = q.up<double>(1);
+      double* z = q.res<double>(0);
+      if (!q.ok) break;
+      if (which == 0)
+        hipLaunchKernelGGL((trmv_kernel<T>), dim3(rows / 4, batch), dim3(256), 0, st, W, npad * npad, (int)npad, r, (int)npad,
+                           z, row0);
+      else
+        hipLaunchKernelGGL((trmv_low_kernel<T>), dim3(npad / 16, batch), dim3(256), 0, st, W, npad * npad, (int)npad, r,
+                           (int)npad, z);
+      break;
+    }
+    case 2: {  // gemv_sub_kernel: plan.h:434 (forward_solve; :339 and :405 launch it with the same grid)
+      const long long npad = ip[0], batch = ip[1];
+      const int row0 = ip[2], nrows = ip[3], col0 = ip[4], ncols = ip[5];
+      B1_REQ(npad > 0 && npad % TILE == 0 && batch > 0 && row0 >= 0 && nrows > 0 && nrows % 4 == 0 && row0 + nrows <= npad &&
+             col0 >= 0 && col0 % TILE == 0 && ncols > 0 && ncols % TILE == 0 && col0 + ncols <= npad);
+      B1_REQ(has_in(0, batch * npad * npad) && has_in(1, batch * npad) && has_in(2, batch * npad) && has_out(0, batch * npad));
+      const T* A = q.up<T>(0);
+      const double* z = q.up<double>(1);
+      double* r = q.res<double>(0, 2);
+      if (!q.ok) break;
+      hipLaunchKernelGGL((gemv_sub_kernel<T>), dim3(nrows / 4, batch), dim3(256), 0, st, A, npad * npad, (int)npad, z, r,
+                         (int)npad, row0, col0, ncols);
+      break;
+    }
+    case 3:    // trmv_t_part_kernel<T, 8>: gpcore.hip:1152
+    case 4: {  // trmv_t_part_low_kernel: gpcore.hip:1149
+      const long long npad = ip[0], batch = ip[1];
+      const bool quad = ip[2] != 0;
+      B1_REQ(npad > 0 && npad % TILE == 0 && batch > 0);
+      B1_REQ(has_in(0, batch * npad * npad) && has_in(1, batch * npad) && has_out(0, batch * (npad / TRC) * npad) &&
+             (!quad || has_out(1, batch)));
+      B1_REQ(finite(1, batch, npad, 0, npad));
+      const T* W = q.up<T>(0);
+      const double* z = q.up<double>(1);
+      double* part = q.res<double>(0);
+      double* qd = quad ? q.res<double>(1) : nullptr;
+      if (!q.ok) break;
+      const dim3 gt((npad + 64 * VEC - 1) / (64 * VEC), npad / TRC, batch);
+      if (which == 3)
+        hipLaunchKernelGGL((trmv_t_part_kernel<T, 8>), gt, dim3(256), 0, st, W, npad * npad, (int)npad, z, (int)npad, part, qd);
+      else
+        hipLaunchKernelGGL((trmv_t_part_low_kernel<T>), gt, dim3(256), 0, st, W, npad * npad, (int)npad, z, (int)npad, part,
+                           qd);
+      break;
+    }
+    case 5: {  // trmv_t_sum_kernel: gpcore.hip:1154 (with the scale), :5043 (without)
+      const long long npad = ip[0], batch = ip[1];
+      const int sp_stride = ip[2], sp_off = ip[3];
+      B1_REQ(npad > 0 && npad % TILE == 0 && batch > 0);
+      B1_REQ(has_in(0, batch * (npad / TRC) * npad) && has_out(0, batch * npad) &&
+             (!in[1] || (sp_off >= 0 && sp_off < sp_stride && has_in(1, batch * sp_stride))));
+      const double* part = q.up<double>(0);
+      const double* sp = q.up<double>(1);
+      double* o = q.res<double>(0);
+      if (!q.ok) break;
+      hipLaunchKernelGGL(trmv_t_sum_kernel, dim3(npad / 128, batch), dim3(128), 0, st, part, (int)npad, sp, sp_stride, sp_off, o);
+      break;
+    }
+    case 6: {  // dot_kernel: gpcore.hip:1143
+      const long long n = ip[0], stride = ip[1], batch = ip[2];
+      B1_REQ(n > 0 && stride >= n && batch > 0);
+      B1_REQ(has_in(0, batch * stride) && has_in(1, batch * stride) && has_out(0, batch));
+      const double* x = q.up<double>(0);
+      const double* y = q.up<double>(1);
+      double* o = q.res<double>(0);
+      if (!q.ok) break;
+      hipLaunchKernelGGL(dot_kernel, dim3(1, batch), dim3(256), 0, st, x, y, (int)n, (int)stride, o);
+      break;
+    }
+    case 7: {  // mat_t_vec_kernel: gpcore.hip:1215
+      const long long n = ip[0], P = ip[1], vstride = ip[2], batch = ip[3];
+      B1_REQ(n > 0 && P > 0 && vstride >= n && batch > 0);
+      B1_REQ(has_in(0, batch * n * P) && has_in(1, batch * vstride) && has_out(0, batch * P));
+      const double* M = q.up<double>(0);
+      const double* v = q.up<double>(1);
+      double* o = q.res<double>(0);
+      if (!q.ok) break;
+      hipLaunchKernelGGL(mat_t_vec_kernel, dim3(P, batch), dim3(256), 0, st, M, (int)n, (int)P, v, (int)vstride, o);
+      break;
+    }
+    case 8: {  // grad_tail_kernel: gpcore.hip:1205
+      const long long ntiles = ip[0], P = ip[1], n = ip[2], mN = ip[3], nN = ip[4], vstride = ip[5], batch = ip[6];
+      B1_REQ(ntiles > 0 && P > 0 && n > 0 && mN >= 0 && nN >= 0 && vstride >= n && batch > 0);
+      // alpha and diagq are always there, as in the production call; mg and ng always have a buffer -- without mean or
+      // noise slots the guard alone, where the production call passes nullptr: a stray write shows instead of faulting
+      B1_REQ(has_in(0, batch * ntiles * P) && has_in(2, batch * vstride) && has_in(4, batch * vstride) &&
+             has_out(0, batch * P) && has_out(1, batch * mN) && has_out(2, batch * nN));
+      B1_REQ((mN == 0 || !in[1] || has_in(1, batch * n * mN)) && (nN == 0 || has_in(3, batch * n * nN)));
+      const double* part = q.up<double>(0);
+      const double* dm = mN ? q.up<double>(1) : nullptr;
+      const double* al = q.up<double>(2);
+      const double* ds = nN ? q.up<double>(3) : nullptr;
+      const double* dq = q.up<double>(4);
+      double* gout = q.res<double>(0);
+      double* mg = q.res<double>(1);
+      double* ng = q.res<double>(2);
+      if (!q.ok) break;
+      hipLaunchKernelGGL(grad_tail_kernel, dim3(P + mN + nN, batch), dim3(256), 0, st, part, (int)ntiles, (int)P, gout, dm,
+                         (int)n, (int)mN, al, mg, ds, (int)nN, dq, ng, (int)vstride);
+      break;
+    }
+    case 9:     // colsum_prod_kernel: gpcore.hip:2885
+    case 10: {  // colsum_vec_kernel: gpcore.hip:2853
+      const long long ld = ip[0], nrows = ip[1], mpad = ip[2], vstride = which == 10 ? ip[3] : 0,
+                      batch = which == 10 ? ip[4] : ip[3];
+      B1_REQ(mpad > 0 && mpad % 64 == 0 && ld >= mpad && nrows > 0 && batch > 0);
+      B1_REQ(has_in(0, batch * nrows * ld) && in_n[0] % batch == 0 && has_out(0, batch * mpad));
+      B1_REQ(which == 10 ? (vstride >= nrows && has_in(1, batch * vstride)) : (in[1] != nullptr && in_n[1] == in_n[0]));
+      const long long sA = in_n[0] / batch;
+      const T* A = q.up<T>(0);
+      const T* Bm = which == 9 ? q.up<T>(1) : nullptr;
+      const double* v = which == 10 ? q.up<double>(1) : nullptr;
+      double* o = q.res<double>(0);
+      if (!q.ok) break;
+      if (which == 9)
+        hipLaunchKernelGGL((colsum_prod_kernel<T>), dim3(mpad / 64, batch), dim3(256), 0, st, A, sA, Bm, sA, (int)ld, (int)nrows,
+                           (int)mpad, o);
+      else
+        hipLaunchKernelGGL((colsum_vec_kernel<T>), dim3(mpad / 64, batch), dim3(256), 0, st, A, sA, (int)ld, v, (int)vstride,
+                           (int)nrows, (int)mpad, o);
+      break;
+    }
+    case 11: {  // diagq_kernel: gpcore.hip:1197
+      const long long n = ip[0], ld = ip[1], P = ip[2], batch = ip[3];
+      B1_REQ(n > 0 && n <= ld && P > 0 && batch > 0);
+      B1_REQ(has_in(0, batch * ld * ld) && has_in(1, batch * ld) && has_in(2, batch * SP_STRIDE) && has_out(0, batch * ld) &&
+             has_out(1, batch * P));
+      const T* Ai = q.up<T>(0);
+      const double* al = q.up<double>(1);
+      const double* sp = q.up<double>(2);
+      double* dq = q.res<double>(0);
+      double* o = q.res<double>(1);
+      if (!q.ok) break;
+      hipLaunchKernelGGL((diagq_kernel<T>), dim3(1, batch), dim3(256), 0, st, Ai, ld * ld, (int)ld, al, sp, (int)n, dq, o, (int)P);
+      break;
+    }
+    case 12: {  // trace_plane_kernel: gpcore.hip:966
+      const long long n = ip[0], ld = ip[1], nblk = ip[2];
+      B1_REQ(n > 0 && n <= ld && nblk > 0 && nblk <= 1024);
+      B1_REQ(has_in(0, n * ld) && has_in(1, n) && has_in(2, SP_STRIDE) && has_in(3, n * n) && has_out(0, nblk));
+      const T* Ai = q.up<T>(0);
+      const double* al = q.up<double>(1);
+      const double* sp = q.up<double>(2);
+      const double* dK = q.up<double>(3);
+      double* part = q.res<double>(0);
+      if (!q.ok) break;
+      hipLaunchKernelGGL((trace_plane_kernel<T>), dim3(nblk), dim3(256), 0, st, Ai, (int)ld, al, sp, dK, (int)n, part);
+      break;
+    }
+    case 13: {  // extract_kernel: gpcore.hip:4605 (mode 0), :2969 (mode 2); mode 1 has no caller left: the same grid
+      const long long n = ip[0], ld = ip[1];
+      const int mode = ip[2];
+      B1_REQ(n > 0 && n <= ld && mode >= 0 && mode <= 2);
+      B1_REQ(has_in(0, n * ld) && has_out(0, n * n));
+      const T* src = q.up<T>(0);
+      double* dst = q.res<double>(0);
+      if (!q.ok) break;
+      hipLaunchKernelGGL((extract_kernel<T>), dim3((n + 63) / 64, (n + 3) / 4), blk, 0, st, src, (int)ld, (int)n, mode, dst);
+      break;
+    }
+    case 14: {  // neg_sym_kernel: gpcore.hip:2473
+      const long long npad = ip[0], ld = ip[1], batch = ip[2];
+      B1_REQ(npad > 0 && npad % TILE == 0 && ld >= npad && batch > 0);
+      B1_REQ(has_in(0, batch * npad * ld) && in_n[0] % batch == 0 && has_out(0, in_n[0]));
+      T* buf = q.res<T>(0, 0);
+      nT = 1;
+      if (!q.ok) break;
+      hipLaunchKernelGGL((neg_sym_kernel<T>), dim3(npad / 64, npad / 4, batch), blk, 0, st, buf, in_n[0] / batch, (int)ld,
+                         (int)npad);
+      break;
+    }
+    case 15: {  // pad_load_kernel: gpcore.hip:4587
+      const long long n = ip[0], npad = ip[1];
+      B1_REQ(n > 0 && n <= npad && npad % TILE == 0);
+      B1_REQ(has_in(0, n * n) && has_out(0, npad * npad));
+      const double* src = q.up<double>(0);
+      T* dst = q.res<T>(0);
+      nT = 1;
+      if (!q.ok) break;
+      hipLaunchKernelGGL((pad_load_kernel<T>), dim3(npad / 64, npad / 4), blk, 0, st, src, (int)n, (int)npad, dst);
+      break;
+    }
+    case 16: {  // pad_rect_kernel: gpcore.hip:2831
+      const long long r = ip[0], cc = ip[1], rpad = ip[2], cpad = ip[3];
+      B1_REQ(r > 0 && cc > 0 && r <= rpad && cc <= cpad && rpad % TILE == 0 && cpad % TILE == 0);
+      B1_REQ(has_in(0, r * cc) && has_out(0, rpad * cpad));
+      const double* src = q.up<double>(0);
+      T* dst = q.res<T>(0);
+      nT = 1;
+      if (!q.ok) break;
+      hipLaunchKernelGGL((pad_rect_kernel<T>), dim3(cpad / 64, rpad / 4), blk, 0, st, src, (int)r, (int)cc, (int)rpad, (int)cpad,
+                         dst);
+      break;
+    }
+    case 17: {  // load_K_kernel: gpcore.hip:1005
+      const long long n = ip[0], npad = ip[1];
+      B1_REQ(n > 0 && n <= npad && npad % TILE == 0);
+      B1_REQ(has_in(0, n * n) && has_in(1, SP_STRIDE) && has_in(2, n) && has_out(0, npad * npad));
+      const double* K = q.up<double>(0);
+      const double* sp = q.up<double>(1);
+      const double* dv = q.up<double>(2);
+      T* A = q.res<T>(0);
+      nT = 1;
+      if (!q.ok) break;
+      hipLaunchKernelGGL((load_K_kernel<T>), dim3(npad / 64, npad / 4), blk, 0, st, K, (int)n, (int)npad, sp, dv, A);
+      break;
+    }
+    case 18: {  // rect_copy_kernel: plan.h:273
+      const long long rows = ip[0], cols = ip[1], lds_ = ip[2], ldd = ip[3], batch = ip[4];
+      B1_REQ(rows > 0 && rows % 32 == 0 && cols > 0 && cols % TILE == 0 && lds_ >= cols && ldd >= cols && lds_ % 4 == 0 &&
+             ldd % 4 == 0 && batch > 0);  // (16-byte aligned rows in either type)
+      B1_REQ(has_in(0, batch * rows * lds_) && has_in(1, batch * rows * ldd) && in_n[0] % (4 * batch) == 0 &&
+             in_n[1] % (4 * batch) == 0 && has_out(0, in_n[1]));
+      const T* src = q.up<T>(0);
+      T* dst = q.res<T>(0, 1);
+      nT = 1;
+      if (!q.ok) break;
+      hipLaunchKernelGGL((rect_copy_kernel<T>), dim3((cols + 64 * VEC - 1) / (64 * VEC), rows / 32, batch), blk, 0, st, src,
+                         in_n[0] / batch, (int)lds_, dst, in_n[1] / batch, (int)ldd, (int)rows, (int)cols);
+      break;
+    }
+    case 19: {  // grow_copy_kernel: gpcore.hip:4968
+      const long long np = ip[0], npn = ip[1], batch = ip[2];
+      B1_REQ(np > 0 && np <= npn && npn % TILE == 0 && batch > 0);
+      B1_REQ(has_in(0, batch * np * np) && has_out(0, batch * npn * npn));
+      const T* src = q.up<T>(0);
+      T* dst = q.res<T>(0);
+      nT = 1;
+      if (!q.ok) break;
+      hipLaunchKernelGGL((grow_copy_kernel<T>), dim3(npn / 64, npn / 4, batch), blk, 0, st, src, (int)np, dst, (int)npn);
+      break;
+    }
+    case 20: {  // append_row_kernel: gpcore.hip:5104 (there one launch per sample)
+      const long long npad = ip[0], n = ip[1], batch = ip[2];
+      B1_REQ(npad > 0 && npad % TILE == 0 && n >= 0 && n < npad && batch > 0);
+      B1_REQ(has_in(0, batch * npad * npad) && has_in(1, batch * npad * npad) && has_in(2, batch * npad) &&
+             has_in(3, batch * npad) && has_in(4, batch * 5) && has_in(5, batch * npad));
+      B1_REQ(has_out(0, batch * npad * npad) && has_out(1, batch * npad * npad) && has_out(2, batch * npad));
+      T* A = q.res<T>(0, 0);
+      T* W = q.res<T>(1, 1);
+      const double* l = q.up<double>(2);
+      const double* au = q.up<double>(3);
+      const double* cf = q.up<double>(4);
+      double* al = q.res<double>(2, 5);
+      nT = 2;
+      if (!q.ok) break;
+      hipLaunchKernelGGL((append_row_kernel<T>), dim3((n + 256) / 256, batch), dim3(256), 0, st, A, W, npad * npad, (int)npad,
+                         (int)n, l, au, (int)npad, cf, al);
+      break;
+    }
+    case 21: {  // append_low_kernel: gpcore.hip:5109
+      const long long ld = ip[0], n = ip[1];
+      B1_REQ(ld > 0 && n >= 0 && n < ld);
+      B1_REQ(has_in(0, ld * ld) && has_in(1, std::max<long long>(n, 1)) && has_in(2, 5) && has_in(3, ld) && has_out(0, ld * ld) &&
+             has_out(1, ld));
+      T* A = q.res<T>(0, 0);
+      const double* au = q.up<double>(1);
+      const double* cf = q.up<double>(2);
+      double* al = q.res<double>(1, 3);
+      nT = 1;
+      if (!q.ok) break;
+      hipLaunchKernelGGL((append_low_kernel<T>), dim3((n + 64) / 64, (n + 4) / 4), blk, 0, st, A, (int)ld, (int)n, au, cf, al);
+      break;
+    }
+    default:
+      FAIL(c, "gpc_debug_blas1: which must be 0 .. 21");
+  }
+  if (!q.ok) FAIL(c, "gpc_debug_blas1: out of device memory, or a copy failed");
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(st));
+  for (int k = 0; k < 3; ++k)
+    if (!(k < nT ? q.down<T>(k) : q.down<double>(k))) FAIL(c, "gpc_debug_blas1: the copy of a result failed");
+  return 0;
+}
+#undef B1_REQ
+}  // namespace
+
 
 extern "C" {
 
@@ -7417,6 +7775,16 @@ int gpc_debug_block_gram(gpc_ctx* c, int dtype, int n, int M, int Dp, const doub
   HIPCHK(c, hipSetDevice(c->device));
   return dtype == GPC_F64 ? debug_block_gram_impl<double>(c, n, M, Dp, Y, Z, diag_only != 0, out)
                           : debug_block_gram_impl<float>(c, n, M, Dp, Y, Z, diag_only != 0, out);
+}
+
+int gpc_debug_blas1(gpc_ctx* c, int which, int dtype, const int* ip, const double* const* in, const long long* in_n,
+                    double* const* out, const long long* out_n) {
+  if (!c) return -2;
+  if (!ip || !in || !in_n || !out || !out_n || (dtype != GPC_F64 && dtype != GPC_F32))
+    FAIL(c, "gpc_debug_blas1: bad arguments");
+  HIPCHK(c, hipSetDevice(c->device));
+  return dtype == GPC_F64 ? debug_blas1_impl<double>(c, which, ip, in, in_n, out, out_n)
+                          : debug_blas1_impl<float>(c, which, ip, in, in_n, out, out_n);
 }
 
 int gpc_debug_hess_contract(gpc_ctx* c, int kernel_id, int degree, int dtype, const double* hyp_cov, const double* X, int N,

@@ -629,6 +629,48 @@ int gpc_debug_cov(gpc_ctx* ctx, int which, int kernel_id, int degree, int dtype,
                   const double* Xstar, int M, const double* mat, const double* vec, double* out0,
                   double* out1, double* xs_out);
 
+/* ONE launch of one kernel of gpyreg_amd/csrc/blas1.h, with the grid and block of the production call it mirrors, on
+ * buffers of the hook's own (allocated for the call and freed before it returns).  in[0..5]: the operands, in_n[k]
+ * doubles each (NULL / 0: absent), uploaded whole and verbatim -- padding and whatever lies outside the kernel's
+ * contract included; operands the kernel reads as `dtype` are converted with a plain cast, the others stay double.
+ * out[0..2]: every result buffer has out_n[k] elements plus a guard of 128; it is filled with quiet NaNs before the
+ * launch -- or, for a kernel that updates in place, starts from the operand named below -- and comes back WHOLE, the
+ * guard included, as out_n[k] + 128 doubles: "not written" and "written past the end" both show.  All matrices are
+ * dense with the natural batch stride.  grad_tail_kernel always gets alpha, diagq and all three results: without mean
+ * or noise slots mg / ng are the guard alone (out_n = 0), so that a write there shows.  (T): stored in `dtype`.
+ * which, ip[], in[], out[]:
+ *    0 trmv_kernel              npad, batch, row0, rows              W (T), r                    z[batch npad]
+ *    1 trmv_low_kernel          npad, batch                          W (T), r                    z
+ *    2 gemv_sub_kernel          npad, batch, row0, nrows, col0, ncols  A (T), z, r               r, in place (in[2])
+ *    3 trmv_t_part_kernel<T, 8> npad, batch, quad (0 | 1)            W (T), z                    part[batch npad/128 npad],
+ *                                                                                               quad[batch]
+ *    4 trmv_t_part_low_kernel   as 3
+ *    5 trmv_t_sum_kernel        npad, batch, sp_stride, sp_off       part, sp (NULL: no scale)   out[batch npad]
+ *    6 dot_kernel               n, stride, batch                     x, y                        out[batch]
+ *    7 mat_t_vec_kernel         n, P, vstride, batch                 Mat, vec                    out[batch P]
+ *    8 grad_tail_kernel         ntiles, P, n, mean_N, noise_N, vstride, batch
+ *                                                part, dm (NULL: ones), alpha, dsn2, diagq       gout[batch P], mg[batch mean_N],
+ *                                                                                               ng[batch noise_N]
+ *    9 colsum_prod_kernel       ld, nrows, mpad, batch               A (T), B (T)                out[batch mpad]
+ *   10 colsum_vec_kernel        ld, nrows, mpad, vstride, batch      A (T), v                    out[batch mpad]
+ *   11 diagq_kernel             n, ld, P, batch                      Ainv (T), alpha, sp[batch 4]   diagq[batch ld], out[batch P]
+ *   12 trace_plane_kernel       n, ld, blocks                        Ainv (T), alpha, sp[4], dK  part[blocks]
+ *   13 extract_kernel           n, ld, mode                          src (T)                     dst[n n]
+ *   14 neg_sym_kernel           npad, ld, batch                      buf (T)                     buf (T), in place (in[0])
+ *   15 pad_load_kernel          n, npad                              src                         dst (T)[npad npad]
+ *   16 pad_rect_kernel          r, c, rpad, cpad                     src                         dst (T)[rpad cpad]
+ *   17 load_K_kernel            n, npad                              K, sp[4], dvec              A (T)[npad npad]
+ *   18 rect_copy_kernel         rows, cols, lds, ldd, batch          src (T), dst (T)            dst (T), in place (in[1])
+ *   19 grow_copy_kernel         np, npn, batch                       src (T)                     dst (T)[batch npn npn]
+ *   20 append_row_kernel        npad, n, batch          A (T), W (T), l, au, coef[batch 5], alpha   A (T), W (T), alpha, in place
+ *                                                                                               (in[0], in[1], in[5])
+ *   21 append_low_kernel        ld, n                   A (T), au, coef[5], alpha                A (T), alpha, in place
+ *                                                                                               (in[0], in[3])
+ * A launch that would read or write outside these buffers is refused (-2), and so is a vector of which = 0, 1, 3, 4
+ * that is not finite over the rows of the launch: those kernels read W's diagonal tiles unmasked (blas1.h).             */
+int gpc_debug_blas1(gpc_ctx* ctx, int which, int dtype, const int* ip, const double* const* in, const long long* in_n,
+                    double* const* out, const long long* out_n);
+
 /* gpc_grad_post's block Gram kernel on caller-provided panels Y, Z: n rows x (Dp planes of M queries), row major
  * ([i][a][j]), stored in `dtype` and padded to the pipeline's plane width.  Z = NULL: Z = Y.  out[j][a][b] = out[j][b][a]
  * = sum_i Y[i][a][j] Z[i][b][j] for a >= b (the lower triangle, mirrored), accumulated in fp64 in an order fixed by n alone;
