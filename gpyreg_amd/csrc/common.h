@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -24,6 +26,59 @@ inline int chunk_from_budget(int S, size_t per, size_t shared, size_t budget, bo
   if (budget < shared + per) return clamp_to_one ? 1 : 0;
   const size_t fit = (budget - shared) / per;
   return (int)(fit < (size_t)S ? fit : (size_t)S);
+}
+
+// One declaration per scratch block: a layout function lists its arrays once through take(), and the same list sizes
+// the block (counting: default-constructed, take() returns nullptr and `bytes` is the sum) and hands out its pointers
+// (carving: constructed on the block's base).  Every per-sample array is cnt x something, so the count at cnt = 1 is
+// the per-sample share that chunk_from_budget divides by.  Host only, no HIP call.
+struct ScratchCarver {
+  const bool carving = false;  // (its own flag: a carver on a null base still carves, it never counts by accident)
+  char* p = nullptr;
+  size_t bytes = 0;
+  ScratchCarver() = default;
+  explicit ScratchCarver(void* base) : carving(true), p(static_cast<char*>(base)) {}
+  template <typename T = double>
+  T* take(size_t n) {
+    bytes += n * sizeof(T);
+    if (!carving) return nullptr;
+    T* r = reinterpret_cast<T*>(p);
+    p += n * sizeof(T);
+    return r;
+  }
+  // the two uses of a scratch struct's layout(ScratchCarver&, cnt, dims...): its bytes, and its pointers from `base` on
+  template <typename Z, typename... Dims>
+  static size_t count(Dims... dims) {
+    ScratchCarver sc;
+    Z().layout(sc, dims...);
+    return sc.bytes;
+  }
+  template <typename Z, typename... Dims>
+  static void carve(Z& z, void* base, Dims... dims) {
+    ScratchCarver sc(base);
+    z.layout(sc, dims...);
+  }
+};
+
+// The bounded host spin on a completion word that the device writes last: true once *flag == seq, false after
+// limit_us without it (the caller then waits for the stream the ordinary way).  Host only, no HIP call; static: the
+// library exports nothing for it.
+static inline bool poll_word(const unsigned long long* flag, unsigned long long seq, double limit_us) {
+  const volatile unsigned long long* fw = flag;
+  const auto t_poll = std::chrono::steady_clock::now();
+  bool seen = false;
+  for (int spin = 0; !(seen = *fw == seq); ++spin) {
+    if ((spin & 63) == 63 &&
+        std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_poll).count() > limit_us)
+      break;
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#elif defined(__aarch64__)
+    __asm__ __volatile__("yield");
+#endif
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return seen;
 }
 
 // `info` of a factorization: 0 = done, k > 0 = the pivot of row k was not positive (LAPACK's convention; the host

@@ -493,6 +493,7 @@ struct gpc_ctx {
   static constexpr size_t LAND_BYTES = 64u << 10;
   unsigned long long land_seq = 0;
   unsigned long long small_polled = 0, small_synced = 0;  // statistics ("small_polled" / "small_synced")
+  int last_chunk = 0;  // what plan_chunk last returned ("last_chunk")
   unsigned long long grad_post_gram_us = 0;  // Gram passes of the last gpc_grad_post, device microseconds ("grad_post_gram_us")
   unsigned long long hess_contract_us = 0;  // contraction passes of the last gpc_predict_hess, device microseconds ("hess_contract_us")
   unsigned long long nll_hess_gram_us = 0, nll_hess_contract_us = 0;  // Gram pass / second-derivative contraction of the last gpc_nll_hess, device microseconds
@@ -1601,24 +1602,9 @@ struct Pipe {
     } else if (!land) {
       HIPCHK(c, hipMemcpyAsync(hscal.data(), d_logdet, scal_bytes, hipMemcpyDeviceToHost, st));
     }
-    bool seen = false;
-    if (poll && flag && !timing) {
-      // (bounded: a call that has not announced itself after 150 us -- a large batch, a busy device -- is waited for the
-      // ordinary way, which also covers a device that never writes the word)
-      const volatile unsigned long long* fw = flag;
-      const auto t_poll = std::chrono::steady_clock::now();
-      for (int spin = 0; !seen; ++spin) {
-        if (*fw == seq) {
-          seen = true;
-          break;
-        }
-        if ((spin & 63) == 63 &&
-            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_poll).count() > 150.0)
-          break;
-        __builtin_ia32_pause();
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-    }
+    // (bounded: a call that has not announced itself after 150 us -- a large batch, a busy device -- is waited for the
+    // ordinary way, which also covers a device that never writes the word)
+    const bool seen = poll && flag && !timing && poll_word(flag, seq, 150.0);
     if (seen) {
       ++c->small_polled;  // every store of the call is visible (the flag was its last); the stream drains by itself
     } else {
@@ -1733,8 +1719,7 @@ struct Pipe {
     // ... and so does every problem below N_pad = 2048, whose call is 0.1 - 1 ms of dependent launches (the timing of the
     // larger ones feeds bench.py's roofline figures and costs them nothing measurable)
     timing_on = c->small_timing != 0 || npad >= 2048;
-    bool ev0_pending = small_cand && !c->small_timing;
-    if (timing_on && !ev0_pending) HIPCHK(c, hipEventRecord(c->ev[0], st));
+    if (timing_on) HIPCHK(c, hipEventRecord(c->ev[0], st));
     const void* hsp = up(c->spb.p, &b.sp[(size_t)s0 * SP_STRIDE], (size_t)cnt * SP_STRIDE * 8);
     const void* hmul = up(c->mulb.p, &b.mul[(size_t)s0 * D], (size_t)cnt * D * 8);
     const void* hdv = up(c->divb.p, &b.dv[(size_t)s0 * D], (size_t)cnt * D * 8);
@@ -1824,7 +1809,6 @@ struct Pipe {
       return rc;
     }
     // one kernel: every staged segment and the zeroing of [logdet | quad | info] (padded to whole words)
-    if (timing_on && ev0_pending) HIPCHK(c, hipEventRecord(c->ev[0], st));  // (a one-leaf candidate that takes the general pipeline after all)
     // (+ 8 bytes: the counter of the download launch's completion flag, see XferDesc)
     HIPCHK(c, c->pin.flush_up(st, c->scal.p, scal_bytes0 + 8));
 
@@ -1936,22 +1920,7 @@ struct Pipe {
     unsigned long long* flag = poll ? reinterpret_cast<unsigned long long*>(c->land_blk + (gpc_ctx::LAND_BYTES / 8 - 1)) : nullptr;
     const unsigned long long seq = ++c->land_seq;
     HIPCHK(c, c->pin.flush_down(st, flag, seq, reinterpret_cast<int*>(reinterpret_cast<char*>(c->scal.p) + scal_bytes0)));
-    bool seen = false;
-    if (poll) {
-      const volatile unsigned long long* fw = flag;
-      const auto t_poll = std::chrono::steady_clock::now();
-      for (int spin = 0; !seen; ++spin) {
-        if (*fw == seq) {
-          seen = true;
-          break;
-        }
-        if ((spin & 63) == 63 &&
-            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_poll).count() > 2000.0)
-          break;
-        __builtin_ia32_pause();
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-    }
+    const bool seen = poll && poll_word(flag, seq, 2000.0);
     if (seen) {
       ++c->small_polled;
     } else {
@@ -2193,14 +2162,14 @@ template <typename What = std::string (*)(size_t)>
 int plan_chunk(gpc_ctx* c, int S, size_t per, size_t shared, size_t held, bool fits, size_t reserve, bool clamp_to_one,
                What&& what = nullptr) {
   const bool forced = getenv("GPC_MEM_BUDGET_MB") != nullptr;
-  if (!forced && fits) return S;
+  if (!forced && fits) return c->last_chunk = S;
   c->pool_drain();
   size_t avail = free_device_bytes() + (forced ? 0 : held);
   if (!forced) avail = avail > reserve ? avail - reserve : 0;
   const size_t budget = (size_t)(avail * 0.8);
   const int chunk = chunk_from_budget(S, per, shared, budget, clamp_to_one);
   if (!chunk) c->err = what(budget);
-  return chunk;
+  return c->last_chunk = chunk;
 }
 
 // A consumer reads every sample's factor: none may have failed
@@ -2241,6 +2210,14 @@ template <typename T>
 GemmArgs tri_product_args(const gpc_post* po, int s_first, bool lch, const T* B, T* C, long long sB, int ldb, int ncols) {
   const long long sM = (long long)po->npad * po->npad;
   return tri_gemm_args((lch ? po->W.as<T>() : po->A.as<T>()) + (size_t)s_first * sM, sM, po->npad, lch, B, C, sB, ldb, ncols);
+}
+
+// ... and the second product of an L_chol run on top of such a g: Q = W^T V (launched with the A operand transposed:
+// the upper triangular W^T, k from the tile row's diagonal block on)
+inline GemmArgs wt_product_args(GemmArgs g, const void* V, void* Q) {
+  g.B = V, g.C = Q;
+  g.klo = KLO_ROW, g.khi = KHI_FULL;
+  return g;
 }
 
 // The four timing events of a call: gpc_last_timing reports ev[0] -> ev[3] as its device time, ev[1] -> ev[2] as its
@@ -2616,17 +2593,22 @@ int post_consts_resident(gpc_post* po) {
 }
 
 // The posterior's per-sample constants as the kernels of a chunk read them: the resident copies when the call works on
-// all samples at once (the usual case), else the context's buffers, refilled for every chunk by stage()
+// all samples at once (the usual case), else the context's buffers, refilled for every chunk by stage().  The
+// context's buffers are sized for a chunk either way: they count towards what later calls' planning finds held and free
 struct ChunkConsts {
   gpc_post* po = nullptr;
   bool resident = false;
   const double *spb = nullptr, *mulb = nullptr, *divb = nullptr, *xsb = nullptr;
-  int init(gpc_post* po_, bool resident_) {
+  int init(gpc_post* po_, int chunk, bool may_be_resident = true) {
     po = po_;
-    resident = resident_;
+    resident = may_be_resident && chunk == po->S;
+    gpc_ctx* c = po->ctx;
+    HIPCHK(c, c->xs.ensure((size_t)chunk * po->npad * po->D * 8));
+    HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
+    HIPCHK(c, c->mulb.ensure((size_t)chunk * po->D * 8));
+    HIPCHK(c, c->divb.ensure((size_t)chunk * po->D * 8));
     if (resident)
       if (int rc = post_consts_resident(po)) return rc;
-    gpc_ctx* c = po->ctx;
     spb = resident ? po->dsp.as<double>() : c->spb.as<double>();
     mulb = resident ? po->dmul.as<double>() : c->mulb.as<double>();
     divb = resident ? po->ddv.as<double>() : c->divb.as<double>();
@@ -2774,10 +2756,6 @@ struct RhsCall {
     d_mut = qg ? c->qcon.as<double>() : nullptr;
     d_qcon = qg ? d_mut + (size_t)D * mpad : nullptr;
     HIPCHK(c, c->xss.ensure(((size_t)chunk * mpad * D + 2 * (size_t)M * D) * 8));
-    HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
-    HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
-    HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
-    HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
     HIPCHK(c, c->pout.ensure((size_t)chunk * mpad * 2 * 8));
     d_xa = c->xss.as<double>() + (size_t)chunk * mpad * D;
     d_xb = d_xa + (size_t)M * D;
@@ -2803,7 +2781,7 @@ struct RhsCall {
     }
     if (grad) hgrad = landing_block(c, gres_per * (size_t)chunk, hgrad_v);  // the gradient planes of a chunk
     // all samples in one chunk (the usual case): the posterior's constants are resident, see gpc_post
-    return k.init(po, chunk == S && r.rhs != RhsRequest::GIVEN_KS);
+    return k.init(po, chunk, r.rhs != RhsRequest::GIVEN_KS);
   }
 
   // ---- the right-hand sides R_s of a chunk (into Ks) and lin = R_s^T alpha_s ----
@@ -2888,13 +2866,9 @@ struct RhsCall {
       // Q = W^T V (L_chol: the upper triangular A operand W^T, k from the tile row's diagonal block on) | G as it is
       const T* Qs = Va;
       if (lch) {
-        GemmArgs q = g;
-        q.B = Va;
-        q.C = c->qb.as<T>() + (size_t)a * sKs;
-        q.klo = KLO_ROW;
-        q.khi = KHI_FULL;
-        HIPCHK(c, launch_gemm<T>(st, q, true, true, len));
-        Qs = c->qb.as<T>() + (size_t)a * sKs;
+        T* const Qa = c->qb.as<T>() + (size_t)a * sKs;
+        HIPCHK(c, launch_gemm<T>(st, wt_product_args(g, Va, Qa), true, true, len));
+        Qs = Qa;
       }
       if (r.rhs == RhsRequest::QUAD_Z) {
         if (last) HIPCHK(c, tm.mark2());  // (quad_grad: with Q)
@@ -2985,19 +2959,7 @@ struct RhsCall {
       unsigned long long* flag = reinterpret_cast<unsigned long long*>(c->land_blk + (gpc_ctx::LAND_BYTES / 8 - 1));
       const unsigned long long seq = ++c->land_seq;
       HIPCHK(c, c->pin.flush_down(st, flag, seq, nullptr));
-      const volatile unsigned long long* fw = flag;
-      const auto t_poll = std::chrono::steady_clock::now();
-      for (int spin = 0; !seen; ++spin) {
-        if (*fw == seq) {
-          seen = true;
-          break;
-        }
-        if ((spin & 63) == 63 &&
-            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_poll).count() > 2000.0)
-          break;
-        __builtin_ia32_pause();
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
+      seen = poll_word(flag, seq, 2000.0);
     } else if (poll) {
       HIPCHK(c, c->pin.flush_down(st));
     }
@@ -3147,10 +3109,6 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
   HIPCHK(c, c->vb.ensure((size_t)chunk * (sKa + sKb) * sizeof(T)));
   HIPCHK(c, c->kss.ensure((size_t)chunk * sC * sizeof(T)));
   HIPCHK(c, c->xss.ensure(((size_t)chunk * (mapad + mbpad) + Ma + Mb) * D * 8));
-  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
-  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
-  HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
-  HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
   HIPCHK(c, c->pout.ensure((size_t)chunk * mbpad * 2 * 8));
   HIPCHK(c, c->daux.ensure((size_t)chunk * (mapad + 1) * 8));  // [weights: chunk x mapad | the products' factors: chunk]
   HIPCHK(c, c->dbg2.ensure((size_t)chunk * (npad / CT) * mmax * 8));
@@ -3175,7 +3133,7 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
     hcov = static_cast<double*>(c->pin.alloc((size_t)Ma * Mb * 8));
 
   ChunkConsts k;
-  if (int rc = k.init(po, chunk == S)) return rc;
+  if (int rc = k.init(po, chunk)) return rc;
   const double *spb = k.spb, *mulb = k.mulb, *divb = k.divb, *xsb = k.xsb;
 
   // gpc_last_timing: device time of the call and of its products (the first triangular product to the cross product)
@@ -3356,10 +3314,6 @@ int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* 
   HIPCHK(c, c->pout.ensure((size_t)chunk * ld * 8));
   HIPCHK(c, c->daux.ensure((size_t)chunk * 8));
   HIPCHK(c, c->xss.ensure(((size_t)chunk * mb + M) * D * 8));
-  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
-  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
-  HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
-  HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
   T* const P = c->ks.as<T>();
   T* const V = c->vb.as<T>();
   double* const xsq = c->xss.as<double>();
@@ -3374,7 +3328,7 @@ int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* 
   HIPCHK(c, c->pin.up(d_xa, xstar, (size_t)M * D * 8, st));
   std::vector<double> hmean((size_t)chunk * ld), hgram((size_t)chunk * gper), hf0(chunk);
   ChunkConsts k;
-  if (int rc = k.init(po, chunk == S)) return rc;
+  if (int rc = k.init(po, chunk)) return rc;
   c->ms_total = c->ms_factor = 0;
   double gram_us = 0;
   for (int s0 = 0; s0 < S; s0 += chunk) {
@@ -3508,10 +3462,6 @@ int hess_impl(gpc_post* po, const double* xstar, int M, bool var, double* fmu, d
   HIPCHK(c, c->pout.ensure((size_t)chunk * ld * 8));
   HIPCHK(c, c->daux.ensure((size_t)chunk * 8));
   HIPCHK(c, c->xss.ensure(((size_t)chunk * mb + M) * D * 8));
-  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
-  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
-  HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
-  HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
   T* const P = c->ks.as<T>();
   T* const V = c->vb.as<T>();
   T* const Q = c->qb.as<T>();
@@ -3530,7 +3480,7 @@ int hess_impl(gpc_post* po, const double* xstar, int M, bool var, double* fmu, d
   std::vector<double> hmean((size_t)chunk * ld), hgram((size_t)chunk * gper), hsum((size_t)chunk * hper), cs(D),
       Ha((size_t)D * D), Hq((size_t)D * D);
   ChunkConsts k;
-  if (int rc = k.init(po, chunk == S)) return rc;
+  if (int rc = k.init(po, chunk)) return rc;
   c->ms_total = c->ms_factor = 0;
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
@@ -3554,14 +3504,10 @@ int hess_impl(gpc_post* po, const double* xstar, int M, bool var, double* fmu, d
           GemmArgs g = tri_product_args<T>(po, s0 + a, lch, P + (size_t)a * sP, V + (size_t)a * sP, sP, ld, ld);
           HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
           if (lch) {  // Q = W^T V[slot 0]: W^T upper triangular, k from the tile row's diagonal block on
-            GemmArgs q = g;
-            q.B = V + (size_t)a * sP;
-            q.C = Q + (size_t)a * sQ;
+            GemmArgs q = wt_product_args(g, V + (size_t)a * sP, Q + (size_t)a * sQ);
             q.sC = sQ;
             q.ldc = mb;
             q.N = mb;
-            q.klo = KLO_ROW;
-            q.khi = KHI_FULL;
             HIPCHK(c, launch_gemm<T>(st, q, true, true, len));
           }
           return 0;
@@ -3657,35 +3603,24 @@ inline void nh_plane_of(const CovDesc& cd, int p, int* mode, int* dim) {
 struct NhScratch {
   int npad = 0, ppl = 0, cov_N = 0, noise_N = 0, mean_N = 0, nt = 0, ntl = 0, npairs = 0, nd2 = 0;
   double *Q, *B, *Op, *X, *Y, *E, *diagq, *upart, *gpart, *gsum, *grpart, *grsum, *d2part, *d2sum;
-  // doubles of one sample's share
-  static size_t per_sample(int npad, int cov_N, int noise_N, int mean_N, int nd2) {
-    const size_t n2 = (size_t)npad * npad, ppl = cov_N + noise_N, nt = npad / CT, ntl = nt * (nt + 1) / 2;
-    return (ppl + 2) * n2 + (2 * (ppl + mean_N) + noise_N + 1 + nt) * (size_t)npad + nt * nt * 2 + 2 * (size_t)cov_N +
-           (nt * nt + 1) * (ppl * (ppl + 1) / 2) + (ntl + 1) * (size_t)nd2;
-  }
-  void carve(double* p, int cnt, int npad_, int cov_N_, int noise_N_, int mean_N_, int nd2_) {
+  void layout(ScratchCarver& sc, int cnt, int npad_, int cov_N_, int noise_N_, int mean_N_, int nd2_) {
     npad = npad_, cov_N = cov_N_, noise_N = noise_N_, mean_N = mean_N_, nd2 = nd2_;
     ppl = cov_N + noise_N, nt = npad / CT, ntl = nt * (nt + 1) / 2, npairs = ppl * (ppl + 1) / 2;
     const size_t n2 = (size_t)npad * npad, c = cnt;
-    auto take = [&](size_t n) {
-      double* r = p;
-      p += n;
-      return r;
-    };
-    Q = take(c * n2);
-    B = take(c * ppl * n2);
-    Op = take(c * n2);
-    X = take(c * (ppl + mean_N) * npad);
-    Y = take(c * (ppl + mean_N) * npad);
-    E = take(c * noise_N * npad);
-    diagq = take(c * npad);
-    upart = take(c * nt * npad);
-    gpart = take(c * nt * nt * 2);
-    gsum = take(c * cov_N * 2);
-    grpart = take(c * nt * nt * npairs);
-    grsum = take(c * npairs);
-    d2part = take(c * ntl * nd2);
-    d2sum = take(c * nd2);
+    Q = sc.take(c * n2);
+    B = sc.take(c * ppl * n2);
+    Op = sc.take(c * n2);
+    X = sc.take(c * (ppl + mean_N) * npad);
+    Y = sc.take(c * (ppl + mean_N) * npad);
+    E = sc.take(c * noise_N * npad);
+    diagq = sc.take(c * npad);
+    upart = sc.take(c * nt * npad);
+    gpart = sc.take(c * nt * nt * 2);
+    gsum = sc.take(c * cov_N * 2);
+    grpart = sc.take(c * nt * nt * npairs);
+    grsum = sc.take(c * npairs);
+    d2part = sc.take(c * ntl * nd2);
+    d2sum = sc.take(c * nd2);
   }
 };
 
@@ -3747,6 +3682,37 @@ inline double nh_second(const CovDesc& cd, int p, int q, const double* g, int gs
   return q == D ? 2.0 * g1(D + 1) : g2(D + 1);  // shape x sf | shape x shape
 }
 
+// Q = W^T W / sl (L_chol; the lower tiles of the product land in `tiles`, a buffer of cnt n x n matrices that the caller
+// overwrites later) | -A of samples s0 .. s0 + cnt - 1, with diag Q.  Shared by gpc_nll_hess and gpc_cv_grad (fp64)
+int posterior_q(gpc_post* po, const ChunkConsts& k, int s0, int cnt, double* tiles, double* Q, double* diagq) {
+  gpc_ctx* c = po->ctx;
+  hipStream_t st = c->st;
+  const int N = po->N, npad = po->npad;
+  const long long n2 = (long long)npad * npad;
+  const double* alpha = po->alpha.as<double>() + (size_t)s0 * npad;
+  return for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+    const double* src = po->A.as<double>() + (size_t)(s0 + a) * n2;
+    if (lch) {
+      Factor<double> F;
+      F.st = st;
+      F.batch = len;
+      F.npad = npad;
+      F.A = po->A.as<double>() + (size_t)(s0 + a) * n2;
+      F.W = po->W.as<double>() + (size_t)(s0 + a) * n2;
+      F.Tm = tiles + (size_t)a * n2;
+      F.sA = F.sW = F.sT = n2;
+      F.lauum(F.Tm, n2);
+      HIPCHK(c, F.err);
+      src = F.Tm;
+    }
+    hipLaunchKernelGGL(nh_form_q_kernel, dim3((unsigned)(n2 / 256), len), dim3(256), 0, st, src, n2, npad,
+                       k.spb + (size_t)a * SP_STRIDE, lch ? 1 : 0, alpha + (size_t)a * npad, N, npad, Q + (size_t)a * n2, n2,
+                       diagq + (size_t)a * npad);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+  });
+}
+
 int nll_hess_impl(gpc_post* po, const double* dm, int mean_N, const double* dsn2, int dsn2_rows, int noise_N, double* H,
                   double* dnlz, double* alpha_out, double* diagq_out) {
   gpc_ctx* c = po->ctx;
@@ -3755,8 +3721,8 @@ int nll_hess_impl(gpc_post* po, const double* dm, int mean_N, const double* dsn2
   const bool ard = !cov_is_iso(po->cd.kind);
   const int nd2 = ard ? nh_pairs(po->D) : 0;
   hipStream_t st = c->st;
-  const long long n2 = (long long)npad * npad, sM = n2;
-  const size_t per = NhScratch::per_sample(npad, cov_N, noise_N, mean_N, nd2) * 8;
+  const long long n2 = (long long)npad * npad;
+  const size_t per = ScratchCarver::count<NhScratch>(1, npad, cov_N, noise_N, mean_N, nd2);
   const size_t held = c->nhs.bytes;
   const int chunk = plan_chunk(c, S, per, 0, held, (size_t)S * per <= held, 0, false, [&](size_t budget) {
     return "gpc_nll_hess: the scratch of one sample (" + std::to_string(per) + " bytes: N_pad = " + std::to_string(npad) +
@@ -3765,24 +3731,20 @@ int nll_hess_impl(gpc_post* po, const double* dm, int mean_N, const double* dsn2
   });
   if (!chunk) return -2;
   HIPCHK(c, c->nhs.ensure((size_t)chunk * per));
-  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * po->D * 8));
-  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
-  HIPCHK(c, c->mulb.ensure((size_t)chunk * po->D * 8));
-  HIPCHK(c, c->divb.ensure((size_t)chunk * po->D * 8));
   NhScratch z;
-  z.carve(c->nhs.as<double>(), chunk, npad, cov_N, noise_N, mean_N, nd2);
+  ScratchCarver::carve(z, c->nhs.p, chunk, npad, cov_N, noise_N, mean_N, nd2);
   CallTimer tm{c, CallTimer::wanted(c, npad)};
   GramClock gc(tm.on), cc(tm.on);
   double gram_us = 0, contract_us = 0;
   ChunkConsts k;
-  if (int rc = k.init(po, chunk == S)) return rc;
+  if (int rc = k.init(po, chunk)) return rc;
   c->ms_total = c->ms_factor = 0;
   const size_t vlen = (size_t)chunk * npad;
   std::vector<double> hx((size_t)(mean_N + noise_N) * vlen), hX((size_t)ppl * vlen), hY((size_t)nvec * vlen), hal(vlen),
       hdq(vlen), hgr((size_t)chunk * z.npairs), hg((size_t)cov_N * chunk * 2), hd2((size_t)chunk * nd2), uw((size_t)ppl * ppl);
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
-    z.carve(c->nhs.as<double>(), cnt, npad, cov_N, noise_N, mean_N, nd2);
+    ScratchCarver::carve(z, c->nhs.p, cnt, npad, cov_N, noise_N, mean_N, nd2);
     if (int rc = k.stage(s0, cnt, true)) return rc;
     const double* alpha = po->alpha.as<double>() + (size_t)s0 * npad;
     // the mean planes d_k m (rows of X after the u's) and the noise planes' e = mult d sn2, zero in the padding
@@ -3803,29 +3765,7 @@ int nll_hess_impl(gpc_post* po, const double* dm, int mean_N, const double* dsn2
     if (noise_N) HIPCHK(c, hipMemcpyAsync(z.E, he, (size_t)noise_N * cnt * npad * 8, hipMemcpyHostToDevice, st));
     HIPCHK(c, tm.start());
     // a. Q of every sample: W^T W / sl (L_chol; the lower tiles land in the operand buffer) | -A
-    int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
-      const double* src = po->A.as<double>() + (size_t)(s0 + a) * sM;
-      if (lch) {
-        Factor<double> F;
-        F.st = st;
-        F.batch = len;
-        F.npad = npad;
-        F.A = po->A.as<double>() + (size_t)(s0 + a) * sM;
-        F.W = po->W.as<double>() + (size_t)(s0 + a) * sM;
-        F.Tm = z.Op + (size_t)a * n2;
-        F.sA = F.sW = sM;
-        F.sT = n2;
-        F.lauum(F.Tm, n2);
-        HIPCHK(c, F.err);
-        src = F.Tm;
-      }
-      hipLaunchKernelGGL(nh_form_q_kernel, dim3((unsigned)(n2 / 256), len), dim3(256), 0, st, src, n2, npad,
-                         k.spb + (size_t)a * SP_STRIDE, lch ? 1 : 0, alpha + (size_t)a * npad, N, npad, z.Q + (size_t)a * n2,
-                         n2, z.diagq + (size_t)a * npad);
-      HIPCHK(c, hipGetLastError());
-      return 0;
-    });
-    if (rc_runs) return rc_runs;
+    if (int rc = posterior_q(po, k, s0, cnt, z.Op, z.Q, z.diagq)) return rc;
     HIPCHK(c, tm.mark1());
     // b, c. the covariance planes: operand, then B_p = Q d_p K on the plain batched GEMM
     for (int p = 0; p < cov_N; ++p) {
@@ -3917,31 +3857,23 @@ struct CvgScratch {
   double *Q, *QC, *M, *diagq, *u, *b, *part, *out;
   // the block that is downloaded, in order: gsum [cnt][cov_N] | diagG | beta | q | cw, [cnt][npad] each
   double *gsum, *diagG, *beta, *q, *cw;
-  static size_t out_doubles(int cnt, int npad, int cov_N) { return (size_t)cnt * (cov_N + 4 * (size_t)npad); }
-  // doubles of one sample's share
-  static size_t per_sample(int npad, int cov_N) {
-    const size_t n2 = (size_t)npad * npad, nt = npad / CT, ntl = nt * (nt + 1) / 2;
-    return 3 * n2 + 7 * (size_t)npad + (ntl + 1) * (size_t)cov_N;
-  }
-  void carve(double* p, int cnt, int npad, int cov_N) {
+  size_t out_bytes = 0;
+  void layout(ScratchCarver& sc, int cnt, int npad, int cov_N) {
     const size_t n2 = (size_t)npad * npad, nt = npad / CT, ntl = nt * (nt + 1) / 2, c = cnt;
-    auto take = [&](size_t n) {
-      double* r = p;
-      p += n;
-      return r;
-    };
-    Q = take(c * n2);
-    QC = take(c * n2);
-    M = take(c * n2);
-    diagq = take(c * npad);
-    u = take(c * npad);
-    b = take(c * npad);
-    part = take(c * ntl * cov_N);
-    out = gsum = take(c * cov_N);
-    diagG = take(c * npad);
-    beta = take(c * npad);
-    q = take(c * npad);
-    cw = take(c * npad);
+    Q = sc.take(c * n2);
+    QC = sc.take(c * n2);
+    M = sc.take(c * n2);
+    diagq = sc.take(c * npad);
+    u = sc.take(c * npad);
+    b = sc.take(c * npad);
+    part = sc.take(c * ntl * cov_N);
+    const size_t before_out = sc.bytes;
+    out = gsum = sc.take(c * cov_N);
+    diagG = sc.take(c * npad);
+    beta = sc.take(c * npad);
+    q = sc.take(c * npad);
+    cw = sc.take(c * npad);
+    out_bytes = sc.bytes - before_out;
   }
 };
 
@@ -3962,8 +3894,8 @@ int cv_grad_impl(gpc_post* po, int loss, const double* weights, double* gsum_out
   gpc_ctx* c = po->ctx;
   const int S = po->S, N = po->N, npad = po->npad, cov_N = po->cd.cov_N;
   hipStream_t st = c->st;
-  const long long n2 = (long long)npad * npad, sM = n2;
-  const size_t per = CvgScratch::per_sample(npad, cov_N) * 8, shared = (size_t)npad * 8;
+  const long long n2 = (long long)npad * npad;
+  const size_t per = ScratchCarver::count<CvgScratch>(1, npad, cov_N), shared = (size_t)npad * 8;
   const size_t held = c->nhs.bytes;
   const int chunk = plan_chunk(c, S, per, shared, held, shared + (size_t)S * per <= held, 0, false, [&](size_t budget) {
     return "gpc_cv_grad: the scratch of one sample (" + std::to_string(per) + " bytes: N_pad = " + std::to_string(npad) +
@@ -3971,10 +3903,6 @@ int cv_grad_impl(gpc_post* po, int loss, const double* weights, double* gsum_out
   });
   if (!chunk) return -2;
   HIPCHK(c, c->nhs.ensure(shared + (size_t)chunk * per));
-  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * po->D * 8));
-  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
-  HIPCHK(c, c->mulb.ensure((size_t)chunk * po->D * 8));
-  HIPCHK(c, c->divb.ensure((size_t)chunk * po->D * 8));
   double* d_omega = c->nhs.as<double>();  // the weights, shared by the samples, ahead of the chunk's scratch
   std::vector<double> hw(npad, 0.0);
   for (int i = 0; i < N; ++i) hw[i] = weights ? weights[i] : 1.0;
@@ -3984,41 +3912,20 @@ int cv_grad_impl(gpc_post* po, int loss, const double* weights, double* gsum_out
   GramClock tc(tm.on);
   double trace_us = 0;
   ChunkConsts k;
-  if (int rc = k.init(po, chunk == S)) return rc;
+  if (int rc = k.init(po, chunk)) return rc;
   c->ms_total = c->ms_factor = 0;
   const size_t vlen = (size_t)chunk * npad;
-  std::vector<double> ho(CvgScratch::out_doubles(chunk, npad, cov_N)), hal(vlen);
+  ScratchCarver::carve(z, d_omega + npad, chunk, npad, cov_N);
+  std::vector<double> ho(z.out_bytes / 8), hal(vlen);
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
-    z.carve(c->nhs.as<double>() + npad, cnt, npad, cov_N);
+    ScratchCarver::carve(z, d_omega + npad, cnt, npad, cov_N);
     if (int rc = k.stage(s0, cnt, true)) return rc;
     const double* alpha = po->alpha.as<double>() + (size_t)s0 * npad;
     HIPCHK(c, tm.start());
     HIPCHK(c, tm.mark1());
     // a. Q of every sample: W^T W / sl (L_chol; the lower tiles land in M's buffer, overwritten in d) | -A
-    int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
-      const double* src = po->A.as<double>() + (size_t)(s0 + a) * sM;
-      if (lch) {
-        Factor<double> F;
-        F.st = st;
-        F.batch = len;
-        F.npad = npad;
-        F.A = po->A.as<double>() + (size_t)(s0 + a) * sM;
-        F.W = po->W.as<double>() + (size_t)(s0 + a) * sM;
-        F.Tm = z.M + (size_t)a * n2;
-        F.sA = F.sW = sM;
-        F.sT = n2;
-        F.lauum(F.Tm, n2);
-        HIPCHK(c, F.err);
-        src = F.Tm;
-      }
-      hipLaunchKernelGGL(nh_form_q_kernel, dim3((unsigned)(n2 / 256), len), dim3(256), 0, st, src, n2, npad,
-                         k.spb + (size_t)a * SP_STRIDE, lch ? 1 : 0, alpha + (size_t)a * npad, N, npad, z.Q + (size_t)a * n2,
-                         n2, z.diagq + (size_t)a * npad);
-      HIPCHK(c, hipGetLastError());
-      return 0;
-    });
-    if (rc_runs) return rc_runs;
+    if (int rc = posterior_q(po, k, s0, cnt, z.M, z.Q, z.diagq)) return rc;
     // b. c and b per point, beta = Q b
     hipLaunchKernelGGL(cvg_weights_kernel, dim3((npad + 255) / 256, cnt), dim3(256), 0, st, alpha, (const double*)z.Q, n2,
                        npad + 1, (const double*)d_omega, N, npad, loss, z.q, z.cw, z.b);
@@ -4046,7 +3953,7 @@ int cv_grad_impl(gpc_post* po, int loss, const double* weights, double* gsum_out
     HIPCHK(c, tc.record(1, st));
     HIPCHK(c, tm.stop());
     // f. the sums and the vectors; the value and the noise and mean columns are the caller's
-    HIPCHK(c, hipMemcpyAsync(ho.data(), z.out, CvgScratch::out_doubles(cnt, npad, cov_N) * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(ho.data(), z.out, z.out_bytes, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(hal.data(), alpha, (size_t)cnt * npad * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     tm.accumulate();
@@ -4084,37 +3991,25 @@ inline std::vector<int> hg_plane_cols(const CovDesc& cd) {
 // doubles; vectors are [vector][sample][npad], panels [sample][npad][msb])
 struct HgScratch {
   double *Op, *KP, *VP, *Qa, *X, *Y, *Vn, *tmp, *tpart, *upart, *mupart, *cpart, *csum, *dpart, *dsum, *xss, *qs;
-  // doubles of one sample's share
-  static size_t per_sample(int npad, int D, int P, int nvv, int ngp, int msb, bool var, int nout) {
-    const size_t n2 = (size_t)npad * npad, nt = npad / CT, nch = npad / TRC, np = npad, mm = msb;
-    size_t d = (2 * (size_t)P + 1 + nch + nt) * np + (nt + 1) * (size_t)nout * mm + mm * D + 1;
-    if (var) d += n2 + 3 * np * mm + (size_t)nvv * np + nt * mm + nt * (1 + (size_t)nvv) * mm + ((size_t)ngp + nvv) * mm;
-    return d;
-  }
-  void carve(double* p, int cnt, int npad, int D, int P, int nvv, int ngp, int msb, bool var, int nout) {
+  void layout(ScratchCarver& sc, int cnt, int npad, int D, int P, int nvv, int ngp, int msb, bool var, int nout) {
     const size_t n2 = (size_t)npad * npad, nt = npad / CT, nch = npad / TRC, np = npad, mm = msb, c = cnt;
-    auto take = [&](size_t n) {
-      double* r = p;
-      p += n;
-      return r;
-    };
-    Op = take(var ? c * n2 : 0);
-    KP = take(var ? c * np * mm : 0);
-    VP = take(var ? c * np * mm : 0);
-    Qa = take(var ? c * np * mm : 0);
-    dpart = take(var ? c * nt * (1 + (size_t)nvv) * mm : 0);
-    dsum = take(var ? c * ((size_t)ngp + nvv) * mm : 0);
-    mupart = take(var ? c * nt * mm : 0);
-    Vn = take(var ? c * (size_t)nvv * np : 0);
-    X = take(c * P * np);
-    Y = take(c * P * np);
-    tmp = take(c * np);
-    tpart = take(c * nch * np);
-    upart = take(c * nt * np);
-    cpart = take(c * nt * nout * mm);
-    csum = take(c * nout * mm);
-    xss = take(c * mm * D);
-    qs = take(c);
+    Op = sc.take(var ? c * n2 : 0);
+    KP = sc.take(var ? c * np * mm : 0);
+    VP = sc.take(var ? c * np * mm : 0);
+    Qa = sc.take(var ? c * np * mm : 0);
+    dpart = sc.take(var ? c * nt * (1 + (size_t)nvv) * mm : 0);
+    dsum = sc.take(var ? c * ((size_t)ngp + nvv) * mm : 0);
+    mupart = sc.take(var ? c * nt * mm : 0);
+    Vn = sc.take(var ? c * (size_t)nvv * np : 0);
+    X = sc.take(c * P * np);
+    Y = sc.take(c * P * np);
+    tmp = sc.take(c * np);
+    tpart = sc.take(c * nch * np);
+    upart = sc.take(c * nt * np);
+    cpart = sc.take(c * nt * nout * mm);
+    csum = sc.take(c * nout * mm);
+    xss = sc.take(c * mm * D);
+    qs = sc.take(c);
   }
 };
 
@@ -4144,7 +4039,7 @@ int hyp_grad_impl(gpc_post* po, const double* xstar, int M, bool var, const doub
   int msb = pad_tile(M), chunk = 0;
   size_t per = 0;
   for (;;) {
-    per = HgScratch::per_sample(npad, D, P, nvv, ngp, msb, var, nout) * 8;
+    per = ScratchCarver::count<HgScratch>(1, npad, D, P, nvv, ngp, msb, var, nout);
     const size_t held = c->hgs.bytes;
     const int blk = msb;
     chunk = plan_chunk(c, S, per, 0, held, (size_t)S * per <= held, 0, false, [&](size_t budget) {
@@ -4159,16 +4054,12 @@ int hyp_grad_impl(gpc_post* po, const double* xstar, int M, bool var, const doub
   const long long sK = (long long)npad * msb;
   HIPCHK(c, c->hgs.ensure((size_t)chunk * per));
   HIPCHK(c, c->xss.ensure((size_t)M * D * 8));
-  HIPCHK(c, c->xs.ensure((size_t)chunk * npad * D * 8));
-  HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
-  HIPCHK(c, c->mulb.ensure((size_t)chunk * D * 8));
-  HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
   double* const d_xa = c->xss.as<double>();
   HgScratch z;
   CallTimer tm{c, CallTimer::wanted(c, npad)};
   HIPCHK(c, hipMemcpyAsync(d_xa, xstar, (size_t)M * D * 8, hipMemcpyHostToDevice, st));
   ChunkConsts k;
-  if (int rc = k.init(po, chunk == S)) return rc;
+  if (int rc = k.init(po, chunk)) return rc;
   c->ms_total = c->ms_factor = 0;
   const size_t vlen = (size_t)chunk * npad;
   const size_t dper = ((size_t)ngp + nvv) * msb;  // doubles of a sample's quadratic-form sums
@@ -4176,7 +4067,7 @@ int hyp_grad_impl(gpc_post* po, const double* xstar, int M, bool var, const doub
       hd(var ? (size_t)chunk * dper : 0);
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
-    z.carve(c->hgs.as<double>(), cnt, npad, D, P, nvv, ngp, msb, var, nout);
+    ScratchCarver::carve(z, c->hgs.p, cnt, npad, D, P, nvv, ngp, msb, var, nout);
     if (int rc = k.stage(s0, cnt, true)) return rc;
     const double* alpha = po->alpha.as<double>() + (size_t)s0 * npad;
     // what the weights start from, zero in the padding: mult sn2 (log sf), mult d_n sn2 (noise n), d_k m (mean k); the
@@ -4222,12 +4113,7 @@ int hyp_grad_impl(gpc_post* po, const double* xstar, int M, bool var, const doub
                                                 sK, msb, msb);
           HIPCHK(c, launch_gemm<double>(st, g, false, true, len));
           if (lch) {  // W^T upper triangular: k from the tile row's diagonal block on
-            GemmArgs q = g;
-            q.B = z.VP + (size_t)a * sK;
-            q.C = z.Qa + (size_t)a * sK;
-            q.klo = KLO_ROW;
-            q.khi = KHI_FULL;
-            HIPCHK(c, launch_gemm<double>(st, q, true, true, len));
+            HIPCHK(c, launch_gemm<double>(st, wt_product_args(g, z.VP + (size_t)a * sK, z.Qa + (size_t)a * sK), true, true, len));
           }
           return 0;
         });
@@ -5250,12 +5136,7 @@ int append_block_impl(gpc_post* po, int k, const double* m_star, const double* s
         g.tiles_n = kp / TILE;
         HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
         if (lch) {  // Q = W^T V (k from the tile row's diagonal block on)
-          GemmArgs q = g;
-          q.B = Vt + (size_t)a * sK;
-          q.C = Qt + (size_t)a * sK;
-          q.klo = KLO_ROW;
-          q.khi = KHI_FULL;
-          HIPCHK(c, launch_gemm<T>(st, q, true, true, len));
+          HIPCHK(c, launch_gemm<T>(st, wt_product_args(g, Vt + (size_t)a * sK, Qt + (size_t)a * sK), true, true, len));
         }
         return 0;
       });
@@ -5592,21 +5473,28 @@ int paths_create_impl(gpc_post* po, gpc_paths* pa, unsigned long long seed, int 
   const bool use_gemm = c->paths_solve_engine == 2;
   c->paths_solve_engine_ran = use_gemm ? 2 : 1;
   // scratch of one sample: three fp64 N_pad x kq panels (p(X), P, V1) and, for the MFMA engine, three N_pad x kp
-  // panels in the storage type
-  const size_t panel = (size_t)npad * kq * 8, tpanel = use_gemm ? (size_t)npad * kp * sizeof(T) : 0;
-  const size_t per = 3 * panel + 3 * tpanel + 64;
-  const size_t held = c->ks.bytes;
-  int chunk = S;
-  if (getenv("GPC_MEM_BUDGET_MB") || (size_t)S * per > held) {
-    c->pool_drain();
-    const bool forced = getenv("GPC_MEM_BUDGET_MB") != nullptr;
-    const size_t budget = (size_t)((free_device_bytes() + (forced ? 0 : held)) * 0.8);
-    if (budget < per)
-      FAIL(c, "gpc_paths_create: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
-              std::to_string(npad) + ", R = " + std::to_string(R) + ") exceeds the device memory budget (" +
-              std::to_string(budget >> 10) + " KB)");
-    chunk = (int)std::min<size_t>(S, budget / per);
-  }
+  // panels in the storage type (and 64 spare bytes)
+  const long long sP = (long long)npad * kq, sK = (long long)npad * kp;
+  double *pX, *P, *V1;
+  T *Bt, *Vt, *Qt;
+  auto layout = [&](ScratchCarver& sc, size_t cnt) {
+    pX = sc.take(cnt * sP);
+    P = sc.take(cnt * sP);
+    V1 = sc.take(cnt * sP);
+    Bt = sc.take<T>(use_gemm ? cnt * sK : 0);
+    Vt = sc.take<T>(use_gemm ? cnt * sK : 0);
+    Qt = sc.take<T>(use_gemm ? cnt * sK : 0);
+    sc.take<char>(cnt * 64);
+  };
+  ScratchCarver count;
+  layout(count, 1);
+  const size_t per = count.bytes, held = c->ks.bytes;
+  const int chunk = plan_chunk(c, S, per, 0, held, (size_t)S * per <= held, 0, false, [&](size_t budget) {
+    return "gpc_paths_create: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
+           std::to_string(npad) + ", R = " + std::to_string(R) + ") exceeds the device memory budget (" +
+           std::to_string(budget >> 10) + " KB)";
+  });
+  if (!chunk) return -2;
   // the handle's own constants
   HIPCHK(c, pa->sp.ensure_private((size_t)S * SP_STRIDE * 8));
   HIPCHK(c, pa->mul.ensure_private((size_t)S * D * 8));
@@ -5638,7 +5526,8 @@ int paths_create_impl(gpc_post* po, gpc_paths* pa, unsigned long long seed, int 
   HIPCHK(c, hipMemcpyAsync(d_nsd, noise_sd, (size_t)S * N * 8, hipMemcpyHostToDevice, st));
   HIPCHK(c, c->ks.ensure((size_t)chunk * per));
   c->ms_total = c->ms_factor = 0;
-  HIPCHK(c, hipEventRecord(c->ev[0], st));
+  CallTimer tm{c, true};
+  HIPCHK(c, tm.start());
   {
     const long long tot = (long long)npad * D;
     hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), S), dim3(256), 0, st, c->dX.as<double>(), N,
@@ -5657,15 +5546,11 @@ int paths_create_impl(gpc_post* po, gpc_paths* pa, unsigned long long seed, int 
                        pa->wt.as<double>());
     HIPCHK(c, hipGetLastError());
   }
-  const long long sM = (long long)npad * npad, sP = (long long)npad * kq, sK = (long long)npad * kp;
+  const long long sM = (long long)npad * npad;
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
-    double* pX = c->ks.as<double>();
-    double* P = pX + (size_t)cnt * sP;
-    double* V1 = P + (size_t)cnt * sP;
-    T* Bt = reinterpret_cast<T*>(V1 + (size_t)cnt * sP);
-    T* Vt = Bt + (size_t)cnt * sK;
-    T* Qt = Vt + (size_t)cnt * sK;
+    ScratchCarver carver(c->ks.p);
+    layout(carver, cnt);
     const double* parc = d_par + (size_t)s0 * BA_STRIDE;
     const T* Wc = po->W.as<T>() + (size_t)s0 * sM;
     const T* Ac = po->A.as<T>() + (size_t)s0 * sM;
@@ -5698,41 +5583,19 @@ int paths_create_impl(gpc_post* po, gpc_paths* pa, unsigned long long seed, int 
                        cnt, (const double*)d_nsd, S, s0, P);
     HIPCHK(c, hipGetLastError());
     // 3. v = (K + Sigma)^-1 P
-    HIPCHK(c, hipEventRecord(c->ev[1], st));
+    HIPCHK(c, tm.mark1());
     if (use_gemm) {
       hipLaunchKernelGGL((ba_to_panel_kernel<T>), dim3(kp / 64, npad / 4, cnt), dim3(64, 4), 0, st, (const double*)P, N, R,
                          kq, npad, kp, Bt);
-      for (int i = 0; i < cnt;) {
-        const int lch = po->lchol[s0 + i];
-        int e = i + 1;
-        while (e < cnt && po->lchol[s0 + e] == lch) ++e;
-        GemmArgs g;
-        g.A = (lch ? Wc : Ac) + (size_t)i * sM;  // V1 = W P | -(A P)
-        g.B = Bt + (size_t)i * sK;
-        g.C = Vt + (size_t)i * sK;
-        g.sA = sM;
-        g.sB = g.sC = sK;
-        g.lda = npad;
-        g.ldb = g.ldc = kp;
-        g.M = npad;
-        g.N = kp;
-        g.K = npad;
+      const int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
+        GemmArgs g = tri_product_args<T>(po, s0 + a, lch, Bt + (size_t)a * sK, Vt + (size_t)a * sK, sK, kp, kp);  // V1 = W P | -(A P)
         g.alpha = lch ? 1.0 : -1.0;
-        g.beta = 0;
-        g.klo = KLO_ZERO;
-        g.khi = lch ? KHI_ROW : KHI_FULL;
-        g.lower_only = 0;
-        HIPCHK(c, launch_gemm<T>(st, g, false, true, e - i));
-        if (lch) {  // W^T V1 (k from the tile row's diagonal block on)
-          GemmArgs q = g;
-          q.B = Vt + (size_t)i * sK;
-          q.C = Qt + (size_t)i * sK;
-          q.klo = KLO_ROW;
-          q.khi = KHI_FULL;
-          HIPCHK(c, launch_gemm<T>(st, q, true, true, e - i));
-        }
-        i = e;
-      }
+        HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
+        if (lch)  // W^T V1 (k from the tile row's diagonal block on)
+          HIPCHK(c, launch_gemm<T>(st, wt_product_args(g, Vt + (size_t)a * sK, Qt + (size_t)a * sK), true, true, len));
+        return 0;
+      });
+      if (rc_runs) return rc_runs;
       const dim3 gp((kq + 63) / 64, (N + 3) / 4, cnt);
       if (any_high)
         hipLaunchKernelGGL((paths_from_panel_kernel<T>), gp, dim3(64, 4), 0, st, (const T*)Qt, N, kq, npad, kp, 1.0, 1, parc,
@@ -5753,15 +5616,11 @@ int paths_create_impl(gpc_post* po, gpc_paths* pa, unsigned long long seed, int 
                            (const double*)P, sP, kq, vc, sP, kq, -1.0, 0, parc, 0);
     }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev[2], st));
+    HIPCHK(c, tm.mark2());
   }
-  HIPCHK(c, hipEventRecord(c->ev[3], st));
+  HIPCHK(c, tm.stop());
   HIPCHK(c, hipStreamSynchronize(st));
-  float t03 = 0, t12 = 0;
-  (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
-  (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
-  c->ms_total = t03;
-  c->ms_factor = t12;
+  tm.accumulate();
   return 0;
 }
 
@@ -5779,20 +5638,24 @@ int paths_eval_impl(gpc_paths* pa, const double* xstar, int M, double* f, double
   const size_t fbytes = (size_t)M * R * S * 8, dfbytes = df ? fbytes * D : 0;
   const size_t opsz = (size_t)std::max(npad, fpad) * mpad;  // one operand matrix (elements)
   const size_t xq_per = (size_t)mpad * D * 8;
-  const size_t eng_per = engine == 2 ? (opsz + (size_t)mpad * rp + (size_t)npad * rp + (size_t)fpad * rp) * 8 : 0;
-  const size_t per = xq_per + eng_per;
+  // the unfused engine's scratch: the operand, the product, and v and the weights widened to whole tiles
+  double *op = nullptr, *Cb = nullptr, *Vp = nullptr, *Wp = nullptr;
+  auto engine_layout = [&](ScratchCarver& sc, size_t cnt) {
+    op = sc.take(cnt * opsz);
+    Cb = sc.take(cnt * mpad * rp);
+    Vp = sc.take(cnt * npad * rp);
+    Wp = sc.take(cnt * fpad * rp);
+  };
+  ScratchCarver count;
+  if (engine == 2) engine_layout(count, 1);
+  const size_t eng_per = count.bytes, per = xq_per + eng_per, shared = fbytes + dfbytes;
   const size_t held = c->dout.bytes + c->gres.bytes + c->xss.bytes + (engine == 2 ? c->ks.bytes : 0);
-  int chunk = S;
-  if (getenv("GPC_MEM_BUDGET_MB") || fbytes + dfbytes + (size_t)S * per > held) {
-    c->pool_drain();
-    const bool forced = getenv("GPC_MEM_BUDGET_MB") != nullptr;
-    const size_t budget = (size_t)((free_device_bytes() + (forced ? 0 : held)) * 0.8);
-    if (budget < fbytes + dfbytes + per)
-      FAIL(c, "gpc_paths_eval: the results (" + std::to_string((fbytes + dfbytes) >> 10) + " KB) and the scratch of one "
-              "sample (" + std::to_string(per >> 10) + " KB: M_pad = " + std::to_string(mpad) + ") exceed the device "
-              "memory budget (" + std::to_string(budget >> 10) + " KB)");
-    chunk = (int)std::min<size_t>(S, (budget - fbytes - dfbytes) / per);
-  }
+  const int chunk = plan_chunk(c, S, per, shared, held, shared + (size_t)S * per <= held, 0, false, [&](size_t budget) {
+    return "gpc_paths_eval: the results (" + std::to_string(shared >> 10) + " KB) and the scratch of one "
+           "sample (" + std::to_string(per >> 10) + " KB: M_pad = " + std::to_string(mpad) + ") exceed the device "
+           "memory budget (" + std::to_string(budget >> 10) + " KB)";
+  });
+  if (!chunk) return -2;
   HIPCHK(c, c->dout.ensure(fbytes));
   if (df) HIPCHK(c, c->gres.ensure(dfbytes));
   HIPCHK(c, c->xss.ensure((size_t)chunk * xq_per + (size_t)M * D * 8));
@@ -5800,9 +5663,11 @@ int paths_eval_impl(gpc_paths* pa, const double* xstar, int M, double* f, double
   double* xq = c->xss.as<double>();
   double* d_x = xq + (size_t)chunk * mpad * D;
   c->pin.begin();
-  HIPCHK(c, hipEventRecord(c->ev[0], st));
+  c->ms_total = c->ms_factor = 0;
+  CallTimer tm{c, true};
+  HIPCHK(c, tm.start());
   HIPCHK(c, c->pin.up(d_x, xstar, (size_t)M * D * 8, st));
-  HIPCHK(c, hipEventRecord(c->ev[1], st));
+  HIPCHK(c, tm.mark1());
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
     const long long tot = (long long)mpad * D;
@@ -5836,10 +5701,8 @@ int paths_eval_impl(gpc_paths* pa, const double* xstar, int M, double* f, double
       HIPCHK(c, launch_paths_eval(st, pa->cd, a, cnt));
       continue;
     }
-    double* op = c->ks.as<double>();
-    double* Cb = op + (size_t)cnt * opsz;
-    double* Vp = Cb + (size_t)cnt * mpad * rp;
-    double* Wp = Vp + (size_t)cnt * npad * rp;
+    ScratchCarver carver(c->ks.p);
+    engine_layout(carver, cnt);
     const dim3 blk(64, 4);
     hipLaunchKernelGGL(paths_widen_kernel, dim3(rp / 64, npad / 4, cnt), blk, 0, st, a.v, npad, kq, rp, Vp);
     hipLaunchKernelGGL(paths_widen_kernel, dim3(rp / 64, fpad / 4, cnt), blk, 0, st, a.wt, fpad, kq, rp, Wp);
@@ -5877,17 +5740,13 @@ int paths_eval_impl(gpc_paths* pa, const double* xstar, int M, double* f, double
     }
     HIPCHK(c, hipGetLastError());
   }
-  HIPCHK(c, hipEventRecord(c->ev[2], st));
+  HIPCHK(c, tm.mark2());
   HIPCHK(c, hipMemcpyAsync(f, c->dout.p, fbytes, hipMemcpyDeviceToHost, st));
   if (df) HIPCHK(c, hipMemcpyAsync(df, c->gres.p, dfbytes, hipMemcpyDeviceToHost, st));
-  HIPCHK(c, hipEventRecord(c->ev[3], st));
+  HIPCHK(c, tm.stop());
   HIPCHK(c, hipStreamSynchronize(st));
   c->pin.finish();
-  float t03 = 0, t12 = 0;
-  (void)hipEventElapsedTime(&t03, c->ev[0], c->ev[3]);
-  (void)hipEventElapsedTime(&t12, c->ev[1], c->ev[2]);
-  c->ms_total = t03;
-  c->ms_factor = t12;
+  tm.accumulate();
   return 0;
 }
 }  // namespace
@@ -5945,14 +5804,36 @@ int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const dou
   const int gnq = var ? (grad ? 1 + 2 * D : 1) : 0;  // quantities of the pair kernel
   const int npl = gpl + (var && grad ? 2 : 0);
   const size_t ss = (size_t)mpad * D;
-  // doubles per sample
-  const size_t n_con = (size_t)(D + 1) * mpad, n_cpart = (size_t)gnt * mpad, n_rpart = (size_t)mnt * npad;
-  const size_t n_vec = var ? 2 * (size_t)npad : 0, n_tpart = var ? (size_t)nch * npad : 0;
-  const size_t n_zqpart = var ? (size_t)gnt * mpad : 0, n_gpart = (size_t)gnt * gpl * D * mpad;
-  const size_t n_gmpart = (size_t)mnt * gnq * mpad;
-  const size_t n_res = 3 * (size_t)mpad + 2 + (size_t)npl * ss;
-  const size_t per = (n_con + n_cpart + n_rpart + (size_t)npad + n_vec + n_tpart + n_zqpart + n_gpart + n_gmpart + n_res) * 8;
-  const size_t shared = (2 * ss + (size_t)mpad + 2 * (size_t)M * D + M) * 8;
+  // the scratch, one allocation: the measures' block that the samples share, then the arrays of `cnt` samples
+  double *d_mut, *d_sgt, *d_wpad, *d_mu, *d_sg, *d_w;
+  auto shared_layout = [&](ScratchCarver& sc) {
+    d_mut = sc.take(ss);
+    d_sgt = sc.take(ss);
+    d_wpad = sc.take(mpad);
+    d_mu = sc.take((size_t)M * D);
+    d_sg = sc.take((size_t)M * D);
+    d_w = sc.take(M);
+  };
+  double *d_con, *d_cpart, *d_rpart, *d_zbar, *d_v, *d_q, *d_tpart, *d_zqpart, *d_gpart, *d_gmpart, *d_res;
+  const size_t n_res = 3 * (size_t)mpad + 2 + (size_t)npl * ss;  // doubles of a sample's results
+  auto layout = [&](ScratchCarver& sc, size_t cnt) {
+    d_con = sc.take(cnt * (D + 1) * mpad);
+    d_cpart = sc.take(cnt * gnt * mpad);
+    d_rpart = sc.take(cnt * mnt * npad);
+    d_zbar = sc.take(cnt * npad);
+    d_v = sc.take(var ? cnt * npad : 0);
+    d_q = sc.take(var ? cnt * npad : 0);
+    d_tpart = sc.take(var ? cnt * nch * npad : 0);
+    d_zqpart = sc.take(var ? cnt * gnt * mpad : 0);
+    d_gpart = sc.take(cnt * gnt * gpl * D * mpad);
+    d_gmpart = sc.take(cnt * mnt * gnq * mpad);
+    // the results, one block: [za | zq | gw | scal (2 per sample) | planes of the tile pass | planes of the pair pass]
+    d_res = sc.take(cnt * n_res);
+  };
+  ScratchCarver count_shared, count_per;
+  shared_layout(count_shared);
+  layout(count_per, 1);
+  const size_t shared = count_shared.bytes, per = count_per.bytes;
   const int chunk = plan_chunk(c, S, per, shared, c->qmix.bytes, (size_t)S * per + shared <= c->qmix.bytes, 0, false, [&](size_t budget) {
     return "gpc_quad_mix: the scratch of one sample (" + std::to_string((per + shared) >> 10) + " KB: N_pad = " +
            std::to_string(npad) + ", M_pad = " + std::to_string(mpad) + ", D = " + std::to_string(D) +
@@ -5962,30 +5843,9 @@ int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const dou
   HIPCHK(c, c->qmix.ensure((size_t)chunk * per + shared));
   HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
   HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
-  double* p = c->qmix.as<double>();
-  auto take = [&](size_t n) {
-    double* r = p;
-    p += n;
-    return r;
-  };
-  double* d_mut = take(ss);
-  double* d_sgt = take(ss);
-  double* d_wpad = take(mpad);
-  double* d_mu = take((size_t)M * D);
-  double* d_sg = take((size_t)M * D);
-  double* d_w = take(M);
-  double* d_con = take(chunk * n_con);
-  double* d_cpart = take(chunk * n_cpart);
-  double* d_rpart = take(chunk * n_rpart);
-  double* d_zbar = take((size_t)chunk * npad);
-  double* d_v = take(var ? (size_t)chunk * npad : 0);
-  double* d_q = take(var ? (size_t)chunk * npad : 0);
-  double* d_tpart = take(chunk * n_tpart);
-  double* d_zqpart = take(chunk * n_zqpart);
-  double* d_gpart = take(chunk * n_gpart);
-  double* d_gmpart = take(chunk * n_gmpart);
-  // the results, one block: [za | zq | gw | scal (2 per sample) | planes of the tile pass | planes of the pair pass]
-  double* d_res = take(chunk * n_res);
+  ScratchCarver carver(c->qmix.p);
+  shared_layout(carver);
+  layout(carver, chunk);
   double* d_za = d_res;
   double* d_zq = d_za + (size_t)chunk * mpad;
   double* d_gw = d_zq + (size_t)chunk * mpad;
@@ -7498,6 +7358,7 @@ const Option OPTIONS[] = {
     {"cv_engine_ran", GPC_GET(c->cv_engine_ran), nullptr},
     {"block_appended", GPC_COUNTER(block_appended)},  // samples gpc_post_append_block appended ...
     {"block_stale", GPC_COUNTER(block_stale)},        // ... and left stale for gpc_post_recompute
+    {"last_chunk", GPC_GET(c->last_chunk), nullptr},  // samples per chunk that the last posterior consumer planned (plan_chunk; 0: it refused)
     {"experiments", GPC_GET(IS_EXPERIMENTS_BUILD), nullptr},  // 1: this library is the experiments build (tests/ and tools/ ask before they use its options)
 };
 #ifdef GPC_EXPERIMENTS
@@ -7853,9 +7714,9 @@ struct NhHookSample {
     sp = sd.get<double>(SP_STRIDE);
     al = sd.get<double>(npad);
     xs = sd.get<double>((size_t)npad * D);
-    double* blk = sd.get<double>(NhScratch::per_sample(npad, cd.cov_N, 0, 0, nd2));
+    char* blk = sd.get<char>(ScratchCarver::count<NhScratch>(1, npad, cd.cov_N, 0, 0, nd2));
     if (!dX || !dmul || !ddv || !sp || !al || !xs || !blk) FAIL(c, std::string(fn) + ": out of device memory");
-    z.carve(blk, 1, npad, cd.cov_N, 0, 0, nd2);
+    ScratchCarver::carve(z, blk, 1, npad, cd.cov_N, 0, 0, nd2);
     HIPCHK(c, hipMemcpy(dX, X, (size_t)N * D * 8, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(dmul, mul.data(), (size_t)D * 8, hipMemcpyHostToDevice));
     HIPCHK(c, hipMemcpy(ddv, dv.data(), (size_t)D * 8, hipMemcpyHostToDevice));
@@ -7916,9 +7777,9 @@ int gpc_debug_nll_gram(gpc_ctx* c, int npad, int P, const double* planes, double
   HIPCHK(c, hipSetDevice(c->device));
   ScratchDev sd;
   NhScratch z;
-  double* blk = sd.get<double>(NhScratch::per_sample(npad, P, 0, 0, 0));
+  char* blk = sd.get<char>(ScratchCarver::count<NhScratch>(1, npad, P, 0, 0, 0));
   if (!blk) FAIL(c, "gpc_debug_nll_gram: out of device memory");
-  z.carve(blk, 1, npad, P, 0, 0, 0);
+  ScratchCarver::carve(z, blk, 1, npad, P, 0, 0, 0);
   HIPCHK(c, hipMemcpy(z.B, planes, (size_t)P * npad * npad * 8, hipMemcpyHostToDevice));
   if (int rc = nh_launch_gram(c, z, 1)) return rc;
   HIPCHK(c, hipMemcpyAsync(out, z.grsum, (size_t)z.npairs * 8, hipMemcpyDeviceToHost, c->st));

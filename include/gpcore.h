@@ -582,6 +582,8 @@ int gpc_last_lauum_timing(gpc_ctx* ctx, double* ms, double* flops);
  * for the stream after all); "small_timing" (default 0) = such calls record their timing events, so that gpc_last_timing
  * reports their device section (it reports 0 for them otherwise; from N_pad = 2048 on the events are always recorded).
  * "small_polled" / "small_synced" (get only): how many calls ended either way.
+ * "last_chunk" (get only): how many samples per chunk the last posterior consumer (predictions, gradients, Hessians,
+ * cross-validation, quadrature, paths, appends) planned for its scratch; S when the call ran whole, 0 when it refused.
  * "cov_fused" (get only): how many gpc_predict_cov calls formed their reduction in the product's epilogue.
  * "quad_mix_gemms" (get only): MFMA GEMM launches issued inside gpc_quad_mix over the life of the context (0 by design).
  * "paths_engine" / "paths_solve_engine" (test hooks) and "paths_engine_ran" / "paths_solve_engine_ran" (get only): see

@@ -215,15 +215,22 @@ try:
     np.save(sys.argv[1], np.c_[L, dL])
 except RuntimeError as e:
     print("REFUSED:", e)
+from gpyreg_amd import _lib
+print("LAST_CHUNK", _lib.context().get_option("last_chunk"))
 """
 
 
 def test_chunking_changes_no_bit_and_the_budget_refusal(tmp_path):
     """GPC_MEM_BUDGET_MB in child processes: budgets that fit one and two samples per chunk (a sample's scratch at
     N_pad = 256 is 3 N_pad^2 doubles = 1.6 MB and vectors; the planner takes 80 %) give the bits of the unchunked call;
-    1 MB fits no sample and is refused with the sizes in the message."""
+    1 MB fits no sample and is refused with the sizes in the message.  Each child reports the chunk the library planned
+    ("last_chunk"): it is the one that the scratch's closed form (scratch_sizes.cv_grad_per) gives."""
+    from scratch_sizes import cv_grad_per, planned_chunk
+
     gp, X, y, s2, hyp = _problem("matern", 3, "const", 130, 3, S=5)
     L, dL = gp.cv_nll_batch(hyp)
+    per, shared = cv_grad_per(256, gp._counts()[0]), 256 * 8
+    assert [planned_chunk(5, mb, per, shared) for mb in (3, 5, 1)] == [1, 2, 0]
     script = tmp_path / "child.py"
     script.write_text(_CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests")))
     for mb, refused in ((3, False), (5, False), (1, True)):
@@ -231,8 +238,10 @@ def test_chunking_changes_no_bit_and_the_budget_refusal(tmp_path):
         env = dict(os.environ, GPC_MEM_BUDGET_MB=str(mb))
         r = subprocess.run([sys.executable, str(script), str(out)], env=env, capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, r.stderr
+        assert f"LAST_CHUNK {planned_chunk(5, mb, per, shared)}\n" in r.stdout, r.stdout
         if refused:
-            assert "REFUSED" in r.stdout and "gpc_cv_grad: the scratch of one sample" in r.stdout
+            # (with the scratch's size to the byte: the closed form pins every array of the layout, not only the chunk)
+            assert "REFUSED" in r.stdout and f"gpc_cv_grad: the scratch of one sample ({per} bytes:" in r.stdout
             assert "N_pad = 256" in r.stdout
         else:
             assert np.array_equal(np.load(out), np.c_[L, dL]), mb

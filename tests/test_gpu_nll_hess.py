@@ -279,6 +279,14 @@ _CHILD = """
 import sys, numpy as np
 sys.path.insert(0, {root!r}); sys.path.insert(0, {tests!r})
 from test_gpu_nll_hess import _problem
+from gpyreg_amd import _lib
+device_call = _lib.PostHandle.nll_hess
+def reporting(self, *args):  # the chunk gpc_nll_hess planned (nll_hess_batch evaluates nlZ after it, which plans again)
+    try:
+        return device_call(self, *args)
+    finally:
+        print("LAST_CHUNK", self.ctx.get_option("last_chunk"))
+_lib.PostHandle.nll_hess = reporting
 gp, X, y, s2, hyp = _problem("matern", 3, "const", 130, 3, S=3)
 try:
     nlz, g, H = gp.nll_hess_batch(hyp)
@@ -291,9 +299,15 @@ except RuntimeError as e:
 def test_chunking_changes_no_bit_and_the_budget_refusal(tmp_path):
     """GPC_MEM_BUDGET_MB in child processes: budgets that fit one and two samples per chunk (a sample's scratch at
     N_pad = 256 with 5 planes is 7 N_pad^2 doubles = 3.7 MB and vectors; the planner takes 80 %) give the bits of the
-    unchunked call; 2 MB fits no sample and is refused with the sizes in the message."""
+    unchunked call; 2 MB fits no sample and is refused with the sizes in the message.  Each child reports the chunk the
+    library planned ("last_chunk"): it is the one that the scratch's closed form (scratch_sizes.nll_hess_per) gives."""
+    from scratch_sizes import nll_hess_per, planned_chunk
+
     gp, X, y, s2, hyp = _problem("matern", 3, "const", 130, 3, S=3)
     _, _, H = gp.nll_hess_batch(hyp)
+    cov_N, noise_N, mean_N = gp._counts()
+    per = nll_hess_per(256, cov_N, noise_N, mean_N, 3 * 4 // 2)
+    assert [planned_chunk(3, mb, per) for mb in (6, 11, 2)] == [1, 2, 0]
     script = tmp_path / "child.py"
     script.write_text(_CHILD.format(root=ROOT, tests=os.path.join(ROOT, "tests")))
     for mb, refused in ((6, False), (11, False), (2, True)):
@@ -301,8 +315,10 @@ def test_chunking_changes_no_bit_and_the_budget_refusal(tmp_path):
         env = dict(os.environ, GPC_MEM_BUDGET_MB=str(mb))
         r = subprocess.run([sys.executable, str(script), str(out)], env=env, capture_output=True, text=True, timeout=120)
         assert r.returncode == 0, r.stderr
+        assert f"LAST_CHUNK {planned_chunk(3, mb, per)}\n" in r.stdout, r.stdout
         if refused:
-            assert "REFUSED" in r.stdout and "gpc_nll_hess: the scratch of one sample" in r.stdout
+            # (with the scratch's size to the byte: the closed form pins every array of the layout, not only the chunk)
+            assert "REFUSED" in r.stdout and f"gpc_nll_hess: the scratch of one sample ({per} bytes:" in r.stdout
             assert "N_pad = 256" in r.stdout and "planes = 5" in r.stdout
         else:
             assert np.array_equal(np.load(out), H), mb

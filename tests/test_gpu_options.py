@@ -34,7 +34,7 @@ SETTABLE = {
 }
 SET_ONLY = {"leaf_fault": 0, "start_mult_log10": 0, "append_fail_mask": 0}  # name -> the default to put back
 GET_ONLY = ("small_polled", "small_synced", "cov_fused", "quad_mix_gemms", "block_engine_ran", "paths_engine_ran",
-            "paths_solve_engine_ran", "block_appended", "block_stale", "experiments")
+            "paths_solve_engine_ran", "block_appended", "block_stale", "last_chunk", "experiments")
 EXPERIMENTS = {
     "rect_min": RAW,
     "rect_mode": FLAG,

@@ -327,10 +327,18 @@ def test_sample_alone_in_a_batch_chunked_and_mean_only_bitwise(monkeypatch):
         for a, b in zip(one.predict_hyp_grad(xs), whole):
             assert np.array_equal(a[..., 0], b[..., s]), s
     # scratch of one sample at npad = 128, D = 3, P = 6, one block of 128 queries: the plane, three panels and the
-    # partials, 74753 doubles = 0.6 MB; 80 % of 1 MB holds one sample, not two
+    # partials, 74753 doubles = 0.6 MB; 80 % of 1 MB holds one sample, not two.  Without the variance a sample needs 6273
+    # doubles and all five fit: that call runs the forced path in one chunk.  The library reports the chunk it planned
+    from scratch_sizes import hyp_grad_per, planned_chunk
+
+    per_var, per_mean = hyp_grad_per(128, 3, 6, 1, 3, 128, True, 6 + 2 * 4), hyp_grad_per(128, 3, 6, 1, 3, 128, False, 6 + 4)
+    assert (per_var, per_mean) == (74753 * 8, 6273 * 8)
+    assert (planned_chunk(5, 1, per_var), planned_chunk(5, 1, per_mean)) == (1, 5)
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", "1")
     chunked = gp.predict_hyp_grad(xs)
+    assert c.get_option("last_chunk") == planned_chunk(5, 1, per_var)
     chunked_mean = gp.predict_hyp_grad(xs, compute_var=False)
+    assert c.get_option("last_chunk") == planned_chunk(5, 1, per_mean)
     monkeypatch.delenv("GPC_MEM_BUDGET_MB")
     for a, b in zip(whole, chunked):
         assert np.array_equal(a, b)
@@ -346,8 +354,14 @@ def test_query_blocks_to_rounding(monkeypatch):
     xs = np.random.default_rng(15).uniform(-2, 2, (260, X.shape[1]))
     whole = gp.predict_hyp_grad(xs)
     pieces = [gp.predict_hyp_grad(xs[a:b]) for a, b in ((0, 128), (128, 256), (256, 260))]
+    # the planner refuses the blocks of 384 and 256 padded queries and halves down to 128, of which one sample fits
+    from scratch_sizes import hyp_grad_per, planned_chunk
+
+    fit = [planned_chunk(2, 1, hyp_grad_per(128, 3, 6, 1, 3, msb, True, 6 + 2 * 4)) for msb in (384, 256, 128)]
+    assert fit[:2] == [0, 0] and fit[2] >= 1
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", "1")
     split = gp.predict_hyp_grad(xs)
+    assert gp._post_handle.ctx.get_option("last_chunk") == fit[2]
     monkeypatch.delenv("GPC_MEM_BUDGET_MB")
     for i in range(4):
         joined = np.concatenate([p[i] for p in pieces], axis=0)
@@ -565,9 +579,13 @@ def test_refusals(ctx):
 def test_budget_failure_names_the_sizes(monkeypatch):
     gp, model, X, y, hyp = _lownoise_problem((1e-2,), N=300, D=3)
     xs = np.zeros((5, 3))
-    # at N_pad = 384 the dense plane alone is 1.2 MB
+    # at N_pad = 384 the dense plane alone is 1.2 MB; the message carries the scratch's bytes, to the byte what the
+    # closed form gives (P = 6, one noise vector, three planes, 6 + 2 * 4 sums per query)
+    from scratch_sizes import hyp_grad_per
+
+    per = hyp_grad_per(384, 3, 6, 1, 3, 128, True, 6 + 2 * 4)
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", "1")
-    with pytest.raises(RuntimeError, match=r"gpc_predict_hyp_grad: the scratch of one sample with one query block \(\d+ "
+    with pytest.raises(RuntimeError, match=r"gpc_predict_hyp_grad: the scratch of one sample with one query block \(%d " % per +
                                            r"bytes: N_pad = 384, planes = 3, block = 128 queries\) exceeds the device "
                                            r"memory budget \(\d+ bytes\)"):
         gp.predict_hyp_grad(xs)

@@ -208,9 +208,19 @@ def test_batch_single_chunks_bitwise_and_budget_message(monkeypatch):
     flags = ((True, True), (True, False), (False, True), (False, False))
     whole = [gp.quad_mixture(mu, sigma, w, cv, cg, separate_samples=True) for cv, cg in flags]
     cov = gp.quad_cov(mu, sigma, separate_samples=True)
+    from gpyreg_amd import _lib
+    from scratch_sizes import planned_chunk, quad_mix_per, quad_mix_shared
+
+    ctx, shared = _lib.context(gp.device), quad_mix_shared(300, 384, 4)
+    # (the chunk the library reports is the one that the scratch's closed form gives: with variance and gradient, one
+    # sample under 1 MB and two under 2 MB)
+    assert [planned_chunk(10, mb, quad_mix_per(384, 384, 4, True, True), shared) for mb in (1, 2)] == [1, 2]
     for mb in ("1", "2"):
         monkeypatch.setenv("GPC_MEM_BUDGET_MB", mb)
-        chunked = [gp.quad_mixture(mu, sigma, w, cv, cg, separate_samples=True) for cv, cg in flags]
+        chunked = []
+        for cv, cg in flags:
+            chunked.append(gp.quad_mixture(mu, sigma, w, cv, cg, separate_samples=True))
+            assert ctx.get_option("last_chunk") == planned_chunk(10, int(mb), quad_mix_per(384, 384, 4, cv, cg), shared), (mb, cv, cg)
         monkeypatch.delenv("GPC_MEM_BUDGET_MB")
         for a, b in zip(whole, chunked):
             a, b = (a, b) if isinstance(a, tuple) else ((a,), (b,))

@@ -210,6 +210,23 @@ def consumers(dtype):
         per = (3 * npad * npad + 7 * npad + (ntl + 1) * (D + 1)) * 8
         for loss in ("lpd", "mse"):
             both(f"cv_nll_batch {loss}", dtype, lambda: gp.cv_nll_batch(loss=loss, weights=wm.repeat(3)[:N]), per, npad * 8)
+    # nll_hess_batch and predict_hyp_grad on the resident posteriors (fp64 only), P = cov_N + one noise + one mean
+    # hyperparameter: the doubles per sample of nll_hess_impl (Q, one B per plane and the operand, the vectors, the
+    # partials of the Gram and second-derivative passes) and of hyp_grad_impl (one block of 128 queries; with the variance
+    # the plane, three panels and the column dots' partials)
+    if dtype == "f64":
+        cov_N, ppl, P, nd2, nch = D + 1, D + 2, D + 3, D * (D + 1) // 2, npad // 128
+        ntl = gnt * (gnt + 1) // 2
+        per = ((ppl + 2) * npad * npad + (2 * P + 1 + 1 + gnt) * npad + gnt * gnt * 2 + 2 * cov_N
+               + (gnt * gnt + 1) * (ppl * (ppl + 1) // 2) + (ntl + 1) * nd2) * 8
+        both("nll_hess_batch", dtype, lambda: gp.nll_hess_batch(), per)
+        for var in (True, False):
+            nout = P + cov_N * (2 if var else 1)
+            per = (2 * P + 1 + nch + gnt) * npad + (gnt + 1) * nout * mpad + mpad * D + 1
+            if var:
+                per += npad * npad + 3 * npad * mpad + npad + gnt * mpad + gnt * 2 * mpad + (D + 1) * mpad
+            both("predict_hyp_grad" + ("" if var else " without variance"), dtype,
+                 lambda: gp.predict_hyp_grad(xq, compute_var=var), per * 8)
     # sample_paths: creation under both solve engines, evaluation with gradients under both engines
     kq, kp = pad(R_PATHS, 16), pad(R_PATHS)
     try:
