@@ -104,6 +104,7 @@ SIGNATURES = {
     ),
     "gpc_debug_leaf": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _ip]),
     "gpc_debug_factor": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "gpc_debug_factor_plan": (C.c_int, [_vp] + [C.c_int] * 7 + [_dp] * 7 + [_ip]),
     "gpc_debug_cov": (
         C.c_int,
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_double, _dp, _dp, C.c_int, C.c_int, _dp,
@@ -528,6 +529,34 @@ class Context:
                                         C.byref(logdet), C.byref(info))
         self._check(rc, "gpc_debug_factor")
         return L, W, Ainv, logdet.value, info.value
+
+    @_serial
+    def debug_factor_plan(self, A, W, T, nvalid, plan=0, nll_block=0, stable=False, keep_L=False, want_inv=False,
+                          r=None, dtype=F64):
+        """gpc_debug_factor_plan: the launch plan of plan.h on a batch, as the product runs it.  A, W, T: (batch, npad,
+        npad), uploaded whole and verbatim -- padding and poison included -- and returned whole as the factorization
+        left them (the arguments are not modified).  plan 0 / 1: potrf_inv with / without the whole inverse, 2:
+        potrf_nll with ``nll_block``.  ``r`` (batch, npad): also the plan's forward solve z = L^-1 r.  ``want_inv``
+        (plan 0): also the scratch after Ainv = W^T W went into it.  Returns a dict A, W, T, z, Ainv, logdet, info."""
+        A, W, T = _f64(A).copy(), _f64(W).copy(), _f64(T).copy()
+        if A.ndim != 3 or A.shape[1] != A.shape[2] or W.shape != A.shape or T.shape != A.shape:
+            raise ValueError("debug_factor_plan: A, W, T (batch, npad, npad)")
+        batch, npad, _ = A.shape
+        rr = z = None
+        if r is not None:
+            rr = _f64(r)
+            if rr.shape != (batch, npad):
+                raise ValueError("debug_factor_plan: r (batch, npad)")
+            z = np.empty((batch, npad))
+        Ainv = np.empty_like(A) if want_inv else None
+        logdet = np.empty(batch)
+        info = np.empty(batch, dtype=np.int32)
+        flags = (1 if stable else 0) | (2 if keep_L else 0) | (4 if want_inv else 0)
+        rc = self._lib.gpc_debug_factor_plan(self._h, dtype, npad, int(nvalid), batch, int(plan), int(nll_block), flags,
+                                             _ptr(A), _ptr(W), _ptr(T), _ptr(rr), _ptr(z), _ptr(Ainv), _ptr(logdet),
+                                             info.ctypes.data)
+        self._check(rc, "gpc_debug_factor_plan")
+        return dict(A=A, W=W, T=T, z=z, Ainv=Ainv, logdet=logdet, info=info)
 
     @_serial
     def debug_cov(self, which, kid, degree, hyp_cov, X, dtype=F64, kscale=1.0, sl=1.0, dvec=None, X_star=None,

@@ -4528,6 +4528,76 @@ struct ScratchDev {
   }
 };
 
+// gpc_debug_factor_plan: the plan of plan.h on a batch, in every mode the product runs it in (debug_factor_impl above
+// runs one sample, fast mode, full inverse, keep_L).  The buffers are the caller's, cast and uploaded whole, and come
+// back whole: what a launch reads outside the plan's contract is what the caller put there, what it writes shows.
+template <typename T>
+int debug_factor_plan_impl(gpc_ctx* c, int npad, int nvalid, int batch, int plan, int nll_block, int flags, double* A,
+                           double* W, double* Tm, const double* r, double* z, double* Ainv, double* logdet, int* info) {
+  const size_t msz = (size_t)npad * npad, tot = msz * batch, vtot = (size_t)npad * batch;
+  ScratchDev sd;
+  T* dA = sd.get<T>(tot);
+  T* dW = sd.get<T>(tot);
+  T* dT = sd.get<T>(tot);
+  double* dld = sd.get<double>(batch);
+  int* dinfo = sd.get<int>(batch);
+  double* dr = r ? sd.get<double>(vtot) : nullptr;
+  double* dz = r ? sd.get<double>(vtot) : nullptr;
+  if (!dA || !dW || !dT || !dld || !dinfo || (r && (!dr || !dz))) FAIL(c, "gpc_debug_factor_plan: out of device memory");
+  auto up = [&](T* dst, const double* src) -> int {
+    std::vector<T> h(src, src + tot);  // a plain cast: a NaN stays a NaN
+    HIPCHK(c, hipMemcpy(dst, h.data(), tot * sizeof(T), hipMemcpyHostToDevice));
+    return 0;
+  };
+  if (up(dA, A) || up(dW, W) || up(dT, Tm)) return -1;
+  HIPCHK(c, hipMemsetAsync(dld, 0, batch * sizeof(double), c->st));
+  HIPCHK(c, hipMemsetAsync(dinfo, 0, batch * sizeof(int), c->st));
+  if (r) {
+    HIPCHK(c, hipMemcpyAsync(dr, r, vtot * 8, hipMemcpyHostToDevice, c->st));
+    HIPCHK(c, hipMemsetAsync(dz, 0xff, vtot * 8, c->st));  // NaN: an entry no launch wrote shows
+  }
+  Factor<T> F;
+  F.st = c->st;
+  F.batch = batch;
+  F.npad = npad;
+  F.nvalid = nvalid;
+  F.A = dA;
+  F.W = dW;
+  F.Tm = dT;
+  F.sA = F.sW = F.sT = (long long)msz;
+  F.logdet = dld;
+  F.info = dinfo;
+  F.stable = (flags & 1) != 0;
+  const bool keep_L = (flags & 2) != 0;
+  if (plan == 2) {
+    F.nll_block = nll_block;
+    F.potrf_nll(0, npad);
+  } else {
+    F.potrf_inv(0, npad, plan == 0, keep_L);
+  }
+  HIPCHK(c, F.err);
+  HIPCHK(c, hipGetLastError());
+  if (r) {
+    if (plan == 2)
+      F.forward_solve_nll(0, npad, dr, dz);
+    else
+      F.forward_solve(0, npad, plan == 0, dr, dz);
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  if (download_as<T>(c, dA, A, tot) || download_as<T>(c, dW, W, tot) || download_as<T>(c, dT, Tm, tot)) return -1;
+  if (r) HIPCHK(c, hipMemcpy(z, dz, vtot * 8, hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(logdet, dld, batch * sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(info, dinfo, batch * sizeof(int), hipMemcpyDeviceToHost));
+  if (flags & 4) {
+    F.lauum(F.Tm, F.sT);
+    HIPCHK(c, F.err);
+    HIPCHK(c, hipGetLastError());
+    if (download_as<T>(c, dT, Ainv, tot)) return -1;
+  }
+  return 0;
+}
+
 template <typename T>
 int debug_cov_impl(gpc_ctx* c, int which, CovDesc cd, const double* hyp, double kscale, double sl, const double* dvec,
                    const double* X, int N, const double* Xstar, int M, const double* mat, const double* vec,
@@ -7605,6 +7675,28 @@ int gpc_debug_factor(gpc_ctx* c, int dtype, int n, const double* A, double* L, d
   HIPCHK(c, hipSetDevice(c->device));
   return dtype == GPC_F64 ? debug_factor_impl<double>(c, n, A, L, W, Ainv, logdet, info)
                           : debug_factor_impl<float>(c, n, A, L, W, Ainv, logdet, info);
+}
+
+int gpc_debug_factor_plan(gpc_ctx* c, int dtype, int npad, int nvalid, int batch, int plan, int nll_block, int flags,
+                          double* A, double* W, double* T, const double* r, double* z, double* Ainv, double* logdet,
+                          int* info) {
+  if (!c) return -2;
+  if (dtype != GPC_F64 && dtype != GPC_F32) FAIL(c, "gpc_debug_factor_plan: dtype must be GPC_F64 or GPC_F32");
+  if (npad < TILE || npad % TILE != 0 || npad > 2048)
+    FAIL(c, "gpc_debug_factor_plan: npad must be a multiple of 128 in 128 .. 2048");
+  if (batch < 1 || batch > 16) FAIL(c, "gpc_debug_factor_plan: batch must be 1 .. 16");
+  if (plan < 0 || plan > 2) FAIL(c, "gpc_debug_factor_plan: plan must be 0, 1 or 2");
+  if (plan == 2 && (nll_block < TILE || nll_block % TILE != 0 || nll_block > npad))
+    FAIL(c, "gpc_debug_factor_plan: nll_block must be a multiple of 128 in 128 .. npad");
+  if (flags < 0 || flags > 7) FAIL(c, "gpc_debug_factor_plan: flags has bits 0 .. 2");
+  if ((flags & 4) && plan != 0) FAIL(c, "gpc_debug_factor_plan: the inverse (bit 2) belongs to plan 0");
+  if (nvalid < 0 || !A || !W || !T || !logdet || !info || (r && !z) || ((flags & 4) && !Ainv))
+    FAIL(c, "gpc_debug_factor_plan: bad arguments");
+  HIPCHK(c, hipSetDevice(c->device));
+  return dtype == GPC_F64 ? debug_factor_plan_impl<double>(c, npad, nvalid, batch, plan, nll_block, flags, A, W, T, r, z,
+                                                           Ainv, logdet, info)
+                          : debug_factor_plan_impl<float>(c, npad, nvalid, batch, plan, nll_block, flags, A, W, T, r, z,
+                                                          Ainv, logdet, info);
 }
 
 int gpc_debug_cov(gpc_ctx* c, int which, int kernel_id, int degree, int dtype, const double* hyp_cov, double kscale,

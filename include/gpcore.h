@@ -613,6 +613,22 @@ int gpc_debug_leaf(gpc_ctx* ctx, int dtype, const double* A, double* L, double* 
 /* Blocked factorization of an n x n SPD matrix (any n): L, W = L^-1, Ainv (lower).   */
 int gpc_debug_factor(gpc_ctx* ctx, int dtype, int n, const double* A, double* L,
                      double* W, double* Ainv, double* logdet, int* info);
+/* The launch plan of gpyreg_amd/csrc/plan.h as the product runs it: `batch` samples of npad x npad (a multiple of 128,
+ * at most 2048; batch 1 .. 16) in one call, on buffers of the hook's own.  A, W, T: [batch][npad][npad], uploaded WHOLE
+ * and verbatim (a plain cast for fp32) -- identity padding, the part above the diagonal and whatever the caller poisons
+ * W and the scratch T with included -- and downloaded whole after the factorization, so that a read of something no
+ * launch wrote and a write outside the plan's contract both show.  nvalid: rows below it are data, the rest padding.
+ *   plan   0  potrf_inv(0, npad, need_inv = true, keep_L)     1  potrf_inv(0, npad, need_inv = false, keep_L)
+ *          2  potrf_nll(0, npad) with nll_block (a multiple of 128 in 128 .. npad)
+ *   flags  bit 0: stable mode;  bit 1: keep_L;  bit 2 (plan 0 only): after the download, Ainv = W^T W (lauum) goes into
+ *          the scratch and the whole scratch comes back in Ainv[batch][npad][npad]
+ * r, z (optional, [batch][npad] each): z = L^-1 r by the forward solve that belongs to the plan -- forward_solve with
+ * the plan's need_inv, forward_solve_nll for plan 2 -- on a device copy of r (the solve consumes it).  r must be finite,
+ * padding included (blas1.h: trmv_kernel).  logdet, info: [batch].  No persistent-launch counters, no side stream;
+ * "dual_launch" and "leaf" follow gpc_set_option.  Anything else is refused (-2).                                      */
+int gpc_debug_factor_plan(gpc_ctx* ctx, int dtype, int npad, int nvalid, int batch, int plan, int nll_block, int flags,
+                          double* A, double* W, double* T, const double* r, double* z, double* Ainv, double* logdet,
+                          int* info);
 /* The covariance kernels of the evaluation and prediction paths on ONE sample, launched as those paths launch them
  * (the inputs scaled by scale_x_kernel from hyp_cov, the per-sample scalars sf2 / alpha_rq from hyp_cov, kscale and sl
  * from the caller), on buffers of the hook's own; npad / mpad = N / M rounded up to 128.  which:

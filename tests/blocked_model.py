@@ -68,14 +68,23 @@ def leaf(Ablk, Wblk):
     return 0
 
 
-def leaf_panels(Ablk, Wblk, pw=16, refine=False):
+def leaf_panels(Ablk, Wblk, pw=16, refine=False, nvalid=None, logdet=None):
     """The device leaf's own arithmetic (gpyreg_amd/csrc/leaf.h): right-looking with `pw`-wide panels, the panel
     solve L_iP = A_iP W_PP^T as a PRODUCT with the explicit inverse of the pw x pw diagonal block; with `refine`
-    (the device's stable mode) followed by one step of refinement, L_iP += (A_iP - L_iP L_PP^T) W_PP^T."""
+    (the device's stable mode) followed by one step of refinement, L_iP += (A_iP - L_iP L_PP^T) W_PP^T.
+
+    The arithmetic runs in the dtype of `Ablk` (float32 arrays model the fp32 leaf).  `nvalid`: panels that start at or
+    beyond it are identity padding and are skipped, except the first (leaf.h: `if (nvalid > 16 P)`); what they hold
+    stays where it is.  `logdet` (a one-element list): the sum of log L_ii over the panels that ran is added to it, in
+    double as on the device."""
     n = Ablk.shape[0]
+    dt = Ablk.dtype
     S = np.tril(Ablk) + np.tril(Ablk, -1).T
-    L = np.zeros((n, n))
+    L = np.tril(Ablk).copy()
+    lg = 0.0
     for p in range(0, n, pw):
+        if p > 0 and nvalid is not None and not nvalid > p:
+            continue
         P = slice(p, min(p + pw, n))
         m = P.stop - P.start
         Lpp = np.tril(S[P, P]).copy()
@@ -83,14 +92,15 @@ def leaf_panels(Ablk, Wblk, pw=16, refine=False):
             d = Lpp[j, j]
             if not (d > 0):
                 return p + j + 1
-            r = 1.0 / np.sqrt(d)
+            r = (1.0 / np.sqrt(d)).astype(dt) if dt != np.float64 else 1.0 / np.sqrt(d)
             Lpp[j:, j] *= r
             for k in range(j + 1, m):
                 Lpp[k:, k] -= Lpp[k:, j] * Lpp[k, j]
         L[P, P] = Lpp
+        lg += float(np.log(np.diag(Lpp).astype(np.float64)).sum())
         if P.stop < n:
             R = slice(P.stop, n)
-            Wpp = np.linalg.solve(Lpp, np.eye(m))
+            Wpp = np.linalg.solve(Lpp, np.eye(m, dtype=dt))
             Lr = S[R, P] @ Wpp.T
             if refine:
                 Lr = Lr + (S[R, P] - Lr @ Lpp.T) @ Wpp.T
@@ -99,8 +109,10 @@ def leaf_panels(Ablk, Wblk, pw=16, refine=False):
     Ablk[np.tril_indices(n)] = L[np.tril_indices(n)]
     if refine:
         Ablk[np.triu_indices(n, 1)] = 0.0  # stable mode: L11 becomes a GEMM operand, its diagonal tiles must be clean
-    Wblk[:, :] = np.linalg.solve(L, np.eye(n))
+    Wblk[:, :] = np.linalg.solve(np.tril(L), np.eye(n, dtype=dt))
     Wblk[np.triu_indices(n, 1)] = 0.0
+    if logdet is not None:
+        logdet[0] += lg
     return 0
 
 
@@ -186,41 +198,47 @@ def forward_solve(T, W, r, off, n, tile, need_inv):
     forward_solve(T, W, r, off + n1, n2, tile, need_inv)
 
 
-def trsm_nll(A, W, T, r0, m, c0, n, tile, blk, log=None):
+def trsm_nll(A, W, T, r0, m, c0, n, tile, blk, log=None, stable=False):
     """plan.h: trsm_nll.  T[r0:, c0:] = A[r0:, c0:] L[c0:, c0:]^-T by blocks: blocks of at most `blk` rows own an
-    inverse, above that the solve splits like the factorization (A21 is updated in place)."""
+    inverse, above that the solve splits like the factorization (A21 is updated in place).  `stable`: the product with
+    the inverse of a block is refined against the block's factor, complete in A (stable mode keeps L21 at every node)."""
     rows = slice(r0, r0 + m)
     if n <= blk:
         c = slice(c0, c0 + n)
         tiled_gemm(T[rows, c], A[rows, c], W[c, c], m, n, n, tile, a_kmajor=False, b_kmajor=False, alpha=1.0,
                    beta=0.0, khi=KHI_COL, log=log)
+        if stable:
+            tiled_gemm(A[rows, c], T[rows, c], A[c, c], m, n, n, tile, a_kmajor=False, b_kmajor=False, alpha=-1.0,
+                       beta=1.0, khi=KHI_COL, log=log)
+            tiled_gemm(T[rows, c], A[rows, c], W[c, c], m, n, n, tile, a_kmajor=False, b_kmajor=False, alpha=1.0,
+                       beta=1.0, khi=KHI_COL, log=log)
         return
     q = n // tile
     n1 = (q // 2) * tile
     n2 = n - n1
     ca, cc = slice(c0, c0 + n1), slice(c0 + n1, c0 + n)
-    trsm_nll(A, W, T, r0, m, c0, n1, tile, blk, log)
+    trsm_nll(A, W, T, r0, m, c0, n1, tile, blk, log, stable)
     tiled_gemm(A[rows, cc], T[rows, ca], T[cc, ca], m, n2, n1, tile, a_kmajor=False, b_kmajor=False, alpha=-1.0,
                beta=1.0, log=log)
-    trsm_nll(A, W, T, r0, m, c0 + n1, n2, tile, blk, log)
+    trsm_nll(A, W, T, r0, m, c0 + n1, n2, tile, blk, log, stable)
 
 
-def potrf_nll(A, W, T, off, n, tile, blk, log=None):
+def potrf_nll(A, W, T, off, n, tile, blk, log=None, stable=False, leaf_fn=None):
     """plan.h: potrf_nll -- the factorization of an NLL-only evaluation at N^3/3."""
     if n <= blk or n == tile:
-        return potrf_inv(A, W, T, off, n, tile, True, False, log)
+        return potrf_inv(A, W, T, off, n, tile, True, False, log, stable, leaf_fn)
     q = n // tile
     n1 = (q // 2) * tile
     n2 = n - n1
     o1, o2 = off, off + n1
     r1, r2 = slice(o1, o1 + n1), slice(o2, o2 + n2)
-    info = potrf_nll(A, W, T, o1, n1, tile, blk, log)
+    info = potrf_nll(A, W, T, o1, n1, tile, blk, log, stable, leaf_fn)
     if info:
         return info
-    trsm_nll(A, W, T, o2, n2, o1, n1, tile, blk, log)
+    trsm_nll(A, W, T, o2, n2, o1, n1, tile, blk, log, stable)
     tiled_gemm(A[r2, r2], T[r2, r1], T[r2, r1], n2, n2, n1, tile, a_kmajor=False, b_kmajor=False, alpha=-1.0,
                beta=1.0, lower_only=True, log=log)
-    return potrf_nll(A, W, T, o2, n2, tile, blk, log)
+    return potrf_nll(A, W, T, o2, n2, tile, blk, log, stable, leaf_fn)
 
 
 def forward_solve_nll(T, W, r, off, n, tile, blk):
