@@ -82,6 +82,7 @@ SIGNATURES = {
     "gpc_post_recompute_K": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_predict_full": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "gpc_predict_cov": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
+    "gpc_lookahead_batch": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _ip, _dp]),
     "gpc_draw": (C.c_int, [_vp, _dp, C.c_int, C.c_int, C.c_ulonglong, C.c_int, _dp, _dp, _dp]),
     "gpc_paths_create": (C.c_int, [_vp, C.c_int, C.c_int, C.c_ulonglong, C.c_int, _dp, _dp, C.POINTER(_vp)]),
     "gpc_paths_eval": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
@@ -1025,6 +1026,25 @@ class PostHandle:
                                            1 if (w is not None and w.ndim == 2) else 0, _ptr(fs2b), _ptr(cov), _ptr(wsq))
         self.ctx._check(rc, "gpc_predict_cov")
         return cov, wsq, fs2b
+
+    @_serial
+    def lookahead_batch(self, x_ref, x_cand, q, weights, noise):
+        """gpc_lookahead_batch: (idx (q,), gain (q, S)) of q greedy look-ahead steps.  ``weights`` (Mr,) or (Mr, S);
+        ``noise`` (Mc, S) is the predictive noise of every candidate under every sample."""
+        xr, xc = _f64(x_ref), _f64(x_cand)
+        Mr, Mc = xr.shape[0], xc.shape[0]
+        w, nz = _f64(weights), _f64(noise)
+        if w.shape not in ((Mr,), (Mr, self.S)):
+            raise ValueError(f"lookahead_batch: weights must be ({Mr},) or ({Mr}, {self.S}), got {w.shape}")
+        if nz.shape != (Mc, self.S):
+            raise ValueError(f"lookahead_batch: noise must be ({Mc}, {self.S}), got {nz.shape}")
+        q = int(q)
+        idx = np.empty(max(q, 0), dtype=np.int32)
+        gain = np.empty((max(q, 0), self.S))
+        rc = self.ctx._lib.gpc_lookahead_batch(self._h, _ptr(xr), Mr, _ptr(xc), Mc, _ptr(w), 1 if w.ndim == 2 else 0,
+                                               _ptr(nz), q, idx.ctypes.data, _ptr(gain))
+        self.ctx._check(rc, "gpc_lookahead_batch")
+        return idx.astype(np.int64), gain
 
     @_serial
     def draw(self, x_star, n_draws, seed, s_offset=0, noise_sd=None):

@@ -33,6 +33,7 @@
 #include "nll_hess.h"
 #include "leaf.h"
 #include "lookahead.h"
+#include "lookahead_batch.h"
 #include "paths.h"
 #include "plan.h"
 #include "quad.h"
@@ -498,6 +499,7 @@ struct gpc_ctx {
   unsigned long long hess_contract_us = 0;  // contraction passes of the last gpc_predict_hess, device microseconds ("hess_contract_us")
   unsigned long long nll_hess_gram_us = 0, nll_hess_contract_us = 0;  // Gram pass / second-derivative contraction of the last gpc_nll_hess, device microseconds
   unsigned long long cv_grad_trace_us = 0;  // contraction pass of the last gpc_cv_grad, device microseconds ("cv_grad_trace_us")
+  unsigned long long lookahead_batch_loop_us = 0;  // the q steps of the last gpc_lookahead_batch, device microseconds
   unsigned long long cov_fused = 0;  // gpc_predict_cov calls whose reduction ran in the product's epilogue ("cov_fused")
   unsigned long long quad_mix_gemms = 0;  // MFMA GEMM launches inside gpc_quad_mix ("quad_mix_gemms"; there should be none)
   int check_queues = 0;  // debug option: verify after every pipeline that the tile queues of its persistent launches were drained
@@ -526,6 +528,7 @@ struct gpc_ctx {
   DevBuf qcon;                   // quad_grad: the measures' constants (quad.h: quad_grad_prep_kernel)
   DevBuf qmix;                   // quad_mix: the whole scratch of a chunk, carved up in quad_mix_impl
   DevBuf nhs;                    // nll_hess: the whole scratch of a chunk, carved up in nll_hess_impl (NhScratch)
+  DevBuf lab;                    // lookahead_batch: the resident state of the step loop, carved up in lookahead_batch_impl (LabScratch)
   DevBuf hgs;                    // predict_hyp_grad: the whole scratch of a chunk, carved up in hyp_grad_impl (HgScratch)
   DevBuf zb, fb, dout, daux;     // draw: Z, F = L Z, the draws, [logdet | info | noise sd] (the factor: mA mW mT)
   DevBuf dbg1, dbg2, dbg3;       // debug hooks / fetch staging
@@ -3085,7 +3088,7 @@ int predict_impl(gpc_post* po, const double* xstar, int M, double* fmu, double* 
 // the same budget as rhs_products.
 template <typename T>
 int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int Mb, const double* w, int w_per_sample,
-                 double* fs2b, double* cov, double* wsq) {
+                 double* fs2b, double* cov, double* wsq, double* keep = nullptr) {
   gpc_ctx* c = po->ctx;
   const int S = po->S, N = po->N, D = po->D, npad = po->npad;
   const int mapad = pad_tile(Ma), mbpad = pad_tile(Mb), mmax = std::max(mapad, mbpad);
@@ -3227,6 +3230,10 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
     if (rc_runs) return rc_runs;
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, tm.mark2());
+    if (keep)  // gpc_lookahead_batch: the stored C of every sample stays on the device, in fp64 (Ma x mbpad each)
+      for (int i = 0; i < cnt; ++i)
+        hipLaunchKernelGGL((lab_load_kernel<T>), dim3(mbpad / 64, (Ma + 3) / 4), dim3(64, 4), 0, st,
+                           (const T*)(Kab + (size_t)i * sC), mbpad, Ma, Mb, keep + (size_t)(s0 + i) * Ma * mbpad);
     HIPCHK(c, hipMemcpyAsync(hout.data(), d_v, 2 * (size_t)chunk * mbpad * 8, hipMemcpyDeviceToHost, st));
     if (cov) {
       for (int i = 0; i < cnt; ++i) {
@@ -3258,17 +3265,7 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
   return 0;
 }
 
-// gpc_grad_post: the joint posterior of (f, grad f) at every query, rhs_products' sibling (gradpost.h).  The queries are
-// worked on in blocks of GQB = 128 whatever the shape or the budget; per block and sample
-//   panel = [ k(X, x*) | dk/dx*_1 | ... | dk/dx*_D ]  (npad x (D + 1) 128, slot-major planes; the mean product fused in)
-//   L_chol:    V = W panel,   Gram = per query V_j^T V_j,         C_j = H - Gram / sl
-//   low noise: Z = L panel,   Gram = per query panel_j^T Z_j,     C_j = H + Gram
-// `diag`: the D + 1 variances only -- for L_chol samples the column sums of squares of V from the product's epilogue
-// (gemm.h: EPI = 1, V is never written), for the others the diagonal form of the Gram kernel.  The forms depend on
-// (npad, D, diag) alone, so a sample carries the same bits in any batch, chunk or run.  The budget decides the samples
-// per chunk only; a sample with one query block that does not fit is refused.
-// gpc_last_timing: the device sections of all (chunk, block) steps and, of these, the products with W (or L).
-struct GramClock {  // the Gram passes of a timed call, for the "grad_post_gram_us" counter
+struct GramClock {  // one timed device section of a call: the Gram passes of "grad_post_gram_us", the step loop below
   hipEvent_t e[2] = {nullptr, nullptr};
   bool on;
   explicit GramClock(bool on_) : on(on_) {
@@ -3285,6 +3282,114 @@ struct GramClock {  // the Gram passes of a timed call, for the "grad_post_gram_
     return 1e3 * ms;
   }
 };
+
+// ---- gpc_lookahead_batch: q greedy look-ahead steps on the device (lookahead_batch.h) ----------------------------------
+// The resident state of ALL samples, carved from one allocation (c->lab): the score of a step needs every sample, so the
+// step loop cannot be chunked over them.  C comes first (its rows are read 16 bytes at a time); every double block has
+// an even length; the block that is downloaded (the gains, then the indices) is contiguous.
+struct LabScratch {
+  double *C, *lpan, *part, *gains, *score, *v, *noise, *w, *sd, *gain_out;
+  int *idx, *cur, *chosen;
+  size_t out_bytes = 0;
+  static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
+  void layout(ScratchCarver& sc, int S, int Mr, int Mc, int ld, int q) {
+    const size_t s = S, nslab = (Mr + LB_T - 1) / LB_T;
+    C = sc.take(s * (Mr + Mc) * ld);
+    lpan = sc.take(even(s * q * (Mr + ld)));
+    part = sc.take(s * nslab * ld);
+    gains = sc.take(s * ld);
+    score = sc.take(ld);
+    v = sc.take(s * ld);
+    noise = sc.take(s * ld);
+    w = sc.take(even(s * Mr));
+    sd = sc.take(even(s));
+    const size_t before_out = sc.bytes;
+    gain_out = sc.take(even(s * q));
+    idx = sc.take<int>(even(q));
+    out_bytes = sc.bytes - before_out;
+    cur = sc.take<int>(2);
+    chosen = sc.take<int>(ld);
+  }
+};
+
+template <typename T>
+int lookahead_batch_impl(gpc_post* po, const double* xr, int Mr, const double* xc, int Mc, const double* w, int w_per_sample,
+                         const double* noise, int q, int* idx, double* gain) {
+  gpc_ctx* c = po->ctx;
+  const int S = po->S, D = po->D, Ma = Mr + Mc, ld = pad_tile(Mc), nslab = (Mr + LB_T - 1) / LB_T, Rl = Mr + ld;
+  hipStream_t st = c->st;
+  const size_t need = ScratchCarver::count<LabScratch>(S, Mr, Mc, ld, q);
+  // the budget of the resident state: what plan_chunk gives a consumer's scratch, for all samples at once
+  const bool forced = getenv("GPC_MEM_BUDGET_MB") != nullptr;
+  if (forced || need > c->lab.bytes) {
+    c->pool_drain();
+    const size_t budget = (size_t)((free_device_bytes() + (forced ? 0 : c->lab.bytes)) * 0.8);
+    if (need > budget)
+      FAIL(c, "gpc_lookahead_batch: the resident state of the step loop (" + std::to_string(need >> 10) + " KB: S = " +
+                  std::to_string(S) + ", Mr = " + std::to_string(Mr) + ", Mc_pad = " + std::to_string(ld) + ", q = " +
+                  std::to_string(q) + "; S (Mr + Mc) Mc_pad doubles and the l panels, not chunked over the samples) "
+                  "exceeds the device memory budget (" + std::to_string(budget >> 10) + " KB)");
+  }
+  HIPCHK(c, c->lab.ensure(need));
+  LabScratch z;
+  ScratchCarver::carve(z, c->lab.p, S, Mr, Mc, ld, q);
+  // C^0 of [x_ref; x_cand] against x_cand and predict's variance of the candidates: cov_products' stored form, chunked
+  // over the samples under its own budget; the covariances stay on the device
+  std::vector<double> xa((size_t)Ma * D), fs2((size_t)Mc * S);
+  std::copy_n(xr, (size_t)Mr * D, xa.begin());
+  std::copy_n(xc, (size_t)Mc * D, xa.begin() + (size_t)Mr * D);
+  if (int rc = cov_products<T>(po, xa.data(), Ma, xc, Mc, nullptr, 0, fs2.data(), nullptr, nullptr, z.C)) return rc;
+  // per-sample rows of the variances, the noise and the weights (zero in the padding: den = 0 there)
+  std::vector<double> hv((size_t)S * ld, 0.0), hn((size_t)S * ld, 0.0), hw((size_t)S * Mr);
+  for (int s = 0; s < S; ++s) {
+    for (int j = 0; j < Mc; ++j) {
+      hv[(size_t)s * ld + j] = fs2[(size_t)j * S + s];
+      hn[(size_t)s * ld + j] = noise[(size_t)j * S + s];
+    }
+    for (int r = 0; r < Mr; ++r) hw[(size_t)s * Mr + r] = w_per_sample ? w[(size_t)r * S + s] : w[r];
+  }
+  HIPCHK(c, hipMemcpyAsync(z.v, hv.data(), hv.size() * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(z.noise, hn.data(), hn.size() * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(z.w, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(z.lpan, 0, (size_t)S * q * Rl * 8, st));
+  HIPCHK(c, hipMemsetAsync(z.chosen, 0, (size_t)ld * sizeof(int), st));
+  const long long sC = (long long)Ma * ld, sL = (long long)q * Rl;
+  GramClock clk(true);
+  HIPCHK(c, clk.record(0, st));
+  // all q steps, enqueued without waiting: a step's launches hand c_t and sqrt(den) on through device memory
+  for (int t = 0; t < q; ++t) {
+    hipLaunchKernelGGL(lab_step_kernel, dim3(ld / LB_T, nslab, S), dim3(256), 0, st, z.C, sC, ld, Mr, (const double*)z.w,
+                       t ? (const double*)(z.lpan + (size_t)(t - 1) * Rl) : (const double*)nullptr, sL, z.part, nslab);
+    hipLaunchKernelGGL(lab_score_kernel, dim3(ld / LB_T), dim3(256), 0, st, (const double*)z.part, nslab, ld, S,
+                       (const double*)z.v, (const double*)z.noise, z.gains, z.score);
+    hipLaunchKernelGGL(lab_pick_kernel, dim3(1), dim3(256), 0, st, (const double*)z.score, Mc, ld, S, t,
+                       (const double*)z.gains, (const double*)z.v, (const double*)z.noise, z.chosen, z.idx, z.cur, z.sd,
+                       z.gain_out);
+    if (t + 1 < q)
+      hipLaunchKernelGGL(lab_col_kernel, dim3((Ma + 255) / 256, S), dim3(256), 0, st, (const double*)z.C, sC, ld, Mr, Mc,
+                         (const int*)z.cur, (const double*)z.sd, z.lpan, sL, Rl, t, z.v);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, clk.record(1, st));
+  std::vector<char> ho(z.out_bytes);
+  HIPCHK(c, hipMemcpyAsync(ho.data(), z.gain_out, z.out_bytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  c->lookahead_batch_loop_us = (unsigned long long)clk.elapsed_us();
+  memcpy(gain, ho.data(), (size_t)q * S * 8);
+  memcpy(idx, ho.data() + LabScratch::even((size_t)S * q) * 8, (size_t)q * sizeof(int));
+  return 0;
+}
+
+// gpc_grad_post: the joint posterior of (f, grad f) at every query, rhs_products' sibling (gradpost.h).  The queries are
+// worked on in blocks of GQB = 128 whatever the shape or the budget; per block and sample
+//   panel = [ k(X, x*) | dk/dx*_1 | ... | dk/dx*_D ]  (npad x (D + 1) 128, slot-major planes; the mean product fused in)
+//   L_chol:    V = W panel,   Gram = per query V_j^T V_j,         C_j = H - Gram / sl
+//   low noise: Z = L panel,   Gram = per query panel_j^T Z_j,     C_j = H + Gram
+// `diag`: the D + 1 variances only -- for L_chol samples the column sums of squares of V from the product's epilogue
+// (gemm.h: EPI = 1, V is never written), for the others the diagonal form of the Gram kernel.  The forms depend on
+// (npad, D, diag) alone, so a sample carries the same bits in any batch, chunk or run.  The budget decides the samples
+// per chunk only; a sample with one query block that does not fit is refused.
+// gpc_last_timing: the device sections of all (chunk, block) steps and, of these, the products with W (or L).
 
 template <typename T>
 int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* fmu, double* dfmu, double* cov) {
@@ -6503,7 +6608,7 @@ void gpc_destroy(gpc_ctx* c) {
   DevBuf* bufs[] = {&c->dX,   &c->dY,  &c->mA,    &c->mW,  &c->mT,   &c->xs,   &c->spb,  &c->mulb, &c->divb,
                     &c->dvec, &c->rvec,  &c->zvec, &c->avec, &c->scal, &c->parts, &c->gout, &c->diagq,
                     &c->dmb,  &c->dsn2b, &c->mg,  &c->ng,   &c->ks,   &c->vb,   &c->xss,  &c->pout, &c->kss,
-                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->qmix, &c->nhs, &c->hgs, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
+                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->qmix, &c->nhs, &c->hgs, &c->lab, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
   for (auto& g : c->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (DevBuf* b : bufs) b->release();
@@ -7218,6 +7323,21 @@ int gpc_predict_cov(gpc_post* po, const double* xa, int Ma, const double* xb, in
                               : cov_products<float>(po, xa, Ma, xb, Mb, w, w_per_sample, fs2b, cov, wsq);
 }
 
+int gpc_lookahead_batch(gpc_post* po, const double* xr, int Mr, const double* xc, int Mc, const double* w, int w_per_sample,
+                        const double* noise, int q, int* idx, double* gain) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!xr || !xc || !w || !noise || !idx || !gain || Mr <= 0 || Mc <= 0 || q < 1 || q > Mc)
+    FAIL(c, "gpc_lookahead_batch: bad arguments (Mr = " + std::to_string(Mr) + ", Mc = " + std::to_string(Mc) +
+                ", q = " + std::to_string(q) + "; 1 <= q <= Mc, no null pointers)");
+  if (po->cd.kind < 0)
+    FAIL(c, "gpc_lookahead_batch: this posterior was built from caller-provided K; there is no k(xa, xb) to start from");
+  if (int rc = require_factorized(po, "gpc_lookahead_batch")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? lookahead_batch_impl<double>(po, xr, Mr, xc, Mc, w, w_per_sample, noise, q, idx, gain)
+                              : lookahead_batch_impl<float>(po, xr, Mr, xc, Mc, w, w_per_sample, noise, q, idx, gain);
+}
+
 namespace {
 // z (K + sn2_eff I)^-1 z^T: |W z|^2 / sl (L_chol) or -(z . L z) (L = -inv)   (:1946-1962)
 void quad_scale_zkz(const gpc_post* po, int M, double* zKz) {
@@ -7412,7 +7532,8 @@ const Option OPTIONS[] = {
     {"nll_hess_contract_us", GPC_COUNTER(nll_hess_contract_us)},  // ... of its second-derivative contraction (ARD families; 0 for the isotropic ones)
     {"cv_grad_trace_us", GPC_COUNTER(cv_grad_trace_us)},  // device time of the contraction pass (kernel + reduction) of the last gpc_cv_grad (timed calls only)
     {"grad_post_gram_us", GPC_COUNTER(grad_post_gram_us)},  // device time of the Gram passes of the last gpc_grad_post (timed calls only)
-    {"cov_fused", GPC_COUNTER(cov_fused)},        // gpc_predict_cov calls reduced in the product's epilogue
+    {"lookahead_batch_loop_us", GPC_COUNTER(lookahead_batch_loop_us)},  // device time of the step loop (all q steps, without the formation of C^0) of the last gpc_lookahead_batch
+    {"cov_fused", GPC_COUNTER(cov_fused)},       // gpc_predict_cov calls reduced in the product's epilogue
     {"quad_mix_gemms", GPC_COUNTER(quad_mix_gemms)},  // MFMA GEMM launches inside gpc_quad_mix
     {"start_mult_log10", nullptr, GPC_SET(c->start_mult = std::pow(10.0, clamp_to(0, 9, v)))},  // test hook: first jitter multiplier 10^value
     {"append_fail_mask", nullptr, GPC_SET(c->append_fail_mask = (unsigned)v)},  // test hook: samples whose rank-one append is declared unstable

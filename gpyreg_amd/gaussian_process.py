@@ -2141,14 +2141,7 @@ class GP:
         s_N = self.posteriors.size
         Mc, Mr = x_cand.shape[0], x_ref.shape[0]
         cov_N = self._counts()[0]
-        if weights is None:
-            w = np.full(Mr, 1.0 / Mr)
-        else:
-            w = np.asarray(weights, dtype=float)
-            if w.shape not in ((Mr,), (Mr, s_N)):
-                raise ValueError(f"lookahead_variance: weights must be ({Mr},) or ({Mr}, {s_N}), got {w.shape}")
-            if not np.all(np.isfinite(w)):
-                raise ValueError("lookahead_variance: weights must be finite")
+        w = self._lookahead_weights("lookahead_variance", weights, Mr)
         if self.y is None:  # no data: the prior
             wsq = np.empty((Mc, s_N))
             fs2 = np.empty((Mc, s_N))
@@ -2160,13 +2153,108 @@ class GP:
                 fs2[:, s] = self.covariance.compute(hyp[0:cov_N], x_cand, compute_diag=True)[:, 0]
         else:
             _, wsq, fs2 = self._cov_on_device(x_ref, x_cand, w)
-        den = np.empty((Mc, s_N))
-        for s, post in enumerate(self.posteriors):
-            den[:, s:s + 1] = np.maximum(fs2[:, s:s + 1], 0) + self._noise_star(post, x_cand, y_cand, s2_cand)
+        den = np.maximum(fs2, 0) + self._lookahead_noise(x_cand, y_cand, s2_cand)
         red = np.where(den > 0, wsq / np.where(den > 0, den, 1.0), 0.0)
         if not separate_samples:
             red = np.reshape(np.sum(red, 1) / s_N, (-1, 1))
         return red
+
+    def _lookahead_weights(self, who, weights, Mr):
+        """The reference points' weights of ``lookahead_variance`` / ``lookahead_batch``: None -> 1 / Mr each, else
+        (Mr,) or (Mr, S), finite."""
+        s_N = self.posteriors.size
+        if weights is None:
+            return np.full(Mr, 1.0 / Mr)
+        w = np.asarray(weights, dtype=float)
+        if w.shape not in ((Mr,), (Mr, s_N)):
+            raise ValueError(f"{who}: weights must be ({Mr},) or ({Mr}, {s_N}), got {w.shape}")
+        if not np.all(np.isfinite(w)):
+            raise ValueError(f"{who}: weights must be finite")
+        return w
+
+    def _lookahead_noise(self, x_cand, y_cand, s2_cand, mult=None):
+        """The noise part of the look-ahead denominators: (Mc, S), sn2_s(x_c) * sn2_mult_s as ``predict(add_noise=True)``
+        forms it (``mult``: multipliers to use instead of the records')."""
+        nz = np.empty((x_cand.shape[0], self.posteriors.size))
+        for s, post in enumerate(self.posteriors):
+            if mult is None:
+                nz[:, s:s + 1] = self._noise_star(post, x_cand, y_cand, s2_cand)
+            else:
+                cov_N, noise_N, _ = self._counts()
+                nz[:, s:s + 1] = self.noise.compute(post.hyp[cov_N:cov_N + noise_N], x_cand, y_cand, s2_cand) * mult[s]
+        return nz
+
+    def lookahead_batch(self, x_cand, x_ref, q, weights=None, y_cand=None, s2_cand=None,
+                        separate_samples: bool = False):
+        """Greedy batch design by the weighted integrated variance: the q candidates that ``lookahead_variance``,
+        argmax and ``update`` with a fantasy target would pick one after the other -- without the loop, and without
+        touching this GP.  Returns ``(idx, gain)``: idx (q,) the selection order; gain (q, S) with
+        ``separate_samples``, else (q, 1), the chosen candidate's reduction at the step it was chosen (its cumulative
+        sum is the total expected reduction).
+
+        The posterior covariance after conditioning does not depend on the observed value, so per sample s, from
+        C_s = ``predict_cov([x_ref; x_cand], x_cand)``, v_s = ``predict``'s unclamped variance of the candidates and
+        n_s = sn2_s(x_c) * sn2_mult_s (``y_cand``, ``s2_cand`` as ``lookahead_variance``'s), step t is
+
+            den_s(c)  = max(v_s(c), 0) + n_s(c)
+            gain_s(c) = sum_r w_rs C_s(r, c)^2 / den_s(c)            (0 where den_s(c) <= 0)
+            c_t       = argmax_c (1/S) sum_s gain_s(c) over the candidates not yet chosen, lowest index on a tie
+            l_s(a)    = C_s(a, c_t) / sqrt(den_s(c_t));  C_s(a, b) -= l_s(a) l_s(Mr + b);  v_s(b) -= l_s(Mr + b)^2
+
+        (``_lookahead_batch`` restates it).  A candidate is chosen at most once; step 0's gains are
+        ``lookahead_variance``'s.  ``weights`` as ``lookahead_variance``'s; ``1 <= q <= Mc`` (``ValueError``).  With
+        data the whole loop runs on the device (gpc_lookahead_batch) in fp64, also for fp32 posteriors, and q indices
+        and q x S gains come back; a GP without data runs the same recurrence on the prior, on the host.  Built-in
+        covariance functions only.  Under a process group the call is NOT sharded (the selection needs every sample at
+        every step): it runs on the calling rank alone and exchanges nothing; resident posteriors that are sharded are
+        rebuilt locally as temporaries."""
+        from . import _lookahead_batch as _lb
+
+        if not self._builtin:
+            raise NotImplementedError(f"lookahead_batch: the covariance function {self.covariance!r} is user-defined; "
+                                      "the cross covariance runs on the built-in covariance functions only")
+        x_cand, y_cand, s2_cand = self._convert_shapes(x_cand, y_cand, s2_cand)
+        x_ref, _, _ = self._convert_shapes(x_ref, None, None)
+        s_N = self.posteriors.size
+        Mc, Mr = x_cand.shape[0], x_ref.shape[0]
+        if isinstance(q, bool) or int(q) != q or not 1 <= int(q) <= Mc:
+            raise ValueError(f"lookahead_batch: q must be an integer in [1, {Mc}] (the number of candidates), got {q!r}")
+        q = int(q)
+        w = self._lookahead_weights("lookahead_batch", weights, Mr)
+        if self.y is None:  # no data: the prior
+            cov_N = self._counts()[0]
+            x_all = np.vstack([x_ref, x_cand])
+            C0 = np.stack([self.covariance.compute(p.hyp[0:cov_N], x_all, x_cand) for p in self.posteriors])
+            v0 = np.stack([self.covariance.compute(p.hyp[0:cov_N], x_cand, compute_diag=True)[:, 0]
+                           for p in self.posteriors], axis=1)
+            w2 = w if w.ndim == 2 else np.repeat(w[:, None], s_N, axis=1)
+            idx, gain = _lb.greedy_batch(C0, v0, self._lookahead_noise(x_cand, y_cand, s2_cand), w2, q)
+        else:
+            idx, gain = self._lookahead_batch_local(x_cand, x_ref, q, w, y_cand, s2_cand)
+        if not separate_samples:
+            gain = np.reshape(np.sum(gain, 1) / s_N, (-1, 1))
+        return idx, gain
+
+    @_on_device
+    def _lookahead_batch_local(self, x_cand, x_ref, q, w, y_cand, s2_cand):
+        """``lookahead_batch`` after its refusals: this rank's device call, on the resident posteriors or (sharded)
+        on temporaries built for all samples."""
+        self._require_posteriors()
+        ctx = self._ctx()
+        if self._post_range is None and self._post_handle is not None:
+            return self._post_handle.lookahead_batch(x_ref, x_cand, q, w, self._lookahead_noise(x_cand, y_cand, s2_cand))
+        cov_N = self._counts()[0]
+        hyp = np.stack([p.hyp for p in self.posteriors])
+        pv = self._plugin_values(hyp, False)
+        kid, deg = self._kid()
+        handle, mult, _, info = ctx.posterior_batch(kid, deg, _DTYPES[self.dtype], hyp[:, :cov_N], pv["m"], pv["sn2"],
+                                                    pv["vec"])
+        try:
+            if np.any(info != 0):
+                raise LinAlgError("Singular matrix for L Cholesky decomposition")
+            return handle.lookahead_batch(x_ref, x_cand, q, w, self._lookahead_noise(x_cand, y_cand, s2_cand, mult))
+        finally:
+            handle.free()
 
     @_on_device
     def _cov_on_device(self, x_a, x_b, weights):

@@ -460,6 +460,31 @@ int gpc_predict_full(gpc_post* post, const double* xstar, int M, double* fmu, do
 int gpc_predict_cov(gpc_post* post, const double* xa, int Ma, const double* xb, int Mb, const double* w,
                     int w_per_sample, double* fs2b, double* cov, double* wsq);
 
+/* ---- GP.lookahead_batch: q greedy look-ahead steps without the host ----------------------------------
+ * xr: Mr x D reference points, xc: Mc x D candidates, w as gpc_predict_cov's (Mr doubles, or Mr x S as
+ * w[r*S + s] when w_per_sample), noise[c*S + s] the predictive noise of candidate c under sample s (the
+ * noise function's value times the sample's multiplier), 1 <= q <= Mc.  Per sample C^0 is gpc_predict_cov's
+ * covariance of [xr; xc] against xc and v^0 gpc_predict's unclamped variance of xc; for t = 0 .. q-1
+ *   den_s(c)  = max(v_s(c), 0) + noise[c*S + s]
+ *   gain_s(c) = sum_r w_rs C_s(r, c)^2 / den_s(c)          (0 where den_s(c) <= 0)
+ *   c_t       = argmax_c (1/S) sum_s gain_s(c) over the candidates not yet chosen, the lowest index on a tie
+ *               (samples added in ascending order; a NaN score counts as -inf)
+ *   l_s(a)    = C_s(a, c_t) / sqrt(den_s(c_t)) for every row a (0 where den_s(c_t) <= 0),
+ *   C_s(a, b) -= l_s(a) l_s(Mr + b),   v_s(b) -= l_s(Mr + b)^2
+ * idx[t] = c_t, gain[t*S + s] = gain_s(c_t) at step t.  The posterior is not modified.  C^0 is formed by
+ * gpc_predict_cov's stored form, chunked over the samples under the same budget, and kept on the device in
+ * fp64 (also for fp32 posteriors): the step loop is fp64.  Its reference rows are updated in place, one
+ * read and one write per step; the Mc x Mc candidate block is never rewritten -- its column c_t is formed
+ * from C^0 and the stored l vectors.  All q steps are enqueued without a host synchronisation; idx and gain
+ * come back in one transfer.  Fixed summation orders and no atomics: the same bits on every call, whatever
+ * the chunking of the formation.  Returns -2 with a message that names the sizes when the resident state
+ * (S (Mr + Mc) Mc_pad doubles and q l vectors per sample; it cannot be chunked over the samples) does not
+ * fit the memory budget (GPC_MEM_BUDGET_MB), on a posterior from caller-provided K, on one that holds a
+ * failed factorization and on bad arguments.  gpc_get_option "lookahead_batch_loop_us": the device time
+ * of the step loop. */
+int gpc_lookahead_batch(gpc_post* post, const double* xr, int Mr, const double* xc, int Mc, const double* w,
+                        int w_per_sample, const double* noise, int q, int* idx, double* gain);
+
 /* ---- GP.quad: Bayesian quadrature products (gaussian_process.py:1908-1966), SE kernels ----
  * mu, sigma: M x D (means and standard deviations of the Gaussian measures).  With z the
  * kernel mean vector of measure j under sample s:
@@ -585,6 +610,7 @@ int gpc_last_lauum_timing(gpc_ctx* ctx, double* ms, double* flops);
  * "last_chunk" (get only): how many samples per chunk the last posterior consumer (predictions, gradients, Hessians,
  * cross-validation, quadrature, paths, appends) planned for its scratch; S when the call ran whole, 0 when it refused.
  * "cov_fused" (get only): how many gpc_predict_cov calls formed their reduction in the product's epilogue.
+ * "lookahead_batch_loop_us" (get only): device microseconds of the step loop of the last gpc_lookahead_batch.
  * "quad_mix_gemms" (get only): MFMA GEMM launches issued inside gpc_quad_mix over the life of the context (0 by design).
  * "paths_engine" / "paths_solve_engine" (test hooks) and "paths_engine_ran" / "paths_solve_engine_ran" (get only): see
  * gpc_paths_create / gpc_paths_eval.  "cv_engine" (test hook) and "cv_engine_ran" (get only): see gpc_cv. */
