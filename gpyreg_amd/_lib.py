@@ -79,6 +79,9 @@ SIGNATURES = {
     "gpc_post_append_K": (C.c_int, [_vp, _dp, _dp, _dp, _dp, C.c_double, _ip]),
     "gpc_post_append_block": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _ip]),
     "gpc_post_append_block_K": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip]),
+    "gpc_post_remove": (C.c_int, [_vp, C.c_int, _ip, _dp, _ip]),
+    "gpc_debug_remove_panel": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, _dp]),
+    "gpc_debug_remove_apply": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp]),
     "gpc_post_recompute_K": (C.c_int, [_vp, C.c_int, _ip, _dp, _dp, _dp, C.c_int, _dp, _ip, _ip]),
     "gpc_predict_full": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
     "gpc_predict_cov": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
@@ -627,6 +630,40 @@ class Context:
         return [o for o in outs if o is not None]
 
     @_serial
+    def debug_remove_panel(self, D, Vp, dtype=F64):
+        """gpc_debug_remove_panel: the panel kernel of the point removal on D (64, 64; lower triangle) and Vp (64, k).
+        Returns (Theta (64 + k, 64 + k), Dnew (64, 64)) with [D | Vp] Theta = [Dnew | 0]."""
+        D, Vp = _f64(D), _f64(Vp)
+        if D.shape != (64, 64) or Vp.ndim != 2 or Vp.shape[0] != 64:
+            raise ValueError("debug_remove_panel: D (64, 64) and Vp (64, k)")
+        k = Vp.shape[1]
+        theta, dnew = np.empty((64 + k, 64 + k)), np.empty((64, 64))
+        rc = self._lib.gpc_debug_remove_panel(self._h, dtype, k, _ptr(D), _ptr(Vp), _ptr(theta), _ptr(dnew))
+        self._check(rc, "gpc_debug_remove_panel")
+        return theta, dnew
+
+    @_serial
+    def debug_remove_apply(self, side, a, Theta, P, Cr, dtype=F64):
+        """gpc_debug_remove_apply: the apply kernel of the point removal on a given Theta (64 + k, 64 + k) for the
+        panel [a, a + 64).  ``side`` "L": P (rows, 64) = L[a+64:, a:a+64], Cr (rows, k) -> [P | Cr] Theta;  "W":
+        P (64, n) = W[a:a+64, :n], Cr (k, n) -> Theta^T [P ; Cr] (entries of P above the diagonal come back as given).
+        Returns the new (P, Cr)."""
+        Theta, P, Cr = _f64(Theta), _f64(P).copy(), _f64(Cr).copy()
+        k = Theta.shape[0] - 64
+        if side == "L":
+            n = a + 64 + P.shape[0]
+            good = P.shape == (n - a - 64, 64) and Cr.shape == (P.shape[0], k)
+        else:
+            n = P.shape[1]
+            good = side == "W" and P.shape == (64, n) and Cr.shape == (k, n)
+        if not good or Theta.shape != (64 + k, 64 + k):
+            raise ValueError("debug_remove_apply: Theta (64 + k, 64 + k); L: P (rows, 64), Cr (rows, k); W: P (64, n), Cr (k, n)")
+        rc = self._lib.gpc_debug_remove_apply(self._h, dtype, 0 if side == "L" else 1, int(a), n, k, _ptr(Theta), _ptr(P),
+                                              _ptr(Cr))
+        self._check(rc, "gpc_debug_remove_apply")
+        return P, Cr
+
+    @_serial
     def debug_block_gram(self, Y, Z=None, dtype=F64, diag_only=False):
         """gpc_debug_block_gram: Y, Z (n, Dp, M) panels (Z None: Z = Y).  Returns (M, Dp, Dp): [j, a, b] = [j, b, a] =
         sum_i Y[i, a, j] Z[i, b, j] for a >= b, accumulated in fp64 from the values stored in ``dtype``; with
@@ -971,6 +1008,22 @@ class PostHandle:
                                                    _ptr(y_new), ok.ctypes.data)
         self.ctx._check(rc, "gpc_post_append_block_K")
         self.N += k
+        return ok.astype(bool)
+
+    @_serial
+    def remove(self, idx, ym):
+        """Removal of the rows ``idx`` (sorted, distinct; numbered in the posterior's N rows) that have already left the
+        context's data (gpc_post_remove): ym (S, N - k) = y - m_s(X) on the kept rows.  Returns the per-sample outcome
+        (bool array): False entries were left stale in the compacted storage and must be recomputed (``recompute``)."""
+        idx = np.ascontiguousarray(idx, dtype=np.int32).ravel()
+        k = idx.size
+        ym = _f64(ym)
+        if ym.shape != (self.S, self.N - k):
+            raise ValueError("ym must be (S, N - k)")
+        ok = np.zeros(self.S, dtype=np.int32)
+        rc = self.ctx._lib.gpc_post_remove(self._h, k, idx.ctypes.data, _ptr(ym), ok.ctypes.data)
+        self.ctx._check(rc, "gpc_post_remove")
+        self.N -= k
         return ok.astype(bool)
 
     @_serial

@@ -38,6 +38,7 @@
 #include "plan.h"
 #include "quad.h"
 #include "quad_mix.h"
+#include "remove.h"
 #ifdef GPC_EXPERIMENTS
 // Schedules that were built, measured and rejected -- the tile-level dataflow graph, independent
 // per-sample pipelines, rectangular / eight-wave tiles, right-looking panels -- are compiled only into the experiments
@@ -590,6 +591,9 @@ struct gpc_ctx {
   int block_engine_ran = 0;  // the engine the last gpc_post_append_block ran (1: skinny kernel, 2: MFMA GEMM; get-only)
   int block_engine = 0;  // test hook: the engine of the block append's products with W (0: by k, 1: skinny kernel, 2: MFMA GEMM)
   long long block_appended = 0, block_stale = 0;  // samples gpc_post_append_block appended / left stale (get-only options)
+  unsigned remove_fail_mask = 0;  // test hook: samples gpc_post_remove declares stale
+  int remove_force = 0;           // test hook: "remove_max_panels" / "remove_min_rows" report no limit (GP.remove_points takes the device path whatever the shape)
+  long long points_removed = 0, remove_stale = 0;  // samples gpc_post_remove shrank / left stale (get-only options "removed" / "remove_stale")
   int paths_engine = 0;      // test hook: the engine of gpc_paths_eval (0: paths.h's PA_DEFAULT_ENGINE, 1: fused kernel, 2: operand matrices + library GEMM)
   int paths_engine_ran = 0;  // the engine the last gpc_paths_eval ran (get-only)
   int paths_solve_engine = 0;      // test hook: the products of gpc_paths_create's solve (0 / 1: skinny kernel, 2: MFMA GEMM)
@@ -5407,6 +5411,335 @@ int append_block_check(gpc_post* po, int k, const char* fn) {
   if (c->N != po->N + k) FAIL(c, f + ": call gpc_set_data with the extended X, y (N + k rows) first");
   return 0;
 }
+
+// ---- removal of k points (remove.h has the algebra and the kernels) ------------------------------------------------
+// Device buffers of one sweep over a chunk of `cnt` samples, carved from the context's cross-covariance buffer
+template <typename T>
+struct RmScratch {
+  double *V, *C, *H, *Th, *aI, *tv, *zv;
+  T *fA, *fW, *fT;
+  void layout(ScratchCarver& sc, int cnt, int npn, int kq, int kp) {
+    const size_t c = cnt, panel = (size_t)npn * kq, mp = RM_P + kq;
+    V = sc.take(c * panel);    // A[R, I]: the L-side carrier | the low-noise panel
+    C = sc.take(c * panel);    // W[I, R]: the W-side carrier
+    H = sc.take(c * panel);    // low noise: A[R, I] Wq^T
+    Th = sc.take(c * mp * mp);
+    aI = sc.take(c * kq);
+    tv = sc.take(c * kq);
+    zv = sc.take(c * kq);
+    fA = sc.take<T>(c * kp * kp);  // the three slabs of the k x k factorization
+    fW = sc.take<T>(c * kp * kp);
+    fT = sc.take<T>(c * kp * kp);
+  }
+};
+
+// One sweep: the kk <= RM_KMAX sorted rows idx[] leave a posterior of po->N rows.  New storage at the padded size of
+// n = N - kk (pool first), the old one to the pool.  dead[s] != 0: the sample is stale already and is only compacted;
+// a low-noise sample whose Q_II does not factorize becomes dead.  d_par: the samples' parameters (block_append.h).
+template <typename T>
+int remove_sweep(gpc_post* po, int kk, const int* idx, int chunk, std::vector<double>& par, std::vector<int>& dead,
+                 bool timed, double& sweep_ms) {
+  gpc_ctx* c = po->ctx;
+  hipStream_t st = c->st;
+  const int S = po->S, No = po->N, n = No - kk, ldo = po->npad, npn = pad_tile(n);
+  const int kq = rm_kq(kk), kp = pad_tile(kk), mp = RM_P + kq;
+  const long long sMo = (long long)ldo * ldo, sMn = (long long)npn * npn, sV = (long long)npn * kq;
+  const size_t per = ScratchCarver::count<RmScratch<T>>(1, npn, kq, kp);
+  // the kept rows, and the panel that holds the first removed one (in the compacted numbering)
+  std::vector<int> maps((size_t)npn + kk, -1);
+  for (int i = 0, r = 0, j = 0; r < No; ++r) {
+    if (j < kk && idx[j] == r) ++j;
+    else maps[i++] = r;
+  }
+  std::copy_n(idx, kk, maps.begin() + npn);
+  const int a0 = (idx[0] / RM_P) * RM_P;
+  for (int s = 0; s < S; ++s) par[(size_t)s * BA_STRIDE + BA_PRE] = dead[s] ? 0.0 : 1.0;
+  DevBuf nA = c->pool_take((size_t)S * sMn * sizeof(T)), nW = c->pool_take((size_t)S * sMn * sizeof(T)),
+         nal = c->pool_take((size_t)S * npn * sizeof(double));
+  std::vector<hipEvent_t> evs;  // around the panel loop of every chunk (timed calls)
+  auto fail = [&](int rc) {
+    for (DevBuf* b : {&nA, &nW, &nal}) b->release();
+    for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+    return rc;
+  };
+  auto mark = [&]() -> hipError_t {
+    if (!timed) return hipSuccess;
+    hipEvent_t e;
+    if (hipError_t rc = hipEventCreate(&e)) return rc;
+    evs.push_back(e);
+    return hipEventRecord(e, st);
+  };
+#define RM_CHK(expr)                                                  \
+  do {                                                                \
+    hipError_t _e = (expr);                                           \
+    if (_e != hipSuccess) {                                           \
+      c->err = std::string(#expr) + ": " + hipGetErrorString(_e);     \
+      return fail(-1);                                                \
+    }                                                                 \
+  } while (0)
+  RM_CHK(nA.ensure((size_t)S * sMn * sizeof(T)));
+  RM_CHK(nW.ensure((size_t)S * sMn * sizeof(T)));
+  RM_CHK(nal.ensure((size_t)S * npn * sizeof(double)));
+  RM_CHK(c->ks.ensure((size_t)chunk * per));
+  RM_CHK(c->dvec.ensure((size_t)S * BA_STRIDE * 8));
+  RM_CHK(c->scal.ensure((size_t)S * 16));
+  RM_CHK(c->dbg2.ensure(maps.size() * sizeof(int)));
+  double* d_par = c->dvec.as<double>();
+  double* d_logdet = c->scal.as<double>();
+  int* d_info = reinterpret_cast<int*>(d_logdet + S);
+  const int* d_rmap = c->dbg2.as<int>();
+  const int* d_idx = d_rmap + npn;
+  // (pageable sources: the copies are staged before the calls return)
+  RM_CHK(hipMemcpy(c->dbg2.p, maps.data(), maps.size() * sizeof(int), hipMemcpyHostToDevice));
+  RM_CHK(hipMemcpy(d_par, par.data(), par.size() * 8, hipMemcpyHostToDevice));
+  RM_CHK(hipMemsetAsync(c->scal.p, 0, (size_t)S * 16, st));
+  bool any_high = false, any_low = false;
+  for (int s = 0; s < S; ++s)
+    if (!dead[s]) (po->lchol[s] ? any_high : any_low) = true;
+  RmScratch<T> z;
+  for (int s0 = 0; s0 < S; s0 += chunk) {
+    const int cnt = std::min(chunk, S - s0);
+    ScratchCarver::carve(z, c->ks.p, cnt, npn, kq, kp);
+    const double* parc = d_par + (size_t)s0 * BA_STRIDE;
+    const T* Ao = po->A.as<T>() + (size_t)s0 * sMo;
+    const T* Wo = po->W.as<T>() + (size_t)s0 * sMo;
+    const double* alo = po->alpha.as<double>() + (size_t)s0 * ldo;
+    T* An = nA.as<T>() + (size_t)s0 * sMn;
+    T* Wn = nW.as<T>() + (size_t)s0 * sMn;
+    double* aln = nal.as<double>() + (size_t)s0 * npn;
+    // 1. compaction and the carriers
+    hipLaunchKernelGGL((rm_compact_kernel<T>), dim3(npn / 64, npn / 4, cnt), dim3(64, 4), 0, st, Ao, Wo, sMo, ldo, An, Wn,
+                       sMn, npn, n, d_rmap, parc);
+    hipLaunchKernelGGL((rm_carrier_kernel<T>), dim3((unsigned)((sV + 255) / 256), cnt), dim3(256), 0, st, Ao, Wo, sMo, ldo,
+                       n, kk, kq, npn, d_rmap, d_idx, parc, z.V, z.C);
+    hipLaunchKernelGGL(rm_alpha_gather_kernel, dim3((npn + 255) / 256, cnt), dim3(256), 0, st, alo, ldo, aln, npn, n,
+                       d_rmap);
+    RM_CHK(hipGetLastError());
+    // 2. high noise: the sweep, two launches per panel, stream-ordered
+    RM_CHK(mark());
+    if (any_high) {
+      for (int a = a0; a < n; a += RM_P) {
+        hipLaunchKernelGGL((rm_panel_kernel<T>), dim3(cnt), dim3(256), 0, st, An, sMn, npn, a, z.V, sV, kq, z.Th, parc);
+        const int nLb = std::max(0, (n - (a + RM_P) + 63) / 64), nWb = (n + 63) / 64;
+        hipLaunchKernelGGL((rm_apply_kernel<T>), dim3(nLb + nWb, cnt), dim3(256), 0, st, An, Wn, sMn, npn, n, a, z.V, z.C,
+                           sV, npn, kq, (const double*)z.Th, nLb, parc);
+      }
+      RM_CHK(hipGetLastError());
+    }
+    RM_CHK(mark());
+    // 3. low noise: Q_II through the blocked factorization (no jitter), the correction while compacting
+    if (any_low) {
+      hipLaunchKernelGGL((rm_qii_kernel<T>), dim3(kp / 64, kp / 4, cnt), dim3(64, 4), 0, st, Ao, sMo, ldo, kk, kq, kp,
+                         d_idx, parc, alo, ldo, z.fA, z.aI);
+      RM_CHK(hipGetLastError());
+      Factor<T> F;
+      F.st = st;
+      F.batch = cnt;
+      F.npad = kp;
+      F.A = z.fA;
+      F.W = z.fW;
+      F.Tm = z.fT;
+      F.sA = F.sW = F.sT = (long long)kp * kp;
+      F.logdet = d_logdet + s0;
+      F.info = d_info + s0;
+      F.nvalid = kk;
+      F.potrf_inv(0, kp, true, true);
+      RM_CHK(F.err);
+      RM_CHK(hipGetLastError());
+      const int* infoc = d_info + s0;
+      hipLaunchKernelGGL((ba_small_vec_kernel<T>), dim3(cnt), dim3(256), 0, st, (const T*)z.fW, kp, kk, kq,
+                         (const double*)z.aI, z.tv, z.zv);
+      hipLaunchKernelGGL(rm_alpha_low_kernel, dim3((n + 255) / 256, cnt), dim3(256), 0, st, aln, npn, n, kk, kq,
+                         (const double*)z.V, (const double*)z.zv, parc, infoc);
+      hipLaunchKernelGGL((ba_panel_w22_kernel<T>), dim3((unsigned)(((long long)n * kk + 255) / 256), cnt), dim3(256), 0, st,
+                         (const double*)z.V, z.H, sV, n, kk, kq, (const T*)z.fW, kp, 0, parc);
+      hipLaunchKernelGGL((rm_low_kernel<T>), dim3((n + 63) / 64, (n + 15) / 16, cnt), dim3(64, 4), 0, st, Ao, sMo, ldo, An,
+                         sMn, npn, n, kk, kq, d_rmap, (const double*)z.H, parc, infoc);
+      RM_CHK(hipGetLastError());
+    }
+  }
+  std::vector<int> info(S, 0);
+  RM_CHK(hipMemcpyAsync(info.data(), d_info, (size_t)S * sizeof(int), hipMemcpyDeviceToHost, st));
+  RM_CHK(hipStreamSynchronize(st));
+#undef RM_CHK
+  for (size_t i = 0; i + 1 < evs.size(); i += 2) {
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, evs[i], evs[i + 1]);
+    sweep_ms += ms;
+  }
+  for (hipEvent_t e : evs) (void)hipEventDestroy(e);
+  for (int s = 0; s < S; ++s)
+    if (!po->lchol[s] && info[s] != 0) dead[s] = 1;
+  for (DevBuf* b : {&po->A, &po->W, &po->alpha}) c->pool_give(*b);
+  po->A = nA;
+  po->W = nW;
+  po->alpha = nal;
+  po->npad = npn;
+  po->N = n;
+  return 0;
+}
+
+// the scratch of one sample in the largest sweep of a removal of k rows from N
+template <typename T>
+size_t remove_per_sample(int N, int k) {
+  const int kk = std::min(k, RM_KMAX);
+  return ScratchCarver::count<RmScratch<T>>(1, pad_tile(N - kk), rm_kq(kk), pad_tile(kk));
+}
+
+template <typename T>
+int remove_impl(gpc_post* po, int k, const int* idx, const double* ym, int* ok) {
+  gpc_ctx* c = po->ctx;
+  hipStream_t st = c->st;
+  const int S = po->S, nfin = po->N - k;
+  // every sweep's scratch is bounded by the first one's (the most rows, and k or RM_KMAX removed rows)
+  const size_t per = remove_per_sample<T>(po->N, k);
+  const int np1 = pad_tile(po->N - std::min(k, RM_KMAX));
+  const size_t new_bytes = (size_t)S * np1 * ((size_t)np1 * 2 * sizeof(T) + 8);
+  const size_t held = c->ks.bytes;
+  const int chunk = plan_chunk(c, S, per, 0, held, (size_t)S * per <= held, new_bytes, false, [&](size_t budget) {
+    return "gpc_post_remove: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
+           std::to_string(np1) + ", k = " + std::to_string(k) + ") exceeds the device memory budget (" +
+           std::to_string(budget >> 10) + " KB beside " + std::to_string(new_bytes >> 10) + " KB of compacted storage)";
+  });
+  if (!chunk) return -2;
+  std::vector<double> par((size_t)S * BA_STRIDE, 0.0);
+  std::vector<int> dead(S, 0);
+  for (int s = 0; s < S; ++s) {
+    par[(size_t)s * BA_STRIDE + BA_SL] = po->sp[(size_t)s * SP_STRIDE + SP_SL];
+    par[(size_t)s * BA_STRIDE + BA_LCH] = po->lchol[s] ? 1.0 : 0.0;
+    dead[s] = (po->info[s] != 0 || ((c->remove_fail_mask >> (s & 31)) & 1u)) ? 1 : 0;
+  }
+  // gpc_last_timing: device time of the call, and of the panel loops alone, summed over the chunks and the sweeps
+  c->ms_total = c->ms_factor = 0;
+  CallTimer tm{c, true};
+  double sweep_ms = 0;
+  HIPCHK(c, tm.start());
+  HIPCHK(c, tm.mark1());
+  HIPCHK(c, tm.mark2());
+  std::vector<int> grp(RM_KMAX);
+  for (int j0 = 0; j0 < k; j0 += RM_KMAX) {  // the rows before a group are gone by the time it is removed
+    const int kk = std::min(RM_KMAX, k - j0);
+    for (int j = 0; j < kk; ++j) grp[j] = idx[j0 + j] - j0;
+    if (int rc = remove_sweep<T>(po, kk, grp.data(), chunk, par, dead, tm.on, sweep_ms)) return rc;
+  }
+  po->dev_consts = false;
+  // alpha of the high-noise samples from the new factor: W'^T (W' (y_R - m_R)) / sl
+  const int npad = po->npad;
+  const long long sM = (long long)npad * npad;
+  const size_t vb = (size_t)npad * 8;
+  bool any_high = false;
+  for (int s = 0; s < S; ++s) any_high = any_high || (po->lchol[s] && !dead[s]);
+  if (any_high) {
+    HIPCHK(c, c->rvec.ensure(S * vb));
+    HIPCHK(c, c->zvec.ensure(S * vb));
+    HIPCHK(c, c->avec.ensure(S * vb));
+    HIPCHK(c, c->tpart.ensure((size_t)S * (npad / TRC + 1) * vb));
+    double* r = c->rvec.as<double>();
+    double* lv = c->zvec.as<double>();
+    double* au = c->avec.as<double>();
+    double* tpart = c->tpart.as<double>();
+    HIPCHK(c, hipMemsetAsync(r, 0, S * vb, st));
+    HIPCHK(c, hipMemcpy2DAsync(r, vb, ym, (size_t)nfin * 8, (size_t)nfin * 8, S, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL((trmv_kernel<T>), dim3(npad / 4, S), dim3(256), 0, st, (const T*)po->W.as<T>(), sM, npad,
+                       (const double*)r, npad, lv, 0);
+    hipLaunchKernelGGL((trmv_t_part_kernel<T>), dim3((npad + 64 * MM<T>::VEC - 1) / (64 * MM<T>::VEC), npad / TRC, S),
+                       dim3(256), 0, st, (const T*)po->W.as<T>(), sM, npad, (const double*)lv, npad, tpart, (double*)nullptr);
+    hipLaunchKernelGGL(trmv_t_sum_kernel, dim3(npad / 128, S), dim3(128), 0, st, (const double*)tpart, npad,
+                       (const double*)nullptr, 0, 0, au);
+    hipLaunchKernelGGL(rm_alpha_high_kernel, dim3((npad + 255) / 256, S), dim3(256), 0, st, po->alpha.as<double>(), npad,
+                       nfin, (const double*)au, (const double*)c->dvec.as<double>());
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, tm.stop());
+  HIPCHK(c, hipStreamSynchronize(st));
+  tm.accumulate();
+  c->ms_factor = sweep_ms;
+  for (int s = 0; s < S; ++s) {
+    ok[s] = dead[s] ? 0 : 1;
+    ++(ok[s] ? c->points_removed : c->remove_stale);
+  }
+  return 0;
+}
+
+// gpc_debug_remove_panel / gpc_debug_remove_apply: the two kernels of the sweep alone, on buffers of their own laid out
+// as remove_sweep lays them out (storage in T, carriers and Theta in fp64)
+template <typename T>
+int debug_remove_panel_impl(gpc_ctx* c, int k, const double* D, const double* Vp, double* Theta, double* Dnew) {
+  const int kq = rm_kq(k), mp = RM_P + kq, m = RM_P + k;
+  ScratchDev sd;
+  T* dA = sd.get<T>(RM_P * RM_P);
+  double* dV = sd.get<double>((size_t)RM_P * kq);
+  double* dTh = sd.get<double>((size_t)mp * mp);
+  double* dpar = sd.get<double>(BA_STRIDE);
+  if (!dA || !dV || !dTh || !dpar) FAIL(c, "gpc_debug_remove_panel: out of device memory");
+  std::vector<T> hA(D, D + RM_P * RM_P);
+  std::vector<double> hV((size_t)RM_P * kq, 0.0), hTh((size_t)mp * mp);
+  for (int r = 0; r < RM_P; ++r) std::copy_n(Vp + (size_t)r * k, k, &hV[(size_t)r * kq]);
+  const double par[BA_STRIDE] = {1.0, 0.0, 1.0, 1.0};
+  HIPCHK(c, hipMemcpy(dA, hA.data(), hA.size() * sizeof(T), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dV, hV.data(), hV.size() * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dpar, par, sizeof(par), hipMemcpyHostToDevice));
+  hipLaunchKernelGGL((rm_panel_kernel<T>), dim3(1), dim3(256), 0, c->st, dA, (long long)RM_P * RM_P, RM_P, 0, dV,
+                     (long long)RM_P * kq, kq, dTh, (const double*)dpar);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  HIPCHK(c, hipMemcpy(hTh.data(), dTh, hTh.size() * 8, hipMemcpyDeviceToHost));
+  for (int i = 0; i < m; ++i) std::copy_n(&hTh[(size_t)i * mp], m, Theta + (size_t)i * m);
+  return download_as<T>(c, dA, Dnew, (size_t)RM_P * RM_P);
+}
+
+// which = 0: P = L[a+64 : n, a : a+64] ((n - a - 64) x 64), Cr = V[a+64 : n, :k];  which = 1: P = W[a : a+64, :n]
+// (64 x n; what lies above the diagonal is neither read nor written), Cr = C (k x n)
+template <typename T>
+int debug_remove_apply_impl(gpc_ctx* c, int which, int a, int n, int k, const double* Theta, double* P, double* Cr) {
+  const int kq = rm_kq(k), mp = RM_P + kq, m = RM_P + k, ld = pad_tile(std::max(n, a + RM_P));
+  const size_t msz = (size_t)ld * ld, vsz = (size_t)ld * kq;
+  const int rows = n - a - RM_P;
+  ScratchDev sd;
+  T* dM = sd.get<T>(msz);
+  double* dV = sd.get<double>(vsz);
+  double* dTh = sd.get<double>((size_t)mp * mp);
+  double* dpar = sd.get<double>(BA_STRIDE);
+  if (!dM || !dV || !dTh || !dpar) FAIL(c, "gpc_debug_remove_apply: out of device memory");
+  std::vector<T> hM(msz, (T)0);
+  std::vector<double> hV(vsz, 0.0), hTh((size_t)mp * mp, 0.0);
+  for (int i = 0; i < mp; ++i) hTh[(size_t)i * mp + i] = 1.0;
+  for (int i = 0; i < m; ++i) std::copy_n(Theta + (size_t)i * m, m, &hTh[(size_t)i * mp]);
+  if (which == 0) {
+    for (int r = 0; r < rows; ++r) {
+      for (int q = 0; q < RM_P; ++q) hM[(size_t)(a + RM_P + r) * ld + a + q] = (T)P[(size_t)r * RM_P + q];
+      std::copy_n(Cr + (size_t)r * k, k, &hV[(size_t)(a + RM_P + r) * kq]);
+    }
+  } else {
+    for (int q = 0; q < RM_P; ++q)
+      for (int l = 0; l < n; ++l) hM[(size_t)(a + q) * ld + l] = (T)P[(size_t)q * n + l];
+    for (int j = 0; j < k; ++j) std::copy_n(Cr + (size_t)j * n, n, &hV[(size_t)j * ld]);
+  }
+  const double par[BA_STRIDE] = {1.0, 0.0, 1.0, 1.0};
+  HIPCHK(c, hipMemcpy(dM, hM.data(), msz * sizeof(T), hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dV, hV.data(), vsz * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dTh, hTh.data(), hTh.size() * 8, hipMemcpyHostToDevice));
+  HIPCHK(c, hipMemcpy(dpar, par, sizeof(par), hipMemcpyHostToDevice));
+  const int nLb = which == 0 ? (rows + 63) / 64 : 0, nWb = which == 0 ? 0 : (n + 63) / 64;
+  hipLaunchKernelGGL((rm_apply_kernel<T>), dim3(nLb + nWb, 1), dim3(256), 0, c->st, dM, dM, (long long)msz, ld, n, a, dV, dV,
+                     (long long)vsz, ld, kq, (const double*)dTh, nLb, (const double*)dpar);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  std::vector<double> oM(msz);
+  if (int rc = download_as<T>(c, dM, oM.data(), msz)) return rc;
+  HIPCHK(c, hipMemcpy(hV.data(), dV, vsz * 8, hipMemcpyDeviceToHost));
+  if (which == 0) {
+    for (int r = 0; r < rows; ++r) {
+      for (int q = 0; q < RM_P; ++q) P[(size_t)r * RM_P + q] = oM[(size_t)(a + RM_P + r) * ld + a + q];
+      std::copy_n(&hV[(size_t)(a + RM_P + r) * kq], k, Cr + (size_t)r * k);
+    }
+  } else {
+    for (int q = 0; q < RM_P; ++q)
+      for (int l = 0; l < n; ++l) P[(size_t)q * n + l] = oM[(size_t)(a + q) * ld + l];
+    for (int j = 0; j < k; ++j) std::copy_n(&hV[(size_t)j * ld], n, Cr + (size_t)j * n);
+  }
+  return 0;
+}
 }  // namespace
 
 
@@ -7046,6 +7379,42 @@ int gpc_post_append_block_K(gpc_post* po, int k, const double* Ks, const double*
                               : append_block_impl<float>(po, k, m_star, sn2_star, y_new, ok, Ks, Kss);
 }
 
+int gpc_post_remove(gpc_post* po, int k, const int* idx, const double* ym, int* ok) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!idx || !ym || !ok) FAIL(c, "gpc_post_remove: null argument");
+  if (k < 1 || k >= po->N)
+    FAIL(c, "gpc_post_remove: k = " + std::to_string(k) + " must be at least 1 and less than N = " + std::to_string(po->N));
+  for (int j = 0; j < k; ++j)
+    if (idx[j] < 0 || idx[j] >= po->N || (j > 0 && idx[j] <= idx[j - 1]))
+      FAIL(c, "gpc_post_remove: the indices must be sorted, distinct and in [0, N)");
+  if (c->N != po->N - k || c->D != po->D)
+    FAIL(c, "gpc_post_remove: call gpc_set_data with the reduced X, y (N - k rows) first");
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? remove_impl<double>(po, k, idx, ym, ok) : remove_impl<float>(po, k, idx, ym, ok);
+}
+
+int gpc_debug_remove_panel(gpc_ctx* c, int dtype, int k, const double* D, const double* Vp, double* Theta, double* Dnew) {
+  if (!c) return -2;
+  if (!D || !Vp || !Theta || !Dnew) FAIL(c, "gpc_debug_remove_panel: null argument");
+  if (k < 1 || k > RM_KMAX) FAIL(c, "gpc_debug_remove_panel: k must be in 1 .. 64");
+  HIPCHK(c, hipSetDevice(c->device));
+  return dtype == GPC_F64 ? debug_remove_panel_impl<double>(c, k, D, Vp, Theta, Dnew)
+                          : debug_remove_panel_impl<float>(c, k, D, Vp, Theta, Dnew);
+}
+
+int gpc_debug_remove_apply(gpc_ctx* c, int dtype, int which, int a, int n, int k, const double* Theta, double* P,
+                           double* Cr) {
+  if (!c) return -2;
+  if (!Theta || !P || !Cr) FAIL(c, "gpc_debug_remove_apply: null argument");
+  if (k < 1 || k > RM_KMAX || a < 0 || a % RM_P || (which != 0 && which != 1) || n > 4096 ||
+      (which == 0 ? n <= a + RM_P : n <= a))
+    FAIL(c, "gpc_debug_remove_apply: bad shape (k in 1 .. 64, a a multiple of 64, n beyond the panel and at most 4096)");
+  HIPCHK(c, hipSetDevice(c->device));
+  return dtype == GPC_F64 ? debug_remove_apply_impl<double>(c, which, a, n, k, Theta, P, Cr)
+                          : debug_remove_apply_impl<float>(c, which, a, n, k, Theta, P, Cr);
+}
+
 int gpc_post_recompute_K(gpc_post* po, int cnt, const int* idx, const double* K, const double* m, const double* sn2,
                          int sn2_is_vector, double* sn2_mult, int* L_chol, int* info) {
   if (!po) return -2;
@@ -7549,6 +7918,14 @@ const Option OPTIONS[] = {
     {"cv_engine_ran", GPC_GET(c->cv_engine_ran), nullptr},
     {"block_appended", GPC_COUNTER(block_appended)},  // samples gpc_post_append_block appended ...
     {"block_stale", GPC_COUNTER(block_stale)},        // ... and left stale for gpc_post_recompute
+    {"remove_fail_mask", nullptr, GPC_SET(c->remove_fail_mask = (unsigned)v)},  // test hook: samples gpc_post_remove leaves stale
+    {"remove_force", GPC_GET(c->remove_force), GPC_SET(c->remove_force = v != 0)},  // test hook: lifts the limit below
+    // the longest sweep (in panels) that GP.remove_points gives to gpc_post_remove (remove.h: RM_SWEEP_MAX_PANELS)
+    {"remove_max_panels", GPC_GET(c->remove_force ? (1 << 30) : RM_SWEEP_MAX_PANELS), nullptr},
+    // ... and the number of kept rows it has to exceed (remove.h: RM_MIN_KEPT_ROWS)
+    {"remove_min_rows", GPC_GET(c->remove_force ? 0 : RM_MIN_KEPT_ROWS), nullptr},
+    {"removed", GPC_COUNTER(points_removed)},         // samples gpc_post_remove shrank ...
+    {"remove_stale", GPC_COUNTER(remove_stale)},      // ... and left stale for gpc_post_recompute[_K]
     {"last_chunk", GPC_GET(c->last_chunk), nullptr},  // samples per chunk that the last posterior consumer planned (plan_chunk; 0: it refused)
     {"experiments", GPC_GET(IS_EXPERIMENTS_BUILD), nullptr},  // 1: this library is the experiments build (tests/ and tools/ ask before they use its options)
 };

@@ -25,6 +25,7 @@ import scipy.optimize
 from numpy.linalg import LinAlgError  # scipy.linalg.LinAlgError is this class
 
 from . import _lib
+from . import _remove as _rm
 from . import priors as _pr
 from . import sharding as _sh
 from .f_min_fill import f_min_fill
@@ -1425,6 +1426,89 @@ class GP:
             m = full[i, 0]
             p.sn2_mult = int(m) if m < 2**62 else m
             p.L_chol = bool(full[i, 1])
+            p._alpha = p._sW = p._L = None  # cached host copies are stale; refetched lazily
+            p._have = {"alpha": False, "sW": False, "L": False}
+
+    def remove_points(self, idx, recompute: bool = False):
+        """Drop training rows: ``idx`` is an integer array (negative values count from the end) or a boolean mask over
+        the rows of ``X``; the rows leave ``X``, ``y`` and ``s2`` and every posterior is brought to the reduced data.
+
+        With resident posteriors, scalar noise, no ``s2`` and no process group the rows are taken out of every
+        resident posterior on the device in O(S N^2 k) (``gpc_post_remove``, the inverse of the block append: a blocked
+        orthogonal sweep over the factor and its inverse for high-noise samples, from the 64-column panel that holds
+        the first removed row on, and a rank-k correction of -inv for low-noise ones; no covariance is evaluated, so a
+        user-defined covariance object takes the same path).  A sample whose k x k block is not positive definite is
+        recomputed alone, and the posterior handle stays the same object.  The result agrees with the recompute to
+        rounding (1e-8 relative in fp64), not to the bit.  Anything else -- and ``recompute=True`` -- is the full
+        recompute on the reduced data, silently, as ``update``'s fallbacks are; so is a removal that would sweep more
+        than one panel or that leaves at most 128 rows, because the device path as it stands LOSES to the recompute
+        there.  Measured on an MI355X (``profiles/remove_points_cfg3.json``, wall time, device path / recompute): taking
+        back the LAST rows (what a kriging-believer batch does with its fantasy observations) costs 2.4 / 14.2 ms at
+        N = 4096, S = 16 for k = 1 .. 64 and 0.42 / 0.74 ms at N = 400, S = 8 (k = 5); dropping the FIRST rows would cost
+        19.1 / 14.5 ms (k <= 16) to 78.0 / 13.4 ms (k = 128), and at N = 100 even the last rows cost 0.33 / 0.18 ms: both
+        are therefore recomputed."""
+        if self.X is None or self.y is None:
+            raise ValueError("GP has no training data")
+        idx = _rm.check_indices(idx, self.X.shape[0])
+        keep = np.setdiff1d(np.arange(self.X.shape[0]), idx)
+        self._restore()  # (a copied GP: the fast path shrinks RESIDENT posteriors)
+        fast = (not recompute and self.s2 is None and self.posteriors is not None and self._post_handle is not None
+                and self._post_range is None and _sh.active_group(self.process_group) is None)
+        if fast:
+            cov_N, noise_N, _ = self._counts()
+            h0 = self.posteriors[0].hyp
+            fast = bool(np.isscalar(self.noise.compute(h0[cov_N:cov_N + noise_N], self.X[keep], self.y[keep], 0)))
+        fast = fast and self._remove_pays(idx)
+        had_posteriors = self.posteriors is not None and any(p is not None and p.L_chol is not None for p in self.posteriors)
+        self.X, self.y = self.X[keep].copy(), self.y[keep].copy()
+        if self.s2 is not None:
+            self.s2 = self.s2[keep].copy()
+        if fast:
+            self._remove_resident(idx)
+            return
+        if self.posteriors is None:
+            return
+        hyp = self.get_hyperparameters(as_array=True)
+        s_N = hyp.shape[0]
+        self._drop_handle()
+        self.posteriors = np.empty((s_N,), dtype=Posterior)
+        if had_posteriors:
+            self._compute_posteriors(hyp)
+        else:  # (records without posteriors, as update(compute_posterior=False) leaves them)
+            for i in range(s_N):
+                self.posteriors[i] = Posterior(hyp[i, :], None, None, None, None, None)
+
+    def _remove_pays(self, idx):
+        """Is this removal inside the limits within which the device path was measured to beat the full recompute
+        (remove.h: a sweep of at most RM_SWEEP_MAX_PANELS panels, more than RM_MIN_KEPT_ROWS rows kept)?"""
+        ctx = _lib.context(self.device)
+        N = self.X.shape[0]
+        return (N - idx.size > ctx.get_option("remove_min_rows")
+                and _rm.swept_panels(N, idx) <= ctx.get_option("remove_max_panels"))
+
+    @_on_device
+    def _remove_resident(self, idx):
+        """The fast path of ``remove_points`` (X, y hold the kept rows already): shrink on the device, recompute alone
+        the samples it left stale, refresh the records the way ``_append_points`` does."""
+        counts = self._counts()
+        cov_N = counts[0]
+        posts = list(self.posteriors)
+        hyp = np.stack([p.hyp for p in posts])
+        ym = np.ravel(self.y)[None, :] - np.reshape(self._plugin_values(hyp, False)["m"], (len(posts), -1))
+        self._ctx()  # uploads the reduced X, y
+        h = self._post_handle
+        ok = h.remove(idx, ym)
+        redo = np.flatnonzero(~ok)
+        if redo.size:  # stale for these posteriors only: full update of exactly those
+            pv = self._plugin_values(hyp[redo], False)
+            K = None if self._builtin else self._user_cov(hyp[redo, :cov_N], False)[0]
+            mult, lchol, info = h.recompute(redo, hyp[redo, :cov_N], pv["m"], pv["sn2"], pv["vec"], K=K)
+            if np.any(info != 0):
+                raise LinAlgError("Singular matrix for L Cholesky decomposition")
+            for j, i in enumerate(redo):
+                posts[i].sn2_mult = int(mult[j]) if mult[j] < 2**62 else mult[j]
+                posts[i].L_chol = bool(lchol[j])
+        for p in posts:
             p._alpha = p._sW = p._L = None  # cached host copies are stale; refetched lazily
             p._have = {"alpha": False, "sW": False, "L": False}
 

@@ -435,6 +435,41 @@ int gpc_post_append_block(gpc_post* post, int k, const double* m_star, const dou
 int gpc_post_append_block_K(gpc_post* post, int k, const double* Ks, const double* Kss, const double* m_star,
                             const double* sn2_star, const double* y_new, int* ok);
 
+/* ---- removal of k >= 1 training points from resident posteriors in O(N^2 k) (GP.remove_points; scalar noise).
+ *      The inverse of the block append; the reference has no such path (it recomputes).  No covariance is evaluated:
+ *      posteriors of either origin (device kernel, caller-provided K) take the same call.
+ * Call gpc_set_data with the reduced X, y (N-k rows) first.
+ *   idx[j]        the removed rows, numbered in the posterior's N rows: sorted, distinct, in [0, N)
+ *   ym[s*n + i]   y_R - m_s(X_R), the centred observations of the n = N-k kept rows, per sample
+ * With I = idx, R = the kept rows in order:
+ *   high-noise samples (L_chol; A = Lo, W = Lo^-1):  Lr = Lo[R, R], Wr = W[R, R], V = Lo[R, I], C = W[I, R];  the new
+ *     factor has L' L'^T = Lr Lr^T + V V^T (a rank-k UPDATE: always positive definite).  For every 64-column panel
+ *     [a, b) from the one that holds the first removed row on, an orthogonal Theta of order 64 + k with
+ *     [Lr[a:b, a:b] | V[a:b, :]] Theta = [D' | 0] is formed by Householder reflections in fp64 (positive diagonal) and
+ *     applied with fp64 MFMA:  [Lr[b:, a:b] | V[b:, :]] <- [...] Theta,  [Wr[a:b, :b] ; C] <- Theta^T [...].  Rows
+ *     above the first removed one keep their bits; removing the LAST rows only truncates.  alpha = W'^T (W' ym) / sl
+ *     from the new factor, never from the old alpha: repeated removals do not drift away from the factor.
+ *   low-noise samples (A = -(K + Sigma)^-1 = -Q, full symmetric):  Q_II = Lq Lq^T through the library's blocked
+ *     factorization WITHOUT jitter, H = A[R, I] Lq^-T:  A' = A[R, R] + H H^T,  alpha' = alpha_R + A[R, I] Q_II^-1 alpha_I.
+ * Up to 64 rows leave in one sweep; a larger k goes in consecutive sweeps of at most 64.  The storage of EVERY sample is
+ * compacted to the padded size of N-k (it shrinks by whole 128-tiles when that allows: the layout of a fresh
+ * posterior), the old buffers go to the context's pool.  ok[s] = 1 if sample s was shrunk; ok[s] = 0 (a low-noise
+ * sample whose Q_II is not positive definite, a sample whose own factorization had failed, or one named by the test
+ * option "remove_fail_mask") leaves a stale sample in the compacted storage: the caller recomputes exactly those with
+ * gpc_post_recompute[_K].  Scratch (three fp64 N_pad x k panels, Theta and the k x k factorization per sample) lives
+ * in the context's cross-covariance buffer, is budgeted like gpc_post_append_block's (GPC_MEM_BUDGET_MB) and chunked
+ * over the samples; the bits of a sample depend neither on the batch nor on the chunk.  No host synchronisation
+ * between the panels of a sweep.  gpc_last_timing: the device section, and the panel loops alone (summed over chunks and sweeps).
+ * Returns -2 with a message, the posterior untouched, for k < 1, k >= N, indices that are unsorted, repeated or out
+ * of range, data that was not reduced first, null arguments, or one sample's scratch exceeding the budget.
+ * The get-only options "removed" / "remove_stale" count the samples that ended either way over the life of the
+ * context.  The get-only options "remove_max_panels" (the longest sweep, in panels summed over the sweeps) and
+ * "remove_min_rows" (the number of kept rows that has to be exceeded) bound the shapes for which the call was measured
+ * to beat the full recompute (remove.h: RM_SWEEP_MAX_PANELS, RM_MIN_KEPT_ROWS, with the measurement): the entry point
+ * itself does whatever it is given, GP.remove_points recomputes outside the limits; the test option "remove_force" = 1
+ * makes both options report no limit.                                                                     */
+int gpc_post_remove(gpc_post* post, int k, const int* idx, const double* ym, int* ok);
+
 /* ---- GP.predict_full (gaussian_process.py:1603-1650) -------------------------------------
  * fmu[j*S + s] = Ks^T alpha;  cov[s] (M x M, row-major) = K** - V^T V  or  K** + Ks^T (L Ks)
  * (the caller symmetrises and adds noise, :1647-1659).                                    */
@@ -714,6 +749,22 @@ int gpc_debug_cov(gpc_ctx* ctx, int which, int kernel_id, int degree, int dtype,
  * that is not finite over the rows of the launch: those kernels read W's diagonal tiles unmasked (blas1.h).             */
 int gpc_debug_blas1(gpc_ctx* ctx, int which, int dtype, const int* ip, const double* const* in, const long long* in_n,
                     double* const* out, const long long* out_n);
+
+/* The panel kernel of gpc_post_remove alone on one 64 x 64 block (remove.h: rm_panel_kernel), launched as the sweep
+ * launches it: D (64 x 64, row major; the lower triangle is read, cast to `dtype`), Vp (64 x k, fp64), 1 <= k <= 64.
+ * Theta ((64 + k) x (64 + k), row major): the orthogonal matrix with [D | Vp] Theta = [Dnew | 0];  Dnew (64 x 64): the
+ * block as stored afterwards (lower triangular with a positive diagonal; the upper triangle is D's, untouched).    */
+int gpc_debug_remove_panel(gpc_ctx* ctx, int dtype, int k, const double* D, const double* Vp, double* Theta,
+                           double* Dnew);
+
+/* The apply kernel of gpc_post_remove alone (remove.h: rm_apply_kernel) on a given Theta ((64 + k)^2, row major) for
+ * the panel [a, a + 64) of a matrix of n rows (a a multiple of 64), storage in `dtype`, carriers fp64, in place:
+ *   which = 0, the L side:  P = L[a+64 : n, a : a+64] ((n - a - 64) x 64),  Cr = V[a+64 : n, :] ((n - a - 64) x k):
+ *                           [P | Cr] <- [P | Cr] Theta                                              (n > a + 64)
+ *   which = 1, the W side:  P = W[a : a+64, :n] (64 x n; rows a + p >= n and entries above the diagonal are neither
+ *                           read nor written),  Cr = C (k x n):   [P ; Cr] <- Theta^T [P ; Cr]      (n > a)     */
+int gpc_debug_remove_apply(gpc_ctx* ctx, int dtype, int which, int a, int n, int k, const double* Theta, double* P,
+                           double* Cr);
 
 /* gpc_grad_post's block Gram kernel on caller-provided panels Y, Z: n rows x (Dp planes of M queries), row major
  * ([i][a][j]), stored in `dtype` and padded to the pipeline's plane width.  Z = NULL: Z = Y.  out[j][a][b] = out[j][b][a]
