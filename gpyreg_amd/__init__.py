@@ -13,10 +13,11 @@ from . import (
     mean_functions,
     noise_functions,
 )
-from .gaussian_process import GP, Posterior, PosteriorPaths
+from .gaussian_process import GP, GradientConditionedPosterior, Posterior, PosteriorPaths
 
 __all__ = [
     "GP",
+    "GradientConditionedPosterior",
     "Posterior",
     "PosteriorPaths",
     "covariance_functions",

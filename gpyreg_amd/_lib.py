@@ -64,6 +64,14 @@ SIGNATURES = {
     "gpc_posterior_batch_K": (
         C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, C.POINTER(_vp), _dp, _ip, _ip]),
     "gpc_predict_K": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "gpc_set_data_gobs": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, C.c_int]),
+    "gpc_posterior_batch_gobs": (
+        C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(_vp), _dp, _dp, _ip, _ip]),
+    "gpc_nll_batch_gobs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "gpc_predict_gobs": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
+    "gpc_debug_gobs_cov": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp]),
+    "gpc_debug_gobs_cross": (
+        C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
     "gpc_post_fetch": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "gpc_post_free": (C.c_int, [_vp]),
     "gpc_predict": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
@@ -258,6 +266,7 @@ class Context:
         self.device = int(device)
         self.data_token = None
         self.N = self.D = 0
+        self.gobs = None  # (N, Ng) while gradient observations are resident (set_data_gobs)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -287,7 +296,78 @@ class Context:
             raise ValueError(f"X has {N} points and y has {y.size}: every input needs its observation")
         self._check(self._lib.gpc_set_data(self._h, _ptr(X), _ptr(y), N, D), "gpc_set_data")
         self.N, self.D = N, D
+        self.gobs = None
         self.data_token = token
+
+    @_serial
+    def set_data_gobs(self, X, y, Xg, dy, token=None):
+        """gpc_set_data_gobs: values y (N,) at X (N, D) and gradients dy (Ng, D) at Xg (Ng, D).  The context's problem
+        order becomes the joint order n = N + Ng D (``self.N``); ``self.gobs`` = (N, Ng)."""
+        X, y, Xg, dy = _f64(X), _f64(y).ravel(), _f64(Xg), _f64(dy)
+        N, D = X.shape
+        Ng = Xg.shape[0]
+        if y.size != N or Xg.shape != (Ng, D) or dy.shape != (Ng, D):
+            raise ValueError(f"X is {X.shape}, y has {y.size} values, Xg is {Xg.shape} and dy {dy.shape}: y needs N values, "
+                             "Xg and dy (Ng, D)")
+        self._check(self._lib.gpc_set_data_gobs(self._h, _ptr(X), _ptr(y), N, D, _ptr(Xg), _ptr(dy), Ng),
+                    "gpc_set_data_gobs")
+        self.N, self.D = N + Ng * D, D
+        self.gobs = (N, Ng)
+        self.data_token = token
+
+    def _gobs_args(self, hyp_cov, m, sn2):
+        hyp_cov, m, sn2 = _f64(hyp_cov), _f64(m), _f64(sn2)
+        S = hyp_cov.shape[0]
+        if m.shape != (S, self.N) or sn2.shape != (S, self.N):
+            raise ValueError(f"m and sn2 must be (S, n) = ({S}, {self.N}) in joint order")
+        return hyp_cov, m, sn2, S, np.empty(S), np.empty(S), np.empty(S, dtype=np.int32), np.empty(S, dtype=np.int32)
+
+    @_serial
+    def posterior_batch_gobs(self, kid, degree, dtype, hyp_cov, m, sn2):
+        """gpc_posterior_batch_gobs on the data of ``set_data_gobs``: (handle, nlz, mult, lchol, info)."""
+        hyp_cov, m, sn2, S, nlz, mult, lchol, info = self._gobs_args(hyp_cov, m, sn2)
+        h = _vp()
+        rc = self._lib.gpc_posterior_batch_gobs(self._h, kid, degree, dtype, S, _ptr(hyp_cov), _ptr(m), _ptr(sn2),
+                                                C.byref(h), _ptr(nlz), _ptr(mult), lchol.ctypes.data, info.ctypes.data)
+        self._check(rc, "gpc_posterior_batch_gobs")
+        return PostHandle(self, h, S, self.N), nlz, mult, lchol.astype(bool), info
+
+    @_serial
+    def nll_batch_gobs(self, kid, degree, dtype, hyp_cov, m, sn2):
+        """gpc_nll_batch_gobs: (nlz, mult, lchol, info) for the rows of hyp_cov."""
+        hyp_cov, m, sn2, S, nlz, mult, lchol, info = self._gobs_args(hyp_cov, m, sn2)
+        rc = self._lib.gpc_nll_batch_gobs(self._h, kid, degree, dtype, S, _ptr(hyp_cov), _ptr(m), _ptr(sn2), _ptr(nlz),
+                                          _ptr(mult), lchol.ctypes.data, info.ctypes.data)
+        self._check(rc, "gpc_nll_batch_gobs")
+        return nlz, mult, lchol.astype(bool), info
+
+    @_serial
+    def debug_gobs_cov(self, kid, degree, hyp_cov, X, Xg):
+        """gpc_debug_gobs_cov: the n x n joint covariance of one hyperparameter row, as gobs_cov_kernel writes it."""
+        hyp_cov, X, Xg = _f64(hyp_cov).ravel(), _f64(X), _f64(Xg)
+        (N, D), Ng = X.shape, Xg.shape[0]
+        out = np.empty((N + Ng * D, N + Ng * D))
+        rc = self._lib.gpc_debug_gobs_cov(self._h, kid, degree, _ptr(hyp_cov), _ptr(X), N, D, _ptr(Xg), Ng, _ptr(out))
+        self._check(rc, "gpc_debug_gobs_cov")
+        return out
+
+    @_serial
+    def debug_gobs_cross(self, kid, degree, hyp_cov, X, Xg, x_star, alpha=None):
+        """gpc_debug_gobs_cross: (operand (n, M), the whole padded panel it is a corner of, fused column sums (M,) |
+        None without alpha), as gobs_cross_tile_kernel writes them."""
+        hyp_cov, X, Xg, xs = _f64(hyp_cov).ravel(), _f64(X), _f64(Xg), _f64(x_star)
+        (N, D), Ng, M = X.shape, Xg.shape[0], xs.shape[0]
+        n = N + Ng * D
+        npad, mpad = -(-n // 128) * 128, -(-M // 128) * 128
+        al = None if alpha is None else _f64(alpha).ravel()
+        if al is not None and al.size != n:
+            raise ValueError(f"alpha must hold n = {n} values in joint order")
+        panel = np.empty((npad, mpad))
+        col = None if al is None else np.empty(mpad)
+        rc = self._lib.gpc_debug_gobs_cross(self._h, kid, degree, _ptr(hyp_cov), _ptr(X), N, D, _ptr(Xg), Ng, _ptr(xs), M,
+                                            _ptr(al), _ptr(panel), _ptr(col))
+        self._check(rc, "gpc_debug_gobs_cross")
+        return panel[:n, :M].copy(), panel, (None if col is None else col[:M].copy())
 
     # ---- covariance.compute ---------------------------------------------------
     @_serial
@@ -822,6 +902,17 @@ class PostHandle:
         fs2 = np.empty((M, self.S))
         rc = self.ctx._lib.gpc_predict(self._h, _ptr(xs), M, _ptr(fmu), _ptr(fs2))
         self.ctx._check(rc, "gpc_predict")
+        return fmu, fs2
+
+    @_serial
+    def predict_gobs(self, x_star):
+        """gpc_predict_gobs: fmu, fs2 (M, S) of a gradient-observation posterior (``Context.posterior_batch_gobs``)."""
+        xs = _f64(x_star)
+        M = xs.shape[0]
+        fmu = np.empty((M, self.S))
+        fs2 = np.empty((M, self.S))
+        rc = self.ctx._lib.gpc_predict_gobs(self._h, _ptr(xs), M, _ptr(fmu), _ptr(fs2))
+        self.ctx._check(rc, "gpc_predict_gobs")
         return fmu, fs2
 
     @_serial

@@ -27,6 +27,7 @@
 #include "cvgrad.h"
 #include "draw.h"
 #include "gemm.h"
+#include "gradobs.h"
 #include "gradpost.h"
 #include "hess.h"
 #include "hypgrad.h"
@@ -497,6 +498,7 @@ struct gpc_ctx {
   unsigned long long small_polled = 0, small_synced = 0;  // statistics ("small_polled" / "small_synced")
   int last_chunk = 0;  // what plan_chunk last returned ("last_chunk")
   unsigned long long grad_post_gram_us = 0;  // Gram passes of the last gpc_grad_post, device microseconds ("grad_post_gram_us")
+  unsigned long long gobs_cov_us = 0, gobs_cross_us = 0;  // the kernel of the last gpc_debug_gobs_cov / the build of the last gpc_debug_gobs_cross, device microseconds
   unsigned long long hess_contract_us = 0;  // contraction passes of the last gpc_predict_hess, device microseconds ("hess_contract_us")
   unsigned long long nll_hess_gram_us = 0, nll_hess_contract_us = 0;  // Gram pass / second-derivative contraction of the last gpc_nll_hess, device microseconds
   unsigned long long cv_grad_trace_us = 0;  // contraction pass of the last gpc_cv_grad, device microseconds ("cv_grad_trace_us")
@@ -515,6 +517,10 @@ struct gpc_ctx {
   int N = 0, D = 0, npad = 0;
   DevBuf dX;  // N x D
   DevBuf dY;  // N (gpc_nll_batch_cm forms r = y - m0 on the device)
+  // gradient observations (gpc_set_data_gobs; gradobs.h): gobs.Ng > 0 says that N above is the JOINT order N + Ng D and
+  // hy / dY the joint target; dX is not used then -- the raw point list (gobs.P() x D) is gpts, gxs its scaled copies
+  GobsDims gobs;
+  DevBuf gpts, gxs;
   std::vector<double> hy;
   // workspace
   DevBuf mA, mW, mT;             // matrices of the current chunk
@@ -648,6 +654,10 @@ struct gpc_post {
   // kernel less per call); any change of sp / mul / dv / N clears the flag.
   DevBuf dsp, dmul, ddv, dxs;
   bool dev_consts = false;
+  // A gradient-observation posterior (gpc_posterior_batch_gobs): gobs.Ng > 0, N is the joint order, and the handle owns
+  // the raw point list its predictions are built from (gradobs.h; dxs then holds the scaled LISTS, gobs.P() rows each)
+  GobsDims gobs;
+  DevBuf gpts;
 };
 
 // Pathwise posterior samples (paths.h): everything an evaluation needs, copied at creation -- the handle describes the
@@ -953,7 +963,10 @@ struct Pipe {
   gpc_dk_plane_fn dk_cb = nullptr;
   void* dk_user = nullptr;
   std::vector<int> orig;  // index of each sample in the caller's numbering (for the callback)
-  bool kmode() const { return !Kptr.empty(); }
+  // gradient observations (gobs.Ng > 0): the K-mode pipeline with the staging buffer filled by gobs_cov_kernel from the
+  // context's point list instead of an upload (b.N is the joint order, b.hyp_cov the kernel's hyperparameters)
+  GobsDims gobs;
+  bool kmode() const { return !Kptr.empty() || gobs.Ng > 0; }
 
   int P() const { return B->cd.cov_N + 1; }
 
@@ -1006,9 +1019,20 @@ struct Pipe {
       // A = K / (sn2_div * sn2_mult) + diag from the caller's matrix, one sample at a time through one
       // N x N staging buffer (stream order keeps the upload of sample i+1 behind the kernel reading i)
       HIPCHK(c, c->dbg1.ensure((size_t)N * N * sizeof(double)));
+      const size_t gper = (size_t)gobs.P() * D;
+      if (gobs.Ng > 0) {
+        HIPCHK(c, c->gxs.ensure((size_t)chunk_cnt * gper * sizeof(double)));
+        launch_gobs_scale(st, gobs, c->gpts.as<double>(), c->mulb.as<double>() + (size_t)off * D,
+                          c->divb.as<double>() + (size_t)off * D, n, c->gxs.as<double>() + (size_t)off * gper);
+      }
       for (int i = 0; i < n; ++i) {
-        HIPCHK(c, hipMemcpyAsync(c->dbg1.p, Kptr[chunk_s0 + off + i], (size_t)N * N * sizeof(double),
-                                 hipMemcpyHostToDevice, st));
+        if (gobs.Ng > 0)
+          launch_gobs_cov(st, b.cd, gobs, c->gxs.as<double>() + (size_t)(off + i) * gper, spb + (size_t)i * SP_STRIDE,
+                          c->mulb.as<double>() + (size_t)(off + i) * D, c->divb.as<double>() + (size_t)(off + i) * D,
+                          c->dbg1.as<double>());
+        else
+          HIPCHK(c, hipMemcpyAsync(c->dbg1.p, Kptr[chunk_s0 + off + i], (size_t)N * N * sizeof(double),
+                                   hipMemcpyHostToDevice, st));
         dim3 gl(npad / 64, npad / 4), bl(64, 4);
         hipLaunchKernelGGL((load_K_kernel<T>), gl, bl, 0, st, (const double*)c->dbg1.p, N, npad,
                            (const double*)(spb + (size_t)i * SP_STRIDE),
@@ -2110,7 +2134,8 @@ struct Pipe {
       q.mean_N = mean_N;
       q.dsn2 = gn ? gds.data() : dsn2;
       q.noise_N = noise_N;
-      if (kmode()) {
+      q.gobs = gobs;
+      if (!Kptr.empty()) {
         q.dk_cb = dk_cb;
         q.dk_user = dk_user;
         for (int i = 0; i < nf; ++i) {
@@ -2183,6 +2208,14 @@ int plan_chunk(gpc_ctx* c, int S, size_t per, size_t shared, size_t held, bool f
 inline int require_factorized(const gpc_post* po, const char* fn) {
   for (int s = 0; s < po->S; ++s)
     if (po->info[s] != 0) FAIL(po->ctx, std::string(fn) + ": posterior contains a failed factorization");
+  return 0;
+}
+
+// Posteriors over values AND gradients have joint rows no other consumer knows how to build operands for
+inline int refuse_gobs(const gpc_post* po, const char* fn) {
+  if (po->gobs.Ng > 0)
+    FAIL(po->ctx, std::string(fn) + ": this posterior was conditioned on gradient observations (gpc_posterior_batch_gobs); "
+                  "only gpc_predict_gobs, gpc_post_fetch and gpc_post_free work on it");
   return 0;
 }
 
@@ -2266,15 +2299,18 @@ inline void scatter_plane(double* out, const double* plane, size_t n, size_t ss,
 }
 
 // caller-provided covariance matrices (K-mode): S matrices of N x N doubles, and the dK plane callback
+// (K == nullptr with gobs.Ng > 0: the matrices are built on the device from gradient observations, gradobs.h)
 struct KArgs {
   const double* K = nullptr;
   gpc_dk_plane_fn cb = nullptr;
   void* user = nullptr;
+  GobsDims gobs;
 };
 template <typename PipeT>
 void set_kmode(PipeT& p, const KArgs* km, int S, int N) {
   if (!km) return;
-  for (int s = 0; s < S; ++s) p.Kptr.push_back(km->K + (size_t)s * N * N);
+  p.gobs = km->gobs;
+  for (int s = 0; km->K && s < S; ++s) p.Kptr.push_back(km->K + (size_t)s * N * N);
   p.dk_cb = km->cb;
   p.dk_user = km->user;
 }
@@ -2348,9 +2384,13 @@ int nll_impl(gpc_ctx* c, Batch& b, int want_grad, const double* dm, int mean_N, 
   return 0;
 }
 
-int check_batch_args(gpc_ctx* c, int kernel_id, int degree, int dtype, int S) {
+int check_batch_args(gpc_ctx* c, int kernel_id, int degree, int dtype, int S, bool gobs = false) {
   if (!c) return -2;
   if (c->N <= 0) FAIL(c, "gpc_set_data has not been called");
+  if (gobs != (c->gobs.Ng > 0) && kernel_id != -1)
+    FAIL(c, gobs ? "the resident data hold no gradient observations: call gpc_set_data_gobs first"
+                 : "the resident data hold gradient observations (gpc_set_data_gobs): only the _gobs and _K entry points "
+                   "evaluate them; call gpc_set_data for the others");
   if (kernel_id != -1 && !valid_kernel(kernel_id, degree)) FAIL(c, "unknown covariance kernel / degree");
   if (dtype != GPC_F64 && dtype != GPC_F32) FAIL(c, "dtype must be GPC_F64 or GPC_F32");
   if (S <= 0) FAIL(c, "S must be positive");
@@ -2382,7 +2422,7 @@ void fill_batch(gpc_ctx* c, Batch& b, int kernel_id, int degree, int S, const do
 
 template <typename T>
 int post_impl(gpc_ctx* c, Batch& b, gpc_post* po, double* sn2_mult, int* L_chol, int* info,
-              const KArgs* km = nullptr) {
+              const KArgs* km = nullptr, double* nlz = nullptr) {
   const int S = b.S, npad = b.npad;
   const size_t msz = (size_t)npad * npad * sizeof(T);
   HostClock hc("post");
@@ -2471,6 +2511,7 @@ int post_impl(gpc_ctx* c, Batch& b, gpc_post* po, double* sn2_mult, int* L_chol,
   po->sW.resize(S);
   for (int s = 0; s < S; ++s) {
     po->sW[s] = 1.0 / std::sqrt(b.smin[s] * b.mult[s]);  // :2517
+    if (nlz) nlz[s] = 0.5 * p.quad[s] / b.sl[s] + p.logdet[s] + b.N * std::log(2 * M_PI * b.sl[s]) / 2;  // (as nll_impl)
     sn2_mult[s] = b.mult[s];
     L_chol[s] = b.lchol[s];
     info[s] = b.info[s];
@@ -2591,6 +2632,14 @@ int post_consts_resident(gpc_post* po) {
   HIPCHK(c, hipMemcpyAsync(po->dsp.p, po->sp.data(), (size_t)S * SP_STRIDE * 8, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(po->dmul.p, po->mul.data(), (size_t)S * D * 8, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(po->ddv.p, po->dv.data(), (size_t)S * D * 8, hipMemcpyHostToDevice, st));
+  if (po->gobs.Ng > 0) {  // the scaled point lists of a gradient-observation posterior, from its own raw list
+    HIPCHK(c, po->dxs.ensure_private((size_t)S * po->gobs.P() * D * 8));
+    launch_gobs_scale(st, po->gobs, po->gpts.as<double>(), po->dmul.as<double>(), po->ddv.as<double>(), S,
+                      po->dxs.as<double>());
+    HIPCHK(c, hipGetLastError());
+    po->dev_consts = true;
+    return 0;
+  }
   const long long tot = (long long)npad * D;
   hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), S), dim3(256), 0, st, c->dX.as<double>(), N,
                      npad, D, po->dmul.as<double>(), po->ddv.as<double>(), po->dxs.as<double>());
@@ -2660,7 +2709,8 @@ struct RhsRequest {
   enum Rhs {
     CROSS,    // cross covariance of xa (M x D) with the training inputs
     QUAD_Z,   // quadrature vectors z of the Gaussian measures N(xa[j], diag(xb[j]^2)) (gaussian_process.py:1908-1921)
-    GIVEN_KS  // the caller's own Ks_s (xa: S x N x M doubles) and, with `full`, K**_s (xb: S x M x M): K-mode posteriors
+    GIVEN_KS, // the caller's own Ks_s (xa: S x N x M doubles) and, with `full`, K**_s (xb: S x M x M): K-mode posteriors
+    GOBS      // the joint cross operand [k(X, xa) ; dk(X_g, xa)/dx_g] of a gradient-observation posterior (gradobs.h)
   };
   Rhs rhs = CROSS;
   const double* xa = nullptr;
@@ -2806,6 +2856,24 @@ struct RhsCall {
                          c->xss.as<double>(), c->xss.as<double>(), k.spb, M, mpad, M, mpad, c->kss.as<T>(), sKss);
     hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
                        (const double*)c->dbg2.as<double>(), npad / CT, mpad, d_mu());
+    return 0;
+  }
+  // the joint cross operand of a gradient-observation posterior with the mean product fused in (gradobs.h:
+  // gobs_cross_tile_kernel), from the posterior's own point list
+  int build_gobs(int s0, int cnt) {
+    const GobsDims& gd = po->gobs;
+    const long long tot = (long long)mpad * D;
+    hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, st,
+                       (const double*)d_xa, M, mpad, D, k.mulb, k.divb, c->xss.as<double>());
+    const double* xp = k.xsb;  // (all samples in one chunk: the posterior's resident scaled lists)
+    if (!k.resident) {
+      HIPCHK(c, c->gxs.ensure((size_t)cnt * gd.P() * D * 8));
+      launch_gobs_scale(st, gd, po->gpts.as<double>(), k.mulb, k.divb, cnt, c->gxs.as<double>());
+      xp = c->gxs.as<double>();
+    }
+    HIPCHK(c, c->dbg2.ensure((size_t)cnt * (gd.P() / CT) * mpad * 8));
+    HIPCHK(c, launch_gobs_cross<T>(st, po->cd, gd, xp, c->xss.as<double>(), k.spb, k.mulb, k.divb, alpha(s0), npad, npad, M,
+                                   mpad, cnt, Ks(), sKs, c->dbg2.as<double>(), d_mu()));
     return 0;
   }
   // caller-provided cross covariances Ks_s (N x M doubles, xa) and, with `full`, K**_s (M x M, xb)
@@ -2998,6 +3066,7 @@ struct RhsCall {
     if (int rc = k.stage(s0, cnt, r.rhs == RhsRequest::CROSS)) return rc;
     if (int rc = r.rhs == RhsRequest::CROSS      ? build_cross(s0, cnt)
                  : r.rhs == RhsRequest::GIVEN_KS ? build_given(s0, cnt)
+                 : r.rhs == RhsRequest::GOBS     ? build_gobs(s0, cnt)
                                                  : build_quad_z(s0, cnt))
       return rc;
     HIPCHK(c, hipGetLastError());
@@ -3049,10 +3118,11 @@ RhsRequest quad_request(const double* mu, const double* sigma, int M, bool want_
 
 template <typename T>
 int predict_impl(gpc_post* po, const double* xstar, int M, double* fmu, double* fs2, double* dfmu = nullptr,
-                 double* dfs2 = nullptr) {
+                 double* dfs2 = nullptr, RhsRequest::Rhs rhs = RhsRequest::CROSS) {
   // (with dfmu: the gradients come back complete -- kss is constant for stationary kernels, and the 1/sl of the
   // L_chol samples is applied to Q on the device)
   RhsRequest r;
+  r.rhs = rhs;
   r.xa = xstar;
   r.M = M;
   r.want_quad = true;
@@ -6938,7 +7008,7 @@ void gpc_destroy(gpc_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
   (void)hipStreamSynchronize(c->st);
-  DevBuf* bufs[] = {&c->dX,   &c->dY,  &c->mA,    &c->mW,  &c->mT,   &c->xs,   &c->spb,  &c->mulb, &c->divb,
+  DevBuf* bufs[] = {&c->dX,   &c->dY,  &c->gpts,  &c->gxs, &c->mA,    &c->mW,  &c->mT,   &c->xs,   &c->spb,  &c->mulb, &c->divb,
                     &c->dvec, &c->rvec,  &c->zvec, &c->avec, &c->scal, &c->parts, &c->gout, &c->diagq,
                     &c->dmb,  &c->dsn2b, &c->mg,  &c->ng,   &c->ks,   &c->vb,   &c->xss,  &c->pout, &c->kss,
                     &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->qmix, &c->nhs, &c->hgs, &c->lab, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
@@ -7013,6 +7083,7 @@ int gpc_set_data(gpc_ctx* c, const double* X, const double* y, int N, int D) {
   c->N = N;
   c->D = D;
   c->npad = pad_tile(N);
+  c->gobs = GobsDims();
   return 0;
 }
 
@@ -7193,6 +7264,7 @@ int gpc_predict_K(gpc_post* po, int M, const double* Ks, const double* Kss, doub
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!Ks || !fmu || M <= 0 || (!fq && !cov) || (cov && !Kss)) FAIL(c, "gpc_predict_K: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (int rc = require_factorized(po, "gpc_predict_K")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   RhsRequest r;
@@ -7213,6 +7285,225 @@ int gpc_predict_K(gpc_post* po, int M, const double* Ks, const double* Kss, doub
       q = po->lchol[s] ? -q / sl : q;
     }
   }
+  return 0;
+}
+
+// ---- gradient observations (gradobs.h): the K-mode pipeline with the joint matrix built on the device ----
+namespace {
+int gobs_kernel_check(gpc_ctx* c, int kernel_id, int degree, const char* fn) {
+  if (kernel_id < 0 || !valid_kernel(kernel_id, degree))
+    FAIL(c, std::string(fn) + ": unknown covariance kernel / degree (gradient observations need a built-in kernel)");
+  if ((kernel_id == K_MATERN || kernel_id == K_MATERN_ISO) && degree == 1)
+    FAIL(c, std::string(fn) + ": the Matern kernel of degree 1 has no mean-square derivative (the prior variance of its "
+                              "gradient is infinite)");
+  return 0;
+}
+int gobs_dims_check(gpc_ctx* c, const GobsDims& gd, const char* fn) {
+  if (gd.N <= 0 || gd.Ng <= 0 || gd.D <= 0) FAIL(c, std::string(fn) + ": N, Ng and D must be positive");
+  if (gd.n() > (1 << 20)) FAIL(c, std::string(fn) + ": the joint order N + Ng D is beyond 2^20");
+  return 0;
+}
+// the raw point list of gradobs.h: X in rows [0, N), X_g from row pad64(N) on, zero rows elsewhere
+void gobs_point_list(const GobsDims& gd, const double* X, const double* Xg, std::vector<double>& pts) {
+  pts.assign((size_t)gd.P() * gd.D, 0.0);
+  std::copy_n(X, (size_t)gd.N * gd.D, pts.begin());
+  std::copy_n(Xg, (size_t)gd.Ng * gd.D, pts.begin() + (size_t)gd.Np() * gd.D);
+}
+}  // namespace
+
+int gpc_set_data_gobs(gpc_ctx* c, const double* X, const double* y, int N, int D, const double* Xg, const double* dy,
+                      int Ng) {
+  if (!c) return -2;
+  if (!X || !y || !Xg || !dy) FAIL(c, "gpc_set_data_gobs: null argument");
+  GobsDims gd;
+  gd.N = N, gd.Ng = Ng, gd.D = D;
+  if (int rc = gobs_dims_check(c, gd, "gpc_set_data_gobs")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const int n = (int)gd.n();
+  std::vector<double> pts, t((size_t)n);
+  gobs_point_list(gd, X, Xg, pts);
+  std::copy_n(y, N, t.begin());
+  for (int g = 0; g < Ng; ++g)
+    for (int l = 0; l < D; ++l) t[(size_t)N + (size_t)l * Ng + g] = dy[(size_t)g * D + l];  // dimension-major joint rows
+  HIPCHK(c, c->gpts.ensure(pts.size() * sizeof(double)));
+  HIPCHK(c, c->dY.ensure((size_t)n * sizeof(double)));
+  HIPCHK(c, hipMemcpyAsync(c->gpts.p, pts.data(), pts.size() * sizeof(double), hipMemcpyHostToDevice, c->st));
+  HIPCHK(c, hipMemcpyAsync(c->dY.p, t.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->st));
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  c->hy = t;
+  c->N = n;
+  c->D = D;
+  c->npad = pad_tile(n);
+  c->gobs = gd;
+  return 0;
+}
+
+int gpc_posterior_batch_gobs(gpc_ctx* c, int kernel_id, int degree, int dtype, int S, const double* hyp_cov,
+                             const double* m, const double* sn2, gpc_post** post, double* nlz, double* sn2_mult,
+                             int* L_chol, int* info) {
+  if (!c) return -2;
+  if (int rc = gobs_kernel_check(c, kernel_id, degree, "gpc_posterior_batch_gobs")) return rc;
+  if (int rc = check_batch_args(c, kernel_id, degree, dtype, S, true)) return rc;
+  if (!hyp_cov || !m || !sn2 || !post || !sn2_mult || !L_chol || !info) FAIL(c, "gpc_posterior_batch_gobs: null argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  Batch b;
+  fill_batch(c, b, kernel_id, degree, S, hyp_cov, m, sn2, 1);
+  gpc_post* po = new gpc_post();
+  po->ctx = c;
+  po->dtype = dtype;
+  po->S = S;
+  po->N = c->N;
+  po->D = c->D;
+  po->npad = c->npad;
+  po->cd = b.cd;
+  po->gobs = c->gobs;
+  KArgs km;
+  km.gobs = c->gobs;
+  const size_t pb = (size_t)c->gobs.P() * c->D * sizeof(double);
+  hipError_t e = po->gpts.ensure_private(pb);
+  if (e == hipSuccess) e = hipMemcpyAsync(po->gpts.p, c->gpts.p, pb, hipMemcpyDeviceToDevice, c->st);
+  int rc = 0;
+  if (e != hipSuccess) {
+    c->err = std::string("gpc_posterior_batch_gobs: ") + hipGetErrorString(e);
+    rc = -1;
+  } else {
+    rc = (dtype == GPC_F64) ? post_impl<double>(c, b, po, sn2_mult, L_chol, info, &km, nlz)
+                            : post_impl<float>(c, b, po, sn2_mult, L_chol, info, &km, nlz);
+  }
+  if (rc) {
+    c->pool_give(po->A);
+    c->pool_give(po->W);
+    c->pool_give(po->alpha);
+    po->gpts.release();
+    delete po;
+    return rc;
+  }
+  *post = po;
+  return 0;
+}
+
+int gpc_nll_batch_gobs(gpc_ctx* c, int kernel_id, int degree, int dtype, int S, const double* hyp_cov, const double* m,
+                       const double* sn2, double* nlz, double* sn2_mult, int* L_chol, int* info) {
+  if (!c) return -2;
+  if (int rc = gobs_kernel_check(c, kernel_id, degree, "gpc_nll_batch_gobs")) return rc;
+  if (int rc = check_batch_args(c, kernel_id, degree, dtype, S, true)) return rc;
+  if (!hyp_cov || !m || !sn2 || !nlz || !sn2_mult || !L_chol || !info) FAIL(c, "gpc_nll_batch_gobs: null argument");
+  HIPCHK(c, hipSetDevice(c->device));
+  Batch b;
+  fill_batch(c, b, kernel_id, degree, S, hyp_cov, m, sn2, 1);
+  KArgs km;
+  km.gobs = c->gobs;
+  if (dtype == GPC_F64) return nll_impl<double>(c, b, 0, nullptr, 0, nullptr, 0, nlz, nullptr, sn2_mult, L_chol, info, &km);
+  return nll_impl<float>(c, b, 0, nullptr, 0, nullptr, 0, nlz, nullptr, sn2_mult, L_chol, info, &km);
+}
+
+int gpc_predict_gobs(gpc_post* po, const double* xstar, int M, double* fmu, double* fs2) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!xstar || !fmu || !fs2 || M <= 0) FAIL(c, "gpc_predict_gobs: bad arguments");
+  if (po->gobs.Ng <= 0)
+    FAIL(c, "gpc_predict_gobs: this posterior holds no gradient observations (gpc_posterior_batch_gobs builds those); use "
+            "gpc_predict");
+  if (int rc = require_factorized(po, "gpc_predict_gobs")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? predict_impl<double>(po, xstar, M, fmu, fs2, nullptr, nullptr, RhsRequest::GOBS)
+                              : predict_impl<float>(po, xstar, M, fmu, fs2, nullptr, nullptr, RhsRequest::GOBS);
+}
+
+namespace {
+// what both debug hooks start from: one sample's raw and scaled point list, scaling and scalars in dbg2
+struct GobsDebug {
+  GobsDims gd;
+  CovDesc cd{};
+  double *pts = nullptr, *xs = nullptr, *mul = nullptr, *dv = nullptr, *sp = nullptr, *rest = nullptr;
+};
+int gobs_debug_begin(gpc_ctx* c, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                     const double* Xg, int Ng, size_t extra_doubles, GobsDebug& g, const char* fn) {
+  if (int rc = gobs_kernel_check(c, kernel_id, degree, fn)) return rc;
+  if (!hyp_cov || !X || !Xg) FAIL(c, std::string(fn) + ": null argument");
+  g.gd.N = N, g.gd.Ng = Ng, g.gd.D = D;
+  if (int rc = gobs_dims_check(c, g.gd, fn)) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  g.cd = CovDesc{kernel_id, degree, D, cov_count_of(kernel_id, D)};
+  const size_t pd = (size_t)g.gd.P() * D;
+  std::vector<double> h(2 * (size_t)D + SP_STRIDE, 0.0);
+  scaling_of(kernel_id, degree, D, hyp_cov, &h[0], &h[D], &h[2 * D + SP_SF2], &h[2 * D + SP_RQA]);
+  h[2 * D + SP_KSCALE] = h[2 * D + SP_SL] = 1.0;
+  std::vector<double> pts;
+  gobs_point_list(g.gd, X, Xg, pts);
+  HIPCHK(c, c->dbg2.ensure((2 * pd + h.size() + extra_doubles) * 8));
+  g.pts = c->dbg2.as<double>();
+  g.xs = g.pts + pd;
+  g.mul = g.xs + pd;
+  g.dv = g.mul + D;
+  g.sp = g.dv + D;
+  g.rest = g.sp + SP_STRIDE;
+  HIPCHK(c, hipMemcpyAsync(g.pts, pts.data(), pd * 8, hipMemcpyHostToDevice, c->st));
+  HIPCHK(c, hipMemcpyAsync(g.mul, h.data(), h.size() * 8, hipMemcpyHostToDevice, c->st));
+  HIPCHK(c, hipStreamSynchronize(c->st));  // (the host vectors go out of scope)
+  launch_gobs_scale(c->st, g.gd, g.pts, g.mul, g.dv, 1, g.xs);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+}  // namespace
+
+int gpc_debug_gobs_cov(gpc_ctx* c, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                       const double* Xg, int Ng, double* out) {
+  if (!c) return -2;
+  if (!out) FAIL(c, "gpc_debug_gobs_cov: null argument");
+  GobsDebug g;
+  if (int rc = gobs_debug_begin(c, kernel_id, degree, hyp_cov, X, N, D, Xg, Ng, 0, g, "gpc_debug_gobs_cov")) return rc;
+  const size_t nn = (size_t)g.gd.n() * (size_t)g.gd.n();
+  HIPCHK(c, c->dbg1.ensure(nn * 8));
+  HIPCHK(c, hipMemsetAsync(c->dbg1.p, 0xFF, nn * 8, c->st));  // (NaN: an entry no block wrote shows)
+  GramClock clk(true);
+  HIPCHK(c, clk.record(0, c->st));
+  launch_gobs_cov(c->st, g.cd, g.gd, g.xs, g.sp, g.mul, g.dv, c->dbg1.as<double>());
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, clk.record(1, c->st));
+  HIPCHK(c, hipMemcpyAsync(out, c->dbg1.p, nn * 8, hipMemcpyDeviceToHost, c->st));
+  HIPCHK(c, hipStreamSynchronize(c->st));
+  c->gobs_cov_us = (unsigned long long)clk.elapsed_us();
+  return 0;
+}
+
+int gpc_debug_gobs_cross(gpc_ctx* c, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                         const double* Xg, int Ng, const double* xstar, int M, const double* alpha, double* out,
+                         double* colsum) {
+  if (!c) return -2;
+  if (!xstar || !out || M <= 0) FAIL(c, "gpc_debug_gobs_cross: bad arguments");
+  const int mpad = pad_tile(M);
+  GobsDims gd;
+  gd.N = N, gd.Ng = Ng, gd.D = D;
+  if (int rc = gobs_dims_check(c, gd, "gpc_debug_gobs_cross")) return rc;
+  const int n = (int)gd.n(), npad = pad_tile(n), pt = gd.P() / CT;
+  // after the common part: raw queries M x D | scaled queries mpad x D | alpha npad | partials pt x mpad | sums mpad
+  const size_t extra = (size_t)M * D + (size_t)mpad * D + npad + (size_t)pt * mpad + mpad;
+  GobsDebug g;
+  if (int rc = gobs_debug_begin(c, kernel_id, degree, hyp_cov, X, N, D, Xg, Ng, extra, g, "gpc_debug_gobs_cross")) return rc;
+  double* d_xq = g.rest;
+  double* d_xss = d_xq + (size_t)M * D;
+  double* d_alpha = d_xss + (size_t)mpad * D;
+  double* d_part = d_alpha + npad;
+  double* d_mu = d_part + (size_t)pt * mpad;
+  hipStream_t st = c->st;
+  HIPCHK(c, hipMemcpyAsync(d_xq, xstar, (size_t)M * D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(d_alpha, 0, (size_t)npad * 8, st));
+  if (alpha) HIPCHK(c, hipMemcpyAsync(d_alpha, alpha, (size_t)n * 8, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mpad * D + 255) / 256), 1), dim3(256), 0, st,
+                     (const double*)d_xq, M, mpad, D, (const double*)g.mul, (const double*)g.dv, d_xss);
+  const size_t pb = (size_t)npad * mpad * 8;
+  HIPCHK(c, c->dbg1.ensure(pb));
+  HIPCHK(c, hipMemsetAsync(c->dbg1.p, 0xFF, pb, st));  // (NaN: padding the kernel left unwritten shows)
+  GramClock clk(true);
+  HIPCHK(c, clk.record(0, st));
+  HIPCHK(c, launch_gobs_cross<double>(st, g.cd, g.gd, g.xs, d_xss, g.sp, g.mul, g.dv, d_alpha, npad, npad, M, mpad, 1,
+                                      c->dbg1.as<double>(), (long long)npad * mpad, d_part, d_mu));
+  HIPCHK(c, clk.record(1, st));
+  HIPCHK(c, hipMemcpyAsync(out, c->dbg1.p, pb, hipMemcpyDeviceToHost, st));
+  if (colsum) HIPCHK(c, hipMemcpyAsync(colsum, d_mu, (size_t)mpad * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  c->gobs_cross_us = (unsigned long long)clk.elapsed_us();
   return 0;
 }
 
@@ -7257,6 +7548,7 @@ int gpc_post_free(gpc_post* po) {
   po->dmul.release();
   po->ddv.release();
   po->dxs.release();
+  po->gpts.release();
   delete po;
   return 0;
 }
@@ -7265,6 +7557,7 @@ int gpc_post_append(gpc_post* po, const double* m_star, const double* sn2_star, 
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!m_star || !sn2_star || !ok) FAIL(c, "gpc_post_append: null argument");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0) FAIL(c, "gpc_post_append: not available for posteriors built from caller-provided K");
   HIPCHK(c, hipSetDevice(c->device));
   return po->dtype == GPC_F64 ? append_impl<double>(po, m_star, sn2_star, y_new, ok)
@@ -7276,6 +7569,7 @@ int gpc_post_append_K(gpc_post* po, const double* Ks, const double* kss, const d
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!Ks || !kss || !m_star || !sn2_star || !ok) FAIL(c, "gpc_post_append_K: null argument");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind >= 0) FAIL(c, "gpc_post_append_K: this posterior was built from a device kernel; use gpc_post_append");
   HIPCHK(c, hipSetDevice(c->device));
   return po->dtype == GPC_F64 ? append_impl<double>(po, m_star, sn2_star, y_new, ok, Ks, kss)
@@ -7349,6 +7643,7 @@ int gpc_post_recompute(gpc_post* po, int cnt, const int* idx, const double* hyp_
   gpc_ctx* c = po->ctx;
   if (cnt <= 0 || !idx || !hyp_cov || !m || !sn2 || !sn2_mult || !L_chol || !info)
     FAIL(c, "gpc_post_recompute: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0) FAIL(c, "gpc_post_recompute: this posterior was built from caller-provided K; use gpc_post_recompute_K");
   return recompute_impl(po, cnt, idx, hyp_cov, nullptr, m, sn2, sn2_is_vector, sn2_mult, L_chol, info);
 }
@@ -7358,6 +7653,7 @@ int gpc_post_append_block(gpc_post* po, int k, const double* m_star, const doubl
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!m_star || !sn2_star || !y_new || !ok) FAIL(c, "gpc_post_append_block: null argument");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_post_append_block: not available for posteriors built from caller-provided K; use gpc_post_append_block_K");
   if (int rc = append_block_check(po, k, "gpc_post_append_block")) return rc;
@@ -7371,6 +7667,7 @@ int gpc_post_append_block_K(gpc_post* po, int k, const double* Ks, const double*
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!Ks || !Kss || !m_star || !sn2_star || !y_new || !ok) FAIL(c, "gpc_post_append_block_K: null argument");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind >= 0)
     FAIL(c, "gpc_post_append_block_K: this posterior was built from a device kernel; use gpc_post_append_block");
   if (int rc = append_block_check(po, k, "gpc_post_append_block_K")) return rc;
@@ -7383,6 +7680,7 @@ int gpc_post_remove(gpc_post* po, int k, const int* idx, const double* ym, int* 
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!idx || !ym || !ok) FAIL(c, "gpc_post_remove: null argument");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (k < 1 || k >= po->N)
     FAIL(c, "gpc_post_remove: k = " + std::to_string(k) + " must be at least 1 and less than N = " + std::to_string(po->N));
   for (int j = 0; j < k; ++j)
@@ -7421,6 +7719,7 @@ int gpc_post_recompute_K(gpc_post* po, int cnt, const int* idx, const double* K,
   gpc_ctx* c = po->ctx;
   if (cnt <= 0 || !idx || !K || !m || !sn2 || !sn2_mult || !L_chol || !info)
     FAIL(c, "gpc_post_recompute_K: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind >= 0) FAIL(c, "gpc_post_recompute_K: this posterior was built from a device kernel; use gpc_post_recompute");
   return recompute_impl(po, cnt, idx, nullptr, K, m, sn2, sn2_is_vector, sn2_mult, L_chol, info);
 }
@@ -7429,6 +7728,7 @@ int gpc_predict(gpc_post* po, const double* xstar, int M, double* fmu, double* f
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!xstar || !fmu || !fs2 || M <= 0) FAIL(c, "gpc_predict: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0) FAIL(c, "gpc_predict: this posterior was built from caller-provided K; use gpc_predict_K");
   if (int rc = require_factorized(po, "gpc_predict")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -7440,6 +7740,7 @@ int gpc_predict_grad(gpc_post* po, const double* xstar, int M, double* fmu, doub
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!xstar || !fmu || !fs2 || !dfmu || !dfs2 || M <= 0) FAIL(c, "gpc_predict_grad: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_predict_grad: this posterior was built from caller-provided K; a caller-provided kernel has no "
             "derivative with respect to x*");
@@ -7453,6 +7754,7 @@ int gpc_grad_post(gpc_post* po, const double* xstar, int M, int diag_only, doubl
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!xstar || !fmu || !dfmu || !cov || M <= 0) FAIL(c, "gpc_grad_post: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_grad_post: this posterior was built from caller-provided K; a caller-provided kernel has no "
             "derivative with respect to x*");
@@ -7472,6 +7774,7 @@ int gpc_predict_hess(gpc_post* po, const double* xstar, int M, int compute_var, 
   const bool var = compute_var != 0;
   if (!xstar || !fmu || !dfmu || !hmu || (var && (!fs2 || !dfs2 || !hs2)) || M <= 0)
     FAIL(c, "gpc_predict_hess: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_predict_hess: this posterior was built from caller-provided K; a caller-provided kernel has no "
             "derivative with respect to x*");
@@ -7491,6 +7794,7 @@ int gpc_nll_hess(gpc_post* po, const double* dm, int mean_N, const double* dsn2,
       (noise_N > 0 && dsn2_rows != 1 && dsn2_rows != po->N))
     FAIL(c, "gpc_nll_hess: bad arguments (H, dnlz, alpha, diagq are required; dm with mean_N > 0; dsn2 with noise_N > 0 "
             "and dsn2_rows 1 or N)");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_nll_hess: this posterior was built from caller-provided K; a caller-provided kernel has no second "
             "derivative with respect to its hyperparameters");
@@ -7518,6 +7822,7 @@ int gpc_cv_grad(gpc_post* po, int loss, const double* weights, double* gsum, dou
   if (weights)
     for (int i = 0; i < po->N; ++i)
       if (!(weights[i] >= 0.0) || !std::isfinite(weights[i])) FAIL(c, "gpc_cv_grad: the weights must be finite and >= 0");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_cv_grad: this posterior was built from caller-provided K; a caller-provided kernel has no derivative "
             "with respect to its hyperparameters");
@@ -7539,6 +7844,7 @@ int gpc_predict_hyp_grad(gpc_post* po, const double* xstar, int M, int compute_v
       (noise_N > 0 && !dsn2) || (mean_N > 0 && !dm) || (noise_rows != 1 && noise_rows != po->N))
     FAIL(c, "gpc_predict_hyp_grad: bad arguments (xstar, sn2, fmu, dfmu are required, fs2 and dfs2 with compute_var; dsn2 "
             "with noise_N > 0; dm with mean_N > 0; noise_rows 1 or N)");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_predict_hyp_grad: this posterior was built from caller-provided K; a caller-provided kernel has no "
             "derivative with respect to its hyperparameters");
@@ -7557,6 +7863,7 @@ int gpc_draw(gpc_post* po, const double* xstar, int M, int R, unsigned long long
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!xstar || !f || !tau || M <= 0 || R <= 0 || s_offset < 0) FAIL(c, "gpc_draw: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0) FAIL(c, "gpc_draw: this posterior was built from caller-provided K; there is no K** to draw from");
   if (int rc = require_factorized(po, "gpc_draw")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -7593,6 +7900,7 @@ int gpc_paths_create(gpc_post* po, int R, int F, unsigned long long seed, int s_
   if (!ym || !noise_sd || !out) FAIL(c, "gpc_paths_create: null argument (ym, noise_sd and out are required)");
   if (R < 1 || F < 1) FAIL(c, "gpc_paths_create: R and F must be at least 1 (R = " + std::to_string(R) + ", F = " + std::to_string(F) + ")");
   if (R > (1 << 16) || F > (1 << 22) || s_offset < 0) FAIL(c, "gpc_paths_create: bad arguments (R <= 65536, F <= 4194304, s_offset >= 0)");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_paths_create: this posterior was built from caller-provided K; a caller-provided kernel has no "
             "spectral density to draw features from");
@@ -7668,6 +7976,7 @@ int gpc_predict_full(gpc_post* po, const double* xstar, int M, double* fmu, doub
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!xstar || !fmu || !cov || M <= 0) FAIL(c, "gpc_predict_full: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0) FAIL(c, "gpc_predict_full: this posterior was built from caller-provided K; use gpc_predict_K");
   if (int rc = require_factorized(po, "gpc_predict_full")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -7684,6 +7993,7 @@ int gpc_predict_cov(gpc_post* po, const double* xa, int Ma, const double* xb, in
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!xa || !xb || Ma <= 0 || Mb <= 0 || (!cov && !wsq) || (wsq && !w)) FAIL(c, "gpc_predict_cov: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_predict_cov: this posterior was built from caller-provided K; there is no k(xa, xb) to start from");
   if (int rc = require_factorized(po, "gpc_predict_cov")) return rc;
@@ -7699,6 +8009,7 @@ int gpc_lookahead_batch(gpc_post* po, const double* xr, int Mr, const double* xc
   if (!xr || !xc || !w || !noise || !idx || !gain || Mr <= 0 || Mc <= 0 || q < 1 || q > Mc)
     FAIL(c, "gpc_lookahead_batch: bad arguments (Mr = " + std::to_string(Mr) + ", Mc = " + std::to_string(Mc) +
                 ", q = " + std::to_string(q) + "; 1 <= q <= Mc, no null pointers)");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_lookahead_batch: this posterior was built from caller-provided K; there is no k(xa, xb) to start from");
   if (int rc = require_factorized(po, "gpc_lookahead_batch")) return rc;
@@ -7725,6 +8036,7 @@ int gpc_quad(gpc_post* po, const double* mu, const double* sigma, int M, int com
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!mu || !sigma || !zalpha || M <= 0 || (compute_var && !zKz)) FAIL(c, "gpc_quad: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
     FAIL(c, "Bayesian quadrature only supports the squared exponential kernel.");
   HIPCHK(c, hipSetDevice(c->device));
@@ -7741,6 +8053,7 @@ int gpc_quad_grad(gpc_post* po, const double* mu, const double* sigma, int M, in
   if (!mu || !sigma || !zalpha || M <= 0 || (compute_var && !zKz) || !dza_dmu || !dza_dsigma ||
       (compute_var && (!dzkz_dmu || !dzkz_dsigma)))
     FAIL(c, "gpc_quad_grad: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
     FAIL(c, "Bayesian quadrature only supports the squared exponential kernel.");
   if (int rc = require_factorized(po, "gpc_quad_grad")) return rc;
@@ -7758,6 +8071,7 @@ int gpc_quad_cov(gpc_post* po, const double* mu, const double* sigma, int M, dou
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
   if (!mu || !sigma || !zalpha || !cov || M <= 0) FAIL(c, "gpc_quad_cov: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_quad_cov: this posterior was built from caller-provided K; it has no kernel to integrate");
   if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
@@ -7778,6 +8092,7 @@ int gpc_quad_mix(gpc_post* po, const double* mu, const double* sigma, const doub
   if (!mu || !sigma || !w || !zalpha || M <= 0 || (var && (!zbkzb || !gw || !zq)) || (grad && (!dza_dmu || !dza_dsigma)) ||
       (var && grad && (!dzq_dmu || !dzq_dsigma || !dgw_dmu || !dgw_dsigma)))
     FAIL(c, "gpc_quad_mix: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (po->cd.kind < 0)
     FAIL(c, "gpc_quad_mix: this posterior was built from caller-provided K; it has no kernel to integrate");
   if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
@@ -7799,6 +8114,7 @@ int gpc_cv(gpc_post* po, int F, const int* fold_ptr, const int* fold_idx, double
   const int N = po->N, S = po->S;
   if (!dmu || !s2 || F < 0 || (F > 0 && (!fold_ptr || !fold_idx)) || (F == 0 && (fold_ptr || fold_idx)))
     FAIL(c, "gpc_cv: bad arguments");
+  if (int rc = refuse_gobs(po, __func__)) return rc;
   if (N < 2) FAIL(c, "gpc_cv: cross-validation needs at least two training points");
   if (F > 65535) FAIL(c, "gpc_cv: at most 65535 folds per call, got " + std::to_string(F));
   bool singletons = true;
@@ -7900,6 +8216,8 @@ const Option OPTIONS[] = {
     {"nll_hess_gram_us", GPC_COUNTER(nll_hess_gram_us)},  // device time of the Gram pass (kernel + reduction) of the last gpc_nll_hess (timed calls only)
     {"nll_hess_contract_us", GPC_COUNTER(nll_hess_contract_us)},  // ... of its second-derivative contraction (ARD families; 0 for the isotropic ones)
     {"cv_grad_trace_us", GPC_COUNTER(cv_grad_trace_us)},  // device time of the contraction pass (kernel + reduction) of the last gpc_cv_grad (timed calls only)
+    {"gobs_cov_us", GPC_COUNTER(gobs_cov_us)},      // device time of the kernel of the last gpc_debug_gobs_cov
+    {"gobs_cross_us", GPC_COUNTER(gobs_cross_us)},  // device time of the build (operand + mean product) of the last gpc_debug_gobs_cross
     {"grad_post_gram_us", GPC_COUNTER(grad_post_gram_us)},  // device time of the Gram passes of the last gpc_grad_post (timed calls only)
     {"lookahead_batch_loop_us", GPC_COUNTER(lookahead_batch_loop_us)},  // device time of the step loop (all q steps, without the formation of C^0) of the last gpc_lookahead_batch
     {"cov_fused", GPC_COUNTER(cov_fused)},       // gpc_predict_cov calls reduced in the product's epilogue

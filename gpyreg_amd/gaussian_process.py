@@ -310,6 +310,80 @@ _DTYPES = {"f64": _lib.F64, "fp64": _lib.F64, "float64": _lib.F64,
            "f32": _lib.F32, "fp32": _lib.F32, "float32": _lib.F32}
 
 
+class GradientConditionedPosterior:
+    """``GP.condition_on_gradients``' result: for every hyperparameter sample of the GP, the posterior given its data
+    (X, y, s2) AND the gradient observations (X_g, dy, s2_grad) (``_gradobs`` has the formulas).  The object owns the
+    device factors of the joint system of order n = N + Ng D and a copy of the points: it describes the GP as it was
+    when it was made and stays valid after the GP changes.  ``nlZ`` (S,) is the joint negative log marginal likelihood
+    (the number ``GP.nll_batch_grad_obs`` returns for the same hyperparameters), ``sn2_mult`` (S,) and ``L_chol`` (S,)
+    the jitter multiplier and the branch of each sample's joint factorization, ``alpha`` a list of (values (N,),
+    gradients (Ng, D)) pairs in the user's order.  ``close()`` (or leaving a ``with`` block, or garbage collection)
+    frees the device memory."""
+
+    def __init__(self, handle, mean, noise, counts, hyps, dims, nlZ, sn2_mult, L_chol):
+        self._handle, self._mean, self._noise, self._counts, self._hyps = handle, mean, noise, counts, hyps
+        self._N, self._Ng, self.D = dims
+        self.nlZ, self.sn2_mult, self.L_chol = nlZ, sn2_mult, L_chol
+        self._alpha = None
+
+    def _live(self):
+        if self._handle is None:
+            raise ValueError("this GradientConditionedPosterior has been closed")
+        return self._handle
+
+    @property
+    def alpha(self):
+        from . import _gradobs
+
+        if self._alpha is None:
+            h = self._live()
+            self._alpha = [_gradobs.from_joint(h.fetch(s, sW=False, L=False)[0], self._N, self._Ng, self.D)
+                           for s in range(len(self._hyps))]
+        return self._alpha
+
+    def predict(self, x_star, add_noise: bool = False, s2_star=None, separate_samples: bool = False):
+        """Posterior mean and variance at ``x_star`` (M, D) with ``GP.predict``'s conventions: (mu, s2), each (M, S)
+        with ``separate_samples``, else the (M, 1) moments of the equal-weight mixture over the samples (divisor
+        S - 1 for the spread of the means).  The variance is clamped at 0; ``add_noise`` adds the noise function's
+        value (with ``s2_star``) times the joint factorization's multiplier."""
+        x_star = np.atleast_2d(np.asarray(x_star, dtype=float))
+        if x_star.ndim != 2 or x_star.shape[1] != self.D or x_star.shape[0] < 1:
+            raise ValueError(f"x_star must be (M, {self.D}), got {x_star.shape}")
+        if not np.all(np.isfinite(x_star)):
+            raise ValueError("x_star must be finite")
+        cov_N, noise_N, _ = self._counts
+        fmu, fs2 = self._live().predict_gobs(x_star)
+        S = len(self._hyps)
+        mu, s2 = np.empty(fmu.shape), np.empty(fs2.shape)
+        for s, hyp in enumerate(self._hyps):
+            mu[:, s] = np.reshape(self._mean.compute(_mean_hyp(hyp, self._counts), x_star), (-1,)) + fmu[:, s]
+            s2[:, s] = np.maximum(fs2[:, s], 0)
+            if add_noise:
+                sn2 = self._noise.compute(hyp[cov_N:cov_N + noise_N], x_star, None, s2_star) * self.sn2_mult[s]
+                s2[:, s] += np.reshape(np.broadcast_to(sn2, (x_star.shape[0], 1)), (-1,))
+        if not separate_samples and S >= 1:
+            mu, s2, _ = _mix_samples(mu, s2)
+        return mu, s2
+
+    def close(self):
+        if self._handle is not None:
+            self._handle.free()
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class GP:
     """A single Gaussian process (reference gaussian_process.py:24-62).
 
@@ -2497,6 +2571,126 @@ class GP:
         mult = np.array([float(_sn2_mult(p)) for p in local_posts])
         nsd = np.sqrt(np.broadcast_to(pv["sn2"], (len(local_posts), N)) * mult[:, None]).T
         return self._post_handle.paths(n_paths, n_features, seed, lo, ym, nsd), self._post_range
+
+    # ------------------------------------------------------------------ gradient observations
+    def _grad_obs_inputs(self, who, X_g, dy, s2_grad):
+        """Validated (X_g (Ng, D), dy (Ng, D), s2_grad (Ng, D)) of ``condition_on_gradients`` / ``nll_batch_grad_obs``."""
+        from . import _gradpost
+
+        if not self._builtin:
+            raise NotImplementedError(f"{who}: the covariance function {self.covariance!r} is user-defined; gradient "
+                                      "observations need the derivatives of a built-in covariance function")
+        kid, degree = self._kid()
+        if kid in _gradpost._MATERN and degree == 1:
+            raise NotImplementedError(f"{who}: the Matern kernel of degree 1 has no mean-square derivative (the prior "
+                                      "variance of its gradient is infinite)")
+        if self.X is None or self.y is None:
+            raise ValueError(f"{who}: the GP has no training data (gradient-only data are not supported)")
+        D = self.D
+        X_g, dy = np.asarray(X_g, dtype=float), np.asarray(dy, dtype=float)
+        if X_g.ndim != 2 or X_g.shape[1] != D or X_g.shape[0] < 1:
+            raise ValueError(f"{who}: X_g must be (Ng, {D}) with Ng >= 1, got {X_g.shape}")
+        Ng = X_g.shape[0]
+        if dy.shape != (Ng, D):
+            raise ValueError(f"{who}: dy must be (Ng, D) = ({Ng}, {D}), one gradient per row of X_g, got {dy.shape}")
+        if s2_grad is None:
+            raise ValueError(f"{who}: s2_grad is required (the variances of the gradient observations; 0 is allowed)")
+        s2g = np.asarray(s2_grad, dtype=float)
+        if s2g.ndim == 0:
+            s2g = np.full((Ng, D), float(s2g))
+        elif s2g.shape == (Ng,):
+            s2g = np.repeat(s2g[:, None], D, axis=1)
+        elif s2g.shape != (Ng, D):
+            raise ValueError(f"{who}: s2_grad must be a scalar, (Ng,) = ({Ng},) or (Ng, D) = ({Ng}, {D}), got {s2g.shape}")
+        if not (np.all(np.isfinite(X_g)) and np.all(np.isfinite(dy)) and np.all(np.isfinite(s2g))):
+            raise ValueError(f"{who}: X_g, dy and s2_grad must be finite")
+        if np.any(s2g < 0):
+            raise ValueError(f"{who}: s2_grad holds negative variances")
+        return np.ascontiguousarray(X_g), np.ascontiguousarray(dy), s2g
+
+    def _grad_obs_rows(self, who, hyp, X_g, s2g):
+        """(m (S, n), sn2 (S, n)) in joint order for the rows of ``hyp``: the mean function at X with its x-gradient at
+        X_g, and [the noise function's variances at X | s2_grad]."""
+        from . import _gradobs
+
+        counts = self._counts()
+        S, N = hyp.shape[0], self.X.shape[0]
+        Ng, D = X_g.shape
+        idx = _gradobs.order(N, Ng, D)
+        pv = self._plugin_values(hyp, False)
+        m, sn2 = np.empty((S, N + Ng * D)), np.empty((S, N + Ng * D))
+        m[:, :N] = pv["m"]
+        sn2[:, :N] = np.broadcast_to(pv["sn2"], (S, N))
+        sn2[:, idx] = s2g
+        for s in range(S):
+            m[s, idx] = _mean_grad_x(self.mean, _mean_hyp(hyp[s], counts), X_g, who)
+        return m, sn2
+
+    @_on_device
+    def condition_on_gradients(self, X_g, dy, s2_grad):
+        """Condition every resident hyperparameter sample on the GP's data (X, y, s2) AND on gradient observations:
+        ``dy`` (Ng, D), row g the observed gradient of f at ``X_g[g]`` (rows of ``X_g`` may repeat rows of X), with
+        noise variances ``s2_grad`` -- a scalar, (Ng,) or (Ng, D), required, zeros allowed (they take the reference's
+        low-noise branch by its own rule min(sn2) < 1e-6).  Returns a ``GradientConditionedPosterior``; the GP itself --
+        its posteriors, its data -- is not modified.  The joint covariance of order n = N + Ng D and the n x M operand
+        of every prediction are built on the device (gpc_posterior_batch_gobs / gpc_predict_gobs); the factorization,
+        the jitter ladder and the solves are those of every other posterior.  Built-in covariance functions except the
+        Matern kernel of degree 1 (NotImplementedError); ``LinAlgError`` after ten failed factorizations.  Not
+        sharded: every rank holds every sample's hyperparameters, and the calling rank computes all of them."""
+        who = "condition_on_gradients"
+        X_g, dy, s2g = self._grad_obs_inputs(who, X_g, dy, s2_grad)
+        if self.posteriors is None or len(self.posteriors) == 0 or any(p is None for p in self.posteriors):
+            raise ValueError(f"{who}: the GP has no posteriors; call update() or set_hyperparameters() first")
+        self._require_posteriors()  # (conditions on the RESIDENT samples: a GP whose posteriors were never computed, or cleaned, is refused)
+        hyp = np.stack([np.array(p.hyp, dtype=float) for p in self.posteriors])
+        nlz, handle, mult, lchol = self._grad_obs_device(who, hyp, X_g, dy, s2g, True)
+        return GradientConditionedPosterior(handle, self.mean, self.noise, self._counts(), list(hyp),
+                                            (self.X.shape[0], X_g.shape[0], self.D), nlz, mult, lchol)
+
+    @_on_device
+    def nll_batch_grad_obs(self, hyp, X_g, dy, s2_grad):
+        """The joint negative log marginal likelihood of the GP's data and the gradient observations (arguments as
+        ``condition_on_gradients``) for MANY hyperparameter vectors: ``hyp`` (S, hyp_N) -> nlZ (S,).  Priors are not
+        added and there is no gradient: the joint counterpart of ``nll_batch(hyp, compute_grad=False)``.  Not sharded."""
+        who = "nll_batch_grad_obs"
+        X_g, dy, s2g = self._grad_obs_inputs(who, X_g, dy, s2_grad)
+        hyp = np.atleast_2d(np.asarray(hyp, dtype=float))
+        if hyp.ndim != 2 or hyp.shape[1] != sum(self._counts()):
+            raise ValueError("Input hyperparameter array is the wrong shape!")
+        if not np.all(np.isfinite(hyp)):
+            raise ValueError(f"{who}: hyp must be finite")
+        return self._grad_obs_device(who, hyp, X_g, dy, s2g, False)[0]
+
+    def _grad_obs_device(self, who, hyp, X_g, dy, s2g, keep):
+        """(nlZ, handle | None, sn2_mult, L_chol) of the joint systems of the rows of ``hyp``.  The context's resident
+        data become the joint data under a token of their own, so this GP (and any other) uploads its own again on
+        its next call."""
+        cov_N = self._counts()[0]
+        kid, degree = self._kid()
+        m, sn2 = self._grad_obs_rows(who, hyp, X_g, s2g)
+        ctx = _lib.context(self.device)
+        ctx.set_data_gobs(self.X, self.y, X_g, dy, token=object())
+        args = (kid, degree, _DTYPES[self.dtype], hyp[:, :cov_N], m, sn2)
+        handle = None
+        if keep:
+            handle, _, mult, lchol, info = ctx.posterior_batch_gobs(*args)
+            if np.any(info != 0):
+                handle.free()
+                raise LinAlgError("Singular matrix for L Cholesky decomposition")
+        try:
+            # (nlZ always from the evaluation without the inverse: ONE number for the object and for nll_batch_grad_obs)
+            nlz, mult_n, lchol_n, info = ctx.nll_batch_gobs(*args)
+        except Exception:
+            if handle is not None:
+                handle.free()
+            raise
+        if np.any(info != 0):
+            if handle is not None:
+                handle.free()
+            raise LinAlgError("Singular matrix for L Cholesky decomposition")
+        if not keep:
+            mult, lchol = mult_n, lchol_n
+        return nlz, handle, mult, lchol
 
     @staticmethod
     def _jittered_cholesky(C, s):

@@ -888,6 +888,49 @@ enum { GPC_FORM_PLAIN = 0, GPC_FORM_PERSIST = 1, GPC_FORM_PERSIST_RESERVED = 2, 
 int gpc_debug_gemm_form(gpc_ctx* ctx, int dtype, int form, int tile, int batch, int flags, int block_slots,
                         const gpc_gemm_product* p1, const gpc_gemm_product* p2, const double* ep_w, long long ep_sw,
                         const double* ep_alpha, double* colsq, int* counters, int* available);
+
+/* ---- Gradient observations (gpyreg_amd/csrc/gradobs.h; DESIGN.md "Gradient observations") -------------------------
+ * Conditioning on values y at X (N x D) AND gradients dy (Ng x D, row g = grad f(Xg[g])) at Xg (Ng x D; rows may repeat
+ * rows of X).  The joint system has order n = N + Ng D; its rows are the values first, then the gradient rows
+ * DIMENSION-MAJOR: row N + l Ng + g = d f / dx_l at Xg[g].  Every S x n array below (m, sn2) and every fetched alpha / L
+ * is in that order.  The joint covariance is built on the device (k, -c_a F d_a, c_a c_b (F delta_ab - G d_a d_b) with
+ * the pair functor's radial factors); from there on it is the caller-provided-K pipeline: the reference's scaling by
+ * min(sn2) over the JOINT noise vector, its branch rule min(sn2) >= 1e-6, the x 10 jitter ladder, alpha, log det.
+ * Built-in kernels only; the Matern kernel of degree 1 (no mean-square derivative) is an error.
+ *
+ * gpc_set_data_gobs makes the points and the joint target [y | dy in joint order] resident; the context's problem
+ * order becomes n (gpc_max_n applies to n).  While such data are resident only the _gobs and _K entry points evaluate
+ * them; gpc_set_data switches back.                                                                                  */
+int gpc_set_data_gobs(gpc_ctx* ctx, const double* X, const double* y, int N, int D, const double* Xg, const double* dy,
+                      int Ng);
+/* Posteriors of S hyperparameter rows.  m: S x n, the mean function at X and its x-gradient at Xg in joint order;
+ * sn2: S x n joint noise variances (always per row; zeros are allowed and take the low-noise branch by the rule
+ * above).  nlz (S; may be NULL): the joint negative log marginal likelihood as this pipeline rounds it --
+ * gpc_nll_batch_gobs factors without the inverse and agrees with it to rounding, not to the bit.  sn2_mult, L_chol,
+ * info as gpc_posterior_batch.  The handle is a GRADIENT-OBSERVATION posterior: it owns a copy of the points,
+ * gpc_predict_gobs, gpc_post_fetch (alpha: n, L: n x n) and gpc_post_free work on it, and every other consumer
+ * (gpc_predict, gpc_predict_grad, gpc_post_append*, gpc_post_remove, gpc_draw, gpc_paths_create, gpc_cv, gpc_quad*,
+ * gpc_predict_K, ...) returns an error that says so.                                                                 */
+int gpc_posterior_batch_gobs(gpc_ctx* ctx, int kernel_id, int degree, int dtype, int S, const double* hyp_cov,
+                             const double* m, const double* sn2, gpc_post** post, double* nlz, double* sn2_mult,
+                             int* L_chol, int* info);
+/* The joint negative log marginal likelihood alone, for S arbitrary hyperparameter rows (no posterior is kept, no
+ * gradient: the hyperparameter derivatives of the joint matrix need a third radial factor).                         */
+int gpc_nll_batch_gobs(gpc_ctx* ctx, int kernel_id, int degree, int dtype, int S, const double* hyp_cov,
+                       const double* m, const double* sn2, double* nlz, double* sn2_mult, int* L_chol, int* info);
+/* gpc_predict for a gradient-observation posterior: the n x M operand [k(X, x*) ; -c_l F (xs_g - xs*)_l] is built on
+ * the device with the mean product fused in; fmu (caller adds m*) and fs2 (unclamped) as gpc_predict, [j*S + s].    */
+int gpc_predict_gobs(gpc_post* post, const double* xstar, int M, double* fmu, double* fs2);
+/* Test hooks: the two kernels of gradobs.h on their own, fp64, one hyperparameter row.
+ * gpc_debug_gobs_cov: out = the dense n x n joint covariance (preset to NaN, so an entry nobody wrote shows).
+ * gpc_debug_gobs_cross: out = the WHOLE panel, pad128(n) x pad128(M) row-major (preset to NaN; rows >= n and columns
+ * >= M must come back as zeros); colsum (pad128(M); may be NULL) = the fused products out^T alpha with alpha (n; NULL:
+ * zeros) in joint order.                                                                                            */
+int gpc_debug_gobs_cov(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                       const double* Xg, int Ng, double* out);
+int gpc_debug_gobs_cross(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                         const double* Xg, int Ng, const double* xstar, int M, const double* alpha, double* out,
+                         double* colsum);
 /* ---- experiments build only (hipcc -DGPC_EXPERIMENTS -> lib/libgpcore_exp.so; NOT part of the product library) --------
  * Schedules that were built, measured and rejected (tile-level dataflow graph, independent pipelines,
  * rectangular / eight-wave tiles, right-looking panels) and their gpc_set_option names live there;
