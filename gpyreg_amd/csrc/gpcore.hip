@@ -8037,6 +8037,7 @@ int gpc_quad(gpc_post* po, const double* mu, const double* sigma, int M, int com
   gpc_ctx* c = po->ctx;
   if (!mu || !sigma || !zalpha || M <= 0 || (compute_var && !zKz)) FAIL(c, "gpc_quad: bad arguments");
   if (int rc = refuse_gobs(po, __func__)) return rc;
+  if (int rc = require_factorized(po, "gpc_quad")) return rc;
   if (po->cd.kind != K_SE && po->cd.kind != K_SE_ISO)
     FAIL(c, "Bayesian quadrature only supports the squared exponential kernel.");
   HIPCHK(c, hipSetDevice(c->device));

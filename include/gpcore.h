@@ -524,7 +524,9 @@ int gpc_lookahead_batch(gpc_post* post, const double* xr, int Mr, const double* 
  * mu, sigma: M x D (means and standard deviations of the Gaussian measures).  With z the
  * kernel mean vector of measure j under sample s:
  *   zalpha[j*S + s] = z . alpha                      (the caller adds the mean-function terms)
- *   zKz[j*S + s]    = z (K + sn2_eff I)^-1 z^T       (only if compute_var)                  */
+ *   zKz[j*S + s]    = z (K + sn2_eff I)^-1 z^T       (only if compute_var)
+ * Fails with a message on a gradient-observation posterior, on one that holds a failed
+ * factorization, on a kernel that is not squared exponential and on bad arguments.          */
 int gpc_quad(gpc_post* post, const double* mu, const double* sigma, int M, int compute_var,
              double* zalpha, double* zKz);
 

@@ -17,6 +17,18 @@ def planned_chunk(S, mb, per, shared=0):
     return 0 if budget < shared + per else min(S, (budget - shared) // per)
 
 
+def rhs_per(npad, mpad, full, w):
+    """gpc_predict, gpc_predict_full, gpc_quad, gpc_predict_K (rhs_products without gradients or draws): the right-hand
+    side and the product, npad x mpad each, and with `full` the mpad x mpad covariance, in the storage type (w bytes)."""
+    return (2 * npad * mpad + (mpad * mpad if full else 0)) * w
+
+
+def budget_for_chunk(S, chunk, per, shared=0):
+    """The smallest GPC_MEM_BUDGET_MB under which the planner gives `chunk` samples per chunk (None: no whole number of
+    megabytes does)."""
+    return next((mb for mb in range(1, 4096) if planned_chunk(S, mb, per, shared) == chunk), None)
+
+
 def nll_hess_per(npad, cov_N, noise_N, mean_N, nd2):
     """gpc_nll_hess: Q, one B per plane and the operand; the vectors; the partials of the Gram and d2 passes."""
     n2, ppl, nt = npad * npad, cov_N + noise_N, npad // 64

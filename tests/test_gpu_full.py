@@ -28,6 +28,11 @@ def test_predict_full_and_quad_match_reference():
         scale = np.abs(g[tag + "_pf_cov"]).max()
         assert np.abs(C - g[tag + "_pf_cov"]).max() <= 1e-7 * scale, name
         assert np.array_equal(C, C.transpose(1, 0, 2))
+        # (GP.predict_full symmetrises on the host; the device's own covariance, before that: both triangles are within
+        # the 1e-7 above of the recorded -- symmetric -- value)
+        _, Craw = gp._post_handle.predict_full(xs)
+        assert Craw.shape == (hyp.shape[0], xs.shape[0], xs.shape[0])
+        assert np.abs(Craw - Craw.transpose(0, 2, 1)).max() <= 2e-7 * scale, name
         _, Cn = gp.predict_full(xs, None, s2s, add_noise=True)
         assert np.abs(Cn - g[tag + "_pf_cov_noise"]).max() <= 1e-7 * scale, name
         # diagonal of the full covariance == predictive variance of predict()
