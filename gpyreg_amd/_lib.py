@@ -137,6 +137,7 @@ SIGNATURES = {
     "gpc_debug_normals": (C.c_int, [_vp, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp]),
     "gpc_debug_workspace_hash": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp]),
     "gpc_debug_chunk_plan": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_int]),
+    "gpc_debug_scratch_bytes": (C.c_int, [C.c_char_p, C.c_int, _ip, C.c_int, _vp, _vp, _ip]),
     "gpc_debug_gemm_queues": (C.c_int, [C.c_int] * 8 + [_ip] * 4),
     "gpc_debug_gemm_form": (
         C.c_int,

@@ -36,10 +36,14 @@ struct ScratchCarver {
   const bool carving = false;  // (its own flag: a carver on a null base still carves, it never counts by accident)
   char* p = nullptr;
   size_t bytes = 0;
+  int misaligned = 0;  // arrays of at least one element that did not start on their `align` (checked, never padded)
   ScratchCarver() = default;
   explicit ScratchCarver(void* base) : carving(true), p(static_cast<char*>(base)) {}
+  // align: 16 for what the MFMA GEMMs and the MM<T>::vec_t panel reads touch.  Counting checks the offset (a block's
+  // base is 256-byte aligned), carving the address itself.
   template <typename T = double>
-  T* take(size_t n) {
+  T* take(size_t n, size_t align = alignof(T)) {
+    if (n && (carving ? reinterpret_cast<uintptr_t>(p) : bytes) % align) ++misaligned;
     bytes += n * sizeof(T);
     if (!carving) return nullptr;
     T* r = reinterpret_cast<T*>(p);
@@ -54,9 +58,10 @@ struct ScratchCarver {
     return sc.bytes;
   }
   template <typename Z, typename... Dims>
-  static void carve(Z& z, void* base, Dims... dims) {
+  static int carve(Z& z, void* base, Dims... dims) {  // returns the number of misaligned arrays: 0 or the call fails
     ScratchCarver sc(base);
     z.layout(sc, dims...);
+    return sc.misaligned;
   }
 };
 

@@ -40,6 +40,7 @@
 #include "quad.h"
 #include "quad_mix.h"
 #include "remove.h"
+#include "scratch.h"
 #ifdef GPC_EXPERIMENTS
 // Schedules that were built, measured and rejected -- the tile-level dataflow graph, independent
 // per-sample pipelines, rectangular / eight-wave tiles, right-looking panels -- are compiled only into the experiments
@@ -530,15 +531,20 @@ struct gpc_ctx {
   DevBuf scal;                   // logdet | quad | (ints) info
   DevBuf parts, gout, diagq;     // trace pass
   DevBuf dmb, dsn2b, mg, ng;     // mean / noise gradient inputs and outputs
-  DevBuf ks, vb, kss, xss, pout; // predict / predict_full / quad
-  DevBuf qb, gpart, gres;        // predict_grad / quad_grad: Q = W^T V, per-tile partials, the gradients
-  DevBuf qcon;                   // quad_grad: the measures' constants (quad.h: quad_grad_prep_kernel)
+  // Consumer scratch: every posterior consumer declares its device arrays once (scratch.h: a *Scratch struct's layout())
+  // and carves them from ONE block.  Calls on a context are serial, so the consumers that never run inside one another
+  // share `cs`: rhs_products (predict, predict_full, quad, quad_grad, predict_K, predict_gobs, draw), grad_post,
+  // predict_hess, append_block, remove (its sweeps), cv (both passes; the fold pass follows the leave-one-out pass of a
+  // mixed call, it does not run inside it), paths_create, paths_eval and predict_hyp_grad's raw queries.  The nesting
+  // there is: lookahead_batch_impl runs cov_products while its own `lab` is live (gpc_predict_cov runs it alone), so
+  // cov_products carves from `covs`, a block of its own; posterior_q (under nll_hess and cv_grad) writes into its
+  // caller's nhs block and takes nothing itself.
+  DevBuf cs, covs;
   DevBuf qmix;                   // quad_mix: the whole scratch of a chunk, carved up in quad_mix_impl
-  DevBuf nhs;                    // nll_hess: the whole scratch of a chunk, carved up in nll_hess_impl (NhScratch)
-  DevBuf lab;                    // lookahead_batch: the resident state of the step loop, carved up in lookahead_batch_impl (LabScratch)
-  DevBuf hgs;                    // predict_hyp_grad: the whole scratch of a chunk, carved up in hyp_grad_impl (HgScratch)
-  DevBuf zb, fb, dout, daux;     // draw: Z, F = L Z, the draws, [logdet | info | noise sd] (the factor: mA mW mT)
-  DevBuf dbg1, dbg2, dbg3;       // debug hooks / fetch staging
+  DevBuf nhs;                    // nll_hess: the whole scratch of a chunk, carved up in nll_hess_impl (scratch.h: NhScratch)
+  DevBuf lab;                    // lookahead_batch: the resident state of the step loop, carved up in lookahead_batch_impl (scratch.h: LabScratch)
+  DevBuf hgs;                    // predict_hyp_grad: the whole scratch of a chunk, carved up in hyp_grad_impl (scratch.h: HgScratch)
+  DevBuf dbg1, dbg2, dbg3;       // debug hooks / fetch staging / the pipeline's K-mode and trace staging
   PinBuf pin;                    // pinned staging for host<->device transfers (see PinBuf)
   // Launch graphs of the device pipeline for small problems (npad <= graph_max_npad, one sample
   // group): a single evaluation at N = 200 is ~20 dependent launches of a few microseconds each,
@@ -689,6 +695,15 @@ struct gpc_paths {
   do {                   \
     (ctx)->err = (msg);  \
     return -2;           \
+  } while (0)
+
+// ScratchCarver::carve reports the arrays that missed their alignment: the call fails before it launches anything
+#define CARVECHK(ctx, fn, expr)                                                             \
+  do {                                                                                      \
+    if ((expr) != 0) {                                                                      \
+      (ctx)->err = std::string(fn) + ": internal error: a scratch array is misaligned";    \
+      return -1;                                                                            \
+    }                                                                                       \
   } while (0)
 
 namespace {
@@ -2530,22 +2545,23 @@ struct DrawReq {
   double* tau;        // S
 };
 
-// One chunk of draws: C_s (in c->kss, chunk layout) -> A = C_s + tau_s I -> L (batched Factor, stable retries with
+// One chunk of draws: C_s (z.Kss, chunk layout) -> A = C_s + tau_s I -> L (batched Factor, stable retries with
 // jitter for the samples that failed; the diagonal tiles cleaned above the diagonal) -> Z (normals_kernel) -> F = L Z (gemm.h: lower A operand, KHI_ROW skips the
-// zero upper tiles) -> fmu + F (+ noise) into c->dout, copied to hout.  Every step is per sample with a reduction order
+// zero upper tiles) -> fmu + F (+ noise) into z.dout, copied to hout.  Every step is per sample with a reduction order
 // fixed by the shape (the leaf and the product library do not depend on the batch), so a sample's draws carry the same
 // bits in any batch or chunk.  Returns -3 with a message when a sample cannot be factored with the largest jitter.
 template <typename T>
-int draw_chunk(gpc_post* po, const DrawReq& d, int s0, int cnt, int M, const double* d_mu, double* hout) {
+int draw_chunk(gpc_post* po, const DrawReq& d, int s0, int cnt, int M, const RhsScratch<T>& z, const double* d_nsd,
+               double* hout) {
   gpc_ctx* c = po->ctx;
   hipStream_t st = c->st;
   const int mpad = pad_tile(M), R = d.R, rpad = pad_tile(R);
   const long long sKss = (long long)mpad * mpad, sZ = (long long)mpad * rpad;
-  T* C = c->kss.as<T>();
+  T* C = z.Kss;
   T* A = c->mA.as<T>();
-  double* d_nsd = d.nsd ? c->daux.as<double>() : nullptr;
-  double* logdet = c->daux.as<double>() + (size_t)M * po->S;
-  int* info = reinterpret_cast<int*>(logdet + cnt);
+  const double* d_mu = z.mu;
+  double* logdet = z.logdet;
+  int* info = z.info;
   const dim3 blk(64, 4);
   auto factor = [&](int i0, int n, double tau, bool stable) -> int {
     HIPCHK(c, hipMemsetAsync(logdet + i0, 0, (size_t)n * 8, st));
@@ -2608,13 +2624,13 @@ int draw_chunk(gpc_post* po, const DrawReq& d, int s0, int cnt, int M, const dou
   hipLaunchKernelGGL((diag_tile_upper_zero_kernel<T>), dim3(mpad / TILE, cnt), dim3(256), 0, st, A, sKss, mpad);
   const long long s_base = (long long)d.s_offset + s0;
   hipLaunchKernelGGL((normals_kernel<T>), dim3(rpad / 64, mpad / 16, cnt), blk, 0, st, d.seed, 0, s_base, M, R, mpad,
-                     rpad, c->zb.as<T>(), sZ);
-  const GemmArgs g = tri_gemm_args(A, sKss, mpad, true, c->zb.as<T>(), c->fb.as<T>(), sZ, rpad, rpad);  // F = L Z
+                     rpad, z.Z, sZ);
+  const GemmArgs g = tri_gemm_args(A, sKss, mpad, true, z.Z, z.F, sZ, rpad, rpad);  // F = L Z
   HIPCHK(c, launch_gemm<T>(st, g, false, true, cnt));
-  hipLaunchKernelGGL((draw_assemble_kernel<T>), dim3((R + 63) / 64, mpad / 16, cnt), blk, 0, st, (const T*)c->fb.as<T>(),
-                     sZ, rpad, d_mu, mpad, M, R, (const double*)d_nsd, po->S, s0, d.seed, s_base, c->dout.as<double>());
+  hipLaunchKernelGGL((draw_assemble_kernel<T>), dim3((R + 63) / 64, mpad / 16, cnt), blk, 0, st, (const T*)z.F,
+                     sZ, rpad, d_mu, mpad, M, R, d_nsd, po->S, s0, d.seed, s_base, z.dout);
   HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(hout, c->dout.p, (size_t)cnt * M * R * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(hout, z.dout, (size_t)cnt * M * R * 8, hipMemcpyDeviceToHost, st));
   return 0;
 }
 
@@ -2706,11 +2722,11 @@ struct QuadGradOut {
   double* p[4];  // dza_dmu, dza_dsigma, dzkz_dmu, dzkz_dsigma
 };
 struct RhsRequest {
-  enum Rhs {
-    CROSS,    // cross covariance of xa (M x D) with the training inputs
-    QUAD_Z,   // quadrature vectors z of the Gaussian measures N(xa[j], diag(xb[j]^2)) (gaussian_process.py:1908-1921)
-    GIVEN_KS, // the caller's own Ks_s (xa: S x N x M doubles) and, with `full`, K**_s (xb: S x M x M): K-mode posteriors
-    GOBS      // the joint cross operand [k(X, xa) ; dk(X_g, xa)/dx_g] of a gradient-observation posterior (gradobs.h)
+  enum Rhs {  // (RhsDims::of takes the values)
+    CROSS = 0,    // cross covariance of xa (M x D) with the training inputs
+    QUAD_Z = 1,   // quadrature vectors z of the Gaussian measures N(xa[j], diag(xb[j]^2)) (gaussian_process.py:1908-1921)
+    GIVEN_KS = 2, // the caller's own Ks_s (xa: S x N x M doubles) and, with `full`, K**_s (xb: S x M x M): K-mode posteriors
+    GOBS = 3      // the joint cross operand [k(X, xa) ; dk(X_g, xa)/dx_g] of a gradient-observation posterior (gradobs.h)
   };
   Rhs rhs = CROSS;
   const double* xa = nullptr;
@@ -2740,12 +2756,12 @@ struct RhsCall {
   const bool full, grad, gq;  // gq: the gradient pass reads Q (not without a product)
   // gnt: tile rows of the gradient pass; gpl: its result planes, [dmu | ds2] (CROSS) or [dza_dmu | dza_dsigma (| dzkz_dmu |
   // dzkz_dsigma)] (qg)
-  const int gnt, gpl, rpad;
-  const size_t gpart_per, gres_per, qcon_per, sZ;
+  const int gnt, gpl;
   int chunk = 0;
   CallTimer tm;
   ChunkConsts k;
-  double *d_mut = nullptr, *d_qcon = nullptr, *d_xa = nullptr, *d_xb = nullptr;
+  RhsScratch<T> z;
+  RhsShared zs;
   // landing blocks of the per-chunk results
   std::unique_ptr<double[]> hmu_v, hdraw_v, hgrad_v;
   double *hmu = nullptr, *hv = nullptr, *hfull = nullptr, *hdraw = nullptr, *hgrad = nullptr;
@@ -2754,68 +2770,38 @@ struct RhsCall {
       : po(po_), r(r_), c(po_->ctx), st(po_->ctx->st), S(po_->S), N(po_->N), D(po_->D), npad(po_->npad), M(r_.M),
         mpad(pad_tile(r_.M)), sKs((long long)npad * mpad), sKss((long long)mpad * mpad), full(r_.full != nullptr),
         grad(r_.dlin != nullptr || r_.qg != nullptr), gq(grad && (!r_.qg || r_.want_quad)), gnt(npad / CT),
-        gpl(r_.qg && r_.want_quad ? 4 : 2), rpad(r_.draw ? pad_tile(r_.draw->R) : 0),
-        gpart_per(grad ? (size_t)gnt * gpl * D * mpad * 8 : 0), gres_per(grad ? (size_t)gpl * mpad * D * 8 : 0),
-        qcon_per(r_.qg ? (size_t)(D + 1) * mpad * 8 : 0), sZ((size_t)mpad * rpad),
-        tm{po_->ctx, CallTimer::wanted(po_->ctx, po_->npad)} {}
+        gpl(r_.qg && r_.want_quad ? 4 : 2), tm{po_->ctx, CallTimer::wanted(po_->ctx, po_->npad)} {}
 
-  T* Ks() const { return c->ks.as<T>(); }
-  T* V() const { return c->vb.as<T>(); }
-  double* d_mu() const { return c->pout.as<double>(); }
+  T* Ks() const { return z.Ks; }
+  T* V() const { return z.V; }
+  double* d_mu() const { return z.mu; }
   double* d_v() const { return d_mu() + (size_t)chunk * mpad; }
   const double* alpha(int s) const { return po->alpha.as<double>() + (size_t)s * npad; }
+  bool colsq_form() const { return RhsDims::colsq_form(npad, mpad, full, grad); }
+  RhsDims dims() const {
+    return RhsDims::of(N, M, D, S, (int)r.rhs, r.want_quad, full, grad, r.qg != nullptr, r.draw ? r.draw->R : 0,
+                       r.rhs == RhsRequest::GOBS ? po->gobs.P() : 0);
+  }
 
-  // The scratch of one sample, the samples per chunk, and the buffers of a chunk
+  // The scratch of one sample, the samples per chunk, and the block of a chunk
   int plan() {
-    const DrawReq* draw = r.draw;
-    const bool qg = r.qg != nullptr;
-    // gradient scratch per sample: Q (as V), the per-tile partials, the results and (qg) the measures' constants;
-    // draw scratch per sample: the factor's three slabs (mA mW mT), Z and F (mpad x rpad), the draws
-    const size_t draw_per = draw ? (3 * (size_t)sKss + 2 * sZ) * sizeof(T) + (size_t)M * draw->R * 8 : 0;
-    const size_t per = (2ull * npad * mpad + (full ? (size_t)mpad * mpad : 0) + (gq ? (size_t)npad * mpad : 0)) * sizeof(T) +
-                       gpart_per + gres_per + qcon_per + draw_per;
-    const size_t held = c->ks.bytes + c->vb.bytes + c->kss.bytes + (grad ? c->qb.bytes + c->gpart.bytes + c->gres.bytes : 0) +
-                        (qg ? c->qcon.bytes : 0) +
-                        (draw ? c->mA.bytes + c->mW.bytes + c->mT.bytes + c->zb.bytes + c->fb.bytes + c->dout.bytes : 0);
-    const bool fits =
-        !((size_t)S * per > held || (size_t)S * sKs * sizeof(T) > std::min(c->ks.bytes, c->vb.bytes) ||
-          (full && (size_t)S * sKss * sizeof(T) > c->kss.bytes) ||
-          (grad && ((gq && (size_t)S * sKs * sizeof(T) > c->qb.bytes) || (size_t)S * gpart_per > c->gpart.bytes)) ||
-          (qg && (size_t)(S + 1) * qcon_per > c->qcon.bytes) ||
-          (draw && ((size_t)S * sKss * sizeof(T) > std::min({c->mA.bytes, c->mW.bytes, c->mT.bytes}) ||
-                    (size_t)S * sZ * sizeof(T) > std::min(c->zb.bytes, c->fb.bytes) ||
-                    (size_t)S * M * draw->R * 8 > c->dout.bytes)));
+    const RhsDims d = dims();
+    // (a draw factors in the factorization's own three slabs: they count beside the block)
+    const size_t slab = d.template slab_bytes<T>();
+    const size_t own = ScratchCarver::count<RhsScratch<T>>(1, d), per = own + 3 * slab;
+    const size_t shared = ScratchCarver::count<RhsShared>(d);
+    const size_t held = c->cs.bytes + (r.draw ? c->mA.bytes + c->mW.bytes + c->mT.bytes : 0);
+    const bool fits = shared + (size_t)S * own <= c->cs.bytes && (size_t)S * slab <= std::min({c->mA.bytes, c->mW.bytes, c->mT.bytes});
     // (draws refuse a sample that does not fit; everything else runs one sample at a time whatever the budget says)
-    chunk = plan_chunk(c, S, per, 0, held, fits, 0, !draw, [&](size_t budget) {
+    chunk = plan_chunk(c, S, per, shared, held, fits, 0, !r.draw, [&](size_t budget) {
       return "gpc_draw: the scratch of one sample (" + std::to_string(per >> 20) + " MB) exceeds the device memory "
              "budget (" + std::to_string(budget >> 20) + " MB)";
     });
     if (!chunk) return -2;
-    HIPCHK(c, c->ks.ensure((size_t)chunk * sKs * sizeof(T)));
-    HIPCHK(c, c->vb.ensure((size_t)chunk * sKs * sizeof(T)));
-    if (full) HIPCHK(c, c->kss.ensure((size_t)chunk * sKss * sizeof(T)));
-    if (draw) {
-      HIPCHK(c, c->mA.ensure((size_t)chunk * sKss * sizeof(T)));
-      HIPCHK(c, c->mW.ensure((size_t)chunk * sKss * sizeof(T)));
-      HIPCHK(c, c->mT.ensure((size_t)chunk * sKss * sizeof(T)));
-      HIPCHK(c, c->zb.ensure((size_t)chunk * sZ * sizeof(T)));
-      HIPCHK(c, c->fb.ensure((size_t)chunk * sZ * sizeof(T)));
-      HIPCHK(c, c->dout.ensure((size_t)chunk * M * draw->R * 8));
-      HIPCHK(c, c->daux.ensure(((size_t)M * S + 2 * (size_t)chunk) * 8));
-    }
-    if (grad) {
-      if (gq) HIPCHK(c, c->qb.ensure((size_t)chunk * sKs * sizeof(T)));
-      HIPCHK(c, c->gpart.ensure((size_t)chunk * gpart_per));
-      HIPCHK(c, c->gres.ensure((size_t)chunk * gres_per));
-    }
-    // (qg) [mu_jl transposed: D x mpad | per sample: 1/tau_jl, D x mpad, and ln nf_j, mpad]
-    if (qg) HIPCHK(c, c->qcon.ensure((size_t)(chunk + 1) * qcon_per));
-    d_mut = qg ? c->qcon.as<double>() : nullptr;
-    d_qcon = qg ? d_mut + (size_t)D * mpad : nullptr;
-    HIPCHK(c, c->xss.ensure(((size_t)chunk * mpad * D + 2 * (size_t)M * D) * 8));
-    HIPCHK(c, c->pout.ensure((size_t)chunk * mpad * 2 * 8));
-    d_xa = c->xss.as<double>() + (size_t)chunk * mpad * D;
-    d_xb = d_xa + (size_t)M * D;
+    HIPCHK(c, c->cs.ensure(shared + (size_t)chunk * own));
+    for (DevBuf* m : {&c->mA, &c->mW, &c->mT}) HIPCHK(c, m->ensure((size_t)chunk * slab));
+    CARVECHK(c, "rhs_products", ScratchCarver::carve(z, c->cs.p, chunk, d) +
+                                    ScratchCarver::carve(zs, c->cs.as<char>() + (size_t)chunk * own, d));
     return 0;
   }
 
@@ -2824,8 +2810,8 @@ struct RhsCall {
     c->pin.begin();
     c->pin.begin_gather();
     if (r.rhs != RhsRequest::GIVEN_KS) {
-      HIPCHK(c, c->pin.up(d_xa, r.xa, (size_t)M * D * 8, st));
-      if (r.xb) HIPCHK(c, c->pin.up(d_xb, r.xb, (size_t)M * D * 8, st));
+      HIPCHK(c, c->pin.up(zs.xa, r.xa, (size_t)M * D * 8, st));
+      if (r.xb) HIPCHK(c, c->pin.up(zs.xb, r.xb, (size_t)M * D * 8, st));
     }
     // (one block for lin and quad: the device keeps [mu | v] contiguous too, so a call's results come back in ONE copy)
     hmu = landing_block(c, 2 * (size_t)chunk * mpad * 8, hmu_v);
@@ -2834,9 +2820,9 @@ struct RhsCall {
       hfull = static_cast<double*>(c->pin.alloc((size_t)M * M * 8));
     if (r.draw) {  // a chunk's draws, M x R per sample
       hdraw = landing_block(c, (size_t)chunk * M * r.draw->R * 8, hdraw_v);
-      if (r.draw->nsd) HIPCHK(c, hipMemcpyAsync(c->daux.p, r.draw->nsd, (size_t)M * S * 8, hipMemcpyHostToDevice, st));
+      if (r.draw->nsd) HIPCHK(c, hipMemcpyAsync(zs.nsd, r.draw->nsd, (size_t)M * S * 8, hipMemcpyHostToDevice, st));
     }
-    if (grad) hgrad = landing_block(c, gres_per * (size_t)chunk, hgrad_v);  // the gradient planes of a chunk
+    if (grad) hgrad = landing_block(c, (size_t)gpl * chunk * mpad * D * 8, hgrad_v);  // the gradient planes of a chunk
     // all samples in one chunk (the usual case): the posterior's constants are resident, see gpc_post
     return k.init(po, chunk, r.rhs != RhsRequest::GIVEN_KS);
   }
@@ -2846,16 +2832,15 @@ struct RhsCall {
   int build_cross(int s0, int cnt) {
     const long long tot = (long long)mpad * D;
     hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, st,
-                       (const double*)d_xa, M, mpad, D, k.mulb, k.divb, c->xss.as<double>());
-    HIPCHK(c, c->dbg2.ensure((size_t)cnt * (npad / CT) * mpad * 8));
+                       (const double*)zs.xa, M, mpad, D, k.mulb, k.divb, z.xss);
     GPC_COV_DISPATCH(cross_tile_kernel, T, po->cd, dim3(mpad / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
-                     (const double*)c->xss.as<double>(), k.spb, alpha(s0), npad, N, npad, M, mpad, Ks(), sKs,
-                     c->dbg2.as<double>());
+                     (const double*)z.xss, k.spb, alpha(s0), npad, N, npad, M, mpad, Ks(), sKs,
+                     z.part);
     if (full)
       hipLaunchKernelGGL((cross_kernel<T>), dim3(mpad / 64, mpad / 4, cnt), dim3(64, 4), 0, st, po->cd,
-                         c->xss.as<double>(), c->xss.as<double>(), k.spb, M, mpad, M, mpad, c->kss.as<T>(), sKss);
+                         z.xss, z.xss, k.spb, M, mpad, M, mpad, z.Kss, sKss);
     hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
-                       (const double*)c->dbg2.as<double>(), npad / CT, mpad, d_mu());
+                       (const double*)z.part, npad / CT, mpad, d_mu());
     return 0;
   }
   // the joint cross operand of a gradient-observation posterior with the mean product fused in (gradobs.h:
@@ -2864,42 +2849,40 @@ struct RhsCall {
     const GobsDims& gd = po->gobs;
     const long long tot = (long long)mpad * D;
     hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, st,
-                       (const double*)d_xa, M, mpad, D, k.mulb, k.divb, c->xss.as<double>());
+                       (const double*)zs.xa, M, mpad, D, k.mulb, k.divb, z.xss);
     const double* xp = k.xsb;  // (all samples in one chunk: the posterior's resident scaled lists)
     if (!k.resident) {
       HIPCHK(c, c->gxs.ensure((size_t)cnt * gd.P() * D * 8));
       launch_gobs_scale(st, gd, po->gpts.as<double>(), k.mulb, k.divb, cnt, c->gxs.as<double>());
       xp = c->gxs.as<double>();
     }
-    HIPCHK(c, c->dbg2.ensure((size_t)cnt * (gd.P() / CT) * mpad * 8));
-    HIPCHK(c, launch_gobs_cross<T>(st, po->cd, gd, xp, c->xss.as<double>(), k.spb, k.mulb, k.divb, alpha(s0), npad, npad, M,
-                                   mpad, cnt, Ks(), sKs, c->dbg2.as<double>(), d_mu()));
+    HIPCHK(c, launch_gobs_cross<T>(st, po->cd, gd, xp, z.xss, k.spb, k.mulb, k.divb, alpha(s0), npad, npad, M,
+                                   mpad, cnt, Ks(), sKs, z.part, d_mu()));
     return 0;
   }
   // caller-provided cross covariances Ks_s (N x M doubles, xa) and, with `full`, K**_s (M x M, xb)
   int build_given(int s0, int cnt) {
-    HIPCHK(c, c->dbg1.ensure((size_t)std::max(N, M) * M * sizeof(double)));
     for (int i = 0; i < cnt; ++i) {
-      HIPCHK(c, hipMemcpyAsync(c->dbg1.p, r.xa + (size_t)(s0 + i) * N * M, (size_t)N * M * 8, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL((pad_rect_kernel<T>), dim3(mpad / 64, npad / 4), dim3(64, 4), 0, st, (const double*)c->dbg1.p, N,
+      HIPCHK(c, hipMemcpyAsync(zs.given, r.xa + (size_t)(s0 + i) * N * M, (size_t)N * M * 8, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL((pad_rect_kernel<T>), dim3(mpad / 64, npad / 4), dim3(64, 4), 0, st, (const double*)zs.given, N,
                          M, npad, mpad, Ks() + (size_t)i * sKs);
       if (full) {
-        HIPCHK(c, hipMemcpyAsync(c->dbg1.p, r.xb + (size_t)(s0 + i) * M * M, (size_t)M * M * 8, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL((pad_rect_kernel<T>), dim3(mpad / 64, mpad / 4), dim3(64, 4), 0, st, (const double*)c->dbg1.p,
-                           M, M, mpad, mpad, c->kss.as<T>() + (size_t)i * sKss);
+        HIPCHK(c, hipMemcpyAsync(zs.given, r.xb + (size_t)(s0 + i) * M * M, (size_t)M * M * 8, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL((pad_rect_kernel<T>), dim3(mpad / 64, mpad / 4), dim3(64, 4), 0, st, (const double*)zs.given,
+                           M, M, mpad, mpad, z.Kss + (size_t)i * sKss);
       }
     }
     return column_sums(s0, cnt);
   }
   int build_quad_z(int s0, int cnt) {
     hipLaunchKernelGGL((quad_z_kernel<T>), dim3(mpad / 64, npad / 4, cnt), dim3(64, 4), 0, st, c->dX.as<double>(),
-                       (const double*)d_xa, (const double*)d_xb, k.mulb, k.divb, k.spb, N, npad, M, mpad, D, Ks(), sKs);
+                       (const double*)zs.xa, (const double*)zs.xb, k.mulb, k.divb, k.spb, N, npad, M, mpad, D, Ks(), sKs);
     if (r.qg)
-      hipLaunchKernelGGL(quad_grad_prep_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st, (const double*)d_xa,
-                         (const double*)d_xb, k.divb, k.spb, M, mpad, D, d_mut, d_qcon);
+      hipLaunchKernelGGL(quad_grad_prep_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st, (const double*)zs.xa,
+                         (const double*)zs.xb, k.divb, k.spb, M, mpad, D, zs.mut, z.qcon);
     if (full)  // gpc_quad_cov: Gamma where CROSS puts K** (quad_mix.h)
       hipLaunchKernelGGL((quad_gamma_kernel<T>), dim3(mpad / 64, mpad / 4, cnt), dim3(64, 4), 0, st,
-                         (const double*)d_xa, (const double*)d_xb, k.divb, k.spb, M, mpad, D, c->kss.as<T>(), sKss);
+                         (const double*)zs.xa, (const double*)zs.xb, k.divb, k.spb, M, mpad, D, z.Kss, sKss);
     return column_sums(s0, cnt);
   }
   int column_sums(int s0, int cnt) {  // (the builders without a fused mean product)
@@ -2914,23 +2897,18 @@ struct RhsCall {
     T* const Ksa = Ks() + (size_t)a * sKs;
     T* const Va = V() + (size_t)a * sKs;
     GemmArgs g = tri_product_args<T>(po, s0 + a, lch, Ksa, Va, sKs, mpad, mpad);  // V = W R | G = L R
-    // (problems whose product is a handful of 128-tiles keep the 64-tile product + column-sum pass: latency regime.
-    // Decided by the problem size only, never by the number of samples: the two forms add in different orders, and a
-    // sample of a batch must carry the bits of its single evaluation)
-    const long long tiles128 = (long long)(npad / TILE) * (mpad / TILE);
-    if (lch && !full && !grad && tiles128 >= 64) {
+    if (lch && colsq_form()) {
       // the variance needs the column sums of squares of V only: the product's epilogue forms them per tile row and V
       // is never written (gemm.h: EPI = 1); a small reduction over the tile rows follows
       const int tmr = npad / TILE;
-      HIPCHK(c, c->dbg3.ensure((size_t)cnt * tmr * mpad * 8));  // (the whole chunk: no reallocation between runs)
       int* qctr = c->tile_ctr.as<int>() + (size_t)gpc_ctx::MAXG * gpc_ctx::CTR_PER_GROUP;
       HIPCHK(c, hipMemsetAsync(qctr, 0, CTR_STRIDE * sizeof(int), st));
       HIPCHK(c, tm.mark1());
-      g.colsq = c->dbg3.as<double>();
+      g.colsq = z.colsq;
       HIPCHK(c, launch_gemm_colsq<T>(st, g, len, qctr));
       if (last) HIPCHK(c, tm.mark2());
       hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mpad + 255) / 256, len), dim3(256), 0, st,
-                         (const double*)c->dbg3.as<double>(), tmr, mpad, d_v() + (size_t)a * mpad);
+                         (const double*)z.colsq, tmr, mpad, d_v() + (size_t)a * mpad);
       return 0;
     }
     HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
@@ -2941,22 +2919,22 @@ struct RhsCall {
       // Q = W^T V (L_chol: the upper triangular A operand W^T, k from the tile row's diagonal block on) | G as it is
       const T* Qs = Va;
       if (lch) {
-        T* const Qa = c->qb.as<T>() + (size_t)a * sKs;
+        T* const Qa = z.Q + (size_t)a * sKs;
         HIPCHK(c, launch_gemm<T>(st, wt_product_args(g, Va, Qa), true, true, len));
         Qs = Qa;
       }
       if (r.rhs == RhsRequest::QUAD_Z) {
         if (last) HIPCHK(c, tm.mark2());  // (quad_grad: with Q)
         hipLaunchKernelGGL((quad_grad_tile_kernel<T, true>), dim3(mpad / CT, npad / CT, len), dim3(256), 0, st,
-                           (const double*)c->dX.as<double>(), D, (const double*)d_mut,
-                           (const double*)(d_qcon + (size_t)a * (D + 1) * mpad), alpha(s0 + a), npad, Qs, sKs,
+                           (const double*)c->dX.as<double>(), D, (const double*)zs.mut,
+                           (const double*)(z.qcon + (size_t)a * (D + 1) * mpad), alpha(s0 + a), npad, Qs, sKs,
                            k.spb + (size_t)a * SP_STRIDE, lch ? 1 : 0, N, M, mpad,
-                           c->gpart.as<double>() + (size_t)a * gnt * gpl * D * mpad);
+                           z.gpart + (size_t)a * gnt * gpl * D * mpad);
       } else {
         GPC_COV_DISPATCH(cross_grad_tile_kernel, T, po->cd, dim3(mpad / CT, npad / CT, len), dim3(256), 0, st, po->cd,
-                         k.xsb + (size_t)a * npad * D, (const double*)(c->xss.as<double>() + (size_t)a * mpad * D),
+                         k.xsb + (size_t)a * npad * D, (const double*)(z.xss + (size_t)a * mpad * D),
                          k.spb + (size_t)a * SP_STRIDE, alpha(s0 + a), npad, Qs, sKs, lch ? 1 : 0, N, npad, M, mpad,
-                         c->gpart.as<double>() + (size_t)a * gnt * 2 * D * mpad);
+                         z.gpart + (size_t)a * gnt * 2 * D * mpad);
       }
     }
     if (full) {
@@ -2965,7 +2943,7 @@ struct RhsCall {
         GemmArgs f;
         f.A = lch ? (const void*)(V() + (size_t)i * sKs) : (const void*)(Ks() + (size_t)i * sKs);
         f.B = V() + (size_t)i * sKs;
-        f.C = c->kss.as<T>() + (size_t)i * sKss;
+        f.C = z.Kss + (size_t)i * sKss;
         f.sA = f.sB = f.sC = 0;
         f.lda = f.ldb = f.ldc = mpad;
         f.M = f.N = mpad, f.K = npad;
@@ -2981,18 +2959,18 @@ struct RhsCall {
   int reduce_gradients(int s0, int cnt) {
     if (r.qg && !r.want_quad)  // no product: the alpha weights only, the whole chunk in one launch
       hipLaunchKernelGGL((quad_grad_tile_kernel<T, false>), dim3(mpad / CT, npad / CT, cnt), dim3(256), 0, st,
-                         (const double*)c->dX.as<double>(), D, (const double*)d_mut, (const double*)d_qcon, alpha(s0), npad,
-                         (const T*)nullptr, 0LL, k.spb, 0, N, M, mpad, c->gpart.as<double>());
+                         (const double*)c->dX.as<double>(), D, (const double*)zs.mut, (const double*)z.qcon, alpha(s0), npad,
+                         (const T*)nullptr, 0LL, k.spb, 0, N, M, mpad, z.gpart);
     if (!grad) return 0;
-    double* d_dmu = c->gres.as<double>();
+    double* d_dmu = z.gres;
     double* d_ds2 = d_dmu + (size_t)chunk * mpad * D;
     if (r.qg)
       hipLaunchKernelGGL(quad_grad_reduce_kernel, dim3((mpad + 255) / 256, gpl * D, cnt), dim3(256), 0, st,
-                         (const double*)c->gpart.as<double>(), gnt, D, gpl, M, mpad, (const double*)d_xb,
-                         (const double*)d_qcon, d_dmu, (size_t)chunk * mpad * D);
+                         (const double*)z.gpart, gnt, D, gpl, M, mpad, (const double*)zs.xb,
+                         (const double*)z.qcon, d_dmu, (size_t)chunk * mpad * D);
     else
       hipLaunchKernelGGL(grad_reduce_kernel, dim3((mpad + 255) / 256, cnt), dim3(256), 0, st,
-                         (const double*)c->gpart.as<double>(), gnt, D, mpad, k.mulb, k.divb, d_dmu, d_ds2);
+                         (const double*)z.gpart, gnt, D, mpad, k.mulb, k.divb, d_dmu, d_ds2);
     HIPCHK(c, hipMemcpyAsync(hgrad, d_dmu, (size_t)gpl * chunk * mpad * D * 8, hipMemcpyDeviceToHost, st));
     return 0;
   }
@@ -3010,15 +2988,14 @@ struct RhsCall {
       HIPCHK(c, hipMemcpyAsync(hmu, d_mu(), (size_t)cnt * mpad * 8, hipMemcpyDeviceToHost, st));
       if (want_quad) HIPCHK(c, hipMemcpyAsync(hv, d_v(), (size_t)cnt * mpad * 8, hipMemcpyDeviceToHost, st));
     }
-    if (r.draw) return draw_chunk<T>(po, *r.draw, s0, cnt, M, d_mu(), hdraw);
+    if (r.draw) return draw_chunk<T>(po, *r.draw, s0, cnt, M, z, r.draw->nsd ? zs.nsd : nullptr, hdraw);
     if (full) {
-      HIPCHK(c, c->dbg3.ensure((size_t)M * M * 8));
       for (int i = 0; i < cnt; ++i) {
         dim3 gn((M + 63) / 64, (M + 3) / 4), blk(64, 4);
-        hipLaunchKernelGGL((extract_kernel<T>), gn, blk, 0, st, (const T*)(c->kss.as<T>() + (size_t)i * sKss),
-                           mpad, M, 2, c->dbg3.as<double>());
+        hipLaunchKernelGGL((extract_kernel<T>), gn, blk, 0, st, (const T*)(z.Kss + (size_t)i * sKss),
+                           mpad, M, 2, zs.fullout);
         double* dst = r.full + (size_t)(s0 + i) * M * M;
-        HIPCHK(c, hipMemcpyAsync(hfull ? hfull : dst, c->dbg3.p, (size_t)M * M * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(hfull ? hfull : dst, zs.fullout, (size_t)M * M * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if (hfull) memcpy(dst, hfull, (size_t)M * M * 8);
       }
@@ -3158,47 +3135,36 @@ int predict_impl(gpc_post* po, const double* xstar, int M, double* fmu, double* 
 //   fused   (no covariance wanted and at least 64 128-tiles) C is never written: the product's epilogue reads K_ab and
 //           forms the weighted column sums of squares per tile row (gemm.h: EPI = 2), colpart_reduce_kernel adds the
 //           tile rows in ascending order.  No atomics.
-// Scratch per sample: 2 npad (mapad + mbpad) + mapad mbpad elements and small vectors, chunked over the samples under
-// the same budget as rhs_products.
+// Scratch: CovScratch per sample and CovShared once per call, carved from a block of the call's own (c->covs:
+// gpc_lookahead_batch runs this while its resident state is live), chunked over the samples under the same budget as
+// rhs_products.
+
 template <typename T>
 int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int Mb, const double* w, int w_per_sample,
                  double* fs2b, double* cov, double* wsq, double* keep = nullptr) {
   gpc_ctx* c = po->ctx;
   const int S = po->S, N = po->N, D = po->D, npad = po->npad;
-  const int mapad = pad_tile(Ma), mbpad = pad_tile(Mb), mmax = std::max(mapad, mbpad);
+  const int mapad = pad_tile(Ma), mbpad = pad_tile(Mb);
   hipStream_t st = c->st;
   const long long sKa = (long long)npad * mapad, sKb = (long long)npad * mbpad, sC = (long long)mapad * mbpad;
   const int tma = mapad / TILE;
-  const bool fused = wsq && !cov && (long long)tma * (mbpad / TILE) >= 64;
-  const size_t part_per = (size_t)(npad / CT) * mmax * 8 + (fused ? (size_t)tma * mbpad * 8 : 0);
-  const size_t per = (2ull * npad * (mapad + mbpad) + (size_t)sC) * sizeof(T) + part_per +
-                     ((size_t)(mapad + mbpad) * D + mapad + 1 + 2 * mbpad) * 8;
-  const size_t held = c->ks.bytes + c->vb.bytes + c->kss.bytes;
-  const bool fits = (size_t)S * per <= held && (size_t)S * (sKa + sKb) * sizeof(T) <= std::min(c->ks.bytes, c->vb.bytes) &&
-                    (size_t)S * sC * sizeof(T) <= c->kss.bytes;
-  const int chunk = plan_chunk(c, S, per, 0, held, fits, 0, false, [&](size_t budget) {
+  const bool fused = cov_fused_form(mapad, mbpad, wsq != nullptr, cov != nullptr);
+  const size_t per = ScratchCarver::count<CovScratch<T>>(1, npad, mapad, mbpad, D, fused);
+  const size_t shared = ScratchCarver::count<CovShared>(Ma, Mb, D, cov != nullptr), held = c->covs.bytes;
+  const int chunk = plan_chunk(c, S, per, shared, held, shared + (size_t)S * per <= held, 0, false, [&](size_t budget) {
     return "gpc_predict_cov: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
            std::to_string(npad) + ", Ma_pad = " + std::to_string(mapad) + ", Mb_pad = " + std::to_string(mbpad) +
            ") exceeds the device memory budget (" + std::to_string(budget >> 10) + " KB)";
   });
   if (!chunk) return -2;
-  HIPCHK(c, c->ks.ensure((size_t)chunk * (sKa + sKb) * sizeof(T)));
-  HIPCHK(c, c->vb.ensure((size_t)chunk * (sKa + sKb) * sizeof(T)));
-  HIPCHK(c, c->kss.ensure((size_t)chunk * sC * sizeof(T)));
-  HIPCHK(c, c->xss.ensure(((size_t)chunk * (mapad + mbpad) + Ma + Mb) * D * 8));
-  HIPCHK(c, c->pout.ensure((size_t)chunk * mbpad * 2 * 8));
-  HIPCHK(c, c->daux.ensure((size_t)chunk * (mapad + 1) * 8));  // [weights: chunk x mapad | the products' factors: chunk]
-  HIPCHK(c, c->dbg2.ensure((size_t)chunk * (npad / CT) * mmax * 8));
-  if (fused) HIPCHK(c, c->dbg3.ensure((size_t)chunk * tma * mbpad * 8));
-  if (cov) HIPCHK(c, c->dbg1.ensure((size_t)Ma * Mb * 8));
-  double* xsa = c->xss.as<double>();
-  double* xsbq = xsa + (size_t)chunk * mapad * D;
-  double* d_xa = xsbq + (size_t)chunk * mbpad * D;
-  double* d_xb = d_xa + (size_t)Ma * D;
-  double* d_w = c->daux.as<double>();
-  double* d_al = d_w + (size_t)chunk * mapad;
-  double* d_v = c->pout.as<double>();
-  double* d_q = d_v + (size_t)chunk * mbpad;
+  HIPCHK(c, c->covs.ensure(shared + (size_t)chunk * per));
+  CovScratch<T> z;  // (carved once, for the planned chunk: its size is the stride of [v | q] and of the weights)
+  CovShared zs;
+  CARVECHK(c, "gpc_predict_cov", ScratchCarver::carve(z, c->covs.p, chunk, npad, mapad, mbpad, D, fused) +
+                                     ScratchCarver::carve(zs, c->covs.as<char>() + (size_t)chunk * per, Ma, Mb, D, cov != nullptr));
+  double *const xsa = z.xsa, *const xsbq = z.xsbq, *const d_xa = zs.xa, *const d_xb = zs.xb;
+  double *const d_w = z.w, *const d_al = d_w + (size_t)chunk * mapad;
+  double *const d_v = z.vq, *const d_q = d_v + (size_t)chunk * mbpad;
   c->pin.begin();
   c->pin.begin_gather();
   CallTimer tm{c, CallTimer::wanted(c, npad)};
@@ -3227,21 +3193,17 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
       hw[(size_t)chunk * mapad + i] = po->lchol[s0 + i] ? -1.0 / po->sp[(size_t)(s0 + i) * SP_STRIDE + SP_SL] : 1.0;
     }
     HIPCHK(c, hipMemcpyAsync(d_w, hw.data(), hw.size() * 8, hipMemcpyHostToDevice, st));
-    T* Ksa = c->ks.as<T>();
-    T* Ksb = Ksa + (size_t)chunk * sKa;
-    T* Va = c->vb.as<T>();
-    T* Vb = Va + (size_t)chunk * sKa;
-    T* Kab = c->kss.as<T>();
+    T *const Ksa = z.Ksa, *const Ksb = z.Ksb, *const Va = z.Va, *const Vb = z.Vb, *const Kab = z.Kab;
     hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mapad * D + 255) / 256), cnt), dim3(256), 0, st,
                        (const double*)d_xa, Ma, mapad, D, mulb, divb, xsa);
     hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mbpad * D + 255) / 256), cnt), dim3(256), 0, st,
                        (const double*)d_xb, Mb, mbpad, D, mulb, divb, xsbq);
-    // (the builder's fused mean product lands in dbg2 and is not used: the covariance does not involve alpha)
+    // (the builder's fused mean product lands in z.part and is not used: the covariance does not involve alpha)
     const double* al = po->alpha.as<double>() + (size_t)s0 * npad;
     GPC_COV_DISPATCH(cross_tile_kernel, T, po->cd, dim3(mapad / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, xsb,
-                     (const double*)xsa, spb, al, npad, N, npad, Ma, mapad, Ksa, sKa, c->dbg2.as<double>());
+                     (const double*)xsa, spb, al, npad, N, npad, Ma, mapad, Ksa, sKa, z.part);
     GPC_COV_DISPATCH(cross_tile_kernel, T, po->cd, dim3(mbpad / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, xsb,
-                     (const double*)xsbq, spb, al, npad, N, npad, Mb, mbpad, Ksb, sKb, c->dbg2.as<double>());
+                     (const double*)xsbq, spb, al, npad, N, npad, Mb, mbpad, Ksb, sKb, z.part);
     hipLaunchKernelGGL((cross_kernel<T>), dim3(mbpad / 64, mapad / 4, cnt), dim3(64, 4), 0, st, po->cd,
                        (const double*)xsa, (const double*)xsbq, spb, Ma, mapad, Mb, mbpad, Kab, sC);
     HIPCHK(c, hipGetLastError());
@@ -3281,7 +3243,7 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
         f.ep_alpha = d_al + a;
         f.ep_w = d_w + (size_t)a * mapad;
         f.ep_sw = mapad;
-        f.colsq = c->dbg3.as<double>() + (size_t)a * tma * mbpad;
+        f.colsq = z.wpart + (size_t)a * tma * mbpad;
         HIPCHK(c, launch_gemm_wsq<T>(st, f, len));
         hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mbpad + 255) / 256, len), dim3(256), 0, st,
                            (const double*)f.colsq, tma, mbpad, d_q + (size_t)a * mbpad);
@@ -3312,9 +3274,9 @@ int cov_products(gpc_post* po, const double* xa, int Ma, const double* xb, int M
     if (cov) {
       for (int i = 0; i < cnt; ++i) {
         hipLaunchKernelGGL((extract_rect_kernel<T>), dim3((Mb + 63) / 64, (Ma + 3) / 4), dim3(64, 4), 0, st,
-                           (const T*)(Kab + (size_t)i * sC), mbpad, Ma, Mb, c->dbg1.as<double>());
+                           (const T*)(Kab + (size_t)i * sC), mbpad, Ma, Mb, zs.cov);
         double* dst = cov + (size_t)(s0 + i) * Ma * Mb;
-        HIPCHK(c, hipMemcpyAsync(hcov ? hcov : dst, c->dbg1.p, (size_t)Ma * Mb * 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(c, hipMemcpyAsync(hcov ? hcov : dst, zs.cov, (size_t)Ma * Mb * 8, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
         if (hcov) memcpy(dst, hcov, (size_t)Ma * Mb * 8);
       }
@@ -3358,33 +3320,6 @@ struct GramClock {  // one timed device section of a call: the Gram passes of "g
 };
 
 // ---- gpc_lookahead_batch: q greedy look-ahead steps on the device (lookahead_batch.h) ----------------------------------
-// The resident state of ALL samples, carved from one allocation (c->lab): the score of a step needs every sample, so the
-// step loop cannot be chunked over them.  C comes first (its rows are read 16 bytes at a time); every double block has
-// an even length; the block that is downloaded (the gains, then the indices) is contiguous.
-struct LabScratch {
-  double *C, *lpan, *part, *gains, *score, *v, *noise, *w, *sd, *gain_out;
-  int *idx, *cur, *chosen;
-  size_t out_bytes = 0;
-  static size_t even(size_t n) { return (n + 1) & ~(size_t)1; }
-  void layout(ScratchCarver& sc, int S, int Mr, int Mc, int ld, int q) {
-    const size_t s = S, nslab = (Mr + LB_T - 1) / LB_T;
-    C = sc.take(s * (Mr + Mc) * ld);
-    lpan = sc.take(even(s * q * (Mr + ld)));
-    part = sc.take(s * nslab * ld);
-    gains = sc.take(s * ld);
-    score = sc.take(ld);
-    v = sc.take(s * ld);
-    noise = sc.take(s * ld);
-    w = sc.take(even(s * Mr));
-    sd = sc.take(even(s));
-    const size_t before_out = sc.bytes;
-    gain_out = sc.take(even(s * q));
-    idx = sc.take<int>(even(q));
-    out_bytes = sc.bytes - before_out;
-    cur = sc.take<int>(2);
-    chosen = sc.take<int>(ld);
-  }
-};
 
 template <typename T>
 int lookahead_batch_impl(gpc_post* po, const double* xr, int Mr, const double* xc, int Mc, const double* w, int w_per_sample,
@@ -3473,33 +3408,20 @@ int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* 
   const long long sP = (long long)npad * ld;
   const int nt64 = npad / CT, tmr = npad / TILE, nseg = gram_segments(npad);
   const size_t gper = (size_t)mb * Dp * (diag ? 1 : Dp);  // doubles of a sample's Gram result
-  const size_t per = 2 * (size_t)sP * sizeof(T) +
-                     ((size_t)nt64 * ld + (diag ? (size_t)tmr * ld : 0) + (nseg > 1 ? nseg : 0) * gper + gper + ld + 1 +
-                      (size_t)mb * D + (size_t)npad * D + SP_STRIDE + 2 * D) * 8;
-  const size_t held = c->ks.bytes + c->vb.bytes;
-  const bool fits = (size_t)S * per <= held && (size_t)S * sP * sizeof(T) <= std::min(c->ks.bytes, c->vb.bytes);
-  const int chunk = plan_chunk(c, S, per, 0, held, fits, 0, false, [&](size_t budget) {
+  const size_t per = ScratchCarver::count<BlockScratch<T>>(1, npad, D, true, false, diag ? 1 : D + 1, diag, (size_t)0), shared = (size_t)M * D * 8;
+  const size_t held = c->cs.bytes;
+  const int chunk = plan_chunk(c, S, per, shared, held, shared + (size_t)S * per <= held, 0, false, [&](size_t budget) {
     return "gpc_grad_post: the scratch of one sample with one query block (" + std::to_string(per) + " bytes: N_pad = " +
            std::to_string(npad) + ", D = " + std::to_string(D) + ", block = " + std::to_string(mb) +
            " queries) exceeds the device memory budget (" + std::to_string(budget) + " bytes)";
   });
   if (!chunk) return -2;
-  HIPCHK(c, c->ks.ensure((size_t)chunk * sP * sizeof(T)));
-  HIPCHK(c, c->vb.ensure((size_t)chunk * sP * sizeof(T)));
-  HIPCHK(c, c->dbg2.ensure((size_t)chunk * nt64 * ld * 8));
-  if (diag) HIPCHK(c, c->dbg3.ensure((size_t)chunk * tmr * ld * 8));
-  if (nseg > 1) HIPCHK(c, c->gpart.ensure((size_t)chunk * nseg * gper * 8));
-  HIPCHK(c, c->gres.ensure((size_t)chunk * gper * 8));
-  HIPCHK(c, c->pout.ensure((size_t)chunk * ld * 8));
-  HIPCHK(c, c->daux.ensure((size_t)chunk * 8));
-  HIPCHK(c, c->xss.ensure(((size_t)chunk * mb + M) * D * 8));
-  T* const P = c->ks.as<T>();
-  T* const V = c->vb.as<T>();
-  double* const xsq = c->xss.as<double>();
-  double* const d_xa = xsq + (size_t)chunk * mb * D;
-  double* const d_mean = c->pout.as<double>();
-  double* const d_gram = c->gres.as<double>();
-  double* const d_f0 = c->daux.as<double>();
+  HIPCHK(c, c->cs.ensure(shared + (size_t)chunk * per));
+  BlockScratch<T> z;
+  CARVECHK(c, "gpc_grad_post", ScratchCarver::carve(z, c->cs.p, chunk, npad, D, true, false, diag ? 1 : D + 1, diag, (size_t)0));
+  T *const P = z.P, *const V = z.V;
+  double *const xsq = z.xsq, *const d_mean = z.mean, *const d_gram = z.gram, *const d_f0 = z.f0;
+  double* const d_xa = reinterpret_cast<double*>(c->cs.as<char>() + (size_t)chunk * per);  // shared: the raw queries
   c->pin.begin();
   c->pin.begin_gather();
   CallTimer tm{c, CallTimer::wanted(c, npad)};
@@ -3520,9 +3442,9 @@ int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* 
                          (const double*)(d_xa + (size_t)q0 * D), mq, mb, D, k.mulb, k.divb, xsq);
       GPC_COV_DISPATCH(grad_operand_tile_kernel, T, po->cd, dim3(mb / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
                        (const double*)xsq, k.spb, k.mulb, k.divb, po->alpha.as<double>() + (size_t)s0 * npad, npad, N, npad,
-                       mq, mb, P, sP, c->dbg2.as<double>(), d_f0);
+                       mq, mb, P, sP, z.part, d_f0);
       hipLaunchKernelGGL(colpart_reduce_kernel, dim3((ld + 255) / 256, cnt), dim3(256), 0, st,
-                         (const double*)c->dbg2.as<double>(), nt64, ld, d_mean);
+                         (const double*)z.part, nt64, ld, d_mean);
       HIPCHK(c, hipGetLastError());
       HIPCHK(c, tm.mark1());
       // the products of every run of equal L_chol, then (second pass) what reduces them
@@ -3531,7 +3453,7 @@ int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* 
         if (diag && lch) {
           int* qctr = c->tile_ctr.as<int>() + (size_t)gpc_ctx::MAXG * gpc_ctx::CTR_PER_GROUP;
           HIPCHK(c, hipMemsetAsync(qctr, 0, CTR_STRIDE * sizeof(int), st));
-          g.colsq = c->dbg3.as<double>() + (size_t)a * tmr * ld;
+          g.colsq = z.colsq + (size_t)a * tmr * ld;
           HIPCHK(c, launch_gemm_colsq<T>(st, g, len, qctr));
         } else {
           HIPCHK(c, launch_gemm<T>(st, g, false, true, len));
@@ -3544,10 +3466,10 @@ int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* 
       rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
         if (diag && lch)  // [b][a * mb + j]: the panel's own column order
           hipLaunchKernelGGL(colpart_reduce_kernel, dim3((ld + 255) / 256, len), dim3(256), 0, st,
-                             (const double*)(c->dbg3.as<double>() + (size_t)a * tmr * ld), tmr, ld, d_gram + (size_t)a * gper);
+                             (const double*)(z.colsq + (size_t)a * tmr * ld), tmr, ld, d_gram + (size_t)a * gper);
         else
           HIPCHK(c, launch_block_gram<T>(st, (lch ? V : P) + (size_t)a * sP, V + (size_t)a * sP, sP, npad, mb, Dp, len, diag,
-                                         nseg > 1 ? c->gpart.as<double>() + (size_t)a * nseg * gper : nullptr,
+                                         nseg > 1 ? z.gpart + (size_t)a * nseg * gper : nullptr,
                                          d_gram + (size_t)a * gper));
         return 0;
       });
@@ -3615,41 +3537,20 @@ int hess_impl(gpc_post* po, const double* xstar, int M, bool var, double* fmu, d
   const int npl = hess_planes(D), nset = var ? 2 : 1;
   const size_t gper = var ? (size_t)mb * Dp * Dp : 0;   // doubles of a sample's Gram result
   const size_t hper = (size_t)nset * npl * mb;          // ... of its reduced Hessian sums
-  const size_t per = ((var ? 2 : 1) * (size_t)sP + (var ? (size_t)sQ : 0)) * sizeof(T) +
-                     ((size_t)nt64 * ld + (size_t)nt64 * hper + hper + (nseg > 1 ? nseg : 0) * gper + gper + ld + 1 +
-                      (size_t)mb * D + (size_t)npad * D + SP_STRIDE + 2 * D) * 8;
-  const size_t held = c->ks.bytes + c->vb.bytes + c->qb.bytes + c->dbg3.bytes;
-  const bool fits = (size_t)S * per <= held && (size_t)S * sP * sizeof(T) <= c->ks.bytes &&
-                    (!var || ((size_t)S * sP * sizeof(T) <= c->vb.bytes && (size_t)S * sQ * sizeof(T) <= c->qb.bytes)) &&
-                    (size_t)S * nt64 * hper * 8 <= c->dbg3.bytes;
-  const int chunk = plan_chunk(c, S, per, 0, held, fits, 0, false, [&](size_t budget) {
+  const size_t per = ScratchCarver::count<BlockScratch<T>>(1, npad, D, var, var, var ? Dp : 0, false, hper);
+  const size_t shared = (size_t)M * D * 8, held = c->cs.bytes;
+  const int chunk = plan_chunk(c, S, per, shared, held, shared + (size_t)S * per <= held, 0, false, [&](size_t budget) {
     return "gpc_predict_hess: the scratch of one sample with one query block (" + std::to_string(per) +
            " bytes: N_pad = " + std::to_string(npad) + ", D = " + std::to_string(D) + ", block = " + std::to_string(mb) +
            " queries) exceeds the device memory budget (" + std::to_string(budget) + " bytes)";
   });
   if (!chunk) return -2;
-  HIPCHK(c, c->ks.ensure((size_t)chunk * sP * sizeof(T)));
-  if (var) {
-    HIPCHK(c, c->vb.ensure((size_t)chunk * sP * sizeof(T)));
-    HIPCHK(c, c->qb.ensure((size_t)chunk * sQ * sizeof(T)));
-    if (nseg > 1) HIPCHK(c, c->gpart.ensure((size_t)chunk * nseg * gper * 8));
-    HIPCHK(c, c->gres.ensure((size_t)chunk * gper * 8));
-  }
-  HIPCHK(c, c->dbg2.ensure((size_t)chunk * nt64 * ld * 8));
-  HIPCHK(c, c->dbg3.ensure((size_t)chunk * nt64 * hper * 8));
-  HIPCHK(c, c->qcon.ensure((size_t)chunk * hper * 8));
-  HIPCHK(c, c->pout.ensure((size_t)chunk * ld * 8));
-  HIPCHK(c, c->daux.ensure((size_t)chunk * 8));
-  HIPCHK(c, c->xss.ensure(((size_t)chunk * mb + M) * D * 8));
-  T* const P = c->ks.as<T>();
-  T* const V = c->vb.as<T>();
-  T* const Q = c->qb.as<T>();
-  double* const xsq = c->xss.as<double>();
-  double* const d_xa = xsq + (size_t)chunk * mb * D;
-  double* const d_mean = c->pout.as<double>();
-  double* const d_gram = c->gres.as<double>();
-  double* const d_hpart = c->dbg3.as<double>();
-  double* const d_hsum = c->qcon.as<double>();
+  HIPCHK(c, c->cs.ensure(shared + (size_t)chunk * per));
+  BlockScratch<T> z;
+  CARVECHK(c, "gpc_predict_hess", ScratchCarver::carve(z, c->cs.p, chunk, npad, D, var, var, var ? Dp : 0, false, hper));
+  T *const P = z.P, *const V = z.V, *const Q = z.Q;
+  double *const xsq = z.xsq, *const d_mean = z.mean, *const d_gram = z.gram, *const d_hpart = z.hpart, *const d_hsum = z.hsum;
+  double* const d_xa = reinterpret_cast<double*>(c->cs.as<char>() + (size_t)chunk * per);  // shared: the raw queries
   c->pin.begin();
   c->pin.begin_gather();
   CallTimer tm{c, CallTimer::wanted(c, npad)};
@@ -3672,9 +3573,9 @@ int hess_impl(gpc_post* po, const double* xstar, int M, bool var, double* fmu, d
                          (const double*)(d_xa + (size_t)q0 * D), mq, mb, D, k.mulb, k.divb, xsq);
       GPC_COV_DISPATCH(grad_operand_tile_kernel, T, po->cd, dim3(mb / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
                        (const double*)xsq, k.spb, k.mulb, k.divb, alpha, npad, N, npad, mq, mb, P, sP,
-                       c->dbg2.as<double>(), c->daux.as<double>());
+                       z.part, z.f0);
       hipLaunchKernelGGL(colpart_reduce_kernel, dim3((ld + 255) / 256, cnt), dim3(256), 0, st,
-                         (const double*)c->dbg2.as<double>(), nt64, ld, d_mean);
+                         (const double*)z.part, nt64, ld, d_mean);
       HIPCHK(c, hipGetLastError());
       if (var) {
         HIPCHK(c, tm.mark1());
@@ -3695,7 +3596,7 @@ int hess_impl(gpc_post* po, const double* xstar, int M, bool var, double* fmu, d
         HIPCHK(c, tm.mark2());
         rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
           HIPCHK(c, launch_block_gram<T>(st, (lch ? V : P) + (size_t)a * sP, V + (size_t)a * sP, sP, npad, mb, Dp, len, false,
-                                         nseg > 1 ? c->gpart.as<double>() + (size_t)a * nseg * gper : nullptr,
+                                         nseg > 1 ? z.gpart + (size_t)a * nseg * gper : nullptr,
                                          d_gram + (size_t)a * gper));
           return 0;
         });
@@ -3777,31 +3678,6 @@ inline void nh_plane_of(const CovDesc& cd, int p, int* mode, int* dim) {
     *mode = p == cd.D ? NH_SF : NH_SHAPE;
   }
 }
-
-// Device buffers of a chunk of `cnt` samples, carved from one allocation (all doubles; vectors are [plane][sample][npad])
-struct NhScratch {
-  int npad = 0, ppl = 0, cov_N = 0, noise_N = 0, mean_N = 0, nt = 0, ntl = 0, npairs = 0, nd2 = 0;
-  double *Q, *B, *Op, *X, *Y, *E, *diagq, *upart, *gpart, *gsum, *grpart, *grsum, *d2part, *d2sum;
-  void layout(ScratchCarver& sc, int cnt, int npad_, int cov_N_, int noise_N_, int mean_N_, int nd2_) {
-    npad = npad_, cov_N = cov_N_, noise_N = noise_N_, mean_N = mean_N_, nd2 = nd2_;
-    ppl = cov_N + noise_N, nt = npad / CT, ntl = nt * (nt + 1) / 2, npairs = ppl * (ppl + 1) / 2;
-    const size_t n2 = (size_t)npad * npad, c = cnt;
-    Q = sc.take(c * n2);
-    B = sc.take(c * ppl * n2);
-    Op = sc.take(c * n2);
-    X = sc.take(c * (ppl + mean_N) * npad);
-    Y = sc.take(c * (ppl + mean_N) * npad);
-    E = sc.take(c * noise_N * npad);
-    diagq = sc.take(c * npad);
-    upart = sc.take(c * nt * npad);
-    gpart = sc.take(c * nt * nt * 2);
-    gsum = sc.take(c * cov_N * 2);
-    grpart = sc.take(c * nt * nt * npairs);
-    grsum = sc.take(c * npairs);
-    d2part = sc.take(c * ntl * nd2);
-    d2sum = sc.take(c * nd2);
-  }
-};
 
 // One covariance plane of `cnt` samples: the operand into Op, u into X[p], the two sums into gsum[p]
 int nh_launch_plane(gpc_ctx* c, const CovDesc& cd, const NhScratch& z, int cnt, int p, const double* xs, const double* sp,
@@ -4031,30 +3907,6 @@ int nll_hess_impl(gpc_post* po, const double* dm, int mean_N, const double* dsn2
 }
 
 // ---- gpc_cv_grad: the leave-one-out objective's weight matrix and its contraction (cvgrad.h) ---------------------------
-// Device buffers of a chunk of `cnt` samples, carved from one allocation (all doubles; vectors are [sample][npad])
-struct CvgScratch {
-  double *Q, *QC, *M, *diagq, *u, *b, *part, *out;
-  // the block that is downloaded, in order: gsum [cnt][cov_N] | diagG | beta | q | cw, [cnt][npad] each
-  double *gsum, *diagG, *beta, *q, *cw;
-  size_t out_bytes = 0;
-  void layout(ScratchCarver& sc, int cnt, int npad, int cov_N) {
-    const size_t n2 = (size_t)npad * npad, nt = npad / CT, ntl = nt * (nt + 1) / 2, c = cnt;
-    Q = sc.take(c * n2);
-    QC = sc.take(c * n2);
-    M = sc.take(c * n2);
-    diagq = sc.take(c * npad);
-    u = sc.take(c * npad);
-    b = sc.take(c * npad);
-    part = sc.take(c * ntl * cov_N);
-    const size_t before_out = sc.bytes;
-    out = gsum = sc.take(c * cov_N);
-    diagG = sc.take(c * npad);
-    beta = sc.take(c * npad);
-    q = sc.take(c * npad);
-    cw = sc.take(c * npad);
-    out_bytes = sc.bytes - before_out;
-  }
-};
 
 // <d_p K, G> of `cnt` samples into gsum[b][p], diag(G) into diagG: the contraction and the sum of its per-tile partials
 int cvg_launch_trace(gpc_ctx* c, const CovDesc& cd, int cnt, int N, int npad, const double* xs, const double* sp,
@@ -4166,32 +4018,6 @@ inline std::vector<int> hg_plane_cols(const CovDesc& cd) {
   return cols;
 }
 
-// Device buffers of a chunk of `cnt` samples and one super-block of `msb` queries, carved from one allocation (all
-// doubles; vectors are [vector][sample][npad], panels [sample][npad][msb])
-struct HgScratch {
-  double *Op, *KP, *VP, *Qa, *X, *Y, *Vn, *tmp, *tpart, *upart, *mupart, *cpart, *csum, *dpart, *dsum, *xss, *qs;
-  void layout(ScratchCarver& sc, int cnt, int npad, int D, int P, int nvv, int ngp, int msb, bool var, int nout) {
-    const size_t n2 = (size_t)npad * npad, nt = npad / CT, nch = npad / TRC, np = npad, mm = msb, c = cnt;
-    Op = sc.take(var ? c * n2 : 0);
-    KP = sc.take(var ? c * np * mm : 0);
-    VP = sc.take(var ? c * np * mm : 0);
-    Qa = sc.take(var ? c * np * mm : 0);
-    dpart = sc.take(var ? c * nt * (1 + (size_t)nvv) * mm : 0);
-    dsum = sc.take(var ? c * ((size_t)ngp + nvv) * mm : 0);
-    mupart = sc.take(var ? c * nt * mm : 0);
-    Vn = sc.take(var ? c * (size_t)nvv * np : 0);
-    X = sc.take(c * P * np);
-    Y = sc.take(c * P * np);
-    tmp = sc.take(c * np);
-    tpart = sc.take(c * nch * np);
-    upart = sc.take(c * nt * np);
-    cpart = sc.take(c * nt * nout * mm);
-    csum = sc.take(c * nout * mm);
-    xss = sc.take(c * mm * D);
-    qs = sc.take(c);
-  }
-};
-
 // Per chunk of samples and super-block of queries (all of the call's queries unless the budget says otherwise), with
 // the variance:
 //   panel K* = k(X, x*) (cross_tile_kernel),  Qs = W^T (W K*) (L_chol; q = Qs / sl) | L K* (low noise; q = -Qs)
@@ -4232,8 +4058,8 @@ int hyp_grad_impl(gpc_post* po, const double* xstar, int M, bool var, const doub
   if (!chunk) return -2;
   const long long sK = (long long)npad * msb;
   HIPCHK(c, c->hgs.ensure((size_t)chunk * per));
-  HIPCHK(c, c->xss.ensure((size_t)M * D * 8));
-  double* const d_xa = c->xss.as<double>();
+  HIPCHK(c, c->cs.ensure((size_t)M * D * 8));  // (the raw queries: all the consumers' block holds for this call)
+  double* const d_xa = c->cs.as<double>();
   HgScratch z;
   CallTimer tm{c, CallTimer::wanted(c, npad)};
   HIPCHK(c, hipMemcpyAsync(d_xa, xstar, (size_t)M * D * 8, hipMemcpyHostToDevice, st));
@@ -5263,18 +5089,15 @@ int append_block_impl(gpc_post* po, int k, const double* m_star, const double* s
   hipStream_t st = c->st;
   const int npn = pad_tile(n + k);
   const int kq = ((k + BA_R - 1) / BA_R) * BA_R, kp = pad_tile(k);
-  // scratch of one sample: four n x k panels (Bx, V | G, Pt | H, GS), the k x k products, three vectors, and the
-  // three slabs of the k x k factorization
-  const size_t panel = (size_t)npn * kq * 8;
   const bool use_gemm = c->block_engine ? c->block_engine == 2 : k >= BA_GEMM_MIN_K;
   c->block_engine_ran = use_gemm ? 2 : 1;
-  const size_t tpanel = use_gemm ? (size_t)npn * kp * sizeof(T) : 0;  // (MFMA engine: B, V | G and W^T V in the storage type)
-  const size_t per = 4 * panel + 3 * tpanel + (size_t)kq * kq * 8 + 3 * (size_t)kq * 8 + 3 * (size_t)kp * kp * sizeof(T) + 64;
+  const int np_scr = std::max(npn, po->npad);  // the padded size after the growth below
+  const size_t per = ScratchCarver::count<AppendScratch<T>>(1, np_scr, kq, kp, use_gemm);
   const bool grow = npn > po->npad;
   const size_t grow_bytes = grow ? (size_t)S * npn * ((size_t)npn * 2 * sizeof(T) + 8) : 0;
-  // the scratch is the context's cross-covariance buffer (gpc_predict's Ks): kept between calls, so that an
-  // acquisition loop pays no allocation per batch; budgeted like gpc_predict_cov's when it has to grow
-  const size_t held = c->ks.bytes;
+  // the scratch is the consumers' block: kept between calls, so that an acquisition loop pays no allocation per
+  // batch; budgeted like gpc_predict_cov's when it has to grow
+  const size_t held = c->cs.bytes;
   // (a forced budget plans on every call, pool_drain included: it is the tests' way into the chunked path, not a
   // setting for an acquisition loop, which without it allocates only when the scratch or the storage grows.
   // GPC_MEM_BUDGET_MB budgets the SCRATCH; the device's real free memory has to hold the grown storage as well)
@@ -5328,8 +5151,8 @@ int append_block_impl(gpc_post* po, int k, const double* m_star, const double* s
     hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), S), dim3(256), 0, st, c->dX.as<double>(),
                        n + k, npad, D, c->mulb.as<double>(), c->divb.as<double>(), c->xs.as<double>());
   }
-  HIPCHK(c, c->ks.ensure((size_t)chunk * per));
-  DevBuf& scr = c->ks;
+  HIPCHK(c, c->cs.ensure((size_t)chunk * per));
+  AppendScratch<T> z;
   bool any_high = false, any_low = false;
   for (int s = 0; s < S; ++s) (po->lchol[s] ? any_high : any_low) = true;
   // gpc_last_timing: device time of the call (after the growth) and of the skinny products (the last chunk's)
@@ -5338,21 +5161,11 @@ int append_block_impl(gpc_post* po, int k, const double* m_star, const double* s
   HIPCHK(c, tm.start());
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
-    HIPCHK(c, hipMemsetAsync(scr.p, 0, (size_t)cnt * per, st));
-    double* Bx = scr.as<double>();
-    double* V = Bx + (size_t)cnt * sP;    // high noise: W B;  low noise: G = -A B
-    double* Pt = V + (size_t)cnt * sP;    // high noise: (V^T W / sl), k x n;  low noise: H = G W22^T, n x k
-    double* GS = Pt + (size_t)cnt * sP;   // low noise: G Si
-    double* Cm = GS + (size_t)cnt * sP;   // V^T V | B^T G
-    double* ev = Cm + (size_t)cnt * kq * kq;
-    double* tv = ev + (size_t)cnt * kq;
-    double* zv = tv + (size_t)cnt * kq;
-    T* fA = reinterpret_cast<T*>(zv + (size_t)cnt * kq);
-    T* fW = fA + (size_t)cnt * kp * kp;
-    T* fT = fW + (size_t)cnt * kp * kp;
-    T* Bt = fT + (size_t)cnt * kp * kp;
-    T* Vt = Bt + (size_t)cnt * npad * kp;
-    T* Qt = Vt + (size_t)cnt * npad * kp;
+    CARVECHK(c, "gpc_post_append_block", ScratchCarver::carve(z, c->cs.p, cnt, npad, kq, kp, use_gemm));
+    HIPCHK(c, hipMemsetAsync(c->cs.p, 0, (size_t)cnt * per, st));
+    double *const Bx = z.Bx, *const V = z.V, *const Pt = z.Pt, *const GS = z.GS, *const Cm = z.Cm;
+    double *const ev = z.ev, *const tv = z.tv, *const zv = z.zv;
+    T *const fA = z.fA, *const fW = z.fW, *const fT = z.fT, *const Bt = z.Bt, *const Vt = z.Vt, *const Qt = z.Qt;
     const double* parc = d_par + (size_t)s0 * BA_STRIDE;
     T* Ac = po->A.as<T>() + (size_t)s0 * sM;
     T* Wc = po->W.as<T>() + (size_t)s0 * sM;
@@ -5483,25 +5296,6 @@ int append_block_check(gpc_post* po, int k, const char* fn) {
 }
 
 // ---- removal of k points (remove.h has the algebra and the kernels) ------------------------------------------------
-// Device buffers of one sweep over a chunk of `cnt` samples, carved from the context's cross-covariance buffer
-template <typename T>
-struct RmScratch {
-  double *V, *C, *H, *Th, *aI, *tv, *zv;
-  T *fA, *fW, *fT;
-  void layout(ScratchCarver& sc, int cnt, int npn, int kq, int kp) {
-    const size_t c = cnt, panel = (size_t)npn * kq, mp = RM_P + kq;
-    V = sc.take(c * panel);    // A[R, I]: the L-side carrier | the low-noise panel
-    C = sc.take(c * panel);    // W[I, R]: the W-side carrier
-    H = sc.take(c * panel);    // low noise: A[R, I] Wq^T
-    Th = sc.take(c * mp * mp);
-    aI = sc.take(c * kq);
-    tv = sc.take(c * kq);
-    zv = sc.take(c * kq);
-    fA = sc.take<T>(c * kp * kp);  // the three slabs of the k x k factorization
-    fW = sc.take<T>(c * kp * kp);
-    fT = sc.take<T>(c * kp * kp);
-  }
-};
 
 // One sweep: the kk <= RM_KMAX sorted rows idx[] leave a posterior of po->N rows.  New storage at the padded size of
 // n = N - kk (pool first), the old one to the pool.  dead[s] != 0: the sample is stale already and is only compacted;
@@ -5550,17 +5344,16 @@ int remove_sweep(gpc_post* po, int kk, const int* idx, int chunk, std::vector<do
   RM_CHK(nA.ensure((size_t)S * sMn * sizeof(T)));
   RM_CHK(nW.ensure((size_t)S * sMn * sizeof(T)));
   RM_CHK(nal.ensure((size_t)S * npn * sizeof(double)));
-  RM_CHK(c->ks.ensure((size_t)chunk * per));
+  RM_CHK(c->cs.ensure((size_t)chunk * per + maps.size() * sizeof(int)));
   RM_CHK(c->dvec.ensure((size_t)S * BA_STRIDE * 8));
   RM_CHK(c->scal.ensure((size_t)S * 16));
-  RM_CHK(c->dbg2.ensure(maps.size() * sizeof(int)));
   double* d_par = c->dvec.as<double>();
   double* d_logdet = c->scal.as<double>();
   int* d_info = reinterpret_cast<int*>(d_logdet + S);
-  const int* d_rmap = c->dbg2.as<int>();
+  int* const d_rmap = reinterpret_cast<int*>(c->cs.as<char>() + (size_t)chunk * per);
   const int* d_idx = d_rmap + npn;
   // (pageable sources: the copies are staged before the calls return)
-  RM_CHK(hipMemcpy(c->dbg2.p, maps.data(), maps.size() * sizeof(int), hipMemcpyHostToDevice));
+  RM_CHK(hipMemcpy(d_rmap, maps.data(), maps.size() * sizeof(int), hipMemcpyHostToDevice));
   RM_CHK(hipMemcpy(d_par, par.data(), par.size() * 8, hipMemcpyHostToDevice));
   RM_CHK(hipMemsetAsync(c->scal.p, 0, (size_t)S * 16, st));
   bool any_high = false, any_low = false;
@@ -5569,7 +5362,10 @@ int remove_sweep(gpc_post* po, int kk, const int* idx, int chunk, std::vector<do
   RmScratch<T> z;
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
-    ScratchCarver::carve(z, c->ks.p, cnt, npn, kq, kp);
+    if (ScratchCarver::carve(z, c->cs.p, cnt, npn, kq, kp) != 0) {
+      c->err = "gpc_post_remove: internal error: a scratch array is misaligned";
+      return fail(-1);
+    }
     const double* parc = d_par + (size_t)s0 * BA_STRIDE;
     const T* Ao = po->A.as<T>() + (size_t)s0 * sMo;
     const T* Wo = po->W.as<T>() + (size_t)s0 * sMo;
@@ -5665,8 +5461,9 @@ int remove_impl(gpc_post* po, int k, const int* idx, const double* ym, int* ok) 
   const size_t per = remove_per_sample<T>(po->N, k);
   const int np1 = pad_tile(po->N - std::min(k, RM_KMAX));
   const size_t new_bytes = (size_t)S * np1 * ((size_t)np1 * 2 * sizeof(T) + 8);
-  const size_t held = c->ks.bytes;
-  const int chunk = plan_chunk(c, S, per, 0, held, (size_t)S * per <= held, new_bytes, false, [&](size_t budget) {
+  // (shared: the row maps of a sweep)
+  const size_t shared = ((size_t)np1 + std::min(k, RM_KMAX)) * sizeof(int), held = c->cs.bytes;
+  const int chunk = plan_chunk(c, S, per, shared, held, shared + (size_t)S * per <= held, new_bytes, false, [&](size_t budget) {
     return "gpc_post_remove: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
            std::to_string(np1) + ", k = " + std::to_string(k) + ") exceeds the device memory budget (" +
            std::to_string(budget >> 10) + " KB beside " + std::to_string(new_bytes >> 10) + " KB of compacted storage)";
@@ -5842,15 +5639,16 @@ int cv_loo_impl(gpc_post* po, double* dmu, double* s2, double* quad, double* log
   const int S = po->S, N = po->N, npad = po->npad;
   const long long sM = (long long)npad * npad;
   c->cv_engine_ran = 0;
-  const size_t per = 5 * (size_t)npad * 8;
-  const int chunk = plan_chunk(c, S, per, 0, c->ks.bytes, (size_t)S * per <= c->ks.bytes, 0, false, [&](size_t budget) {
+  const size_t per = ScratchCarver::count<CvLooScratch>(1, npad);
+  const int chunk = plan_chunk(c, S, per, 0, c->cs.bytes, (size_t)S * per <= c->cs.bytes, 0, false, [&](size_t budget) {
     return "gpc_cv: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " + std::to_string(npad) +
            ", F = 0, k_max = 1) exceeds the device memory budget (" + std::to_string(budget >> 10) + " KB)";
   });
   if (!chunk) return -2;
   double* d_par = nullptr;
   if (int rc = cv_upload_par(po, &d_par)) return rc;
-  HIPCHK(c, c->ks.ensure((size_t)chunk * per));
+  HIPCHK(c, c->cs.ensure((size_t)chunk * per));
+  CvLooScratch z;
   std::unique_ptr<double[]> spare;
   c->pin.begin();
   double* h = landing_block(c, (size_t)chunk * per, spare);
@@ -5859,14 +5657,14 @@ int cv_loo_impl(gpc_post* po, double* dmu, double* s2, double* quad, double* log
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
     const size_t pl = (size_t)cnt * npad;
-    double* d = c->ks.as<double>();
+    CARVECHK(c, "gpc_cv", ScratchCarver::carve(z, c->cs.p, cnt, npad));
+    double* const d = z.dmu;  // (the five planes are one block: one download)
     HIPCHK(c, tm.start());
     HIPCHK(c, tm.mark1());
     hipLaunchKernelGGL((cv_diag_kernel<T>), dim3((N + CV_T - 1) / CV_T, cnt), dim3(256), 0, st,
                        (const T*)(po->A.as<T>() + (size_t)s0 * sM), (const T*)(po->W.as<T>() + (size_t)s0 * sM), sM, npad, N,
                        (const double*)(po->alpha.as<double>() + (size_t)s0 * npad),
-                       (const double*)(d_par + (size_t)s0 * BA_STRIDE), d, d + pl, d + 2 * pl, d + 3 * pl,
-                       reinterpret_cast<int*>(d + 4 * pl));
+                       (const double*)(d_par + (size_t)s0 * BA_STRIDE), z.dmu, z.s2, z.quad, z.logdet, z.info);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, tm.mark2());
     HIPCHK(c, tm.stop());
@@ -5903,9 +5701,8 @@ int cv_fold_impl(gpc_post* po, int F, const int* fold_ptr, const int* fold_idx, 
   const size_t kk = (size_t)kp * kp;
   // scratch of one sample: G, its inverse factor and the factorization's third slab for every fold, the vectors u, the
   // two output planes, [quad | logdet | ld | info] per fold, and engine 2's gathered panels
-  const size_t per = (size_t)F * (3 * kk + kp) * 8 + (engine == 2 ? (size_t)F * npad * kp * 8 : 0) + 2 * (size_t)npad * 8 +
-                     (size_t)F * 32 + 64;
-  int chunk = plan_chunk(c, S, per, 0, c->ks.bytes, (size_t)S * per <= c->ks.bytes, 0, false, [&](size_t budget) {
+  const size_t per = ScratchCarver::count<CvFoldScratch>(1, npad, F, kp, engine == 2);
+  int chunk = plan_chunk(c, S, per, 0, c->cs.bytes, (size_t)S * per <= c->cs.bytes, 0, false, [&](size_t budget) {
     return "gpc_cv: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " + std::to_string(npad) +
            ", F = " + std::to_string(F) + ", k_max = " + std::to_string(kmax) + ") exceeds the device memory budget (" +
            std::to_string(budget >> 10) + " KB)";
@@ -5919,7 +5716,8 @@ int cv_fold_impl(gpc_post* po, int F, const int* fold_ptr, const int* fold_idx, 
   int* d_idx = d_ptr + F + 1;
   HIPCHK(c, hipMemcpy(d_ptr, fold_ptr, (size_t)(F + 1) * sizeof(int), hipMemcpyHostToDevice));
   HIPCHK(c, hipMemcpy(d_idx, fold_idx, (size_t)total * sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(c, c->ks.ensure((size_t)chunk * per));
+  HIPCHK(c, c->cs.ensure((size_t)chunk * per));
+  CvFoldScratch z;
   const size_t out_doubles = 2 * (size_t)chunk * npad + 4 * (size_t)chunk * F;
   std::unique_ptr<double[]> spare;
   c->pin.begin();
@@ -5928,17 +5726,11 @@ int cv_fold_impl(gpc_post* po, int F, const int* fold_ptr, const int* fold_idx, 
   CallTimer tm{c, true};
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0), np = cnt * F;
-    double* G = c->ks.as<double>();
-    double* Wf = G + (size_t)np * kk;
-    double* Tm = Wf + (size_t)np * kk;
-    double* uv = Tm + (size_t)np * kk;
-    double* o_dmu = uv + (size_t)np * kp;  // the block that is downloaded: [dmu | s2 | quad | logdet | ld | info]
-    double* o_s2 = o_dmu + (size_t)cnt * npad;
-    double* o_quad = o_s2 + (size_t)cnt * npad;
-    double* o_logdet = o_quad + np;
-    double* d_ld = o_logdet + np;
-    int* d_info = reinterpret_cast<int*>(d_ld + np);
-    double* panel = d_ld + 2 * (size_t)np;  // (engine 2; 8-byte aligned behind the ints)
+    CARVECHK(c, "gpc_cv", ScratchCarver::carve(z, c->cs.p, cnt, npad, F, kp, engine == 2));
+    double *const G = z.G, *const Wf = z.Wf, *const Tm = z.Tm, *const panel = z.panel, *const uv = z.uv;
+    double *const o_dmu = z.o_dmu, *const o_s2 = z.o_s2, *const o_quad = z.o_quad, *const o_logdet = z.o_logdet;
+    double* const d_ld = z.ld;
+    int* const d_info = z.info;
     HIPCHK(c, tm.start());
     HIPCHK(c, hipMemsetAsync(G, 0, 3 * (size_t)np * kk * 8, st));
     HIPCHK(c, hipMemsetAsync(o_dmu, 0xff, 2 * (size_t)cnt * npad * 8, st));  // NaN: points in no fold
@@ -6053,20 +5845,7 @@ int paths_create_impl(gpc_post* po, gpc_paths* pa, unsigned long long seed, int 
   // scratch of one sample: three fp64 N_pad x kq panels (p(X), P, V1) and, for the MFMA engine, three N_pad x kp
   // panels in the storage type (and 64 spare bytes)
   const long long sP = (long long)npad * kq, sK = (long long)npad * kp;
-  double *pX, *P, *V1;
-  T *Bt, *Vt, *Qt;
-  auto layout = [&](ScratchCarver& sc, size_t cnt) {
-    pX = sc.take(cnt * sP);
-    P = sc.take(cnt * sP);
-    V1 = sc.take(cnt * sP);
-    Bt = sc.take<T>(use_gemm ? cnt * sK : 0);
-    Vt = sc.take<T>(use_gemm ? cnt * sK : 0);
-    Qt = sc.take<T>(use_gemm ? cnt * sK : 0);
-    sc.take<char>(cnt * 64);
-  };
-  ScratchCarver count;
-  layout(count, 1);
-  const size_t per = count.bytes, held = c->ks.bytes;
+  const size_t per = ScratchCarver::count<PathsCreateScratch<T>>(1, npad, kq, kp, use_gemm), held = c->cs.bytes;
   const int chunk = plan_chunk(c, S, per, 0, held, (size_t)S * per <= held, 0, false, [&](size_t budget) {
     return "gpc_paths_create: the scratch of one sample (" + std::to_string(per >> 10) + " KB: N_pad = " +
            std::to_string(npad) + ", R = " + std::to_string(R) + ") exceeds the device memory budget (" +
@@ -6102,7 +5881,8 @@ int paths_create_impl(gpc_post* po, gpc_paths* pa, unsigned long long seed, int 
   HIPCHK(c, hipMemcpyAsync(d_par, par.data(), par.size() * 8, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(d_ym, ym, (size_t)S * N * 8, hipMemcpyHostToDevice, st));
   HIPCHK(c, hipMemcpyAsync(d_nsd, noise_sd, (size_t)S * N * 8, hipMemcpyHostToDevice, st));
-  HIPCHK(c, c->ks.ensure((size_t)chunk * per));
+  HIPCHK(c, c->cs.ensure((size_t)chunk * per));
+  PathsCreateScratch<T> z;
   c->ms_total = c->ms_factor = 0;
   CallTimer tm{c, true};
   HIPCHK(c, tm.start());
@@ -6127,8 +5907,9 @@ int paths_create_impl(gpc_post* po, gpc_paths* pa, unsigned long long seed, int 
   const long long sM = (long long)npad * npad;
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
-    ScratchCarver carver(c->ks.p);
-    layout(carver, cnt);
+    CARVECHK(c, "gpc_paths_create", ScratchCarver::carve(z, c->cs.p, cnt, npad, kq, kp, use_gemm));
+    double *const pX = z.pX, *const P = z.P, *const V1 = z.V1;
+    T *const Bt = z.Bt, *const Vt = z.Vt, *const Qt = z.Qt;
     const double* parc = d_par + (size_t)s0 * BA_STRIDE;
     const T* Wc = po->W.as<T>() + (size_t)s0 * sM;
     const T* Ac = po->A.as<T>() + (size_t)s0 * sM;
@@ -6214,32 +5995,19 @@ int paths_eval_impl(gpc_paths* pa, const double* xstar, int M, double* f, double
   const int engine = c->paths_engine ? c->paths_engine : PA_DEFAULT_ENGINE;
   c->paths_engine_ran = engine;
   const size_t fbytes = (size_t)M * R * S * 8, dfbytes = df ? fbytes * D : 0;
-  const size_t opsz = (size_t)std::max(npad, fpad) * mpad;  // one operand matrix (elements)
-  const size_t xq_per = (size_t)mpad * D * 8;
-  // the unfused engine's scratch: the operand, the product, and v and the weights widened to whole tiles
-  double *op = nullptr, *Cb = nullptr, *Vp = nullptr, *Wp = nullptr;
-  auto engine_layout = [&](ScratchCarver& sc, size_t cnt) {
-    op = sc.take(cnt * opsz);
-    Cb = sc.take(cnt * mpad * rp);
-    Vp = sc.take(cnt * npad * rp);
-    Wp = sc.take(cnt * fpad * rp);
-  };
-  ScratchCarver count;
-  if (engine == 2) engine_layout(count, 1);
-  const size_t eng_per = count.bytes, per = xq_per + eng_per, shared = fbytes + dfbytes;
-  const size_t held = c->dout.bytes + c->gres.bytes + c->xss.bytes + (engine == 2 ? c->ks.bytes : 0);
+  const size_t per = ScratchCarver::count<PathsEvalScratch>(1, npad, fpad, mpad, rp, D, engine == 2);
+  const size_t shared = ScratchCarver::count<PathsEvalShared>(M, R, S, D, df != nullptr), held = c->cs.bytes;
   const int chunk = plan_chunk(c, S, per, shared, held, shared + (size_t)S * per <= held, 0, false, [&](size_t budget) {
     return "gpc_paths_eval: the results (" + std::to_string(shared >> 10) + " KB) and the scratch of one "
            "sample (" + std::to_string(per >> 10) + " KB: M_pad = " + std::to_string(mpad) + ") exceed the device "
            "memory budget (" + std::to_string(budget >> 10) + " KB)";
   });
   if (!chunk) return -2;
-  HIPCHK(c, c->dout.ensure(fbytes));
-  if (df) HIPCHK(c, c->gres.ensure(dfbytes));
-  HIPCHK(c, c->xss.ensure((size_t)chunk * xq_per + (size_t)M * D * 8));
-  if (engine == 2) HIPCHK(c, c->ks.ensure((size_t)chunk * eng_per));
-  double* xq = c->xss.as<double>();
-  double* d_x = xq + (size_t)chunk * mpad * D;
+  HIPCHK(c, c->cs.ensure(shared + (size_t)chunk * per));
+  PathsEvalScratch z;
+  PathsEvalShared zs;
+  CARVECHK(c, "gpc_paths_eval", ScratchCarver::carve(zs, c->cs.as<char>() + (size_t)chunk * per, M, R, S, D, df != nullptr));
+  double* const d_x = zs.x;
   c->pin.begin();
   c->ms_total = c->ms_factor = 0;
   CallTimer tm{c, true};
@@ -6248,6 +6016,8 @@ int paths_eval_impl(gpc_paths* pa, const double* xstar, int M, double* f, double
   HIPCHK(c, tm.mark1());
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
+    CARVECHK(c, "gpc_paths_eval", ScratchCarver::carve(z, c->cs.p, cnt, npad, fpad, mpad, rp, D, engine == 2));
+    double *const xq = z.xq, *const op = z.op, *const Cb = z.Cb, *const Vp = z.Vp, *const Wp = z.Wp;
     const long long tot = (long long)mpad * D;
     hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)((tot + 255) / 256), cnt), dim3(256), 0, st, (const double*)d_x, M,
                        mpad, D, (const double*)(pa->mul.as<double>() + (size_t)s0 * D),
@@ -6271,16 +6041,14 @@ int paths_eval_impl(gpc_paths* pa, const double* xstar, int M, double* f, double
     a.R = R;
     a.kq = kq;
     a.nslots = nslots;
-    a.f = c->dout.as<double>();
-    a.df = df ? c->gres.as<double>() : nullptr;
+    a.f = zs.f;
+    a.df = df ? zs.df : nullptr;
     a.S_out = S;
     a.s_out0 = s0;
     if (engine != 2) {
       HIPCHK(c, launch_paths_eval(st, pa->cd, a, cnt));
       continue;
     }
-    ScratchCarver carver(c->ks.p);
-    engine_layout(carver, cnt);
     const dim3 blk(64, 4);
     hipLaunchKernelGGL(paths_widen_kernel, dim3(rp / 64, npad / 4, cnt), blk, 0, st, a.v, npad, kq, rp, Vp);
     hipLaunchKernelGGL(paths_widen_kernel, dim3(rp / 64, fpad / 4, cnt), blk, 0, st, a.wt, fpad, kq, rp, Wp);
@@ -6319,8 +6087,8 @@ int paths_eval_impl(gpc_paths* pa, const double* xstar, int M, double* f, double
     HIPCHK(c, hipGetLastError());
   }
   HIPCHK(c, tm.mark2());
-  HIPCHK(c, hipMemcpyAsync(f, c->dout.p, fbytes, hipMemcpyDeviceToHost, st));
-  if (df) HIPCHK(c, hipMemcpyAsync(df, c->gres.p, dfbytes, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(f, zs.f, fbytes, hipMemcpyDeviceToHost, st));
+  if (df) HIPCHK(c, hipMemcpyAsync(df, zs.df, dfbytes, hipMemcpyDeviceToHost, st));
   HIPCHK(c, tm.stop());
   HIPCHK(c, hipStreamSynchronize(st));
   c->pin.finish();
@@ -6382,36 +6150,9 @@ int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const dou
   const int gnq = var ? (grad ? 1 + 2 * D : 1) : 0;  // quantities of the pair kernel
   const int npl = gpl + (var && grad ? 2 : 0);
   const size_t ss = (size_t)mpad * D;
-  // the scratch, one allocation: the measures' block that the samples share, then the arrays of `cnt` samples
-  double *d_mut, *d_sgt, *d_wpad, *d_mu, *d_sg, *d_w;
-  auto shared_layout = [&](ScratchCarver& sc) {
-    d_mut = sc.take(ss);
-    d_sgt = sc.take(ss);
-    d_wpad = sc.take(mpad);
-    d_mu = sc.take((size_t)M * D);
-    d_sg = sc.take((size_t)M * D);
-    d_w = sc.take(M);
-  };
-  double *d_con, *d_cpart, *d_rpart, *d_zbar, *d_v, *d_q, *d_tpart, *d_zqpart, *d_gpart, *d_gmpart, *d_res;
   const size_t n_res = 3 * (size_t)mpad + 2 + (size_t)npl * ss;  // doubles of a sample's results
-  auto layout = [&](ScratchCarver& sc, size_t cnt) {
-    d_con = sc.take(cnt * (D + 1) * mpad);
-    d_cpart = sc.take(cnt * gnt * mpad);
-    d_rpart = sc.take(cnt * mnt * npad);
-    d_zbar = sc.take(cnt * npad);
-    d_v = sc.take(var ? cnt * npad : 0);
-    d_q = sc.take(var ? cnt * npad : 0);
-    d_tpart = sc.take(var ? cnt * nch * npad : 0);
-    d_zqpart = sc.take(var ? cnt * gnt * mpad : 0);
-    d_gpart = sc.take(cnt * gnt * gpl * D * mpad);
-    d_gmpart = sc.take(cnt * mnt * gnq * mpad);
-    // the results, one block: [za | zq | gw | scal (2 per sample) | planes of the tile pass | planes of the pair pass]
-    d_res = sc.take(cnt * n_res);
-  };
-  ScratchCarver count_shared, count_per;
-  shared_layout(count_shared);
-  layout(count_per, 1);
-  const size_t shared = count_shared.bytes, per = count_per.bytes;
+  const size_t shared = ScratchCarver::count<QuadMixShared>(M, mpad, D);
+  const size_t per = ScratchCarver::count<QuadMixScratch>(1, npad, mpad, D, var, grad);
   const int chunk = plan_chunk(c, S, per, shared, c->qmix.bytes, (size_t)S * per + shared <= c->qmix.bytes, 0, false, [&](size_t budget) {
     return "gpc_quad_mix: the scratch of one sample (" + std::to_string((per + shared) >> 10) + " KB: N_pad = " +
            std::to_string(npad) + ", M_pad = " + std::to_string(mpad) + ", D = " + std::to_string(D) +
@@ -6421,9 +6162,13 @@ int quad_mix_impl(gpc_post* po, const double* mu, const double* sigma, const dou
   HIPCHK(c, c->qmix.ensure((size_t)chunk * per + shared));
   HIPCHK(c, c->spb.ensure((size_t)chunk * SP_STRIDE * 8));
   HIPCHK(c, c->divb.ensure((size_t)chunk * D * 8));
-  ScratchCarver carver(c->qmix.p);
-  shared_layout(carver);
-  layout(carver, chunk);
+  QuadMixShared zs;
+  QuadMixScratch z;
+  ScratchCarver::carve(zs, c->qmix.p, M, mpad, D);
+  ScratchCarver::carve(z, c->qmix.as<char>() + shared, chunk, npad, mpad, D, var, grad);
+  double *const d_mut = zs.mut, *const d_sgt = zs.sgt, *const d_wpad = zs.wpad, *const d_mu = zs.mu, *const d_sg = zs.sg, *const d_w = zs.w;
+  double *const d_con = z.con, *const d_cpart = z.cpart, *const d_rpart = z.rpart, *const d_zbar = z.zbar, *const d_v = z.v, *const d_q = z.q;
+  double *const d_tpart = z.tpart, *const d_zqpart = z.zqpart, *const d_gpart = z.gpart, *const d_gmpart = z.gmpart, *const d_res = z.res;
   double* d_za = d_res;
   double* d_zq = d_za + (size_t)chunk * mpad;
   double* d_gw = d_zq + (size_t)chunk * mpad;
@@ -7010,8 +6755,8 @@ void gpc_destroy(gpc_ctx* c) {
   (void)hipStreamSynchronize(c->st);
   DevBuf* bufs[] = {&c->dX,   &c->dY,  &c->gpts,  &c->gxs, &c->mA,    &c->mW,  &c->mT,   &c->xs,   &c->spb,  &c->mulb, &c->divb,
                     &c->dvec, &c->rvec,  &c->zvec, &c->avec, &c->scal, &c->parts, &c->gout, &c->diagq,
-                    &c->dmb,  &c->dsn2b, &c->mg,  &c->ng,   &c->ks,   &c->vb,   &c->xss,  &c->pout, &c->kss,
-                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qb, &c->gpart, &c->gres, &c->qcon, &c->qmix, &c->nhs, &c->hgs, &c->lab, &c->zb, &c->fb, &c->dout, &c->daux, &c->tile_ctr, &c->rsv_tbl};
+                    &c->dmb,  &c->dsn2b, &c->mg,  &c->ng,   &c->cs,   &c->covs,
+                    &c->dbg1, &c->dbg2,  &c->dbg3, &c->tpart, &c->qmix, &c->nhs, &c->hgs, &c->lab, &c->tile_ctr, &c->rsv_tbl};
   for (auto& g : c->graphs)
     if (g.exec) (void)hipGraphExecDestroy(g.exec);
   for (DevBuf* b : bufs) b->release();
@@ -7050,6 +6795,13 @@ int gpc_debug_chunk_plan(int S, unsigned long long per, unsigned long long share
                          int clamp_to_one) {
   if (S <= 0 || per == 0) return -2;
   return chunk_from_budget(S, (size_t)per, (size_t)shared, (size_t)budget, clamp_to_one != 0);
+}
+
+int gpc_debug_scratch_bytes(const char* name, int dtype, const int* dims, int ndims, unsigned long long* per,
+                            unsigned long long* shared, int* misaligned) {
+  if (!name || !dims || ndims < 1 || !per || !shared || !misaligned || (dtype != GPC_F64 && dtype != GPC_F32)) return -2;
+  return dtype == GPC_F64 ? scratch_bytes_of<double>(name, dims, ndims, per, shared, misaligned)
+                          : scratch_bytes_of<float>(name, dims, ndims, per, shared, misaligned);
 }
 
 int gpc_max_n(int dtype) {

@@ -420,7 +420,7 @@ int gpc_post_recompute_K(gpc_post* post, int cnt, const int* idx, const double* 
  * own factorization had failed, a noise value that is not the fitted scalar, or a sample named by the test option
  * "append_fail_mask") leaves sample s exactly as it was apart from the growth: the caller recomputes exactly those
  * samples with gpc_post_recompute.  Scratch (four fp64 N_pad x k panels per sample, three more in the storage type
- * for the MFMA engine) lives in the context's cross-covariance buffer, is budgeted like gpc_predict_cov's
+ * for the MFMA engine) lives in the context's consumer scratch block, is budgeted like gpc_predict_cov's
  * (GPC_MEM_BUDGET_MB) and chunked over the samples.  gpc_last_timing: the device section after the growth, and
  * the products with W.
  * Returns -2 with a message for k < 1, N + k > gpc_max_n, data that was not extended first, a posterior of the
@@ -457,7 +457,7 @@ int gpc_post_append_block_K(gpc_post* post, int k, const double* Ks, const doubl
  * sample whose Q_II is not positive definite, a sample whose own factorization had failed, or one named by the test
  * option "remove_fail_mask") leaves a stale sample in the compacted storage: the caller recomputes exactly those with
  * gpc_post_recompute[_K].  Scratch (three fp64 N_pad x k panels, Theta and the k x k factorization per sample) lives
- * in the context's cross-covariance buffer, is budgeted like gpc_post_append_block's (GPC_MEM_BUDGET_MB) and chunked
+ * in the context's consumer scratch block, is budgeted like gpc_post_append_block's (GPC_MEM_BUDGET_MB) and chunked
  * over the samples; the bits of a sample depend neither on the batch nor on the chunk.  No host synchronisation
  * between the panels of a sweep.  gpc_last_timing: the device section, and the panel loops alone (summed over chunks and sweeps).
  * Returns -2 with a message, the posterior untouched, for k < 1, k >= N, indices that are unsorted, repeated or out
@@ -833,6 +833,21 @@ int gpc_debug_workspace_hash(gpc_ctx* ctx, int dtype, int which, int sample, uns
  * -2 for S <= 0 or per = 0.                                                                                          */
 int gpc_debug_chunk_plan(int S, unsigned long long per, unsigned long long shared, unsigned long long budget,
                          int clamp_to_one);
+/* Debug, HOST ONLY (no device needed): the device scratch a posterior consumer declares (its layout, counted as the
+ * call itself counts it).  per: bytes of one sample, what the planner above divides by (a draw's includes the three
+ * slabs it factors in); shared: bytes the call needs once; misaligned: arrays that would miss their alignment when
+ * the layout is carved for three samples on a 256-byte aligned base (nothing is allocated or dereferenced) -- 0, or
+ * the call itself would fail.  name and dims (N is the number of training points, not padded):
+ *   "rhs"          N, M, D, S, kind (0 cross, 1 quadrature, 2 given Ks, 3 gradient observations), want_quad, full,
+ *                  grad, quad_grad, R (draws; 0: none), points of a gradient-observation posterior
+ *   "predict_cov"  N, Ma, Mb, D, want_cov, want_wsq          "grad_post" N, M, D, diag   "predict_hess" N, M, D, var
+ *   "append_block" N + k, k, engine                          "remove" N, k               "cv_loo" N
+ *   "cv_fold"      N, F, k_max, engine                       "paths_create" N, R, solve engine
+ *   "paths_eval"   N, M, R, S, D, F_pad, engine, grad        "nll_hess" N, cov_N, noise_N, mean_N, nd2
+ *   "cv_grad"      N, cov_N      "hyp_grad" N, D, P, nvv, ngp, msb, var, nout            "quad_mix" N, M, D, var, grad
+ * -2 for an unknown name, a wrong ndims or a null argument.                                                          */
+int gpc_debug_scratch_bytes(const char* name, int dtype, const int* dims, int ndims, unsigned long long* per,
+                            unsigned long long* shared, int* misaligned);
 /* Debug, HOST ONLY (no device needed): the index arithmetic of the GEMM launch forms (gemm.h) enumerated for one
  * launch of `ntiles` tiles and `batch` samples -- tile_of_bx and xcd_order, which the kernels call themselves, and
  * queue_of / queue_total / queue_item / flat_queue_item, the host's restatement of gemm_persist_kernel's queues.

@@ -354,8 +354,9 @@ def _budget_worker(budget_mb, q):
             return
         finally:
             del os.environ["GPC_MEM_BUDGET_MB"]
+        chunk = ctx.get_option("last_chunk")
         mu, s2 = gp.predict(X[:20] + 0.05, separate_samples=True)
-        q.put(dict(mu=mu, s2=s2, alpha=[p.alpha for p in gp.posteriors], L=[np.asarray(p.L) for p in gp.posteriors],
+        q.put(dict(chunk=chunk, mu=mu, s2=s2, alpha=[p.alpha for p in gp.posteriors], L=[np.asarray(p.L) for p in gp.posteriors],
                    counts=(ctx.get_option("block_appended") - a0, ctx.get_option("block_stale") - s0)))
     except Exception:  # noqa: BLE001
         import traceback
@@ -385,6 +386,10 @@ def test_scratch_budget_chunks_over_the_samples_and_refuses_one_sample_that_does
     big, small = _run_budgeted(4096), _run_budgeted(20)
     assert "error" not in big and "error" not in small, (big.get("error"), small.get("error"))
     assert big["counts"] == (5, 0) and small["counts"] == (5, 0)
+    from scratch_sizes import append_block_per, planned_chunk
+
+    want = planned_chunk(5, 20, append_block_per(896, 100, 8, 2))  # (k = 100: the MFMA engine)
+    assert (big["chunk"], small["chunk"]) == (5, want) and want == 2, (big["chunk"], small["chunk"], want)
     assert np.array_equal(big["mu"], small["mu"]) and np.array_equal(big["s2"], small["s2"])
     for a, b in zip(big["alpha"] + big["L"], small["alpha"] + small["L"]):
         assert np.array_equal(a, b)

@@ -207,12 +207,23 @@ def test_chunks_bitwise_and_budget_message(monkeypatch):
     folds = scattered_folds(300, [1, 40, 100])
     whole, loo = gp._post_handle.cv(folds), gp._post_handle.cv(None)
     # one sample's scratch: 3 folds x 3 x 128^2 doubles = 1.1 MB (+ panels for engine 2): budgets of one and two samples
+    from gpyreg_amd import _lib
+    from scratch_sizes import cv_fold_per, cv_loo_per, planned_chunk
+
+    ctx = _lib.context(gp.device)
     for mb in ("2", "4"):
         monkeypatch.setenv("GPC_MEM_BUDGET_MB", mb)
-        chunked, loo_c = gp._post_handle.cv(folds), gp._post_handle.cv(None)
+        chunked = gp._post_handle.cv(folds)
+        chunks, engine = [ctx.get_option("last_chunk")], ctx.get_option("cv_engine_ran")
+        loo_c = gp._post_handle.cv(None)
+        chunks.append(ctx.get_option("last_chunk"))
         monkeypatch.delenv("GPC_MEM_BUDGET_MB")
         assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(whole, chunked)), mb
         assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(loo, loo_c)), mb
+        # ... in the chunks that the scratch's closed forms give (the leave-one-out pass holds all six samples)
+        want = [planned_chunk(6, int(mb), cv_fold_per(384, 3, 100, engine)),
+                planned_chunk(6, int(mb), cv_loo_per(384))]
+        assert chunks == want and want[1] == 6 and 0 < want[0] < 6, (mb, chunks, want)
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", "1")
     with pytest.raises(RuntimeError, match=r"gpc_cv.*rc=-2.*N_pad = 384, F = 3, k_max = 100.*budget"):
         gp._post_handle.cv(folds)

@@ -166,6 +166,13 @@ def test_subset_chunks_repeats_and_deepcopy_bitwise(monkeypatch):
     # ~7 MB of draw scratch per sample at mpad = 384: a few samples per chunk
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", "40")
     chunked = gp.draw_functions(xs, n_draws=R, seed=seed)
+    from gpyreg_amd import _lib
+    from scratch_sizes import planned_chunk, rhs_per, rhs_shared
+
+    # ... in the chunks that the scratch's closed form gives (the factor's three slabs count as the scratch they are)
+    want = planned_chunk(10, 40, rhs_per(384, 384, True, 8, 4, "cross", False, M=300, R=R),
+                         rhs_shared(300, 300, 4, 10, full=True, R=R))
+    assert 1 < want < 10 and _lib.context(gp.device).get_option("last_chunk") == want
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", "1")
     with pytest.raises(RuntimeError, match="exceeds the device memory budget"):
         gp.draw_functions(xs, n_draws=R, seed=seed)

@@ -366,12 +366,20 @@ def test_sample_alone_in_a_batch_and_chunked_bitwise(monkeypatch):
         assert np.array_equal(m1[..., 0], whole[0][..., s]) and np.array_equal(c1[..., 0], whole[1][..., s]), s
     # scratch of one sample at npad = 128, D = 3: two 128 x 512 panels of doubles = 1 MB and small vectors; 80 % of
     # 2 MB holds one sample, not two
+    from gpyreg_amd import _lib
+    from scratch_sizes import grad_post_per, planned_chunk
+
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", "2")
     chunked = gp.gradient_posterior(xs, with_value=True, separate_samples=True)
+    chunks = [_lib.context(gp.device).get_option("last_chunk")]
     chunked_d = gp.gradient_posterior(xs, cov="diag", with_value=True, separate_samples=True)
+    chunks.append(_lib.context(gp.device).get_option("last_chunk"))
     monkeypatch.delenv("GPC_MEM_BUDGET_MB")
     for a, b in zip(whole + whole_d, chunked + chunked_d):
         assert np.array_equal(a, b)
+    # ... in the chunks that the scratch's closed form gives (shared: the raw queries)
+    want = [planned_chunk(3, 2, grad_post_per(128, 3, diag, 8), 70 * 3 * 8) for diag in (False, True)]
+    assert chunks == want == [1, 1], (chunks, want)
 
 
 def test_budget_failure_names_the_sizes(monkeypatch):

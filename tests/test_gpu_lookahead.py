@@ -252,10 +252,22 @@ def test_forced_chunks_on_a_mixed_batch_bitwise(monkeypatch, Mr, Mc, budget):
     xr, xc = _points(4, Mr, Mc)
     w = np.random.default_rng(2).uniform(0, 1, (Mr, 7))
     whole = gp.lookahead_variance(xc, xr, weights=w, separate_samples=True), gp.predict_cov(xr, xc)
+    from gpyreg_amd import _lib
+    from scratch_sizes import cov_per, cov_shared, pad, planned_chunk
+
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", budget)
-    chunked = gp.lookahead_variance(xc, xr, weights=w, separate_samples=True), gp.predict_cov(xr, xc)
+    look = gp.lookahead_variance(xc, xr, weights=w, separate_samples=True)
+    chunks = [_lib.context(gp.device).get_option("last_chunk")]
+    chunked = look, gp.predict_cov(xr, xc)
+    chunks.append(_lib.context(gp.device).get_option("last_chunk"))
     monkeypatch.delenv("GPC_MEM_BUDGET_MB")
     assert np.array_equal(whole[0], chunked[0]) and np.array_equal(whole[1], chunked[1])
+    # ... in the chunks that the scratch's closed form gives: the look-ahead is reduced in the product's epilogue from 64
+    # 128-tiles on, the covariance is always stored (and staged on its way out)
+    fused = (pad(Mr) // 128) * (pad(Mc) // 128) >= 64
+    want = [planned_chunk(7, int(budget), cov_per(384, pad(Mr), pad(Mc), 4, 8, f), cov_shared(Mr, Mc, 4, c))
+            for f, c in ((fused, False), (False, True))]
+    assert chunks == want and 0 < want[0] < 7, (chunks, want)
 
 
 def test_other_entry_points_keep_their_bits():

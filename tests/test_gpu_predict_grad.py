@@ -294,6 +294,12 @@ def test_chunked_samples_bitwise(monkeypatch):
     monkeypatch.delenv("GPC_MEM_BUDGET_MB")
     for a, b in zip(whole, chunked):
         assert np.array_equal(a, b)
+    # ... and the chunk is the one that the scratch's closed form gives
+    from gpyreg_amd import _lib
+    from scratch_sizes import planned_chunk, rhs_per, rhs_shared
+
+    want = planned_chunk(10, 16, rhs_per(384, 384, False, 8, 4, "cross", True, grad=True), rhs_shared(300, 300, 4, 10))
+    assert want == 3 and _lib.context(gp.device).get_option("last_chunk") == want
 
 
 def test_matern1_on_training_points_is_finite_and_the_convention():

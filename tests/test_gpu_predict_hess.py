@@ -342,10 +342,19 @@ def test_symmetric_and_sample_alone_in_a_batch_and_chunked_bitwise(monkeypatch):
             assert np.array_equal(a[..., 0], b[..., s]), s
     # scratch of one sample at npad = 128, D = 3: two 128 x 512 panels and Q, 128 x 128, of doubles = 1.1 MB, the
     # partials and small vectors; 80 % of 2 MB holds one sample, not two
+    from gpyreg_amd import _lib
+    from scratch_sizes import planned_chunk, predict_hess_per
+
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", "2")
     chunked = gp.predict_hess(xs, separate_samples=True)
+    chunks = [_lib.context(gp.device).get_option("last_chunk")]
     chunked_mean = gp.predict_hess(xs, compute_var=False, separate_samples=True)
+    chunks.append(_lib.context(gp.device).get_option("last_chunk"))
     monkeypatch.delenv("GPC_MEM_BUDGET_MB")
+    # the chunks that the scratch's closed form gives (shared: the raw queries): without the variance there is one
+    # panel and no Q, and two samples fit
+    want = [planned_chunk(3, 2, predict_hess_per(128, 3, var, 8), 70 * 3 * 8) for var in (True, False)]
+    assert chunks == want == [1, 2], (chunks, want)
     for a, b in zip(whole, chunked):
         assert np.array_equal(a, b)
     for i in (0, 2, 4):

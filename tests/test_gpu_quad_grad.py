@@ -229,12 +229,22 @@ def test_batch_single_subsets_chunks_bitwise(monkeypatch):
     # a budget that holds a few samples of the scratch per chunk (~4 MB each at npad = mpad = 384): several chunks,
     # non-resident constants; mixed L_chol kinds so that runs split at chunk borders
     gp, model, X, hyp = _problem("se", "const", N=300, D=4, lo=-3, hi=3, sn2s=(1e-2, 1e-7) * 5, seed=6)
+    from gpyreg_amd import _lib
+    from scratch_sizes import planned_chunk, rhs_per, rhs_shared
+
     whole = [gp.quad_grad(mu, sigma, compute_var=cv, separate_samples=True) for cv in (True, False)]
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", "16")
-    chunked = [gp.quad_grad(mu, sigma, compute_var=cv, separate_samples=True) for cv in (True, False)]
+    chunked, chunks = [], []
+    for cv in (True, False):
+        chunked.append(gp.quad_grad(mu, sigma, compute_var=cv, separate_samples=True))
+        chunks.append(_lib.context(gp.device).get_option("last_chunk"))
     monkeypatch.delenv("GPC_MEM_BUDGET_MB")
     for w, c in zip(whole, chunked):
         assert all(np.array_equal(a, b) for a, b in zip(w, c))
+    # ... in the chunks that the scratch's closed form gives (without the variance there is no Q and no product)
+    want = [planned_chunk(10, 16, rhs_per(384, 384, False, 8, 4, "quad", cv, grad=True, qg=True),
+                          rhs_shared(300, 300, 4, 10, "quad", qg=True)) for cv in (True, False)]
+    assert chunks == want and want[0] < 10, (chunks, want)
 
 
 def test_refusals():

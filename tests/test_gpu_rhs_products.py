@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import rhs_ref as rr
-from scratch_sizes import budget_for_chunk, pad, planned_chunk, rhs_per
+from scratch_sizes import budget_for_chunk, pad, planned_chunk, rhs_per, rhs_shared
 
 pytestmark = pytest.mark.gpu
 
@@ -185,7 +185,7 @@ def test_batch_equals_single(ctx, N, M, dtype):
 
 @pytest.mark.parametrize("dtype", [F64, F32], ids=["fp64", "fp32"])
 def test_chunked_equals_whole(ctx, monkeypatch, dtype):
-    """GPC_MEM_BUDGET_MB chosen from the scratch's closed form (scratch_sizes.rhs_per) so that two samples fit: chunks
+    """GPC_MEM_BUDGET_MB chosen from the scratch's closed forms (scratch_sizes.rhs_per, rhs_shared) so that two samples fit: chunks
     of 2, 2 and 1 -- the partial last chunk (RhsCall::download's two-copy branch), constants that are not resident and
     L_chol runs cut at the chunk borders -- give the bits of the call that holds all five."""
     N, M = 300, 300
@@ -195,9 +195,12 @@ def test_chunked_equals_whole(ctx, monkeypatch, dtype):
         whole = dev.calls()
         assert ctx.get_option("last_chunk") == rr.S
         for call in whole:
-            per = rhs_per(pad(N), pad(M), call in ("predict_full", "predict_K+Kss", "predict_K-var"), w)
-            mb = budget_for_chunk(rr.S, 2, per)
-            assert mb is not None and planned_chunk(rr.S, mb, per) == 2
+            kind = "given" if call.startswith("predict_K") else "quad" if call.startswith("quad") else "cross"
+            full, want_quad = call in ("predict_full", "predict_K+Kss", "predict_K-var"), call in ("predict", "quad", "predict_K", "predict_K+Kss")
+            per = rhs_per(pad(N), pad(M), full, w, rr.D, kind, want_quad)
+            shared = rhs_shared(N, M, rr.D, rr.S, kind, full)
+            mb = budget_for_chunk(rr.S, 2, per, shared)
+            assert mb is not None and planned_chunk(rr.S, mb, per, shared) == 2
             monkeypatch.setenv("GPC_MEM_BUDGET_MB", str(mb))
             part = dev.calls(which=(call,))
             chunk = ctx.get_option("last_chunk")

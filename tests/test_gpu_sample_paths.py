@@ -413,13 +413,13 @@ def test_chunked_creation_and_evaluation_keep_the_bits(monkeypatch):
     """Budgets that hold two samples' scratch of the solve (GPC_MEM_BUDGET_MB = 1 at R = 40: three 96 KB panels each) and
     one sample's of the unfused engine (2 MB: 789 KB each beside 268 KB of results): the same bits as one chunk."""
     from gpyreg_amd import _lib
-    from scratch_sizes import paths_create_per, paths_eval_per, planned_chunk
+    from scratch_sizes import paths_create_per, paths_eval_per, paths_eval_shared, planned_chunk
 
     gp, X, y, xq, hyp = _problem()
     ctx = _lib.context()
     S, npad, mpad, fpad = len(SN2), 256, 128, 128
     create_chunk = planned_chunk(S, 1, paths_create_per(npad, 40, 8, 1))
-    eval_chunk = {e: planned_chunk(S, 2, paths_eval_per(npad, mpad, fpad, 40, D, e), M * 40 * S * 8 * (1 + D)) for e in (1, 2)}
+    eval_chunk = {e: planned_chunk(S, 2, paths_eval_per(npad, mpad, fpad, 40, D, e), paths_eval_shared(M, 40, S, D, True)) for e in (1, 2)}
     assert create_chunk == 2 and eval_chunk == {1: 3, 2: 1}  # (the fused engine's scratch is the scaled queries alone)
     ref = gp.sample_paths(n_paths=40, n_features=F, seed=5)
     monkeypatch.setenv("GPC_MEM_BUDGET_MB", "1")

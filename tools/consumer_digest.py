@@ -18,8 +18,9 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import numpy as np  # noqa: E402
+import scratch_sizes as ss  # noqa: E402  (the scratch per sample of every consumer, as closed forms)
 
 from gpyreg_amd import _lib  # noqa: E402
 
@@ -37,8 +38,7 @@ SN2 = (1e-2, 5e-7, 5e-7, 4e-3)
 OUT = open(sys.argv[1], "w") if len(sys.argv) > 1 else None
 
 
-def pad(n, t=128):
-    return -(-n // t) * t
+pad = ss.pad
 
 
 def emit(name, dtype, outs, note=""):
@@ -149,103 +149,78 @@ def consumers(dtype):
     mu, sigma = rng.uniform(-2, 2, (M, D)), rng.uniform(0.3, 1.2, (M, D))
     wm, ws = rng.uniform(0, 1, M), rng.uniform(0, 1, (M, S))
     gp, X, y = problem("se", dtype)
-    rhs = 2 * npad * mpad * w  # Ks and V
-    gnt = npad // 64
-    grad = lambda gpl: gnt * gpl * D * mpad * 8 + gpl * mpad * D * 8  # noqa: E731
-    both("predict", dtype, lambda: gp.predict(xq, separate_samples=True), rhs)
-    both("predict_grad", dtype, lambda: gp.predict_grad(xq, separate_samples=True), rhs + npad * mpad * w + grad(2))
-    both("predict_full", dtype, lambda: gp.predict_full(xq), rhs + mpad * mpad * w)
-    cov_per = (2 * npad * (mpad + mbpad) + mpad * mbpad) * w + gnt * mbpad * 8 + ((mpad + mbpad) * D + mpad + 1 + 2 * mbpad) * 8
-    both("predict_cov", dtype, lambda: gp.predict_cov(xq, xb), cov_per)
+
+    def rhs(kind="cross", want_quad=True, full=False, grad=False, qg=False, R=0):
+        return (ss.rhs_per(npad, mpad, full, w, D, kind, want_quad, grad, qg, M, R),
+                ss.rhs_shared(N, M, D, S, kind, full, qg, R))
+
+    both("predict", dtype, lambda: gp.predict(xq, separate_samples=True), *rhs())
+    both("predict_grad", dtype, lambda: gp.predict_grad(xq, separate_samples=True), *rhs(grad=True))
+    both("predict_full", dtype, lambda: gp.predict_full(xq), *rhs(want_quad=False, full=True))
+    cov_per = ss.cov_per(npad, mpad, mbpad, D, w)
+    both("predict_cov", dtype, lambda: gp.predict_cov(xq, xb), cov_per, ss.cov_shared(M, MB, D, True))
     both("lookahead_variance shared weights", dtype,
-         lambda: gp.lookahead_variance(xb, xq, weights=wm, separate_samples=True), cov_per)
+         lambda: gp.lookahead_variance(xb, xq, weights=wm, separate_samples=True), cov_per, ss.cov_shared(M, MB, D, False))
     both("lookahead_variance per-sample weights", dtype,
-         lambda: gp.lookahead_variance(xb, xq, weights=ws, separate_samples=True), cov_per)
-    rpad = pad(R_DRAW)
+         lambda: gp.lookahead_variance(xb, xq, weights=ws, separate_samples=True), cov_per, ss.cov_shared(M, MB, D, False))
     both("draw_functions", dtype, lambda: gp.draw_functions(xq, n_draws=R_DRAW, seed=11),
-         rhs + mpad * mpad * w + (3 * mpad * mpad + 2 * mpad * rpad) * w + M * R_DRAW * 8)
-    both("quad", dtype, lambda: gp.quad(mu, sigma, compute_var=True, separate_samples=True), rhs)
-    qcon = (D + 1) * mpad * 8
+         *rhs(want_quad=False, full=True, R=R_DRAW))
+    both("quad", dtype, lambda: gp.quad(mu, sigma, compute_var=True, separate_samples=True), *rhs("quad"))
     both("quad_grad with variance", dtype, lambda: gp.quad_grad(mu, sigma, compute_var=True, separate_samples=True),
-         rhs + npad * mpad * w + grad(4) + qcon)
+         *rhs("quad", grad=True, qg=True))
     both("quad_grad", dtype, lambda: gp.quad_grad(mu, sigma, compute_var=False, separate_samples=True),
-         rhs + grad(2) + qcon)
-    both("quad_cov", dtype, lambda: gp.quad_cov(mu, sigma, separate_samples=True), rhs + mpad * mpad * w)
-    # gpc_quad_mix with variance and gradient: the doubles per sample and per call of quad_mix_impl
-    mnt, nch, ss, gpl, gnq, npl = mpad // 64, npad // 128, mpad * D, 4, 1 + 2 * D, 6
-    mix = ((D + 1) * mpad + gnt * mpad + mnt * npad + npad + 2 * npad + nch * npad + gnt * mpad + gnt * gpl * D * mpad
-           + mnt * gnq * mpad + 3 * mpad + 2 + npl * ss) * 8
+         *rhs("quad", want_quad=False, grad=True, qg=True))
+    both("quad_cov", dtype, lambda: gp.quad_cov(mu, sigma, separate_samples=True), *rhs("quad", want_quad=False, full=True))
     both("quad_mixture with variance and gradient", dtype,
-         lambda: gp.quad_mixture(mu, sigma, wm, compute_var=True, compute_grad=True, separate_samples=True), mix,
-         (2 * ss + mpad + 2 * M * D + M) * 8)
-    # gradient_posterior and predict_hess: the bytes per sample of grad_post_impl and hess_impl (one block of 128 queries,
-    # D + 1 slots; the Gram matrix in one segment below N_pad = 1024)
-    qb, dp, nt64 = 128, D + 1, npad // 64
-    ld, vecs = dp * qb, qb * D + npad * D + 4 + 2 * D
+         lambda: gp.quad_mixture(mu, sigma, wm, compute_var=True, compute_grad=True, separate_samples=True),
+         ss.quad_mix_per(npad, mpad, D, True, True), ss.quad_mix_shared(M, mpad, D))
+    # gradient_posterior and predict_hess: one block of 128 queries
     for cov in ("full", "diag"):
-        gper = qb * dp * (1 if cov == "diag" else dp)
-        per = 2 * npad * ld * w + (nt64 * ld + (npad // 128 * ld if cov == "diag" else 0) + gper + ld + 1 + vecs) * 8
         for val in (False, True):
             both(f"gradient_posterior {cov}" + (" with value" if val else ""), dtype,
-                 lambda: gp.gradient_posterior(xq, cov=cov, with_value=val, separate_samples=True), per)
+                 lambda: gp.gradient_posterior(xq, cov=cov, with_value=val, separate_samples=True),
+                 ss.grad_post_per(npad, D, cov == "diag", w), M * D * 8)
     for var in (True, False):
-        gper, hper = (qb * dp * dp if var else 0), (2 if var else 1) * (1 + D * (D + 1) // 2) * qb
-        per = ((2 * npad * ld + npad * qb) if var else npad * ld) * w + \
-            (nt64 * ld + nt64 * hper + hper + gper + ld + 1 + vecs) * 8
         both("predict_hess" + ("" if var else " without variance"), dtype,
-             lambda: gp.predict_hess(xq, compute_var=var, separate_samples=True), per)
+             lambda: gp.predict_hess(xq, compute_var=var, separate_samples=True), ss.predict_hess_per(npad, D, var, w), M * D * 8)
     # cv_predict: the leave-one-out pass (five vectors per sample: one megabyte holds every sample), and three scattered
-    # folds of 5, 9 and 3 points -- cv_fold_impl's three k_pad x k_pad slabs and one vector per fold, two output planes
+    # folds of 5, 9 and 3 points
     both("cv_predict leave-one-out", dtype, lambda: gp.cv_predict(None, separate_samples=True, return_lpd=True),
-         5 * npad * 8)
+         ss.cv_loo_per(npad))
     order = np.random.default_rng(9).permutation(N)
     folds = [np.sort(order[:5]), np.sort(order[5:14]), np.sort(order[14:17])]
-    per = len(folds) * (3 * pad(9) ** 2 + pad(9)) * 8 + 2 * npad * 8 + len(folds) * 32 + 64
+    per = ss.cv_fold_per(npad, len(folds), 9, 1)
     both("cv_predict scattered folds", dtype, lambda: gp.cv_predict(folds, separate_samples=True), per)
     both("cv_predict scattered folds with lpd", dtype, lambda: gp.cv_predict(folds, return_lpd=True), per)
-    # cv_nll_batch on the resident posteriors (fp64 only): Q, Q diag(c) and their product, seven vectors, the per-tile
-    # partials of the contraction; the weights are shared by the samples
+    # cv_nll_batch on the resident posteriors (fp64 only); the weights are shared by the samples
     if dtype == "f64" and hasattr(gp, "cv_nll_batch"):
-        ntl = gnt * (gnt + 1) // 2
-        per = (3 * npad * npad + 7 * npad + (ntl + 1) * (D + 1)) * 8
         for loss in ("lpd", "mse"):
-            both(f"cv_nll_batch {loss}", dtype, lambda: gp.cv_nll_batch(loss=loss, weights=wm.repeat(3)[:N]), per, npad * 8)
+            both(f"cv_nll_batch {loss}", dtype, lambda: gp.cv_nll_batch(loss=loss, weights=wm.repeat(3)[:N]),
+                 ss.cv_grad_per(npad, D + 1), npad * 8)
     # nll_hess_batch and predict_hyp_grad on the resident posteriors (fp64 only), P = cov_N + one noise + one mean
-    # hyperparameter: the doubles per sample of nll_hess_impl (Q, one B per plane and the operand, the vectors, the
-    # partials of the Gram and second-derivative passes) and of hyp_grad_impl (one block of 128 queries; with the variance
-    # the plane, three panels and the column dots' partials)
+    # hyperparameter; one block of 128 queries
     if dtype == "f64":
-        cov_N, ppl, P, nd2, nch = D + 1, D + 2, D + 3, D * (D + 1) // 2, npad // 128
-        ntl = gnt * (gnt + 1) // 2
-        per = ((ppl + 2) * npad * npad + (2 * P + 1 + 1 + gnt) * npad + gnt * gnt * 2 + 2 * cov_N
-               + (gnt * gnt + 1) * (ppl * (ppl + 1) // 2) + (ntl + 1) * nd2) * 8
-        both("nll_hess_batch", dtype, lambda: gp.nll_hess_batch(), per)
+        cov_N, P = D + 1, D + 3
+        both("nll_hess_batch", dtype, lambda: gp.nll_hess_batch(), ss.nll_hess_per(npad, cov_N, 1, 1, D * (D + 1) // 2))
         for var in (True, False):
-            nout = P + cov_N * (2 if var else 1)
-            per = (2 * P + 1 + nch + gnt) * npad + (gnt + 1) * nout * mpad + mpad * D + 1
-            if var:
-                per += npad * npad + 3 * npad * mpad + npad + gnt * mpad + gnt * 2 * mpad + (D + 1) * mpad
             both("predict_hyp_grad" + ("" if var else " without variance"), dtype,
-                 lambda: gp.predict_hyp_grad(xq, compute_var=var), per * 8)
+                 lambda: gp.predict_hyp_grad(xq, compute_var=var),
+                 ss.hyp_grad_per(npad, D, P, 1, D, mpad, var, P + cov_N * (2 if var else 1)))
     # sample_paths: creation under both solve engines, evaluation with gradients under both engines
-    kq, kp = pad(R_PATHS, 16), pad(R_PATHS)
     try:
         for solve in (1, 2):
             ctx.set_option("paths_solve_engine", solve)
-            per = 3 * npad * kq * 8 + (3 * npad * kp * w if solve == 2 else 0) + 64
             made = {}
 
             def create():
                 made["p"] = gp.sample_paths(n_paths=R_PATHS, n_features=F, seed=5)
                 return made["p"](xq, compute_grad=True)
 
-            both(f"sample_paths create, solve engine {solve}", dtype, create, per)
+            both(f"sample_paths create, solve engine {solve}", dtype, create, ss.paths_create_per(npad, R_PATHS, w, solve))
             for engine in (1, 2):
                 ctx.set_option("paths_engine", engine)
-                rp, fpad = pad(R_PATHS), pad(F)
-                eng = (max(npad, fpad) * mpad + mpad * rp + npad * rp + fpad * rp) * 8 if engine == 2 else 0
                 both(f"sample_paths evaluate, engine {engine}", dtype, lambda: made["p"](xq, compute_grad=True),
-                     mpad * D * 8 + eng, M * R_PATHS * S * 8 * (1 + D))
+                     ss.paths_eval_per(npad, mpad, pad(F), R_PATHS, D, engine), ss.paths_eval_shared(M, R_PATHS, S, D, True))
             ctx.set_option("paths_engine", 0)
     finally:
         ctx.set_option("paths_solve_engine", 0)
@@ -264,10 +239,9 @@ def consumers(dtype):
 
     emit("update rank-one", dtype, updated(1, 0, False))
     for k in (8, 17):
-        npn, kq, kp = pad(N + k), pad(k, 16), pad(k)
         for engine in (1, 2):
-            per = 4 * npn * kq * 8 + (3 * npn * kp * w if engine == 2 else 0) + kq * kq * 8 + 3 * kq * 8 + 3 * kp * kp * w + 64
-            both(f"update block_append k={k}, engine {engine}", dtype, lambda: updated(k, engine, True), per)
+            both(f"update block_append k={k}, engine {engine}", dtype, lambda: updated(k, engine, True),
+                 ss.append_block_per(pad(N + k), k, w, engine))
 
 
 def large(dtype):
@@ -288,7 +262,7 @@ def caller_k(dtype):
     gp, X, y = problem("se", dtype, cov=PySE())
     xq = np.random.default_rng(3).uniform(-3, 3, (M, D))
     both("predict, posterior from the caller's K", dtype, lambda: gp.predict(xq, separate_samples=True),
-         2 * pad(N) * pad(M) * (8 if dtype == "f64" else 4))
+         ss.rhs_per(pad(N), pad(M), False, 8 if dtype == "f64" else 4, D, "given"), ss.rhs_shared(N, M, D, S, "given"))
 
 
 def evaluations(dtype):
