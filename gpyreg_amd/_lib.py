@@ -139,6 +139,8 @@ SIGNATURES = {
     "gpc_debug_chunk_plan": (C.c_int, [C.c_int, C.c_ulonglong, C.c_ulonglong, C.c_ulonglong, C.c_int]),
     "gpc_debug_scratch_bytes": (C.c_int, [C.c_char_p, C.c_int, _ip, C.c_int, _vp, _vp, _ip]),
     "gpc_debug_gemm_queues": (C.c_int, [C.c_int] * 8 + [_ip] * 4),
+    "gpc_debug_tri_masks": (C.c_int, [C.c_int] * 3 + [_ip] * 4),
+    "gpc_debug_tri_usable": (C.c_int, [C.c_int] * 11),
     "gpc_debug_gemm_form": (
         C.c_int,
         [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, _dp, C.c_longlong, _dp, _dp, _ip, _ip],
@@ -1386,6 +1388,33 @@ def gemm_queues(ntiles, batch, flags, tiles_m=0, tiles_n=0, klo=0, khi=0, lower_
     ends = np.concatenate([[0], np.cumsum(np.minimum(q_total, n))])
     queues = [q_items[ends[q]:ends[q + 1]].copy() for q in range(8)]
     return queues, q_total, tiles, xcd
+
+
+# GemmArgs::tri of gemm.h, and where gpc_debug_gemm_form's flags carry it
+TRI_A_FIRST, TRI_A_LAST, TRI_B_FIRST, TRI_B_LAST, TRI_DIAG_LOWER = 1, 2, 3, 4, 8
+TRI_FLAGS_SHIFT = 8
+
+
+def tri_masks(tri, diag_tile, slab):
+    """gpc_debug_tri_masks (no device needed): (frag_rows (4, 4), frag_cols (4, 4), issued (4, 4, 4), stored (4, 4, 4)) of
+    the zero-skipping GEMM instantiation ``tri`` in k-slab ``slab`` of the triangular block, per wave 2 wr + wc."""
+    lib = load()
+    rows, cols = np.zeros((4, 4), dtype=np.int32), np.zeros((4, 4), dtype=np.int32)
+    issued, stored = np.zeros((4, 4, 4), dtype=np.int32), np.zeros((4, 4, 4), dtype=np.int32)
+    rc = lib.gpc_debug_tri_masks(int(tri), int(bool(diag_tile)), int(slab), rows.ctypes.data, cols.ctypes.data,
+                                 issued.ctypes.data, stored.ctypes.data)
+    if rc != 0:
+        raise RuntimeError(f"gpc_debug_tri_masks failed (rc={rc})")
+    return rows, cols, issued, stored
+
+
+def tri_usable(tri, a_kmajor, b_kmajor, klo, khi, lower_only, M, N, K, tile=128, dtype=F64):
+    """gpc_debug_tri_usable (no device needed): the zero-skipping instantiation the launcher picks (0: the plain kernel)."""
+    rc = load().gpc_debug_tri_usable(int(dtype), int(tile), int(bool(a_kmajor)), int(bool(b_kmajor)), int(klo), int(khi),
+                                     int(bool(lower_only)), int(M), int(N), int(K), int(tri))
+    if rc < 0:
+        raise RuntimeError(f"gpc_debug_tri_usable failed (rc={rc})")
+    return rc
 
 
 _contexts = {}

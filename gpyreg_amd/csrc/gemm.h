@@ -53,6 +53,69 @@ constexpr int opsz_of(int BT) {
 
 enum { KLO_ZERO = 0, KLO_ROW = 1, KLO_COL = 2 };  // k0 = 0 | ti*128 | tj*128
 enum { KHI_FULL = 0, KHI_ROW = 1, KHI_COL = 2 };  // k1 = K | (ti+1)*128 | (tj+1)*128
+// GemmArgs::tri -- what the CALLER guarantees about an operand inside the one diagonal 128-block of a tile's k-range
+// (bits 0-2: one kind), and what it allows a lower_only launch to leave unwritten (bit 3).  fp64 128-tile launches
+// only; every other launch form ignores the field.
+//   TRI_A_FIRST  A(m, k) is zero for k < m in the FIRST k-block of the range (klo = KLO_ROW)
+//   TRI_A_LAST   A(m, k) is zero for k > m in the LAST k-block (khi = KHI_ROW)
+//   TRI_B_FIRST  B(k, n) is zero for k < n in the FIRST k-block (klo = KLO_COL)
+//   TRI_B_LAST   B(k, n) is zero for k > n in the LAST k-block (khi = KHI_COL)
+//   TRI_DIAG_LOWER  of a diagonal output tile only the 16 x 16 fragments with fragment row >= fragment column are
+//                computed and stored; the others keep what they held
+enum { TRI_NONE = 0, TRI_A_FIRST = 1, TRI_A_LAST = 2, TRI_B_FIRST = 3, TRI_B_LAST = 4, TRI_KIND = 7, TRI_DIAG_LOWER = 8 };
+
+// ---- which of a wave's MR x MR fragments a k-slab issues (host and device: tests/test_tri_skip_cpu.py enumerates it) ----
+// With TRI a wave row wr owns the fragment rows f = 2 i + wr and a wave column wc the fragment columns f = 2 j + wc
+// (cyclic; without TRI f = 4 wr + i).  The fp64 k-slab is as wide as a fragment (16), so inside a triangular diagonal
+// block a fragment is, for a whole slab s = 0..7, either all zero or needed: needed are f <= s where the operand is zero
+// for k < index (the FIRST kinds) and f >= s where it is zero for k > index (the LAST kinds).  Every wave runs the mask
+// of the busier wave row / column -- the first tri_active(kind, s) of its four fragments (FIRST) or the last -- so no
+// slab depends on the wave and all four waves of a block skip together: 1,1,2,2,3,3,4,4 of 4 over the eight slabs,
+// 20 of 32, where contiguous ownership leaves 1,2,3,4,4,4,4,4 to the busier wave.
+__host__ __device__ constexpr int tri_active(int kind, int s) {
+  return (kind == TRI_A_FIRST || kind == TRI_B_FIRST) ? s / 2 + 1 : (kind == TRI_A_LAST || kind == TRI_B_LAST) ? 4 - s / 2 : 4;
+}
+__host__ __device__ constexpr int tri_frag(int w, int i) { return 2 * i + w; }  // global fragment of wave row / column w
+// I0 <= i < I1, J0 <= j < J1, and with LOW only i >= j (the diagonal output tile of TRI_DIAG_LOWER: with cyclic
+// ownership 2 i + wr >= 2 j + wc holds for i > j, fails for i < j, and at i = j fails for the wave (0, 1) alone -- that
+// wave computes its four diagonal fragments with the others and does not store them)
+template <int MRM, int MRN, int I0, int I1, int J0, int J1, bool LOW = false>
+struct FragMask {
+  static constexpr bool ALL = I0 == 0 && I1 == MRM && J0 == 0 && J1 == MRN && !LOW;
+  static constexpr bool a(int i) { return i >= I0 && i < I1; }
+  static constexpr bool b(int j) { return j >= J0 && j < J1; }
+  static constexpr bool m(int i, int j) { return a(i) && b(j) && (!LOW || i >= j); }
+  static constexpr int NA = I1 - I0, NB = J1 - J0;
+  static constexpr int count() {
+    int n = 0;
+    for (int i = 0; i < MRM; ++i)
+      for (int j = 0; j < MRN; ++j) n += m(i, j) ? 1 : 0;
+    return n;
+  }
+  static constexpr int NM = count();
+};
+// the mask of a slab with n active fragment rows (A kinds) or columns (B kinds)
+template <int KIND, int N, int MR>
+using TriMask = std::conditional_t<
+    KIND == TRI_A_FIRST, FragMask<MR, MR, 0, N, 0, MR>,
+    std::conditional_t<KIND == TRI_A_LAST, FragMask<MR, MR, MR - N, MR, 0, MR>,
+                       std::conditional_t<KIND == TRI_B_FIRST, FragMask<MR, MR, 0, MR, 0, N>, FragMask<MR, MR, 0, MR, MR - N, MR>>>>;
+
+// The host's view of gemm_tile<.., TRI> (gpc_debug_tri_masks): does a wave issue the MFMA of its fragment (i, j) in slab s
+// of the boundary block, and does it store the fragment -- through the mask types the kernel's sequences are made of
+template <int KD>
+inline bool tri_mask_m(int n, int i, int j) {
+  return n == 1 ? TriMask<KD, 1, 4>::m(i, j) : n == 2 ? TriMask<KD, 2, 4>::m(i, j) : n == 3 ? TriMask<KD, 3, 4>::m(i, j) : true;
+}
+inline bool tri_issued(int tri, bool diag_tile, int s, int i, int j) {
+  if ((tri & TRI_DIAG_LOWER) && diag_tile) return FragMask<4, 4, 0, 4, 0, 4, true>::m(i, j);
+  const int kind = tri & TRI_KIND, n = tri_active(kind, s);
+  return kind == TRI_A_FIRST ? tri_mask_m<TRI_A_FIRST>(n, i, j) : kind == TRI_A_LAST ? tri_mask_m<TRI_A_LAST>(n, i, j)
+       : kind == TRI_B_FIRST ? tri_mask_m<TRI_B_FIRST>(n, i, j) : kind == TRI_B_LAST ? tri_mask_m<TRI_B_LAST>(n, i, j) : true;
+}
+inline bool tri_stored(int tri, bool diag_tile, int wr, int wc, int i, int j) {
+  return !((tri & TRI_DIAG_LOWER) && diag_tile) || tri_frag(wr, i) >= tri_frag(wc, j);
+}
 
 struct GemmArgs {
   const void* A;
@@ -69,6 +132,7 @@ struct GemmArgs {
   const unsigned short* rsv = nullptr;  // persistent launches: table of the CUs this launch stays off (cu_reserve below)
   int* ctr = nullptr;  // persistent launches: zeroed device counters the blocks draw tiles from
   int ntiles = 0, batch = 0;
+  int tri = TRI_NONE;  // the caller's guarantee about a triangular operand (TRI_* above); 0: nothing, every MFMA is issued
   // EPI = 1 launches (predict): C is not stored; colsq[(b * tiles_m + ti) * N + col] receives the sum over the 128 rows
   // of tile row ti of (alpha * C[row][col])^2 -- the column sums of squares of V = W Ks (gaussian_process.py:1756-1760)
   // per tile row, in a fixed order; a small reduction over the tile rows follows
@@ -257,8 +321,25 @@ __device__ unsigned long long g_tile_trace[2][4];
 // too small for 128-tiles (one wave of tiles, as long as its longest) and run L2-bound as 64-tiles: half the tile-count
 // granularity of the one, 25 % fewer operand bytes per flop than the other.  Triangular k-ranges stay 128-granular, every
 // element keeps its k-order: the bits do not depend on the tile shape.
-template <typename T, bool AKM, bool BKM, int BT, int NW, int HO = 0, int EPI = 0, int BTN = BT>
+// TRI: the instantiation of launches with g.tri != 0 (fp64, 128-tile, stored result).  Its waves own their fragments
+// cyclically (tri_frag), a triangular diagonal k-block runs as a sequence of slab bodies that issue only the
+// fragments tri_active names, and the diagonal output tiles of a TRI_DIAG_LOWER launch run the whole k-loop under
+// the i >= j mask.  Every element receives the products it received before, in the same k-order, less products with
+// stored zeros: the bits are those of the plain instantiation.  Without TRI nothing of this is instantiated.
+template <int TRI, int WT>
+__device__ __forceinline__ int frag_org(int base, int w, int i) {  // base + first row / column of fragment i of wave row / column w
+  if constexpr (TRI)
+    return base + tri_frag(w, i) * 16;
+  else
+    return base + w * WT + i * 16;
+}
+template <typename T, bool AKM, bool BKM, int BT, int NW, int HO = 0, int EPI = 0, int BTN = BT, int TRI = TRI_NONE>
 __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const int by, T* __restrict__ smem) {
+  static_assert(TRI == TRI_NONE || (TRI >= TRI_A_FIRST && TRI <= TRI_B_LAST) || TRI == TRI_DIAG_LOWER ||
+                    TRI == (TRI_A_FIRST | TRI_DIAG_LOWER),
+                "an instantiation holds the paths of ONE launch kind (all of them in one kernel: spills in the k-loop)");
+  static_assert(!TRI || (sizeof(T) == 8 && BT == 128 && BTN == BT && NW == 4 && EPI == 0 && HO == 0),
+                "zero skipping: fp64 128-tiles of 2 x 2 waves; the column-sum epilogues keep contiguous ownership");
 #ifdef GPC_TILE_TRACE
   long long _ts = wall_clock64();
   if (HO && threadIdx.x == 0) atomicAdd(&g_tile_trace[BT == 64][3], 1ull);
@@ -286,6 +367,14 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
   int k1 = g.khi == KHI_ROW ? m128 + TILE : (g.khi == KHI_COL ? n128 + TILE : g.K);
   if (k1 > g.K) k1 = g.K;
   const int nk = (k1 - k0) / BKT_v<T>;
+  // block-uniform: the tile's masked sequence (a TRI_* kind), or TRI_DIAG_LOWER for a diagonal tile of such a launch --
+  // there the i >= j mask runs over the whole k-range and the boundary block is not treated apart (in W^T W, where
+  // B is triangular too on those 32 tiles: left alone)
+  constexpr int TKIND = TRI & TRI_KIND;
+  constexpr bool TRI_HEAD = TKIND == TRI_A_FIRST || TKIND == TRI_B_FIRST, TRI_TAIL = TKIND == TRI_A_LAST || TKIND == TRI_B_LAST;
+  constexpr bool TRI_DIAG = (TRI & TRI_DIAG_LOWER) != 0;  // (the lower_only launches: W^T W and the syrk)
+  bool tdiag = false;
+  if constexpr (TRI_DIAG) tdiag = g.lower_only && ti == tj;
 
   const T* __restrict__ A = reinterpret_cast<const T*>(g.A) + (size_t)by * g.sA;
   const T* __restrict__ B = reinterpret_cast<const T*>(g.B) + (size_t)by * g.sB;
@@ -365,52 +454,69 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
     //   * the global loads of the slab after next are spread between the MFMAs of the last k-step
     //     (in flight during the first k-steps of the next slab; consumed by its k-step KS-2).
     // WR: a next slab exists (ra/rb hold it); LD: a slab after next exists.
+    // M (a FragMask): the fragments a slab reads from LDS and multiplies; FULL except in the masked slabs of TRI
+    using FULL = FragMask<MRM, MRN, 0, MRM, 0, MRN>;
     T af[2][MRM], bf[2][MRN];
-    auto load_frags = [&](int set, const T* a_s, const T* b_s, int kk) {
+    auto load_frags = [&](auto mask_c, int set, const T* a_s, const T* b_s, int kk) {
+      using M = decltype(mask_c);
 #pragma unroll
-      for (int i = 0; i < MRM; ++i) af[set][i] = frag<T, AKM, BT>(a_s, wr * WTM + i * 16, kk, lane);
+      for (int i = 0; i < MRM; ++i)
+        if (M::ALL || M::a(i)) af[set][i] = frag<T, AKM, BT>(a_s, frag_org<TRI, WTM>(0, wr, i), kk, lane);
 #pragma unroll
-      for (int j = 0; j < MRN; ++j) bf[set][j] = frag<T, BKM, BTN>(b_s, wc * WTN + j * 16, kk, lane);
+      for (int j = 0; j < MRN; ++j)
+        if (M::ALL || M::b(j)) bf[set][j] = frag<T, BKM, BTN>(b_s, frag_org<TRI, WTN>(0, wc, j), kk, lane);
     };
-    auto mfmas = [&](int set) {
+    auto mfmas = [&](auto mask_c, int set) {
+      using M = decltype(mask_c);
 #pragma unroll
       for (int i = 0; i < MRM; ++i)
 #pragma unroll
-        for (int j = 0; j < MRN; ++j) acc[i][j] = MM<T>::mma(af[set][i], bf[set][j], acc[i][j]);
+        for (int j = 0; j < MRN; ++j)
+          if (M::ALL || M::m(i, j)) acc[i][j] = MM<T>::mma(af[set][i], bf[set][j], acc[i][j]);
     };
     constexpr int NMEM = NVA + NVB;                 // memory instructions per slab and direction
-    constexpr int PER = (MRM * MRN) / NMEM;         // MFMAs between two of them
-    constexpr int REM = MRM * MRN - PER * NMEM;     // (rectangular tile: 8 MFMAs, 6 memory instructions -- the last two MFMAs follow)
-    static_assert(PER >= 1, "interleave pattern");
+    static_assert((MRM * MRN) / NMEM >= 1, "interleave pattern");
     constexpr int KS = BKT_v<T> / 4;  // k-steps per slab: 4 (fp64) or 8 (fp32)
     static_assert(KS >= 4 && KS % 2 == 0, "fragment sets alternate per k-step and wrap per slab");
-    auto slab = [&](auto cur_c, auto wr_c, auto ld_c) {
+    // M: this slab's mask; MN: the next slab's (its first fragments are read during this slab's last k-step).  The
+    // interleave follows the MFMAs a k-step really has: PER between two memory instructions, the REM left over behind
+    // them; a k-step of fewer MFMAs than memory instructions (one active fragment row: 4 against 8) puts one MFMA
+    // in front of each of the first ones
+    auto slab = [&](auto cur_c, auto wr_c, auto ld_c, auto mask_c, auto next_c) {
       constexpr int CUR = decltype(cur_c)::value;
       constexpr bool WR = decltype(wr_c)::value, LD = decltype(ld_c)::value;
+      using M = decltype(mask_c);
+      using MN = decltype(next_c);
+      constexpr int NM = M::NM;                     // MFMAs per k-step
+      constexpr int PER = NM / NMEM;                // MFMAs between two memory instructions
+      constexpr int REM = NM - PER * NMEM;          // (rectangular tile: 8 MFMAs, 6 memory instructions -- the last two MFMAs follow)
       const T* a_s = smem + CUR * STG;
       const T* b_s = a_s + OPSZA;
       T* a_n = smem + (CUR ^ 1) * STG;
 #pragma unroll
       for (int ks = 0; ks < KS - 2; ++ks) {
-        load_frags((ks + 1) & 1, a_s, b_s, 4 * (ks + 1));
-        mfmas(ks & 1);
-        __builtin_amdgcn_sched_group_barrier(0x100, MRM + MRN, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, MRM * MRN, 0);
+        load_frags(M{}, (ks + 1) & 1, a_s, b_s, 4 * (ks + 1));
+        mfmas(M{}, ks & 1);
+        __builtin_amdgcn_sched_group_barrier(0x100, M::NA + M::NB, 0);
+        __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
       }
       // k-step KS-2: the LDS writes of the next slab between its MFMAs
-      load_frags(1, a_s, b_s, 4 * (KS - 1));
-      mfmas(0);
+      load_frags(M{}, 1, a_s, b_s, 4 * (KS - 1));
+      mfmas(M{}, 0);
       if constexpr (WR) {
         r2s<T, AKM, BT, NT>(a_n, ra, t);
         r2s<T, BKM, BTN, NT>(a_n + OPSZA, rb, t);
       }
-      __builtin_amdgcn_sched_group_barrier(0x100, MRM + MRN, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, M::NA + M::NB, 0);
 #pragma unroll
       for (int q = 0; q < NMEM; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
+        if constexpr (PER >= 1)
+          __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
+        else if (q < REM)
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         if constexpr (WR) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
       }
-      if constexpr (REM > 0) __builtin_amdgcn_sched_group_barrier(0x008, REM, 0);
+      if constexpr (PER >= 1 && REM > 0) __builtin_amdgcn_sched_group_barrier(0x008, REM, 0);
       __syncthreads();
       // k-step KS-1: the global loads of the slab after next between its MFMAs
       if constexpr (LD) {
@@ -418,37 +524,111 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
         g2r<T, AKM, BT, NT, AUX>(ra, rsa, ua, psa, toa);
         g2r<T, BKM, BTN, NT, AUX>(rb, rsb, ub, psb, tob);
       }
-      if constexpr (WR) load_frags(0, a_n, a_n + OPSZA, 0);
-      mfmas(1);
-      if constexpr (WR) __builtin_amdgcn_sched_group_barrier(0x100, MRM + MRN, 0);
+      if constexpr (WR) load_frags(MN{}, 0, a_n, a_n + OPSZA, 0);
+      mfmas(M{}, 1);
+      if constexpr (WR) __builtin_amdgcn_sched_group_barrier(0x100, MN::NA + MN::NB, 0);
 #pragma unroll
       for (int q = 0; q < NMEM; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
+        if constexpr (PER >= 1)
+          __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
+        else if (q < REM)
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         if constexpr (LD) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
-      if constexpr (REM > 0) __builtin_amdgcn_sched_group_barrier(0x008, REM, 0);
+      if constexpr (PER >= 1 && REM > 0) __builtin_amdgcn_sched_group_barrier(0x008, REM, 0);
     };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
-    load_frags(0, smem, smem + OPSZA, 0);
+    using YES = std::true_type;
+    using NO = std::false_type;
+    load_frags(FULL{}, 0, smem, smem + OPSZA, 0);
     int it = 0;
-    for (; it + 3 < nk; it += 2) {
-      slab(I0{}, std::true_type{}, std::true_type{});
-      slab(I1{}, std::true_type{}, std::true_type{});
-      if constexpr (TWO_LEVEL) {
-#pragma unroll
-        for (int i = 0; i < MRM; ++i)
-#pragma unroll
-          for (int j = 0; j < MRN; ++j) {
-            acc2[i][j] += acc[i][j];
-            acc[i][j] = acc_t{0, 0, 0, 0};
-          }
+    if constexpr (TRI) {
+      // Slabs 0..5 of a FIRST kind's boundary block (1,1,2,2,3,3 active; its slabs 6 and 7 are full: the plain loop's) and
+      // slabs 2..7 of a LAST kind's (3,3,2,2,1,1; slabs 0 and 1 are the plain loop's).  Six slabs: the LDS stage and the
+      // fragment set a sequence starts with are the ones it ends with, so either side of the seam is the unmodified
+      // loop; a head always has a slab after next to load (nk >= 8), a tail ends the k-range like the plain loop does.
+      auto tri_head = [&](auto kind_c) {
+        constexpr int KD = decltype(kind_c)::value;
+        using M1 = TriMask<KD, 1, MRM>;
+        using M2 = TriMask<KD, 2, MRM>;
+        using M3 = TriMask<KD, 3, MRM>;
+        static_assert(tri_active(KD, 0) == 1 && tri_active(KD, 1) == 1 && tri_active(KD, 2) == 2 && tri_active(KD, 3) == 2 &&
+                      tri_active(KD, 4) == 3 && tri_active(KD, 5) == 3 && tri_active(KD, 6) == 4 && tri_active(KD, 7) == 4);
+        slab(I0{}, YES{}, YES{}, M1{}, M1{});
+        slab(I1{}, YES{}, YES{}, M1{}, M2{});
+        slab(I0{}, YES{}, YES{}, M2{}, M2{});
+        slab(I1{}, YES{}, YES{}, M2{}, M3{});
+        slab(I0{}, YES{}, YES{}, M3{}, M3{});
+        slab(I1{}, YES{}, YES{}, M3{}, FULL{});
+      };
+      auto tri_tail = [&](auto kind_c) {
+        constexpr int KD = decltype(kind_c)::value;
+        using M1 = TriMask<KD, 1, MRM>;
+        using M2 = TriMask<KD, 2, MRM>;
+        using M3 = TriMask<KD, 3, MRM>;
+        static_assert(tri_active(KD, 0) == 4 && tri_active(KD, 1) == 4 && tri_active(KD, 2) == 3 && tri_active(KD, 3) == 3 &&
+                      tri_active(KD, 4) == 2 && tri_active(KD, 5) == 2 && tri_active(KD, 6) == 1 && tri_active(KD, 7) == 1);
+        slab(I0{}, YES{}, YES{}, M3{}, M3{});
+        slab(I1{}, YES{}, YES{}, M3{}, M2{});
+        slab(I0{}, YES{}, YES{}, M2{}, M2{});
+        slab(I1{}, YES{}, YES{}, M2{}, M1{});
+        slab(I0{}, YES{}, NO{}, M1{}, M1{});
+        slab(I1{}, NO{}, NO{}, M1{}, M1{});
+      };
+      // a diagonal output tile of a TRI_DIAG_LOWER launch: the plain loop under the i >= j mask, boundary block included
+      auto tri_diag = [&](auto low_c) {
+        using LOWM = decltype(low_c);
+        for (; it + 3 < nk; it += 2) {
+          slab(I0{}, YES{}, YES{}, LOWM{}, LOWM{});
+          slab(I1{}, YES{}, YES{}, LOWM{}, LOWM{});
+        }
+        slab(I0{}, YES{}, NO{}, LOWM{}, LOWM{});
+        slab(I1{}, NO{}, NO{}, LOWM{}, LOWM{});
+      };
+      bool done = false;
+      if constexpr (TRI_DIAG) {
+        if (tdiag) {
+          tri_diag(FragMask<MRM, MRN, 0, MRM, 0, MRN, true>{});
+          done = true;
+        }
       }
+      if (!done) {
+        if constexpr (TRI_HEAD) {
+          tri_head(std::integral_constant<int, TKIND>{});
+          it = 6;
+        }
+        const int stop = TRI_TAIL ? nk - 6 : nk - 2;  // (nk is even and >= 8)
+        for (; it < stop; it += 2) {
+          slab(I0{}, YES{}, YES{}, FULL{}, FULL{});
+          slab(I1{}, YES{}, YES{}, FULL{}, FULL{});
+        }
+        if constexpr (TRI_TAIL) {
+          tri_tail(std::integral_constant<int, TKIND>{});
+        } else {
+          slab(I0{}, YES{}, NO{}, FULL{}, FULL{});
+          slab(I1{}, NO{}, NO{}, FULL{}, FULL{});
+        }
+      }
+    } else {
+      for (; it + 3 < nk; it += 2) {
+        slab(I0{}, YES{}, YES{}, FULL{}, FULL{});
+        slab(I1{}, YES{}, YES{}, FULL{}, FULL{});
+        if constexpr (TWO_LEVEL) {
+#pragma unroll
+          for (int i = 0; i < MRM; ++i)
+#pragma unroll
+            for (int j = 0; j < MRN; ++j) {
+              acc2[i][j] += acc[i][j];
+              acc[i][j] = acc_t{0, 0, 0, 0};
+            }
+        }
+      }
+      // nk is even and >= 4, so exactly two slabs are left: the last one that
+      // still stages a successor, and the last one
+      slab(I0{}, YES{}, NO{}, FULL{}, FULL{});
+      slab(I1{}, NO{}, NO{}, FULL{}, FULL{});
     }
-    // nk is even and >= 4, so exactly two slabs are left: the last one that
-    // still stages a successor, and the last one
-    slab(I0{}, std::true_type{}, std::false_type{});
-    slab(I1{}, std::false_type{}, std::false_type{});
   }
 
   TILE_TS(1);
@@ -554,8 +734,10 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
       for (int j = 0; j < MRN; ++j)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const int row = m0 + wr * WTM + i * 16 + MM<T>::row_of(lane, r);
-          const int col = n0 + wc * WTN + j * 16 + (lane & 15);
+          if constexpr (TRI_DIAG)  // (wave-uniform) a fragment above the diagonal of a diagonal tile: neither read nor stored
+            if (tdiag && tri_frag(wr, i) < tri_frag(wc, j)) continue;
+          const int row = frag_org<TRI, WTM>(m0, wr, i) + MM<T>::row_of(lane, r);
+          const int col = frag_org<TRI, WTN>(n0, wc, j) + (lane & 15);
           if constexpr (HO == 1)
             old[j][r] = __hip_atomic_load(&C[(size_t)row * g.ldc + col], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           else
@@ -566,8 +748,10 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
     for (int j = 0; j < MRN; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const int row = m0 + wr * WTM + i * 16 + MM<T>::row_of(lane, r);
-        const int col = n0 + wc * WTN + j * 16 + (lane & 15);
+        if constexpr (TRI_DIAG)
+          if (tdiag && tri_frag(wr, i) < tri_frag(wc, j)) continue;
+        const int row = frag_org<TRI, WTM>(m0, wr, i) + MM<T>::row_of(lane, r);
+        const int col = frag_org<TRI, WTN>(n0, wc, j) + (lane & 15);
         T v;
         if constexpr (TWO_LEVEL)
           v = alpha * (acc[i][j][r] + acc2[i][j][r]);
@@ -583,7 +767,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const int bx, const
   TILE_TS(2);
 }
 
-template <typename T, bool AKM, bool BKM, int BT, int NW, int EPI = 0, int BTN = BT>
+template <typename T, bool AKM, bool BKM, int BT, int NW, int EPI = 0, int BTN = BT, int TRI = TRI_NONE>
 __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) T smem[2 * (opsz_of<T>(BT) + opsz_of<T>(BTN))];
   int bx = blockIdx.x, by = blockIdx.y;
@@ -592,7 +776,7 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_kernel(GemmArgs g) {
     // XCDs would get unequal work -- cfg4, one sample: -6.5 %)
     xcd_order((int)gridDim.x, (int)gridDim.y, bx, by);
   }
-  gemm_tile<T, AKM, BKM, BT, NW, 0, EPI, BTN>(g, bx, by, smem);
+  gemm_tile<T, AKM, BKM, BT, NW, 0, EPI, BTN, TRI>(g, bx, by, smem);
 }
 
 // Two independent products in ONE launch (plan.h: the syrk A22 -= T21 T21^T and the inverse product U = T21 W11 of
@@ -620,7 +804,7 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_dual_kernel(GemmArgs g1,
 // others when its own is empty.  Blocks that share an L2 then work on tiles of the same
 // sample, consecutive tiles of a sample share an operand panel, and the panel is read
 // from HBM / Infinity Cache once per XCD instead of once per tile.
-template <typename T, bool AKM, bool BKM, int BT, int NW, int EPI = 0>
+template <typename T, bool AKM, bool BKM, int BT, int NW, int EPI = 0, int TRI = TRI_NONE>
 __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_persist_kernel(GemmArgs g) {
   __shared__ __attribute__((aligned(16))) T smem[4 * opsz_of<T>(BT)];
   __shared__ int next_tile;
@@ -633,7 +817,7 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_persist_kernel(GemmArgs 
       const int idx = __builtin_amdgcn_readfirstlane(next_tile);
       __syncthreads();  // everyone holds idx before thread 0 may overwrite it; also fences the LDS stages
       if (idx >= total) break;
-      gemm_tile<T, AKM, BKM, BT, NW, 0, EPI>(g, idx / g.batch, idx % g.batch, smem);
+      gemm_tile<T, AKM, BKM, BT, NW, 0, EPI, BT, TRI>(g, idx / g.batch, idx % g.batch, smem);
     }
     return;
   }
@@ -669,7 +853,7 @@ __global__ __launch_bounds__(64 * NW, NW / 2) void gemm_persist_kernel(GemmArgs 
       // into every XCD's L2 at once: cfg3 W^T W 5.58 -> 5.36 ms, step 20.9 -> 20.4 ms; cfg5 552 -> 531 ms.)
       const int ntq = total / nsq;
       const int sq = idx / ntq, tq = idx - sq * ntq;
-      gemm_tile<T, AKM, BKM, BT, NW, 0, EPI>(g, cls + tq * nclass, smp + NQ * sq, smem);
+      gemm_tile<T, AKM, BKM, BT, NW, 0, EPI, BT, TRI>(g, cls + tq * nclass, smp + NQ * sq, smem);
     }
   }
 }
@@ -713,6 +897,63 @@ inline void flat_queue_item(int batch, int idx, int& tile, int& sample) {
 inline int g_persist_spare = 0;     // tunable: GPC_PERSIST_SPARE (block slots a persistent launch leaves free)
 inline long long g_gemm_launches = 0;  // MFMA GEMM launches of this process (gpc_quad_mix checks that it adds none)
 inline int g_block_slots = 512;     // two 128-tile blocks per CU (set from the device's CU count)
+// What a launch of BT-tiles can use of the guarantee g.tri, as the TRI of the instantiation that runs it (0: the plain
+// one): fp64 128-tiles only, a kind only beside the k-range it speaks of (a LAST kind needs the diagonal block to BE
+// the last one: K not cut short of it) and in the operand orientation the product launches it with -- the instantiations
+// that exist are those of plan.h: W^T W (k-major x k-major: TRI_A_FIRST, with or without TRI_DIAG_LOWER), W21 = -W22 U
+// and U = T21 W11 (m-major x k-major: TRI_A_LAST, TRI_B_FIRST), T21 = A21 W11^T and the syrk (m-major x m-major:
+// TRI_B_LAST, TRI_DIAG_LOWER alone).  Anything else is a guarantee nobody uses.
+// What the sequences of gemm_tile rely on follows from these conditions: k-ranges are whole 128-blocks, so a tile with
+// work has nk >= 8 slabs; a FIRST kind's triangular block is the one at k0 (klo names the operand's own index), a LAST
+// kind's the one that ends at k1 (khi names it, and K reaches it).  A range of ONE block may be head and tail at once
+// (klo and khi both given): an instantiation holds one kind, the other end runs plain.
+template <typename T, int BT, int NW>
+inline int tri_usable(const GemmArgs& g, bool akm, bool bkm) {
+  if constexpr (sizeof(T) != 8 || BT != 128 || NW != 4) {
+    return TRI_NONE;
+  } else {
+    const int kind = g.tri & TRI_KIND;
+    const bool diag = (g.tri & TRI_DIAG_LOWER) && g.lower_only;
+    if (akm && bkm) return (kind == TRI_A_FIRST && g.klo == KLO_ROW) ? (kind | (diag ? (int)TRI_DIAG_LOWER : 0)) : (int)TRI_NONE;
+    if (!akm && bkm) {
+      if (kind == TRI_A_LAST && g.khi == KHI_ROW && g.K >= g.M) return kind;
+      if (kind == TRI_B_FIRST && g.klo == KLO_COL) return kind;
+      return TRI_NONE;
+    }
+    if (!akm && !bkm) {
+      if (kind == TRI_B_LAST && g.khi == KHI_COL && g.K >= g.N) return kind;
+      if (kind == TRI_NONE && diag) return TRI_DIAG_LOWER;
+    }
+    return TRI_NONE;
+  }
+}
+// the launch of g.tri's instantiation (tri_usable's pairs of orientation and TRI); false: there is none for this
+// orientation, nothing was launched and the caller runs the plain kernel (a guarantee may always go unused)
+template <typename T, int BT, int NW>
+inline bool launch_gemm_tri(bool persist, dim3 grid, dim3 block, hipStream_t st, const GemmArgs& g, bool akm, bool bkm) {
+  if constexpr (sizeof(T) == 8 && BT == 128 && NW == 4) {
+#define GPC_TRI_LAUNCH(AKM, BKM, TRI)                                                                        \
+  case TRI:                                                                                                  \
+    if (akm != AKM || bkm != BKM) return false;                                                              \
+    if (persist)                                                                                             \
+      hipLaunchKernelGGL((gemm_persist_kernel<T, AKM, BKM, BT, NW, 0, TRI>), grid, block, 0, st, g);         \
+    else                                                                                                     \
+      hipLaunchKernelGGL((gemm_kernel<T, AKM, BKM, BT, NW, 0, BT, TRI>), grid, block, 0, st, g);             \
+    return true;
+    switch (g.tri) {
+      GPC_TRI_LAUNCH(true, true, TRI_A_FIRST)
+      GPC_TRI_LAUNCH(true, true, TRI_A_FIRST | TRI_DIAG_LOWER)
+      GPC_TRI_LAUNCH(false, true, TRI_A_LAST)
+      GPC_TRI_LAUNCH(false, true, TRI_B_FIRST)
+      GPC_TRI_LAUNCH(false, false, TRI_B_LAST)
+      GPC_TRI_LAUNCH(false, false, TRI_DIAG_LOWER)
+      default:
+        return false;
+    }
+#undef GPC_TRI_LAUNCH
+  }
+  return false;
+}
 template <typename T, int BT, int NW>
 inline hipError_t launch_gemm_bt(hipStream_t st, GemmArgs g, bool akm, bool bkm, int batch, int* ctr = nullptr,
                                  const unsigned short* reserve = nullptr) {
@@ -726,6 +967,7 @@ inline hipError_t launch_gemm_bt(hipStream_t st, GemmArgs g, bool akm, bool bkm,
   g.ntiles = ntiles;
   g.batch = batch;
   g.ctr = ctr;
+  g.tri = tri_usable<T, BT, NW>(g, akm, bkm);
   const unsigned dyn = 0u;
   // block slots of the chip for this tile size: two 128-tile workgroups per CU, four 64-tile ones
   const int cap = (BT == 128 ? g_block_slots : 2 * g_block_slots) - g_persist_spare;
@@ -735,6 +977,8 @@ inline hipError_t launch_gemm_bt(hipStream_t st, GemmArgs g, bool akm, bool bkm,
     // every shader engine has some); 64-tiles (round 5, independent pipelines) take the exact-fit grid -- the workgroups
     // that land on reserved CUs return, nothing stays pending in the dispatcher
     dim3 grid(reserve ? (BT == 128 ? cap + 96 : cap) : cap), block(64 * NW);
+    if (g.tri && launch_gemm_tri<T, BT, NW>(true, grid, block, st, g, akm, bkm)) return hipGetLastError();
+    g.tri = TRI_NONE;
     if (!akm && !bkm)
       hipLaunchKernelGGL((gemm_persist_kernel<T, false, false, BT, NW>), grid, block, dyn, st, g);
     else if (!akm && bkm)
@@ -746,6 +990,8 @@ inline hipError_t launch_gemm_bt(hipStream_t st, GemmArgs g, bool akm, bool bkm,
     return hipGetLastError();
   }
   dim3 grid(ntiles, batch), block(64 * NW);
+  if (g.tri && launch_gemm_tri<T, BT, NW>(false, grid, block, st, g, akm, bkm)) return hipGetLastError();
+  g.tri = TRI_NONE;
   if (!akm && !bkm)
     hipLaunchKernelGGL((gemm_kernel<T, false, false, BT, NW>), grid, block, dyn, st, g);
   else if (!akm && bkm)

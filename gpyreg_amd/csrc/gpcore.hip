@@ -480,6 +480,7 @@ struct gpc_ctx {
   // launch-bound and lose with the extra launches of the blocked solves (N=4096 S=1 2.28 / 2.42 / 2.30 / 2.28;
   // N=2048 S=1 0.96 / 1.01 / 0.98 / 0.98; N=1000 S=8 0.52 / 0.53 / 0.54 / 0.54): below npad = 2048 the round-2 scheme stays.
   int nll_block = -1;
+  int tri_skip = 1;  // option: the evaluation pipeline's launches name their triangular operands (plan.h: Factor::tri_skip)
   int solves_beside_lauum = 1;  // option: the two triangular mat-vecs of a gradient evaluation run under the W^T W launch
 #ifdef GPC_EXPERIMENTS
   // right-looking panels with look-ahead for NLL-only evaluations (plan.h: potrf_rl): panel height; 0 = off (default)
@@ -1098,6 +1099,7 @@ struct Pipe {
     F.info = d_info;
     F.nvalid = N;
     F.stable = stable || c->stable;
+    F.tri_skip = c->tri_skip != 0;
     if ((defer_node > 0 || use_rl) && !c->capturing && gpc::g_persist_spare >= 0) {
       F.side = c->sst[gidx];
       F.evs = c->dev_ev[gidx];
@@ -1217,7 +1219,9 @@ struct Pipe {
       }
       if (!dag_has_lauum) {
         if (!c->capturing) HIPCHK(c, hipEventRecord(c->ev_l0[gidx], st));
-        F.lauum(Tc, sM);
+        // the readers of Tc: trace_kernel uses j <= i only (it loads the rest of a diagonal 64-tile and drops it),
+        // diagq_kernel the diagonal; the plane-by-plane contraction of a user kernel is given whole diagonal tiles
+        F.lauum(Tc, sM, !kmode());
         if (!c->capturing) {
           HIPCHK(c, hipEventRecord(c->ev_l1[gidx], st));
           lauum_n[gidx] = n;
@@ -4357,7 +4361,10 @@ int debug_gemm_form_impl(gpc_ctx* c, int form, int tile, int batch, int flags, i
                          const double* ep_alpha, double* colsq, int* counters, int* available) {
   HookMem mem;
   GemmGlobalsGuard guard;
-  if (flags >= 0) gpc::g_gemm_flags = flags;
+  // bits 0-4: the GEMM flags of the call; bits 8-11: GemmArgs::tri of its products (a TRI_* kind, + 8 = TRI_DIAG_LOWER) --
+  // the caller then vouches for the operands it uploads
+  if (flags >= 0) gpc::g_gemm_flags = flags & 0xff;
+  const int tri = flags >= 0 ? (flags >> 8) & 15 : (int)TRI_NONE;
   if (block_slots > 0) {
     gpc::g_block_slots = block_slots;
     gpc::g_persist_spare = 0;
@@ -4408,6 +4415,7 @@ int debug_gemm_form_impl(gpc_ctx* c, int form, int tile, int batch, int flags, i
     a.klo = p.klo;
     a.khi = p.khi;
     a.lower_only = p.lower_only ? 1 : 0;
+    a.tri = tri;
   }
   int* ctr = nullptr;  // the hook's own CTR_STRIDE counters, zeroed
   HIPCHK(c, mem.get(reinterpret_cast<void**>(&ctr), CTR_STRIDE * sizeof(int)));
@@ -4573,6 +4581,7 @@ int debug_factor_plan_impl(gpc_ctx* c, int npad, int nvalid, int batch, int plan
   F.logdet = dld;
   F.info = dinfo;
   F.stable = (flags & 1) != 0;
+  F.tri_skip = c->tri_skip != 0;
   const bool keep_L = (flags & 2) != 0;
   if (plan == 2) {
     F.nll_block = nll_block;
@@ -7958,6 +7967,7 @@ const Option OPTIONS[] = {
     {"leaf_fault", nullptr, GPC_SET(gpc::g_leaf_fault = v != 0)},  // test hook: the pipelined leaf runs with a missing wave, its hand-offs time out
     {"nll_block", GPC_GET(c->nll_block), GPC_SET(c->nll_block = v < 0 ? -1 : (v == 0 ? 0 : tile_multiple(v)))},  // NLL-only: largest diagonal block with an inverse (multiple of 128; 0: left children inverted)
     {"solves_beside_lauum", GPC_GET(c->solves_beside_lauum), GPC_SET(c->solves_beside_lauum = v != 0)},  // 0: the triangular mat-vecs after the W^T W launch (round-2 order)
+    {"tri_skip", GPC_GET(c->tri_skip), GPC_SET(c->tri_skip = v != 0)},  // 0: no GEMM launch of the evaluation pipeline skips the zero MFMAs of triangular diagonal blocks (gemm.h: GemmArgs::tri; same bits either way)
     {"stable", GPC_GET(c->stable), GPC_SET(c->stable = v != 0)},  // every factorization in stable mode (refined panel solves, plan.h), not only the jitter retries
     {"small_path", GPC_GET(c->small_path), GPC_SET(c->small_path = v != 0)},  // 0: problems of one leaf take the general pipeline too (A/B and cross-checks)
     {"check_queues", GPC_GET(c->check_queues), GPC_SET(c->check_queues = v != 0)},  // debug: verify the tile queues of persistent launches after every pipeline
@@ -8203,12 +8213,42 @@ int gpc_debug_gemm_queues(int ntiles, int batch, int flags, int tiles_m, int til
   return 0;
 }
 
+int gpc_debug_tri_masks(int tri, int diag_tile, int slab, int* frag_rows, int* frag_cols, int* issued, int* stored) {
+  const int kind = tri & TRI_KIND;
+  if (tri < 0 || tri > 15 || kind > TRI_B_LAST || slab < 0 || slab > 7 || !frag_rows || !frag_cols || !issued || !stored) return -2;
+  for (int w = 0; w < 4; ++w) {
+    const int wr = w / 2, wc = w % 2;
+    for (int i = 0; i < 4; ++i) {
+      frag_rows[w * 4 + i] = tri_frag(wr, i);
+      frag_cols[w * 4 + i] = tri_frag(wc, i);
+      for (int j = 0; j < 4; ++j) {
+        issued[(w * 4 + i) * 4 + j] = tri_issued(tri, diag_tile != 0, slab, i, j) ? 1 : 0;
+        stored[(w * 4 + i) * 4 + j] = tri_stored(tri, diag_tile != 0, wr, wc, i, j) ? 1 : 0;
+      }
+    }
+  }
+  return 0;
+}
+
+int gpc_debug_tri_usable(int dtype, int tile, int a_kmajor, int b_kmajor, int klo, int khi, int lower_only, int M, int N,
+                         int K, int tri) {
+  if ((dtype != GPC_F64 && dtype != GPC_F32) || (tile != 64 && tile != 128) || tri < 0 || tri > 15) return -2;
+  GemmArgs g;
+  g.M = M, g.N = N, g.K = K;
+  g.klo = klo, g.khi = khi, g.lower_only = lower_only ? 1 : 0;
+  g.tri = tri;
+  const bool akm = a_kmajor != 0, bkm = b_kmajor != 0;
+  if (dtype == GPC_F64) return tile == 128 ? tri_usable<double, 128, 4>(g, akm, bkm) : tri_usable<double, 64, 4>(g, akm, bkm);
+  return tile == 128 ? tri_usable<float, 128, 4>(g, akm, bkm) : tri_usable<float, 64, 4>(g, akm, bkm);
+}
+
 int gpc_debug_gemm_form(gpc_ctx* c, int dtype, int form, int tile, int batch, int flags, int block_slots,
                         const gpc_gemm_product* p1, const gpc_gemm_product* p2, const double* ep_w, long long ep_sw,
                         const double* ep_alpha, double* colsq, int* counters, int* available) {
   if (!c) return -2;
   if (!p1 || !counters || !available || batch <= 0 || batch > 64 || form < GPC_FORM_PLAIN || form > GPC_FORM_WSQ ||
-      (tile != 64 && tile != 128) || (dtype != GPC_F64 && dtype != GPC_F32) || flags > 31 || block_slots > 4096)
+      (tile != 64 && tile != 128) || (dtype != GPC_F64 && dtype != GPC_F32) || (flags >= 0 && ((flags & 0xff) > 31 || (flags >> 8) > 15)) ||
+      block_slots > 4096)
     FAIL(c, "gpc_debug_gemm_form: bad arguments");
   const int vec = dtype == GPC_F64 ? 2 : 4;
   const gpc_gemm_product* prods[2] = {p1, p2};
@@ -8251,8 +8291,9 @@ int gpc_debug_factor_plan(gpc_ctx* c, int dtype, int npad, int nvalid, int batch
                           int* info) {
   if (!c) return -2;
   if (dtype != GPC_F64 && dtype != GPC_F32) FAIL(c, "gpc_debug_factor_plan: dtype must be GPC_F64 or GPC_F32");
-  if (npad < TILE || npad % TILE != 0 || npad > 2048)
-    FAIL(c, "gpc_debug_factor_plan: npad must be a multiple of 128 in 128 .. 2048");
+  // (2304 as well: the 18-tile root, odd halves of 9 tiles below it -- tests/test_gpu_tri_skip.py)
+  if (npad < TILE || npad % TILE != 0 || (npad > 2048 && npad != 2304))
+    FAIL(c, "gpc_debug_factor_plan: npad must be a multiple of 128 in 128 .. 2048, or 2304");
   if (batch < 1 || batch > 16) FAIL(c, "gpc_debug_factor_plan: batch must be 1 .. 16");
   if (plan < 0 || plan > 2) FAIL(c, "gpc_debug_factor_plan: plan must be 0, 1 or 2");
   if (plan == 2 && (nll_block < TILE || nll_block % TILE != 0 || nll_block > npad))

@@ -101,6 +101,11 @@ struct Factor {
       ev_tail = nullptr;
     }
   }
+  // Zero skipping (gemm.h: GemmArgs::tri): the launches below that multiply by a triangular diagonal block say so,
+  // and the chip-filling fp64 launches among them do not issue the MFMAs of its zero half.  Off: no launch says anything
+  // and every launch is the plain one (gpc_set_option "tri_skip").  Same bits either way.
+  bool tri_skip = false;
+  int tri(int what) const { return tri_skip ? what : (int)TRI_NONE; }
   double flops = 0;      // algorithmic flops issued (tile-exact)
   int launches = 0;
   hipError_t err = hipSuccess;
@@ -132,8 +137,9 @@ struct Factor {
 
   void gemm(T* C, long long sC, const T* Aop, long long sAop, const T* Bop, long long sBop, int M,
             int N, int K, bool akm, bool bkm, double alpha, int beta, int klo, int khi, int lower,
-            hipStream_t on = nullptr, const unsigned short* rsv = nullptr) {
+            hipStream_t on = nullptr, const unsigned short* rsv = nullptr, int tri_what = TRI_NONE) {
     GemmArgs g;
+    g.tri = tri(tri_what);
     g.A = Aop;
     g.B = Bop;
     g.C = C;
@@ -205,14 +211,18 @@ struct Factor {
     potrf_inv(o1, n1, true, keep_L);
     need_rows(o2 + n2);
     // 2. T21 = A21 * W11^T
+    // (TRI_B_LAST: B(k, n) = W11[n][k], and W = L^-1 is lower triangular -- the leaf writes its whole diagonal tile of
+    // W, zeros above the diagonal, and nothing else ever writes there: zero for k > n in the block k1 ends with)
     gemm(blk(Tm, o2, o1), sT, blk(A, o2, o1), sA, blk(W, o1, o1), sW, n2, n1, n1, false, false, 1.0,
-         0, KLO_ZERO, KHI_COL, 0);
+         0, KLO_ZERO, KHI_COL, 0, nullptr, nullptr, TRI_B_LAST);
     if (stable) {
       // 2b. R = A21 - T21 * L11^T (in place: A21 is only ever the C operand), T21 += R * W11^T
+      // (TRI_B_LAST for both: B(k, n) = L11[n][k] out of A, whose diagonal tiles the STABLE leaf clears above the
+      // diagonal for this very product (leaf.h); then W11 as in step 2)
       gemm(blk(A, o2, o1), sA, blk(Tm, o2, o1), sT, blk(A, o1, o1), sA, n2, n1, n1, false, false, -1.0, 1, KLO_ZERO,
-           KHI_COL, 0);
+           KHI_COL, 0, nullptr, nullptr, TRI_B_LAST);
       gemm(blk(Tm, o2, o1), sT, blk(A, o2, o1), sA, blk(W, o1, o1), sW, n2, n1, n1, false, false, 1.0, 1, KLO_ZERO,
-           KHI_COL, 0);
+           KHI_COL, 0, nullptr, nullptr, TRI_B_LAST);
     }
     const bool defer = need_inv && side && defer_min > 0 && n >= defer_min && ev_used + 2 <= nev;
     // 3. A22 -= T21 * T21^T  -- and, where both are small launches, 5a. U = T21 * W11 -> A21 in the same launch:
@@ -236,8 +246,11 @@ struct Factor {
       }
       if (!u_done) {
         flops -= gemm_flops(gs, batch);
+        // (TRI_DIAG_LOWER: what a diagonal tile of A22 holds above its diagonal is read by nobody -- the leaf factors
+        // the lower triangle, later syrks only add to it -- except where L survives in A as an operand: keep_L, which
+        // stable mode implies, and there the launch stays whole)
         gemm(blk(A, o2, o2), sA, blk(Tm, o2, o1), sT, blk(Tm, o2, o1), sT, n2, n2, n1, false, false, -1.0, 1,
-             KLO_ZERO, KHI_FULL, 1);
+             KLO_ZERO, KHI_FULL, 1, nullptr, nullptr, keep_L ? TRI_NONE : TRI_DIAG_LOWER);
       }
     }
     hipEvent_t ev_join = nullptr;
@@ -247,8 +260,9 @@ struct Factor {
       ev_join = evs[ev_used++];
       chk(hipEventRecord(ev_fork, st));
       chk(hipStreamWaitEvent(side, ev_fork, 0));
+      // (TRI_B_FIRST: B(k, n) = W11[k][n], lower triangular W as in step 2: zero for k < n in the block k0 starts with)
       gemm(blk(A, o2, o1), sA, blk(Tm, o2, o1), sT, blk(W, o1, o1), sW, n2, n1, n1, false, true, 1.0, 0,
-           KLO_COL, KHI_FULL, 0, side, reserve);
+           KLO_COL, KHI_FULL, 0, side, reserve, TRI_B_FIRST);
       chk(hipEventRecord(ev_join, side));
     }
     potrf_inv(o2, n2, need_inv, keep_L);
@@ -258,10 +272,12 @@ struct Factor {
         chk(hipStreamWaitEvent(st, ev_join, 0));
       else if (!u_done)
         gemm(blk(A, o2, o1), sA, blk(Tm, o2, o1), sT, blk(W, o1, o1), sW, n2, n1, n1, false, true, 1.0, 0,
-             KLO_COL, KHI_FULL, 0);
+             KLO_COL, KHI_FULL, 0, nullptr, nullptr, TRI_B_FIRST);
       // 5b. W21 = -W22 * U
+      // (TRI_A_LAST: A(m, k) = W22[m][k], the right child's complete lower triangular inverse: zero for k > m in the
+      // block k1 ends with)
       gemm(blk(W, o2, o1), sW, blk(W, o2, o2), sW, blk(A, o2, o1), sA, n2, n1, n2, false, true, -1.0,
-           0, KLO_ZERO, KHI_ROW, 0);
+           0, KLO_ZERO, KHI_ROW, 0, nullptr, nullptr, TRI_A_LAST);
     }
     // L21 back into A: only where L must survive as the Cholesky factor (posteriors).  The blocked forward solve
     // of an NLL-only evaluation reads L21 where it was computed, in the scratch (forward_solve below).
@@ -290,13 +306,15 @@ struct Factor {
 
   void trsm_nll(int r0, int m, int c0, int n) {
     if (n <= nll_block) {
+      // (TRI_B_LAST: the block's complete lower triangular inverse, resp. its factor under the STABLE leaf's zeros, as
+      // in potrf_inv steps 2 and 2b)
       gemm(blk(Tm, r0, c0), sT, blk(A, r0, c0), sA, blk(W, c0, c0), sW, m, n, n, false, false, 1.0, 0, KLO_ZERO,
-           KHI_COL, 0);
+           KHI_COL, 0, nullptr, nullptr, TRI_B_LAST);
       if (stable) {  // refinement against the factor of the block, as in potrf_inv (L of the block is complete in A)
         gemm(blk(A, r0, c0), sA, blk(Tm, r0, c0), sT, blk(A, c0, c0), sA, m, n, n, false, false, -1.0, 1, KLO_ZERO,
-             KHI_COL, 0);
+             KHI_COL, 0, nullptr, nullptr, TRI_B_LAST);
         gemm(blk(Tm, r0, c0), sT, blk(A, r0, c0), sA, blk(W, c0, c0), sW, m, n, n, false, false, 1.0, 1, KLO_ZERO,
-             KHI_COL, 0);
+             KHI_COL, 0, nullptr, nullptr, TRI_B_LAST);
       }
       return;
     }
@@ -319,8 +337,9 @@ struct Factor {
     potrf_nll(o1, n1);
     need_rows(o2 + n2);
     trsm_nll(o2, n2, o1, n1);
+    // (TRI_DIAG_LOWER as in potrf_inv step 3: nobody reads a diagonal tile of A22 above its diagonal, stable mode apart)
     gemm(blk(A, o2, o2), sA, blk(Tm, o2, o1), sT, blk(Tm, o2, o1), sT, n2, n2, n1, false, false, -1.0, 1, KLO_ZERO,
-         KHI_FULL, 1);
+         KHI_FULL, 1, nullptr, nullptr, stable ? TRI_NONE : TRI_DIAG_LOWER);
     potrf_nll(o2, n2);
   }
 
@@ -438,8 +457,12 @@ struct Factor {
   }
 
   // Ainv (lower tiles, into `out`) = W^T W
-  void lauum(T* out, long long sOut) {
-    gemm(out, sOut, W, sW, W, sW, npad, npad, npad, true, true, 1.0, 0, KLO_ROW, KHI_FULL, 1);
+  // (TRI_A_FIRST: A(m, k) = W[k][m], W lower triangular with the leaves' zeros above the diagonal of its diagonal tiles:
+  // zero for k < m in the block k0 starts with.  TRI_DIAG_LOWER where the caller says that nobody reads `out` above the
+  // diagonal inside its diagonal tiles -- a beta = 0 launch: those fragments keep whatever the buffer held.)
+  void lauum(T* out, long long sOut, bool lower_frags_only = false) {
+    gemm(out, sOut, W, sW, W, sW, npad, npad, npad, true, true, 1.0, 0, KLO_ROW, KHI_FULL, 1, nullptr, nullptr,
+         TRI_A_FIRST | (lower_frags_only ? TRI_DIAG_LOWER : 0));
   }
 };
 

@@ -634,7 +634,9 @@ int gpc_last_lauum_timing(gpc_ctx* ctx, double* ms, double* flops);
  * GPC_SMALL_BLOCKS, GPC_DEFER_MIN, GPC_DEFER_RESERVE): "groups" = sample groups on separate HIP
  * streams (1..8), "small_blocks" = launch size below which 64x64 tiles are used, "defer_min" = node
  * size from which the inverse product U = T21 W11 runs on a side stream (0 off, -1 auto),
- * "defer_reserve" = CUs per XCD that launch keeps empty (2 | 4 | 8 | 12).  Test hooks:
+ * "defer_reserve" = CUs per XCD that launch keeps empty (2 | 4 | 8 | 12), "tri_skip" (default 1) = the GEMM launches
+ * of the evaluation pipeline name their triangular operands and the fp64 128-tile kernel skips the MFMAs of the zero
+ * halves (gemm.h: GemmArgs::tri; 0: every launch is the plain one -- the same bits either way).  Test hooks:
  * "start_mult_log10" = k starts the jitter escalation of every factorization at 10^k instead of 1
  * (gaussian_process.py:2402), "append_fail_mask" = bit s declares the rank-one append of sample s
  * unstable (:789-798).  "experiments" (get only): 1 when the loaded library is the experiments build.
@@ -677,7 +679,7 @@ int gpc_debug_leaf(gpc_ctx* ctx, int dtype, const double* A, double* L, double* 
 int gpc_debug_factor(gpc_ctx* ctx, int dtype, int n, const double* A, double* L,
                      double* W, double* Ainv, double* logdet, int* info);
 /* The launch plan of gpyreg_amd/csrc/plan.h as the product runs it: `batch` samples of npad x npad (a multiple of 128,
- * at most 2048; batch 1 .. 16) in one call, on buffers of the hook's own.  A, W, T: [batch][npad][npad], uploaded WHOLE
+ * at most 2048, or 2304; batch 1 .. 16) in one call, on buffers of the hook's own.  A, W, T: [batch][npad][npad], uploaded WHOLE
  * and verbatim (a plain cast for fp32) -- identity padding, the part above the diagonal and whatever the caller poisons
  * W and the scratch T with included -- and downloaded whole after the factorization, so that a read of something no
  * launch wrote and a write outside the plan's contract both show.  nvalid: rows below it are data, the rest padding.
@@ -863,6 +865,20 @@ int gpc_debug_scratch_bytes(const char* name, int dtype, const int* dims, int nd
  * Returns 0, -2 (bad arguments), -3 (the queues hold more than ntiles * batch items).                                */
 int gpc_debug_gemm_queues(int ntiles, int batch, int flags, int tiles_m, int tiles_n, int klo, int khi, int lower_only,
                           int* q_total, int* q_items, int* tile_ij, int* xcd_items);
+/* Debug, HOST ONLY (no device needed): what the zero-skipping instantiation `tri` of the fp64 128-tile GEMM (gemm.h:
+ * GemmArgs::tri -- 1 A-first, 2 A-last, 3 B-first, 4 B-last, + 8 diag-lower) does in k-slab `slab` (0..7) of the
+ * triangular diagonal 128-block of a tile's k-range, per wave w = 2 wr + wc of the block, through the mask types the
+ * kernel is built from.  diag_tile: the tile is a diagonal output tile of a lower_only launch.
+ *   frag_rows[4 * 4], frag_cols[4 * 4]  the 16-row / 16-column fragment of the 128-tile that slot i / j of wave w owns
+ *   issued[4 * 4 * 4]                   1 where wave w issues the MFMAs of its fragment (i, j) in that slab
+ *   stored[4 * 4 * 4]                   1 where wave w stores its fragment (i, j) at the end of the tile
+ * Returns 0 or -2 (bad arguments).                                                                                   */
+int gpc_debug_tri_masks(int tri, int diag_tile, int slab, int* frag_rows, int* frag_cols, int* issued, int* stored);
+/* Debug, HOST ONLY: the instantiation (the `tri` of gpc_debug_tri_masks; 0: the plain kernel) that launch_gemm_bt picks
+ * for a launch of `tile`-tiles (64 | 128) that gives the guarantee `tri` with these orientations, k-range modes and
+ * sizes -- gemm.h: tri_usable, the function the launcher calls.  -2: bad arguments.                                  */
+int gpc_debug_tri_usable(int dtype, int tile, int a_kmajor, int b_kmajor, int klo, int khi, int lower_only, int M, int N,
+                         int K, int tri);
 
 /* One product of gpc_debug_gemm_form, as the kernels see it: C[b] (M x N, rows ldc apart, at element off_c + b s_c of
  * an allocation of size_c elements) = beta C[b] + alpha op(A[b]) op(B[b]); A stored K x M when a_kmajor (else M x K)
@@ -899,7 +915,11 @@ enum { GPC_FORM_PLAIN = 0, GPC_FORM_PERSIST = 1, GPC_FORM_PERSIST_RESERVED = 2, 
  *                      those rows of ep_w[b ep_sw + row] (C + ep_alpha[b] acc)^2; ep_w holds (batch - 1) ep_sw + M values
  * tile: 64 or 128 (PLAIN, PERSIST, PERSIST_RESERVED).  flags >= 0 replaces the GEMM flags (bit 3: XCD-affine queues,
  * bit 4: XCD-aware order) and block_slots > 0 the block slots of the chip (and clears persist_spare) for this call
- * only.  The hook checks that every operand lies inside its allocation, allocates and zeroes its own counters, and
+ * only.  Bits 8-11 of flags >= 0 are the GemmArgs::tri of the products (1 A-first, 2 A-last, 3 B-first, 4 B-last: the
+ * operand is lower triangular in the first / last 128-block of each tile's k-range; + 8 diag-lower: the fragments above
+ * the diagonal of the diagonal tiles of a lower_only launch may stay unwritten): the CALLER vouches that the operands it
+ * uploads are zero there -- the fp64 128-tile forms then do not multiply by that half, every other form ignores the
+ * bits (gpc_debug_tri_usable says which instantiation a launch gets).  The hook checks that every operand lies inside its allocation, allocates and zeroes its own counters, and
  * returns the eight queue counters as the launch left them (all 0 after a plain launch).  colsq[batch (M / 128) N]
  * (COLSQ, WSQ) is preset to NaN.                                                                                     */
 int gpc_debug_gemm_form(gpc_ctx* ctx, int dtype, int form, int tile, int batch, int flags, int block_slots,
