@@ -68,7 +68,12 @@ SIGNATURES = {
     "gpc_posterior_batch_gobs": (
         C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.POINTER(_vp), _dp, _dp, _ip, _ip]),
     "gpc_nll_batch_gobs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _ip, _ip]),
+    "gpc_nll_batch_gobs_grad": (
+        C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _ip,
+                  _ip]),
     "gpc_predict_gobs": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
+    "gpc_debug_gobs_trace": (
+        C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, _dp, C.c_double, _dp]),
     "gpc_debug_gobs_cov": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp]),
     "gpc_debug_gobs_cross": (
         C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
@@ -343,6 +348,40 @@ class Context:
                                           _ptr(mult), lchol.ctypes.data, info.ctypes.data)
         self._check(rc, "gpc_nll_batch_gobs")
         return nlz, mult, lchol.astype(bool), info
+
+    @_serial
+    def nll_batch_gobs_grad(self, kid, degree, dtype, hyp_cov, m, sn2, dm=None, dsn2=None):
+        """gpc_nll_batch_gobs_grad: (nlz, dnlz (S, cov_N + noise_N + mean_N), mult, lchol, info).  dm (S, n, mean_N) and
+        dsn2 (S, n, noise_N) are the joint-ordered derivative rows (None: no such hyperparameters)."""
+        hyp_cov, m, sn2, S, nlz, mult, lchol, info = self._gobs_args(hyp_cov, m, sn2)
+        dm = None if dm is None or dm.shape[-1] == 0 else _f64(dm)
+        dsn2 = None if dsn2 is None or dsn2.shape[-1] == 0 else _f64(dsn2)
+        for name, d in (("dm", dm), ("dsn2", dsn2)):
+            if d is not None and d.shape[:2] != (S, self.N):
+                raise ValueError(f"{name} must be (S, n, count) = ({S}, {self.N}, count) in joint order, got {d.shape}")
+        mean_N = 0 if dm is None else dm.shape[2]
+        noise_N = 0 if dsn2 is None else dsn2.shape[2]
+        dnlz = np.empty((S, hyp_cov.shape[1] + noise_N + mean_N))
+        rc = self._lib.gpc_nll_batch_gobs_grad(self._h, kid, degree, dtype, S, _ptr(hyp_cov), _ptr(m), _ptr(sn2), _ptr(dm),
+                                               mean_N, _ptr(dsn2), noise_N, _ptr(nlz), _ptr(dnlz), _ptr(mult),
+                                               lchol.ctypes.data, info.ctypes.data)
+        self._check(rc, "gpc_nll_batch_gobs_grad")
+        return nlz, dnlz, mult, lchol.astype(bool), info
+
+    @_serial
+    def debug_gobs_trace(self, kid, degree, hyp_cov, X, Xg, Ainv, alpha, sl=1.0):
+        """gpc_debug_gobs_trace: (cov_N,) sums of (Ainv / sl - alpha alpha^T) o dK / dtheta_p as gobs_trace_kernel and
+        its reduction compute them; only the lower triangle of Ainv (n, n) is read."""
+        hyp_cov, X, Xg, Ainv, alpha = _f64(hyp_cov).ravel(), _f64(X), _f64(Xg), _f64(Ainv), _f64(alpha).ravel()
+        (N, D), Ng = X.shape, Xg.shape[0]
+        n = N + Ng * D
+        if Ainv.shape != (n, n) or alpha.size != n:
+            raise ValueError(f"Ainv must be (n, n) and alpha (n,) with n = {n} in joint order")
+        out = np.empty(hyp_cov.size)
+        rc = self._lib.gpc_debug_gobs_trace(self._h, kid, degree, _ptr(hyp_cov), _ptr(X), N, D, _ptr(Xg), Ng, _ptr(Ainv),
+                                            _ptr(alpha), float(sl), _ptr(out))
+        self._check(rc, "gpc_debug_gobs_trace")
+        return out
 
     @_serial
     def debug_gobs_cov(self, kid, degree, hyp_cov, X, Xg):

@@ -225,6 +225,52 @@ __device__ __forceinline__ PairFG pair_eval_fg_t(double r2, double sf2, double r
   return o;
 }
 
+// The third radial factor H = -2 dG/d(r2) next to K, F and G, and (rational quadratic) the log-alpha derivatives of K, F
+// and G: what the hyperparameter derivatives of the gradient-observation covariance are made of (gradobs.h:
+// gobs_trace_kernel).  A sibling of pair_eval_fg_t, which stays as it is: K, F, Ka and G are taken from it and from
+// pair_eval_t (the same bits), the rest repeats their subexpressions, which the compiler shares after inlining.
+//   SE: K    Matern 3: e (1 + t) / t^3    Matern 5: e / (3 t)    RQ: (alpha + 2) / alpha G / m
+//   Fa = F (Ka / K + (m - 1) / m)      Ga = G (-1 / (alpha + 1) + Fa / F + (m - 1) / m)
+// Both Matern kernels have H = +inf at r2 = 0 (every term that carries H tends to 0 there: the caller drops them, as it
+// does G's); Matern 1 gets G = H = 0.
+struct PairFGH {
+  double K, F, G, H, Ka, Fa, Ga;
+};
+template <int KIND, int DEG>
+__device__ __forceinline__ PairFGH pair_eval_fgh_t(double r2, double sf2, double rqa, const ExpC& ex) {
+  const PairVal pv = pair_eval_t<KIND, DEG>(r2, sf2, rqa, ex);
+  const PairFG fg = pair_eval_fg_t<KIND, DEG>(r2, sf2, rqa, ex);
+  PairFGH o;
+  o.K = pv.K;
+  o.F = fg.F;
+  o.G = fg.G;
+  o.Ka = pv.Ka;
+  o.Fa = 0.0;
+  o.Ga = 0.0;
+  if constexpr (KIND == K_SE || KIND == K_SE_ISO) {
+    o.H = pv.K;
+  } else if constexpr (KIND == K_MATERN || KIND == K_MATERN_ISO) {
+    const double t = sqrt_fast(r2);
+    if constexpr (DEG == 3) {
+      o.H = pv.K / (t * t * t);  // K = e (1 + t)
+    } else if constexpr (DEG == 5) {
+      o.H = fg.G / t;
+    } else {
+      o.H = 0.0;
+    }
+  } else {
+    const double Mv = fma(r2, 0.5 / rqa, 1.0);
+    const double lM = log(Mv);
+    const double rM = rcp_fast(Mv);
+    const double h = fma(0.5 * r2, rM, -rqa * lM);  // Ka / K
+    const double q = (r2 * (0.5 / rqa)) * rM;       // (m - 1) / m
+    o.H = ((rqa + 2.0) / rqa) * (fg.G * rM);
+    o.Fa = fg.F * (h + q);
+    o.Ga = fg.G * ((h + q) + q - 1.0 / (rqa + 1.0));
+  }
+  return o;
+}
+
 // squared distances of the 4 x 4 pairs of one thread (rows ty + 16a of tile i, rows tx + 16c of tile j),
 // dimensions summed in ascending order; leaves the LAST staged chunk of dimensions in xi / xj
 __device__ __forceinline__ void tile_r2_ab(double (&r2)[4][4], double (*xi)[DCH + 1], double (*xj)[DCH + 1],

@@ -500,6 +500,7 @@ struct gpc_ctx {
   unsigned long long small_polled = 0, small_synced = 0;  // statistics ("small_polled" / "small_synced")
   int last_chunk = 0;  // what plan_chunk last returned ("last_chunk")
   unsigned long long grad_post_gram_us = 0;  // Gram passes of the last gpc_grad_post, device microseconds ("grad_post_gram_us")
+  unsigned long long gobs_trace_us = 0;  // the contraction (kernel + reduction) of the last gpc_debug_gobs_trace, device microseconds
   unsigned long long gobs_cov_us = 0, gobs_cross_us = 0;  // the kernel of the last gpc_debug_gobs_cov / the build of the last gpc_debug_gobs_cross, device microseconds
   unsigned long long hess_contract_us = 0;  // contraction passes of the last gpc_predict_hess, device microseconds ("hess_contract_us")
   unsigned long long nll_hess_gram_us = 0, nll_hess_contract_us = 0;  // Gram pass / second-derivative contraction of the last gpc_nll_hess, device microseconds
@@ -1244,9 +1245,23 @@ struct Pipe {
       double* parts = c->parts.as<double>() + (size_t)off * ntl * Pn;
       double* diagq = c->diagq.as<double>() + (size_t)off * npad;
       if (kmode()) {
-        // diag(Q) and trace(Q) now; the covariance slots are filled plane by plane after the sync (trace_planes)
+        // diag(Q) and trace(Q) now; the covariance slots are filled plane by plane after the sync (trace_planes) -- or,
+        // with gradient observations, here on the stream by the fused contraction of gradobs.h: no plane, no round trip
         hipLaunchKernelGGL((diagq_kernel<T>), dim3(1, n), dim3(256), 0, st, (const T*)Tc, sM, npad, (const double*)avec,
                            (const double*)spb, N, diagq, c->gout.as<double>() + (size_t)off * Pn, Pn);
+        if (gobs.Ng > 0) {
+          if constexpr (sizeof(T) == 8) {
+            GobsTraceScratch z;
+            CARVECHK(c, "gpc_nll_batch_gobs_grad", ScratchCarver::carve(z, c->parts.p, chunk_cnt, gobs, Pn));
+            const size_t gper = (size_t)gobs.P() * D, tiles = (size_t)gobs.trace_rows();
+            launch_gobs_trace(st, b.cd, gobs, n, c->gxs.as<double>() + (size_t)off * gper, spb,
+                              c->mulb.as<double>() + (size_t)off * D, c->divb.as<double>() + (size_t)off * D,
+                              (const double*)Tc, sM, npad, avec, npad, z.part + (size_t)off * tiles * Pn, Pn,
+                              c->gout.as<double>() + (size_t)off * Pn);
+          } else {
+            FAIL(c, "the gradient of the gradient-observation likelihood is fp64 only");
+          }
+        }
       } else {
         GPC_COV_DISPATCH(trace_kernel, T, b.cd, dim3(ntl, n), dim3(256), 4 * (((Pn + 3) & ~3) + 4) * sizeof(double), st,
                          b.cd, (const double*)xs, (const double*)spb, (const double*)avec, N, npad, (const T*)Tc, sM,
@@ -1747,7 +1762,10 @@ struct Pipe {
     double* d_quad = d_logdet + cnt;
     int* d_info = reinterpret_cast<int*>(d_quad + cnt);
     if (mode == MODE_GRAD) {
-      HIPCHK(c, c->parts.ensure((size_t)cnt * ntl * Pn * sizeof(double)));
+      // (gradient observations: the contraction's per-tile partials, scratch.h's GobsTraceScratch, take the place of the
+      // built-in kernels' -- one block serves either)
+      const size_t gtb = gobs.Ng > 0 ? ScratchCarver::count<GobsTraceScratch>(cnt, gobs, Pn) : 0;
+      HIPCHK(c, c->parts.ensure(std::max((size_t)cnt * ntl * Pn * sizeof(double), gtb)));
       HIPCHK(c, c->gout.ensure((size_t)cnt * Pn * sizeof(double)));
       HIPCHK(c, c->diagq.ensure(cnt * vb));
       if (mean_N > 0) {
@@ -2046,7 +2064,7 @@ struct Pipe {
       int rc = verify_queues();
       if (rc) return rc;
     }
-    if (kmode() && mode == MODE_GRAD)
+    if (kmode() && mode == MODE_GRAD && gobs.Ng == 0)
       for (int i = 0; i < cnt; ++i)
         if (hinfo[i] == 0) {
           int rc = trace_planes(s0 + i, slot + i);
@@ -7158,6 +7176,26 @@ int gpc_nll_batch_gobs(gpc_ctx* c, int kernel_id, int degree, int dtype, int S, 
   return nll_impl<float>(c, b, 0, nullptr, 0, nullptr, 0, nlz, nullptr, sn2_mult, L_chol, info, &km);
 }
 
+int gpc_nll_batch_gobs_grad(gpc_ctx* c, int kernel_id, int degree, int dtype, int S, const double* hyp_cov, const double* m,
+                            const double* sn2, const double* dm, int mean_N, const double* dsn2, int noise_N, double* nlz,
+                            double* dnlz, double* sn2_mult, int* L_chol, int* info) {
+  if (!c) return -2;
+  if (int rc = gobs_kernel_check(c, kernel_id, degree, "gpc_nll_batch_gobs_grad")) return rc;
+  if (int rc = check_batch_args(c, kernel_id, degree, dtype, S, true)) return rc;
+  if (dtype != GPC_F64)
+    FAIL(c, "gpc_nll_batch_gobs_grad: fp64 only (the contraction reads the inverse in the precision it accumulates in); "
+            "dtype must be GPC_F64");
+  if (!hyp_cov || !m || !sn2 || !nlz || !dnlz || !sn2_mult || !L_chol || !info) FAIL(c, "gpc_nll_batch_gobs_grad: null argument");
+  if (mean_N < 0 || noise_N < 0 || (mean_N > 0 && !dm) || (noise_N > 0 && !dsn2))
+    FAIL(c, "gpc_nll_batch_gobs_grad: mean_N / noise_N hyperparameters need their joint-ordered rows dm / dsn2");
+  HIPCHK(c, hipSetDevice(c->device));
+  Batch b;
+  fill_batch(c, b, kernel_id, degree, S, hyp_cov, m, sn2, 1);
+  KArgs km;
+  km.gobs = c->gobs;
+  return nll_impl<double>(c, b, 1, dm, mean_N, dsn2, noise_N, nlz, dnlz, sn2_mult, L_chol, info, &km);
+}
+
 int gpc_predict_gobs(gpc_post* po, const double* xstar, int M, double* fmu, double* fs2) {
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
@@ -7225,6 +7263,43 @@ int gpc_debug_gobs_cov(gpc_ctx* c, int kernel_id, int degree, const double* hyp_
   HIPCHK(c, hipMemcpyAsync(out, c->dbg1.p, nn * 8, hipMemcpyDeviceToHost, c->st));
   HIPCHK(c, hipStreamSynchronize(c->st));
   c->gobs_cov_us = (unsigned long long)clk.elapsed_us();
+  return 0;
+}
+
+int gpc_debug_gobs_trace(gpc_ctx* c, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                         const double* Xg, int Ng, const double* Ainv, const double* alpha, double sl, double* out) {
+  if (!c) return -2;
+  if (!Ainv || !alpha || !out || !(sl > 0.0)) FAIL(c, "gpc_debug_gobs_trace: bad arguments");
+  GobsDims gd;
+  gd.N = N, gd.Ng = Ng, gd.D = D;
+  if (int rc = gobs_dims_check(c, gd, "gpc_debug_gobs_trace")) return rc;
+  if (kernel_id < 0 || !valid_kernel(kernel_id, degree)) FAIL(c, "gpc_debug_gobs_trace: unknown covariance kernel / degree");
+  const size_t n = (size_t)gd.n();
+  const int cov_N = cov_count_of(kernel_id, D);
+  // after the common part: alpha n | the sums cov_N | the per-tile partials (scratch.h: GobsTraceScratch)
+  const size_t head = (n + cov_N + 1) & ~(size_t)1;
+  const size_t extra = head + ScratchCarver::count<GobsTraceScratch>(1, gd, cov_N) / 8;
+  GobsDebug g;
+  if (int rc = gobs_debug_begin(c, kernel_id, degree, hyp_cov, X, N, D, Xg, Ng, extra, g, "gpc_debug_gobs_trace")) return rc;
+  double* d_alpha = g.rest;
+  double* d_out = d_alpha + n;
+  GobsTraceScratch z;
+  CARVECHK(c, "gpc_debug_gobs_trace", ScratchCarver::carve(z, g.rest + head, 1, gd, cov_N));
+  hipStream_t st = c->st;
+  HIPCHK(c, c->dbg1.ensure(n * n * 8));
+  HIPCHK(c, hipMemcpyAsync(c->dbg1.p, Ainv, n * n * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(d_alpha, alpha, n * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemcpyAsync(g.sp + SP_SL, &sl, 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  GramClock clk(true);
+  HIPCHK(c, clk.record(0, st));
+  launch_gobs_trace(st, g.cd, g.gd, 1, g.xs, g.sp, g.mul, g.dv, c->dbg1.as<double>(), 0, (int)n, d_alpha, 0, z.part, cov_N,
+                    d_out);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, clk.record(1, st));
+  HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)cov_N * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  c->gobs_trace_us = (unsigned long long)clk.elapsed_us();
   return 0;
 }
 
@@ -7980,6 +8055,7 @@ const Option OPTIONS[] = {
     {"nll_hess_contract_us", GPC_COUNTER(nll_hess_contract_us)},  // ... of its second-derivative contraction (ARD families; 0 for the isotropic ones)
     {"cv_grad_trace_us", GPC_COUNTER(cv_grad_trace_us)},  // device time of the contraction pass (kernel + reduction) of the last gpc_cv_grad (timed calls only)
     {"gobs_cov_us", GPC_COUNTER(gobs_cov_us)},      // device time of the kernel of the last gpc_debug_gobs_cov
+    {"gobs_trace_us", GPC_COUNTER(gobs_trace_us)},  // device time of the contraction of the last gpc_debug_gobs_trace
     {"gobs_cross_us", GPC_COUNTER(gobs_cross_us)},  // device time of the build (operand + mean product) of the last gpc_debug_gobs_cross
     {"grad_post_gram_us", GPC_COUNTER(grad_post_gram_us)},  // device time of the Gram passes of the last gpc_grad_post (timed calls only)
     {"lookahead_batch_loop_us", GPC_COUNTER(lookahead_batch_loop_us)},  // device time of the step loop (all q steps, without the formation of C^0) of the last gpc_lookahead_batch

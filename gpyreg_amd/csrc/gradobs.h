@@ -26,6 +26,12 @@ struct GobsDims {
   __host__ __device__ int Ngp() const { return (Ng + CT - 1) / CT * CT; }
   __host__ __device__ int P() const { return Np() + Ngp(); }  // rows of the point list
   __host__ __device__ long long n() const { return (long long)N + (long long)Ng * D; }  // joint order
+  __host__ __device__ int vt() const { return Np() / CT; }   // tiles of value points, of gradient points
+  __host__ __device__ int gt() const { return Ngp() / CT; }
+  // rows of gobs_trace_kernel's partials: [vv tiles of the lower triangle | gv tiles | gg tiles x D]
+  __host__ __device__ long long trace_rows() const {
+    return (long long)vt() * (vt() + 1) / 2 + (long long)vt() * gt() + (long long)gt() * gt() * D;
+  }
 };
 
 // ---------------------------------------------------------------------------------
@@ -265,6 +271,312 @@ __global__ __launch_bounds__(256) void gobs_cross_tile_kernel(
   if (t < CT) part_all[((size_t)b * (P / CT) + blockIdx.y) * mb + j0 + t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
 }
 
+// ---------------------------------------------------------------------------------
+// The hyperparameter gradient of the joint likelihood (gpc_nll_batch_gobs_grad; DESIGN.md "Gradient-observation
+// likelihood gradient"): out_p = sum_IJ Wt_IJ d K_IJ / d theta_p over the n x n joint matrix, Wt = Tm / sl - alpha alpha^T
+// read from the LOWER triangle of Tm, every d K entry evaluated here from the point list -- no plane exists anywhere.
+// One 64 x 64 tile of pairs of the list per block, 4 x 4 pairs per thread as gobs_cov_kernel; the stored entries I >= J
+// are summed, an off-diagonal one counted twice (m = 2, the diagonal m = 1, above it m = 0).  Three launches, one per
+// kind of tile (TK), so that each kind has its own registers and no block is launched for nothing:
+//   TK = 0  value / value tiles of the lower triangle;
+//   TK = 1  gradient / value tiles, all of them;
+//   TK = 2  gradient / gradient tiles, ALL of them: the blocks (a, b) with a > b lie below the diagonal whole, those
+//           with a = b for the pairs p >= q only.  A block of the grid owns one tile and ONE b: the blocks (a >= b, b).
+// With (k, F, G, H) of the pair (pair_eval_fgh_t; G = H = 0 at r2 = 0: the terms they carry are dropped there), d the
+// scaled difference, u_a = c_a d_a and Wm = m Wt, theta_l = log ell_l gets
+//   value / value:        Wm F d_l^2
+//   gradient / value:     -G d_l^2 A + 2 F Wm_l u_l,                                  A  = sum_a Wm_a u_a
+//   gradient / gradient:  d_l^2 (G T1 - H T2) - 2 F Wm_ll c_l^2 + 2 G u_l R_l,        T1 = sum_a Wm_aa c_a^2,
+//                         T2 = sum_ab Wm_ab u_a u_b,  R_l = sum_b (Wm_lb + Wm_bl) u_b
+// so a pair costs O(D^2) for the sums and O(D) for all outputs: pass 1 walks the blocks once (each weight is read
+// once, lanes along consecutive addresses of the block's 64 x 64 patch) and adds what belongs to a single dimension --
+// x = Wm_ab u_a u_b gives 2 G x to outputs a and b -- and pass 2 adds Z d_l^2 per dimension with the pair's scalar
+// Z = Wm F | -G A | G T1 - H T2 (linear in T1 and T2: a gradient / gradient block runs pass 2 on the share of its b).
+// log sf gets twice the contracted entries (Wm k | -F A | F T1 - G T2), the rational quadratic's log alpha those with
+// (Ka, Fa, Ga) in place of (k, F, G); an isotropic kernel's one length scale the sum over l.  The a-dimensions are
+// staged DCH at a time: any D.
+// Loads carry no branch: a pair beyond the points of its kind reads the last point's entry and a pair above the
+// diagonal of a diagonal block its mirror image (max, min) -- both in the lower triangle -- and m = 0 removes them.
+// Sums: fp64; a thread adds its 16 pairs, the wave its lanes (wave_sum), lane 0 adds into its wave's row of `red`; the
+// block writes the four rows' sum to its row of `part` (p < cov_N of pst slots), and reduce_parts_kernel adds the rows
+// [vv tiles | gv tiles | gg tiles x D] in that order.  No atomics, a fixed order.
+// 256 threads, 4 cov_N doubles of dynamic LDS.  grids: (vt (vt + 1) / 2, 1, batch) | (vt, gt, batch) | (gt^2, D, batch)
+// ---------------------------------------------------------------------------------
+struct GobsTraceArgs {
+  GobsDims gd;
+  int cov_N, ld, astride, pst;
+  long long sT;
+  const double *Xs, *sp, *mul, *dv, *alpha;
+  const void* Tm;
+  double* part;
+};
+
+template <typename T, int KIND, int DEG, int TK>
+__device__ __forceinline__ void gobs_trace_tile(const GobsTraceArgs& A_, int ti, int tj, int lb, long long prow, int bz) {
+  __shared__ double xi[CT][DCH + 1];
+  __shared__ double xj[CT][DCH + 1];
+  __shared__ double bi[CT], bj[CT];
+  extern __shared__ double gobs_red[];  // [4][cov_N]
+  constexpr bool ISO = KIND == K_SE_ISO || KIND == K_MATERN_ISO;
+  constexpr bool gi = TK >= 1, gj = TK == 2;
+  const int t = threadIdx.x, tx = t & 15, ty = t >> 4, lane = t & 63;
+  const GobsDims gd = A_.gd;
+  const int N = gd.N, Ng = gd.Ng, D = gd.D, Np = gd.Np(), P = gd.P(), cov_N = A_.cov_N, ld = A_.ld;
+  const int i0 = ti * CT, j0 = tj * CT;
+  const int pi0 = gi ? i0 - Np : i0, ni = gi ? Ng : N;
+  const int pj0 = gj ? j0 - Np : j0, nj = gj ? Ng : N;
+  double* part = A_.part + ((size_t)bz * gd.trace_rows() + prow) * A_.pst;
+  const double* Xs = A_.Xs + (size_t)bz * P * D;
+  const double* sp = A_.sp + (size_t)bz * SP_STRIDE;
+  const double* mul = A_.mul + (size_t)bz * D;
+  const double* dv = A_.dv + (size_t)bz * D;
+  const T* Tm = static_cast<const T*>(A_.Tm) + (size_t)bz * A_.sT;
+  const double* alpha = A_.alpha + (size_t)bz * A_.astride;
+  double* red = gobs_red + (size_t)(t >> 6) * cov_N;
+  for (int p = t; p < 4 * cov_N; p += 256) gobs_red[p] = 0.0;
+  double r2[4][4];
+  tile_r2_ab(r2, xi, xj, Xs, Xs, D, i0, j0, t, tx, ty);  // (its barriers order the zeroing of `red` before its first use)
+  const double sf2 = sp[SP_SF2], rqa = sp[SP_RQA], invsl = 1.0 / sp[SP_SL];
+  ExpC ex;
+  ex.load();
+  const int sfi = ISO ? 1 : D;
+  // the multiplicity of the entry a pair owns (mult): in a block ON the diagonal of the joint matrix (value / value, and
+  // gradient / gradient with a = b) the points decide, in every other block it is 2; from three 16-bit masks, bit
+  // 4 a + c: both points exist | p < q | p == q.  pc / qc: the points read
+  unsigned okm = 0, ltm = 0, eqm = 0;
+  int pc[4], qc[4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a) pc[a] = min(pi0 + ty + 16 * a, ni - 1);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) qc[c] = min(pj0 + tx + 16 * c, nj - 1);
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int p = pi0 + ty + 16 * a, q = pj0 + tx + 16 * c;
+      okm |= (unsigned)(p < ni && q < nj) << (4 * a + c);
+      ltm |= (unsigned)(p < q) << (4 * a + c);
+      eqm |= (unsigned)(p == q) << (4 * a + c);
+    }
+  const auto mult = [&](int a, int c, bool diag) -> double {
+    const unsigned b = 1u << (4 * a + c);
+    return !(okm & b) || (diag && (ltm & b)) ? 0.0 : (diag && (eqm & b)) ? 1.0 : 2.0;
+  };
+  double Z[4][4];    // pass 2's scalar of the pair
+  double ssf = 0.0;  // this thread's share of the log sf output, and of log alpha
+  double sal = 0.0;
+
+  if constexpr (TK == 0) {
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+      const double ap = alpha[pc[a]];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int r = max(pc[a], qc[c]), cc = min(pc[a], qc[c]);
+        const double w = mult(a, c, true) * fma((double)Tm[(size_t)r * ld + cc], invsl, -ap * alpha[qc[c]]);
+        const PairVal pv = pair_eval_t<KIND, DEG>(r2[a][c], sf2, rqa, ex);
+        Z[a][c] = w * pv.F;
+        ssf = fma(w, pv.K, ssf);
+        if constexpr (KIND == K_RQ) sal = fma(w, pv.Ka, sal);
+      }
+    }
+    ssf *= 2.0;
+  } else {
+    double f[4][4], g[4][4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const PairFG fg = pair_eval_fg_t<KIND, DEG>(r2[a][c], sf2, rqa, ex);
+        f[a][c] = fg.F;
+        g[a][c] = r2[a][c] > 0.0 ? fg.G : 0.0;
+      }
+    if constexpr (TK == 1) {  // gradient / value: rows N + l Ng + p, column q
+      double A[4][4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) A[a][c] = 0.0;
+      double aq[4];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) aq[c] = alpha[qc[c]];
+      for (int h0 = 0; h0 < D; h0 += DCH) {
+        const int dc = min(DCH, D - h0);
+        __syncthreads();
+        stage_x(xi, Xs, D, i0, h0, dc, t);
+        stage_x(xj, Xs, D, j0, h0, dc, t);
+        __syncthreads();
+        for (int h = 0; h < dc; ++h) {
+          const int l = h0 + h;
+          const double cl = mul[l] / dv[l];
+          double vi[4], vj[4];
+#pragma unroll
+          for (int a = 0; a < 4; ++a) vi[a] = xi[ty + 16 * a][h];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) vj[c] = xj[tx + 16 * c][h];
+          double s = 0.0;
+#pragma unroll
+          for (int a = 0; a < 4; ++a) {
+            const size_t row = (size_t)N + (size_t)l * Ng + pc[a];
+            const double ap = alpha[row];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              const double w = mult(a, c, false) * fma((double)Tm[row * ld + qc[c]], invsl, -ap * aq[c]);
+              const double wu = w * (cl * (vi[a] - vj[c]));  // Wm_l u_l
+              A[a][c] += wu;
+              s = fma(f[a][c], wu, s);
+            }
+          }
+          s = wave_sum(2.0 * s);
+          if (lane == 0) red[ISO ? 0 : l] += s;
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          Z[a][c] = -g[a][c] * A[a][c];
+          ssf = fma(-f[a][c], A[a][c], ssf);
+          if constexpr (KIND == K_RQ) sal = fma(-pair_eval_fgh_t<KIND, DEG>(r2[a][c], sf2, rqa, ex).Fa, A[a][c], sal);
+        }
+      ssf *= 2.0;
+    } else {  // gradient / gradient: rows N + la Ng + p, columns N + lb Ng + q, the blocks la >= lb of this block's lb
+      double T1[4][4], T2[4][4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) T1[a][c] = T2[a][c] = 0.0;
+      if (t < CT)
+        bi[t] = Xs[(size_t)(i0 + t) * D + lb];
+      else if (t < 2 * CT)
+        bj[t - CT] = Xs[(size_t)(j0 + t - CT) * D + lb];
+      __syncthreads();
+      const double cb = mul[lb] / dv[lb];
+      double db[4][4], aq[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) db[a][c] = bi[ty + 16 * a] - bj[tx + 16 * c];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) aq[c] = alpha[(size_t)N + (size_t)lb * Ng + qc[c]];
+      for (int h0 = 0; h0 < D; h0 += DCH) {
+        const int dc = min(DCH, D - h0);
+        if (h0 + dc <= lb) continue;  // (no la >= lb in this chunk)
+        __syncthreads();
+        stage_x(xi, Xs, D, i0, h0, dc, t);
+        stage_x(xj, Xs, D, j0, h0, dc, t);
+        __syncthreads();
+        for (int h = max(0, lb - h0); h < dc; ++h) {
+          const int la = h0 + h;
+          const bool dg = la == lb;
+          if (dg && ti < tj) continue;  // (a tile above the diagonal owns nothing of a diagonal block)
+          const double ca = mul[la] / dv[la], cab = ca * cb;
+          double vi[4], vj[4];
+#pragma unroll
+          for (int a = 0; a < 4; ++a) vi[a] = xi[ty + 16 * a][h];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) vj[c] = xj[tx + 16 * c][h];
+          double sg = 0.0, sf = 0.0;
+#pragma unroll
+          for (int a = 0; a < 4; ++a) {
+            const size_t row = (size_t)N + (size_t)la * Ng + pc[a];
+            const double ap = alpha[row];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              const size_t col = (size_t)N + (size_t)lb * Ng + qc[c];
+              // (a diagonal block is read through its mirror image where the pair lies above the diagonal)
+              const size_t r = dg ? max(row, col) : row, cc = dg ? min(row, col) : col;
+              const double m = mult(a, c, dg);
+              const double w = m * fma((double)Tm[r * ld + cc], invsl, -ap * aq[c]);
+              const double x = (w * cab) * ((vi[a] - vj[c]) * db[a][c]);  // Wm_ab u_a u_b
+              T2[a][c] += x;
+              sg = fma(g[a][c], x, sg);
+              if (dg) {
+                T1[a][c] = fma(w, cab, T1[a][c]);
+                sf = fma(f[a][c], w, sf);
+              }
+            }
+          }
+          // 2 G x to the outputs la and lb (twice to one output when they are the same), -2 F Wm_ll c_l^2 to l
+          sg = wave_sum(dg ? 4.0 * sg - 2.0 * cab * sf : 2.0 * sg);
+          if (lane == 0) {
+            red[ISO ? 0 : la] += sg;
+            if (!dg) red[ISO ? 0 : lb] += sg;
+          }
+        }
+      }
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const PairFGH pv = pair_eval_fgh_t<KIND, DEG>(r2[a][c], sf2, rqa, ex);
+          // (the H term is dropped at r2 = 0 and below 1e-200, where Matern 3's t^3 leaves the fp64 range: with T2 =
+          // O(r2) and d_l^2 <= r2 what is dropped is below 1e-100 of the weights)
+          const double ht = r2[a][c] > 1e-200 ? pv.H * T2[a][c] : 0.0;
+          Z[a][c] = fma(g[a][c], T1[a][c], -ht);
+          ssf += fma(f[a][c], T1[a][c], -g[a][c] * T2[a][c]);
+          if constexpr (KIND == K_RQ) sal += fma(pv.Fa, T1[a][c], -pv.Ga * T2[a][c]);
+        }
+      ssf *= 2.0;
+    }
+  }
+
+  // pass 2: Z d_l^2 to every dimension's output
+  for (int h0 = 0; h0 < D; h0 += DCH) {
+    const int dc = min(DCH, D - h0);
+    __syncthreads();
+    stage_x(xi, Xs, D, i0, h0, dc, t);
+    stage_x(xj, Xs, D, j0, h0, dc, t);
+    __syncthreads();
+    for (int h = 0; h < dc; ++h) {
+      double vi[4], vj[4];
+#pragma unroll
+      for (int a = 0; a < 4; ++a) vi[a] = xi[ty + 16 * a][h];
+#pragma unroll
+      for (int c = 0; c < 4; ++c) vj[c] = xj[tx + 16 * c][h];
+      double s = 0.0;
+#pragma unroll
+      for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const double d = vi[a] - vj[c];
+          s = fma(Z[a][c], d * d, s);
+        }
+      s = wave_sum(s);
+      if (lane == 0) red[ISO ? 0 : h0 + h] += s;
+    }
+  }
+  ssf = wave_sum(ssf);
+  if (lane == 0) red[sfi] += ssf;
+  if constexpr (KIND == K_RQ) {
+    sal = wave_sum(sal);
+    if (lane == 0) red[D + 1] += sal;
+  }
+  __syncthreads();
+  for (int p = t; p < cov_N; p += 256)
+    part[p] = (gobs_red[p] + gobs_red[cov_N + p]) + (gobs_red[2 * cov_N + p] + gobs_red[3 * cov_N + p]);
+}
+
+template <typename T, int KIND, int DEG>
+__global__ __launch_bounds__(256) void gobs_trace_vv_kernel(GobsTraceArgs a) {
+  int ti, tj;
+  lower_tile(blockIdx.x, ti, tj);
+  gobs_trace_tile<T, KIND, DEG, 0>(a, ti, tj, 0, blockIdx.x, blockIdx.z);
+}
+template <typename T, int KIND, int DEG>
+__global__ __launch_bounds__(256) void gobs_trace_gv_kernel(GobsTraceArgs a) {
+  const int vt = a.gd.vt();
+  gobs_trace_tile<T, KIND, DEG, 1>(a, vt + blockIdx.y, blockIdx.x, 0,
+                                   (long long)vt * (vt + 1) / 2 + (long long)blockIdx.y * vt + blockIdx.x, blockIdx.z);
+}
+template <typename T, int KIND, int DEG>
+__global__ __launch_bounds__(256) void gobs_trace_gg_kernel(GobsTraceArgs a) {
+  const int vt = a.gd.vt(), gt = a.gd.gt();
+  gobs_trace_tile<T, KIND, DEG, 2>(a, vt + blockIdx.x / gt, vt + blockIdx.x % gt, blockIdx.y,
+                                   (long long)vt * (vt + 1) / 2 + (long long)vt * gt + (long long)blockIdx.x * a.gd.D + blockIdx.y,
+                                   blockIdx.z);
+}
+
 // The scaled point lists of `batch` samples from the raw list `pts` (P x D, zero rows between the kinds)
 inline void launch_gobs_scale(hipStream_t st, const GobsDims& gd, const double* pts, const double* mul, const double* dv,
                               int batch, double* xs) {
@@ -278,6 +590,21 @@ inline void launch_gobs_cov(hipStream_t st, const CovDesc& cd, const GobsDims& g
                             const double* mul, const double* dv, double* out) {
   const int pt = gd.P() / CT;
   GPC_COV_DISPATCH(gobs_cov_kernel, double, cd, dim3(pt, pt), dim3(256), 0, st, gd, xs, sp, mul, dv, out);
+}
+
+// out[b][p], p < cov_N, of `batch` samples (rows of `pst` doubles; a slot p >= cov_N is left as it is) from their scaled
+// point lists, Tm (ld x ld, sT apart) and alpha (astride apart); part: batch x gd.trace_rows() x pst partials
+inline void launch_gobs_trace(hipStream_t st, const CovDesc& cd, const GobsDims& gd, int batch, const double* xs,
+                              const double* sp, const double* mul, const double* dv, const double* Tm, long long sT, int ld,
+                              const double* alpha, int astride, double* part, int pst, double* out) {
+  const int vt = gd.vt(), gt = gd.gt();
+  const size_t shm = 4 * (size_t)cd.cov_N * sizeof(double);
+  GobsTraceArgs a{gd, cd.cov_N, ld, astride, pst, sT, xs, sp, mul, dv, alpha, Tm, part};
+  GPC_COV_DISPATCH(gobs_trace_vv_kernel, double, cd, dim3(vt * (vt + 1) / 2, 1, batch), dim3(256), shm, st, a);
+  GPC_COV_DISPATCH(gobs_trace_gv_kernel, double, cd, dim3(vt, gt, batch), dim3(256), shm, st, a);
+  GPC_COV_DISPATCH(gobs_trace_gg_kernel, double, cd, dim3(gt * gt, gd.D, batch), dim3(256), shm, st, a);
+  hipLaunchKernelGGL(reduce_parts_kernel, dim3(cd.cov_N, batch), dim3(256), 0, st, (const double*)part,
+                     (int)gd.trace_rows(), pst, out);
 }
 
 // The cross operands of `batch` samples (panels sKs apart, npad x mb) with their mean products: part: batch x P/64 x mb

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "covfun.h"
 #include "cv.h"
+#include "gradobs.h"
 #include "gradpost.h"
 #include "hess.h"
 #include "lookahead_batch.h"
@@ -429,6 +430,17 @@ struct QuadMixScratch {
   }
 };
 
+// ---- gpc_nll_batch_gobs_grad, gpc_debug_gobs_trace ---------------------------------------------------------------------
+// The partials of gradobs.h's gobs_trace kernels for a chunk of `cnt` samples: one row of `pst` doubles (the covariance
+// hyperparameters, and whatever else the caller's output row holds) per block of their three grids -- the value / value
+// tiles of the lower triangle, the gradient / value tiles, and D per gradient / gradient tile (GobsDims::trace_rows)
+struct GobsTraceScratch {
+  double* part;
+  void layout(ScratchCarver& sc, int cnt, const GobsDims& gd, int pst) {
+    part = sc.take((size_t)cnt * (size_t)gd.trace_rows() * pst);
+  }
+};
+
 // ---- any layout by name ---------------------------------------------------------------------------------------------------
 // per_layout(sc, cnt) / shared_layout(sc): a consumer's two lists.  Counted, then carved -- three samples and the shared
 // part behind them -- on a 256-byte aligned base that is never dereferenced
@@ -507,6 +519,11 @@ int scratch_bytes_of(const std::string& name, const int* d, int n, unsigned long
   if (name == "hyp_grad" && n == 8)  // N, D, P, nvv, ngp, msb, var, nout
     return scratch_report([&](ScratchCarver& sc, int cnt) { HgScratch().layout(sc, cnt, npad, d[1], d[2], d[3], d[4], d[5], d[6] != 0, d[7]); },
                           none, 0, per, shared, mis);
+  if (name == "gobs_trace" && n == 4) {  // N, Ng, D, doubles per row
+    GobsDims gd;
+    gd.N = d[0], gd.Ng = d[1], gd.D = d[2];
+    return scratch_report([&](ScratchCarver& sc, int cnt) { GobsTraceScratch().layout(sc, cnt, gd, d[3]); }, none, 0, per, shared, mis);
+  }
   if (name == "quad_mix" && n == 5)  // N, M, D, var, grad
     return scratch_report([&](ScratchCarver& sc, int cnt) { QuadMixScratch().layout(sc, cnt, npad, pad_tile(d[1]), d[2], d[3] != 0, d[4] != 0); },
                           [&](ScratchCarver& sc) { QuadMixShared().layout(sc, d[1], pad_tile(d[1]), d[2]); }, 0, per, shared, mis);

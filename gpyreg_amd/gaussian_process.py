@@ -2648,18 +2648,103 @@ class GP:
                                             (self.X.shape[0], X_g.shape[0], self.D), nlz, mult, lchol)
 
     @_on_device
-    def nll_batch_grad_obs(self, hyp, X_g, dy, s2_grad):
+    def nll_batch_grad_obs(self, hyp, X_g, dy, s2_grad, compute_grad=False):
         """The joint negative log marginal likelihood of the GP's data and the gradient observations (arguments as
         ``condition_on_gradients``) for MANY hyperparameter vectors: ``hyp`` (S, hyp_N) -> nlZ (S,).  Priors are not
-        added and there is no gradient: the joint counterpart of ``nll_batch(hyp, compute_grad=False)``.  Not sharded."""
+        added: the joint counterpart of ``nll_batch``.  Not sharded.
+
+        With ``compute_grad`` the result is (nlZ (S,), dnlZ (S, hyp_N)), dnlZ ordered [cov | noise | mean] as
+        ``nll_batch``'s: the analytic gradient at each sample's own jitter multiplier, held fixed.  Its covariance part,
+        1/2 sum ((K + Sigma)^-1 - alpha alpha^T) o dK/dtheta, is contracted on the device with every dK entry evaluated
+        from the points (gpc_nll_batch_gobs_grad; ``_gradobs`` has the formulas): no derivative plane is formed.
+        ``s2_grad`` is data and has no gradient.  nlZ is the number the call without gradient returns, to the bit (a
+        second, inverse-free factorization supplies it, as for ``nll_hess_batch``).  The gradient needs a built-in
+        covariance function (not Matern 1), the stock ``GaussianNoise``, a stock mean function and a float64 GP:
+        ``NotImplementedError`` names what is missing."""
         who = "nll_batch_grad_obs"
         X_g, dy, s2g = self._grad_obs_inputs(who, X_g, dy, s2_grad)
+        if compute_grad:
+            self._grad_obs_grad_check(who)
         hyp = np.atleast_2d(np.asarray(hyp, dtype=float))
         if hyp.ndim != 2 or hyp.shape[1] != sum(self._counts()):
             raise ValueError("Input hyperparameter array is the wrong shape!")
         if not np.all(np.isfinite(hyp)):
             raise ValueError(f"{who}: hyp must be finite")
-        return self._grad_obs_device(who, hyp, X_g, dy, s2g, False)[0]
+        nlz = self._grad_obs_device(who, hyp, X_g, dy, s2g, False)[0]
+        if not compute_grad:
+            return nlz
+        return nlz, self._grad_obs_grad(who, hyp, X_g, s2g)
+
+    def _grad_obs_grad_check(self, who):
+        """The refusals of the gradient of the gradient-observation likelihood beyond ``_grad_obs_inputs``'."""
+        from .mean_functions import ConstantMean, NegativeQuadratic, ZeroMean
+        from .noise_functions import GaussianNoise
+
+        if self.dtype not in ("f64", "fp64", "float64"):
+            raise NotImplementedError(f"{who}: the gradient is computed in fp64 only; this GP's dtype is {self.dtype!r}")
+        if type(self.noise) is not GaussianNoise:
+            raise NotImplementedError(f"{who}: the noise function {self.noise!r} ({type(self.noise).__name__}) is "
+                                      "user-defined; the gradient needs the stock GaussianNoise")
+        if type(self.mean) not in (ZeroMean, ConstantMean, NegativeQuadratic):
+            raise NotImplementedError(f"{who}: the mean function {self.mean!r} ({type(self.mean).__name__}) is "
+                                      "user-defined; the derivatives of its x-gradient with respect to the "
+                                      "hyperparameters are unknown")
+
+    def _grad_obs_grad(self, who, hyp, X_g, s2g):
+        """dnlZ (S, hyp_N) of the joint systems of the rows of ``hyp``; the joint data are resident (``_grad_obs_device``
+        ran in the same locked call)."""
+        from . import _gradobs
+        from .mean_functions import ConstantMean, ZeroMean
+
+        counts = cov_N, noise_N, mean_N = self._counts()
+        kid, degree = self._kid()
+        S, N = hyp.shape[0], self.X.shape[0]
+        Ng, D = X_g.shape
+        m, sn2 = self._grad_obs_rows(who, hyp, X_g, s2g)
+        pv = self._plugin_values(hyp, True)
+        name = {ZeroMean: "zero", ConstantMean: "const"}.get(type(self.mean), "negquad")
+        dm = dsn2 = None
+        if mean_N:
+            dm = np.stack([_gradobs.joint_dm(pv["dm"][s], _gradobs.mean_xgrad_dhyp(name, _mean_hyp(hyp[s], counts), X_g))
+                           for s in range(S)])
+        if noise_N:
+            dsn2 = np.stack([_gradobs.joint_dsn2(pv["dsn2"][s], N, Ng, D) for s in range(S)])
+        ctx = _lib.context(self.device)
+        if ctx.gobs != (N, Ng):  # (cannot happen: the value call above made them resident under this lock)
+            raise RuntimeError(f"{who}: the joint data are not resident")
+        _, dnlz, _, _, info = ctx.nll_batch_gobs_grad(kid, degree, _lib.F64, hyp[:, :cov_N], m, sn2, dm, dsn2)
+        if np.any(info != 0):
+            raise LinAlgError("Singular matrix for L Cholesky decomposition")
+        return dnlz
+
+    def _grad_obs_objective(self, who, hyp, X_g, dy, s2_grad, compute_grad, prior):
+        """``log_likelihood_grad_obs`` / ``log_posterior_grad_obs``: one vector (array or dict), the sign of
+        ``log_likelihood``."""
+        if isinstance(hyp, dict):
+            hyp = self.hyperparameters_from_dict(hyp)[0]
+        hyp = np.asarray(hyp, dtype=float).ravel()
+        r = self.nll_batch_grad_obs(hyp[None, :], X_g, dy, s2_grad, compute_grad)
+        nlZ = float((r[0] if compute_grad else r)[0])
+        dnlZ = r[1][0] if compute_grad else None
+        if prior:
+            if compute_grad:
+                P, dP = self.__compute_log_priors(hyp, True)
+                nlZ -= P
+                dnlZ = dnlZ - dP
+            else:
+                nlZ -= self.__compute_log_priors(hyp, False)
+        return (-nlZ, -dnlZ) if compute_grad else -nlZ
+
+    def log_likelihood_grad_obs(self, hyp, X_g, dy, s2_grad, compute_grad=False):
+        """(Positive) joint log marginal likelihood of the GP's data and the gradient observations at ONE
+        hyperparameter vector (array or dict): ``log_likelihood``'s joint counterpart, (lZ, dlZ) with ``compute_grad``."""
+        return self._grad_obs_objective("log_likelihood_grad_obs", hyp, X_g, dy, s2_grad, compute_grad, False)
+
+    def log_posterior_grad_obs(self, hyp, X_g, dy, s2_grad, compute_grad=False):
+        """Joint log marginal likelihood plus log prior: ``log_posterior``'s joint counterpart.  The negated pair
+        ``lambda h: tuple(-v for v in gp.log_posterior_grad_obs(h, X_g, dy, s2_grad, True))`` is an objective for
+        ``scipy.optimize.minimize(jac=True)``."""
+        return self._grad_obs_objective("log_posterior_grad_obs", hyp, X_g, dy, s2_grad, compute_grad, True)
 
     def _grad_obs_device(self, who, hyp, X_g, dy, s2g, keep):
         """(nlZ, handle | None, sn2_mult, L_chol) of the joint systems of the rows of ``hyp``.  The context's resident

@@ -952,13 +952,24 @@ int gpc_posterior_batch_gobs(gpc_ctx* ctx, int kernel_id, int degree, int dtype,
                              const double* m, const double* sn2, gpc_post** post, double* nlz, double* sn2_mult,
                              int* L_chol, int* info);
 /* The joint negative log marginal likelihood alone, for S arbitrary hyperparameter rows (no posterior is kept, no
- * gradient: the hyperparameter derivatives of the joint matrix need a third radial factor).                         */
+ * gradient: gpc_nll_batch_gobs_grad has it).                                                                        */
 int gpc_nll_batch_gobs(gpc_ctx* ctx, int kernel_id, int degree, int dtype, int S, const double* hyp_cov,
                        const double* m, const double* sn2, double* nlz, double* sn2_mult, int* L_chol, int* info);
+/* gpc_nll_batch_gobs with the hyperparameter gradient: dnlz (S x (cov_N + noise_N + mean_N), ordered
+ * [cov | noise | mean] like gpc_nll_batch) = d nlz / d theta at each sample's final jitter multiplier.  The covariance
+ * part is 1/2 sum_IJ ((K + Sigma)^-1 - alpha alpha^T)_IJ dK_IJ / d theta_p with every dK entry evaluated on the device
+ * from the point list (gradobs.h: gobs_trace_kernel; the third radial factor H = -2 dG/d(r2)) -- no derivative plane
+ * exists on either side of the bus.  dm: S x n x mean_N, the theta-derivatives of the joint mean rows (the mean at X,
+ * its x-gradient at Xg); dsn2: S x n x noise_N, those of the joint noise rows (zeros on the gradient rows: their noise
+ * is data).  Either may be NULL when its count is 0.  nlz is the number of THIS pipeline (it forms the inverse) and
+ * agrees with gpc_nll_batch_gobs to rounding, not to the bit.  fp64 only: any other dtype is an error.               */
+int gpc_nll_batch_gobs_grad(gpc_ctx* ctx, int kernel_id, int degree, int dtype, int S, const double* hyp_cov,
+                            const double* m, const double* sn2, const double* dm, int mean_N, const double* dsn2,
+                            int noise_N, double* nlz, double* dnlz, double* sn2_mult, int* L_chol, int* info);
 /* gpc_predict for a gradient-observation posterior: the n x M operand [k(X, x*) ; -c_l F (xs_g - xs*)_l] is built on
  * the device with the mean product fused in; fmu (caller adds m*) and fs2 (unclamped) as gpc_predict, [j*S + s].    */
 int gpc_predict_gobs(gpc_post* post, const double* xstar, int M, double* fmu, double* fs2);
-/* Test hooks: the two kernels of gradobs.h on their own, fp64, one hyperparameter row.
+/* Test hooks: the kernels of gradobs.h on their own, fp64, one hyperparameter row.
  * gpc_debug_gobs_cov: out = the dense n x n joint covariance (preset to NaN, so an entry nobody wrote shows).
  * gpc_debug_gobs_cross: out = the WHOLE panel, pad128(n) x pad128(M) row-major (preset to NaN; rows >= n and columns
  * >= M must come back as zeros); colsum (pad128(M); may be NULL) = the fused products out^T alpha with alpha (n; NULL:
@@ -968,6 +979,11 @@ int gpc_debug_gobs_cov(gpc_ctx* ctx, int kernel_id, int degree, const double* hy
 int gpc_debug_gobs_cross(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
                          const double* Xg, int Ng, const double* xstar, int M, const double* alpha, double* out,
                          double* colsum);
+/* gpc_debug_gobs_trace: gobs_trace_kernel and its reduction alone.  Ainv: n x n row-major, of which only the LOWER
+ * triangle is read (the weight is Ainv / sl - alpha alpha^T, taken symmetric); alpha: n; sl > 0.  out (cov_N) =
+ * sum_IJ weight_IJ dK_IJ / d theta_p.  Counter "gobs_trace_us": the device time of the contraction.                   */
+int gpc_debug_gobs_trace(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                         const double* Xg, int Ng, const double* Ainv, const double* alpha, double sl, double* out);
 /* ---- experiments build only (hipcc -DGPC_EXPERIMENTS -> lib/libgpcore_exp.so; NOT part of the product library) --------
  * Schedules that were built, measured and rejected (tile-level dataflow graph, independent pipelines,
  * rectangular / eight-wave tiles, right-looking panels) and their gpc_set_option names live there;
