@@ -32,12 +32,24 @@ with a pair's D x D weight block W (u_a = c_a d_a)::
 and with a gradient / value pair's weight vector w:  sum_a w_a d_l E_a = -G d_l^2 sum_a w_a u_a + 2 F w_l u_l.
 dnlZ / dtheta_p = 1/2 sum_ij ((K + mult Sigma)^-1 - alpha alpha^T)_ij d_p K_ij at the record's fixed jitter multiplier.
 
+THE POSTERIOR OF THE GRADIENT (``joint_operand``, ``gradient_joint``; the device: gobs_grad_operand_tile_kernel and
+gpc_grad_post_gobs).  For a query x*, slot 0 = f(x*) and slot 1 + l = d f / dx*_l, the n x (D + 1) operand has, with
+d = xs_i - xs* on a value row i and d = xs_g - xs* on the gradient rows of X_g[g]::
+
+    value row i              slot 0: k              slot 1 + l: -c_l F (xs*_l - xs_il)           (0 at r2 = 0)
+    gradient row N + a Ng + g  slot 0: -c_a F d_a   slot 1 + l: c_a c_l (F delta_al - G d_a d_l)
+                             (slot 0: 0 at r2 = 0;  slot 1 + l: c_a^2 F0 delta_al at r2 = 0, the G term dropped)
+
+The value rows are ``_gradpost.operand``'s, slot 0 is ``joint_cross``, and the gradient rows' slots 1 + l are the
+gradient / gradient block of ``joint_cov`` with p = g and q = *.  From the operand on it is ``_gradpost.joint``'s
+algebra: mean = B^T alpha, C = H - V^T V (V = L^-T (sW B)) or H + B^T (L B), H = diag(kss, F0 c_l^2).
+
 The module is the model the device (gradobs.h) is tested against; nothing of it runs in the product's hot path.
 """
 
 import numpy as np
 
-from ._gradpost import _MATERN, K_MATERN_ISO, K_RQ, K_SE, K_SE_ISO, check_kind, radial, scaling
+from ._gradpost import _MATERN, K_MATERN_ISO, K_RQ, K_SE, K_SE_ISO, check_kind, operand, prior_block, radial, scaling
 
 
 def order(N, Ng, D):
@@ -401,3 +413,44 @@ def predict(kind, degree, hyp_cov, X, Xg, x_star, post):
     else:
         s2 = kss + np.sum(B * (post["L"] @ B), 0)
     return mu, s2
+
+
+def joint_operand(kind, degree, hyp_cov, X, Xg, x_star):
+    """B (n, D + 1, M): the operand of the joint posterior of (f, grad f) at x_star (M, D) under values at X and
+    gradients at X_g, rows in joint order; slot 0 = ``joint_cross``, slot 1 + l the derivative with respect to x*_l
+    (the header's formulas: zeros at r2 = 0 but for c_a^2 F0 on a gradient row's own dimension)."""
+    check_kind(kind, degree)
+    X, Xg = np.atleast_2d(np.asarray(X, dtype=float)), np.atleast_2d(np.asarray(Xg, dtype=float))
+    x_star = np.atleast_2d(np.asarray(x_star, dtype=float))
+    N, D = X.shape
+    Ng, M = Xg.shape[0], x_star.shape[0]
+    c, sf2, rqa = scaling(kind, degree, hyp_cov, D)
+    xsg, xss = Xg * c, x_star * c
+    B = np.empty((N + Ng * D, D + 1, M))
+    B[:N] = operand(kind, degree, hyp_cov, X, x_star)  # the value rows are the plain GP's operand
+    d, r2, _, F, G = _pairs(kind, degree, sf2, rqa, xsg, xss)  # d = xs_g - xs*: (Ng, M, D)
+    for a in range(D):
+        ra = slice(N + a * Ng, N + (a + 1) * Ng)
+        B[ra, 0] = np.where(r2 > 0, -((c[a] * F) * d[:, :, a]), 0.0)
+        for l in range(D):
+            B[ra, 1 + l] = (c[a] * c[l]) * ((F if a == l else 0.0) - G * (d[:, :, a] * d[:, :, l]))
+    return B
+
+
+def gradient_joint(kind, degree, hyp_cov, X, Xg, x_star, post):
+    """(mean (M, D + 1), cov (M, D + 1, D + 1)) of (f, grad f) at every row of x_star under ONE ``posterior`` record,
+    without the mean function: ``_gradpost.joint``'s algebra on ``joint_operand``.  The matrix is returned as computed."""
+    import scipy.linalg as sla
+
+    B = joint_operand(kind, degree, hyp_cov, X, Xg, x_star)
+    n, P, M = B.shape
+    H = np.diag(prior_block(kind, degree, hyp_cov, P - 1))
+    mean = np.einsum("iaj,i->ja", B, np.asarray(post["alpha"], dtype=float).ravel())
+    flat = B.reshape(n, P * M)
+    if post["L_chol"]:
+        V = sla.solve_triangular(post["L"], post["sW"][:, None] * flat, trans=1, check_finite=False).reshape(n, P, M)
+        cov = H[None] - np.einsum("iaj,ibj->jab", V, V)
+    else:
+        Z = (post["L"] @ flat).reshape(n, P, M)
+        cov = H[None] + np.einsum("iaj,ibj->jab", B, Z)
+    return mean, cov

@@ -77,6 +77,9 @@ SIGNATURES = {
     "gpc_debug_gobs_cov": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp]),
     "gpc_debug_gobs_cross": (
         C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
+    "gpc_debug_gobs_grad_operand": (
+        C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp]),
+    "gpc_grad_post_gobs": (C.c_int, [_vp, _dp, C.c_int, C.c_int, _dp, _dp, _dp]),
     "gpc_post_fetch": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp]),
     "gpc_post_free": (C.c_int, [_vp]),
     "gpc_predict": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),
@@ -410,6 +413,25 @@ class Context:
                                             _ptr(al), _ptr(panel), _ptr(col))
         self._check(rc, "gpc_debug_gobs_cross")
         return panel[:n, :M].copy(), panel, (None if col is None else col[:M].copy())
+
+    @_serial
+    def debug_gobs_grad_operand(self, kid, degree, hyp_cov, X, Xg, x_star, alpha=None):
+        """gpc_debug_gobs_grad_operand: (operand (n, D + 1, M), the whole padded panel (npad, D + 1, 128) it is a corner
+        of, fused column sums (D + 1, M) | None without alpha), as gobs_grad_operand_tile_kernel writes them for one
+        block of M <= 128 queries: slot 0 = f(x*), slot 1 + l = d f / dx*_l, rows in joint order."""
+        hyp_cov, X, Xg, xs = _f64(hyp_cov).ravel(), _f64(X), _f64(Xg), _f64(x_star)
+        (N, D), Ng, M = X.shape, Xg.shape[0], xs.shape[0]
+        n = N + Ng * D
+        npad = -(-n // 128) * 128
+        al = None if alpha is None else _f64(alpha).ravel()
+        if al is not None and al.size != n:
+            raise ValueError(f"alpha must hold n = {n} values in joint order")
+        panel = np.empty((npad, D + 1, 128))
+        col = None if al is None else np.empty((D + 1, 128))
+        rc = self._lib.gpc_debug_gobs_grad_operand(self._h, kid, degree, _ptr(hyp_cov), _ptr(X), N, D, _ptr(Xg), Ng,
+                                                   _ptr(xs), M, _ptr(al), _ptr(panel), _ptr(col))
+        self._check(rc, "gpc_debug_gobs_grad_operand")
+        return panel[:n, :, :M].copy(), panel, (None if col is None else col[:, :M].copy())
 
     # ---- covariance.compute ---------------------------------------------------
     @_serial
@@ -983,6 +1005,19 @@ class PostHandle:
         cov = np.empty((M, D + 1, self.S) if diag_only else (M, D + 1, D + 1, self.S))
         rc = self.ctx._lib.gpc_grad_post(self._h, _ptr(xs), M, int(bool(diag_only)), _ptr(fmu), _ptr(dfmu), _ptr(cov))
         self.ctx._check(rc, "gpc_grad_post")
+        return fmu, dfmu, cov
+
+    @_serial
+    def grad_post_gobs(self, x_star, diag_only=False):
+        """gpc_grad_post_gobs: ``grad_post`` for a gradient-observation posterior (``Context.posterior_batch_gobs``):
+        fmu (M, S), dfmu (M, D, S) and cov (M, D + 1, D + 1, S), or (M, D + 1, S) with ``diag_only``."""
+        xs = _f64(x_star)
+        M, D = xs.shape
+        fmu = np.empty((M, self.S))
+        dfmu = np.empty((M, D, self.S))
+        cov = np.empty((M, D + 1, self.S) if diag_only else (M, D + 1, D + 1, self.S))
+        rc = self.ctx._lib.gpc_grad_post_gobs(self._h, _ptr(xs), M, int(bool(diag_only)), _ptr(fmu), _ptr(dfmu), _ptr(cov))
+        self.ctx._check(rc, "gpc_grad_post_gobs")
         return fmu, dfmu, cov
 
     @_serial

@@ -501,6 +501,7 @@ struct gpc_ctx {
   int last_chunk = 0;  // what plan_chunk last returned ("last_chunk")
   unsigned long long grad_post_gram_us = 0;  // Gram passes of the last gpc_grad_post, device microseconds ("grad_post_gram_us")
   unsigned long long gobs_trace_us = 0;  // the contraction (kernel + reduction) of the last gpc_debug_gobs_trace, device microseconds
+  unsigned long long gobs_grad_operand_us = 0;  // the operand builds of the last gpc_grad_post_gobs (timed calls) / gpc_debug_gobs_grad_operand, device microseconds
   unsigned long long gobs_cov_us = 0, gobs_cross_us = 0;  // the kernel of the last gpc_debug_gobs_cov / the build of the last gpc_debug_gobs_cross, device microseconds
   unsigned long long hess_contract_us = 0;  // contraction passes of the last gpc_predict_hess, device microseconds ("hess_contract_us")
   unsigned long long nll_hess_gram_us = 0, nll_hess_contract_us = 0;  // Gram pass / second-derivative contraction of the last gpc_nll_hess, device microseconds
@@ -2252,7 +2253,7 @@ inline int require_factorized(const gpc_post* po, const char* fn) {
 inline int refuse_gobs(const gpc_post* po, const char* fn) {
   if (po->gobs.Ng > 0)
     FAIL(po->ctx, std::string(fn) + ": this posterior was conditioned on gradient observations (gpc_posterior_batch_gobs); "
-                  "only gpc_predict_gobs, gpc_post_fetch and gpc_post_free work on it");
+                  "only gpc_predict_gobs, gpc_grad_post_gobs, gpc_post_fetch and gpc_post_free work on it");
   return 0;
 }
 
@@ -3421,53 +3422,73 @@ int lookahead_batch_impl(gpc_post* po, const double* xr, int Mr, const double* x
 // (npad, D, diag) alone, so a sample carries the same bits in any batch, chunk or run.  The budget decides the samples
 // per chunk only; a sample with one query block that does not fit is refused.
 // gpc_last_timing: the device sections of all (chunk, block) steps and, of these, the products with W (or L).
+// gpc_grad_post_gobs (a posterior with gradient observations: po->gobs.Ng > 0) differs by the operand builder alone: the
+// scaled point list (launch_gobs_scale) and gradobs.h's gobs_grad_operand_tile_kernel, whose partials have one row per
+// 64-tile of the LIST; the panel is npad x (D + 1) 128 with npad = pad128(N + Ng D), and everything after it is the same
+// code.  "gobs_grad_operand_us": the operand builds (scaling, kernel, reduction) of a timed call.
 
 template <typename T>
 int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* fmu, double* dfmu, double* cov) {
   gpc_ctx* c = po->ctx;
   const int S = po->S, N = po->N, D = po->D, npad = po->npad, Dp = D + 1, mb = GQB, ld = Dp * mb;
+  const bool gobs = po->gobs.Ng > 0;
+  const std::string fn = gobs ? "gpc_grad_post_gobs" : "gpc_grad_post";
   hipStream_t st = c->st;
   const long long sP = (long long)npad * ld;
-  const int nt64 = npad / CT, tmr = npad / TILE, nseg = gram_segments(npad);
+  const int nt64 = gobs ? po->gobs.P() / CT : npad / CT, tmr = npad / TILE, nseg = gram_segments(npad);
   const size_t gper = (size_t)mb * Dp * (diag ? 1 : Dp);  // doubles of a sample's Gram result
-  const size_t per = ScratchCarver::count<BlockScratch<T>>(1, npad, D, true, false, diag ? 1 : D + 1, diag, (size_t)0), shared = (size_t)M * D * 8;
+  const size_t per = ScratchCarver::count<BlockScratch<T>>(1, npad, D, true, false, diag ? 1 : D + 1, diag, (size_t)0, nt64), shared = (size_t)M * D * 8;
   const size_t held = c->cs.bytes;
   const int chunk = plan_chunk(c, S, per, shared, held, shared + (size_t)S * per <= held, 0, false, [&](size_t budget) {
-    return "gpc_grad_post: the scratch of one sample with one query block (" + std::to_string(per) + " bytes: N_pad = " +
+    return fn + ": the scratch of one sample with one query block (" + std::to_string(per) + " bytes: N_pad = " +
            std::to_string(npad) + ", D = " + std::to_string(D) + ", block = " + std::to_string(mb) +
            " queries) exceeds the device memory budget (" + std::to_string(budget) + " bytes)";
   });
   if (!chunk) return -2;
   HIPCHK(c, c->cs.ensure(shared + (size_t)chunk * per));
   BlockScratch<T> z;
-  CARVECHK(c, "gpc_grad_post", ScratchCarver::carve(z, c->cs.p, chunk, npad, D, true, false, diag ? 1 : D + 1, diag, (size_t)0));
+  CARVECHK(c, fn.c_str(), ScratchCarver::carve(z, c->cs.p, chunk, npad, D, true, false, diag ? 1 : D + 1, diag, (size_t)0, nt64));
   T *const P = z.P, *const V = z.V;
   double *const xsq = z.xsq, *const d_mean = z.mean, *const d_gram = z.gram, *const d_f0 = z.f0;
   double* const d_xa = reinterpret_cast<double*>(c->cs.as<char>() + (size_t)chunk * per);  // shared: the raw queries
   c->pin.begin();
   c->pin.begin_gather();
   CallTimer tm{c, CallTimer::wanted(c, npad)};
-  GramClock gc(tm.on);
+  GramClock gc(tm.on), oc(gobs && tm.on);
   HIPCHK(c, c->pin.up(d_xa, xstar, (size_t)M * D * 8, st));
   std::vector<double> hmean((size_t)chunk * ld), hgram((size_t)chunk * gper), hf0(chunk);
   ChunkConsts k;
   if (int rc = k.init(po, chunk)) return rc;
   c->ms_total = c->ms_factor = 0;
-  double gram_us = 0;
+  double gram_us = 0, operand_us = 0;
   for (int s0 = 0; s0 < S; s0 += chunk) {
     const int cnt = std::min(chunk, S - s0);
-    if (int rc = k.stage(s0, cnt, true)) return rc;
+    if (int rc = k.stage(s0, cnt, !gobs)) return rc;
+    const double* xp = k.xsb;  // (gobs, all samples in one chunk: the posterior's resident scaled lists)
+    if (gobs && !k.resident) {
+      HIPCHK(c, c->gxs.ensure((size_t)cnt * po->gobs.P() * D * 8));
+      launch_gobs_scale(st, po->gobs, po->gpts.as<double>(), k.mulb, k.divb, cnt, c->gxs.as<double>());
+      xp = c->gxs.as<double>();
+    }
     for (int q0 = 0; q0 < M; q0 += mb) {
       const int mq = std::min(mb, M - q0);
       HIPCHK(c, tm.start());
+      HIPCHK(c, oc.record(0, st));
       hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mb * D + 255) / 256), cnt), dim3(256), 0, st,
                          (const double*)(d_xa + (size_t)q0 * D), mq, mb, D, k.mulb, k.divb, xsq);
-      GPC_COV_DISPATCH(grad_operand_tile_kernel, T, po->cd, dim3(mb / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
-                       (const double*)xsq, k.spb, k.mulb, k.divb, po->alpha.as<double>() + (size_t)s0 * npad, npad, N, npad,
-                       mq, mb, P, sP, z.part, d_f0);
-      hipLaunchKernelGGL(colpart_reduce_kernel, dim3((ld + 255) / 256, cnt), dim3(256), 0, st,
-                         (const double*)z.part, nt64, ld, d_mean);
+      if (gobs) {
+        HIPCHK(c, launch_gobs_grad_operand<T>(st, po->cd, po->gobs, xp, xsq, k.spb, k.mulb, k.divb,
+                                              po->alpha.as<double>() + (size_t)s0 * npad, npad, npad, mq, cnt, P, sP,
+                                              z.part, d_mean, d_f0));
+      } else {
+        GPC_COV_DISPATCH(grad_operand_tile_kernel, T, po->cd, dim3(mb / CT, npad / CT, cnt), dim3(256), 0, st, po->cd, k.xsb,
+                         (const double*)xsq, k.spb, k.mulb, k.divb, po->alpha.as<double>() + (size_t)s0 * npad, npad, N, npad,
+                         mq, mb, P, sP, z.part, d_f0);
+        hipLaunchKernelGGL(colpart_reduce_kernel, dim3((ld + 255) / 256, cnt), dim3(256), 0, st,
+                           (const double*)z.part, nt64, ld, d_mean);
+      }
       HIPCHK(c, hipGetLastError());
+      HIPCHK(c, oc.record(1, st));
       HIPCHK(c, tm.mark1());
       // the products of every run of equal L_chol, then (second pass) what reduces them
       int rc_runs = for_lchol_runs(po, s0, cnt, [&](int a, int len, bool lch) -> int {
@@ -3505,6 +3526,7 @@ int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* 
       HIPCHK(c, hipStreamSynchronize(st));
       tm.accumulate();
       gram_us += gc.elapsed_us();
+      operand_us += oc.elapsed_us();
       // into the caller's layout: C = H - Gram / sl | H + Gram, H = diag(sf2, F0 c_1^2, ..., F0 c_D^2)
       for (int i = 0; i < cnt; ++i) {
         const int s = s0 + i;
@@ -3536,6 +3558,7 @@ int grad_post_impl(gpc_post* po, const double* xstar, int M, bool diag, double* 
   }
   c->pin.finish();
   c->grad_post_gram_us = (unsigned long long)gram_us;
+  if (gobs) c->gobs_grad_operand_us = (unsigned long long)operand_us;
   return 0;
 }
 
@@ -7343,6 +7366,48 @@ int gpc_debug_gobs_cross(gpc_ctx* c, int kernel_id, int degree, const double* hy
   return 0;
 }
 
+int gpc_debug_gobs_grad_operand(gpc_ctx* c, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
+                                const double* Xg, int Ng, const double* xstar, int M, const double* alpha, double* out,
+                                double* colsum) {
+  if (!c) return -2;
+  if (!xstar || !out || M <= 0 || M > GQB) FAIL(c, "gpc_debug_gobs_grad_operand: bad arguments (one block: M <= 128)");
+  const int mb = GQB, ld = (D + 1) * mb;
+  GobsDims gd;
+  gd.N = N, gd.Ng = Ng, gd.D = D;
+  if (int rc = gobs_dims_check(c, gd, "gpc_debug_gobs_grad_operand")) return rc;
+  const int n = (int)gd.n(), npad = pad_tile(n), pt = gd.P() / CT;
+  // after the common part: raw queries M x D | scaled queries mb x D | alpha npad | partials pt x ld | sums ld | F0 (2)
+  const size_t extra = (size_t)M * D + (size_t)mb * D + npad + (size_t)pt * ld + ld + 2;
+  GobsDebug g;
+  if (int rc = gobs_debug_begin(c, kernel_id, degree, hyp_cov, X, N, D, Xg, Ng, extra, g, "gpc_debug_gobs_grad_operand"))
+    return rc;
+  double* d_xq = g.rest;
+  double* d_xss = d_xq + (size_t)M * D;
+  double* d_alpha = d_xss + (size_t)mb * D;
+  double* d_part = d_alpha + npad;
+  double* d_mu = d_part + (size_t)pt * ld;
+  double* d_f0 = d_mu + ld;
+  hipStream_t st = c->st;
+  HIPCHK(c, hipMemcpyAsync(d_xq, xstar, (size_t)M * D * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipMemsetAsync(d_alpha, 0, (size_t)npad * 8, st));
+  if (alpha) HIPCHK(c, hipMemcpyAsync(d_alpha, alpha, (size_t)n * 8, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(scale_x_kernel, dim3((unsigned)(((long long)mb * D + 255) / 256), 1), dim3(256), 0, st,
+                     (const double*)d_xq, M, mb, D, (const double*)g.mul, (const double*)g.dv, d_xss);
+  const size_t pb = (size_t)npad * ld * 8;
+  HIPCHK(c, c->dbg1.ensure(pb));
+  HIPCHK(c, hipMemsetAsync(c->dbg1.p, 0xFF, pb, st));  // (NaN: an entry nobody wrote shows)
+  GramClock clk(true);
+  HIPCHK(c, clk.record(0, st));
+  HIPCHK(c, launch_gobs_grad_operand<double>(st, g.cd, g.gd, g.xs, d_xss, g.sp, g.mul, g.dv, d_alpha, npad, npad, M, 1,
+                                             c->dbg1.as<double>(), (long long)npad * ld, d_part, d_mu, d_f0));
+  HIPCHK(c, clk.record(1, st));
+  HIPCHK(c, hipMemcpyAsync(out, c->dbg1.p, pb, hipMemcpyDeviceToHost, st));
+  if (colsum) HIPCHK(c, hipMemcpyAsync(colsum, d_mu, (size_t)ld * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  c->gobs_grad_operand_us = (unsigned long long)clk.elapsed_us();
+  return 0;
+}
+
 int gpc_post_fetch(gpc_post* po, int s, double* alpha, double* sW, double* L) {
   if (!po) return -2;
   gpc_ctx* c = po->ctx;
@@ -7598,6 +7663,19 @@ int gpc_grad_post(gpc_post* po, const double* xstar, int M, int diag_only, doubl
     FAIL(c, "gpc_grad_post: the Matern kernel of degree 1 has no mean-square derivative (its gradient has infinite "
             "prior variance)");
   if (int rc = require_factorized(po, "gpc_grad_post")) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  return po->dtype == GPC_F64 ? grad_post_impl<double>(po, xstar, M, diag_only != 0, fmu, dfmu, cov)
+                              : grad_post_impl<float>(po, xstar, M, diag_only != 0, fmu, dfmu, cov);
+}
+
+int gpc_grad_post_gobs(gpc_post* po, const double* xstar, int M, int diag_only, double* fmu, double* dfmu, double* cov) {
+  if (!po) return -2;
+  gpc_ctx* c = po->ctx;
+  if (!xstar || !fmu || !dfmu || !cov || M <= 0) FAIL(c, "gpc_grad_post_gobs: bad arguments");
+  if (po->gobs.Ng <= 0)
+    FAIL(c, "gpc_grad_post_gobs: this posterior holds no gradient observations (gpc_posterior_batch_gobs builds those); "
+            "use gpc_grad_post");
+  if (int rc = require_factorized(po, "gpc_grad_post_gobs")) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   return po->dtype == GPC_F64 ? grad_post_impl<double>(po, xstar, M, diag_only != 0, fmu, dfmu, cov)
                               : grad_post_impl<float>(po, xstar, M, diag_only != 0, fmu, dfmu, cov);
@@ -8056,6 +8134,7 @@ const Option OPTIONS[] = {
     {"cv_grad_trace_us", GPC_COUNTER(cv_grad_trace_us)},  // device time of the contraction pass (kernel + reduction) of the last gpc_cv_grad (timed calls only)
     {"gobs_cov_us", GPC_COUNTER(gobs_cov_us)},      // device time of the kernel of the last gpc_debug_gobs_cov
     {"gobs_trace_us", GPC_COUNTER(gobs_trace_us)},  // device time of the contraction of the last gpc_debug_gobs_trace
+    {"gobs_grad_operand_us", GPC_COUNTER(gobs_grad_operand_us)},  // device time of the operand builds of the last gpc_grad_post_gobs (timed calls only) / of the last gpc_debug_gobs_grad_operand
     {"gobs_cross_us", GPC_COUNTER(gobs_cross_us)},  // device time of the build (operand + mean product) of the last gpc_debug_gobs_cross
     {"grad_post_gram_us", GPC_COUNTER(grad_post_gram_us)},  // device time of the Gram passes of the last gpc_grad_post (timed calls only)
     {"lookahead_batch_loop_us", GPC_COUNTER(lookahead_batch_loop_us)},  // device time of the step loop (all q steps, without the formation of C^0) of the last gpc_lookahead_batch

@@ -17,6 +17,7 @@
 // or gradient points -- and the kind is uniform per block.
 #pragma once
 #include "covfun.h"
+#include "gradpost.h"
 
 namespace gpc {
 
@@ -577,6 +578,208 @@ __global__ __launch_bounds__(256) void gobs_trace_gg_kernel(GobsTraceArgs a) {
                                    blockIdx.z);
 }
 
+// ---------------------------------------------------------------------------------
+// The derivative operand of the joint system (gpc_grad_post_gobs; DESIGN.md "Gradient posterior under gradient
+// observations"): one 64 x 64 tile of (point of the list, query) pairs of sample b, all D + 1 slots, into gradpost.h's
+// panel -- npad x (D + 1) mb, slot-major planes: column s mb + j is slot s of query j, slot 0 = f(x*), slot 1 + l =
+// d f / dx*_l -- with the rows in joint order.  The sibling of grad_operand_tile_kernel and of gobs_cross_tile_kernel:
+//   value tile, row i:                 slot 0      k                                     (grad_operand_tile_kernel's
+//                                      slot 1 + l  -c_l F (xs*_l - xs_il), 0 at r2 = 0    expressions, in its order)
+//   gradient tile, row N + a Ng + g:   slot 0      -c_a F d_a, 0 at r2 = 0               (gobs_cross_tile_kernel's)
+//   (d = xs_g - xs*)                   slot 1 + l  c_a c_l (F delta_al - G d_a d_l); c_a^2 F0 delta_al at r2 = 0, the G
+//                                                  term dropped              (gobs_cov_kernel's, with p = g and q = *)
+// Distances by tile_r2_ab, differences before products, (k, F, G) evaluated once per pair.  Queries >= m are written as
+// zeros; a value tile leaves the rows of the points it does not have alone (they are gradient rows); the rows
+// [n, npad) belong to no tile and are zeroed by the launcher.
+// A gradient tile works ONE SLOT per pass over its registers (slot_pass: F and G of the 16 pairs stay, 32 doubles per
+// thread; slot 1 + l adds its 4 + 4 coordinates of dimension l), the a-dimensions staged DCH at a time and the slot's
+// dimension on its own (bi, bj) as gobs_cov_kernel does: any D.  With D <= DCH the one chunk is staged once for all
+// slots.  Registers (gfx950, DESIGN.md has the table): 215 .. 247 VGPRs, no AGPRs, no scratch, two waves per SIMD --
+// the bound is asked for: left alone the scheduler interleaves the 16 entries of a row dimension up to 256 VGPRs + 8
+// AGPRs (one wave), and at three waves (168 VGPRs) it spills ~290 bytes per lane.
+// Fused mean product, per slot: part[b][tile row of the list][slot mb + j] = sum over every row the tile wrote of the
+// STORED value times alpha[row] (dimensions ascending, then the tile's points); colpart_reduce_kernel adds the tile
+// rows in ascending order.  No atomics.  f0[b] receives F0 (block (0, 0) only).
+// grid = (mb/64, P/64, batch), 256 threads.  Xp: batch lists of P x D; Xss: batch x mb x D
+// ---------------------------------------------------------------------------------
+template <typename T, int KIND, int DEG>
+__global__ __launch_bounds__(256, 2) void gobs_grad_operand_tile_kernel(
+    GobsDims gd, const double* __restrict__ Xp_all, const double* __restrict__ Xss_all,
+    const double* __restrict__ sp_all, const double* __restrict__ mul_all, const double* __restrict__ dv_all,
+    const double* __restrict__ alpha_all, int astride, int m, int mb, T* __restrict__ P_all, long long sP,
+    double* __restrict__ part_all, double* __restrict__ f0_all) {
+  __shared__ double xi[CT][DCH + 1];
+  __shared__ double xj[CT][DCH + 1];
+  __shared__ double bi[CT], bj[CT];
+  __shared__ double red[2][4][CT];
+  const int t = threadIdx.x, tx = t & 15, ty = t >> 4, b = blockIdx.z;
+  const int lane = t & 63, w = t >> 6;
+  const int N = gd.N, Ng = gd.Ng, D = gd.D, Np = gd.Np(), P = gd.P(), ld = (D + 1) * mb;
+  const int i0 = blockIdx.y * CT, j0 = blockIdx.x * CT;
+  const bool gi = i0 >= Np;
+  const int pi0 = gi ? i0 - Np : i0, ni = gi ? Ng : N;
+  const double* Xp = Xp_all + (size_t)b * P * D;
+  const double* Xss = Xss_all + (size_t)b * mb * D;
+  const double* sp = sp_all + (size_t)b * SP_STRIDE;
+  const double* mul = mul_all + (size_t)b * D;
+  const double* dv = dv_all + (size_t)b * D;
+  const double* alpha = alpha_all + (size_t)b * astride;
+  T* Pn = P_all + (size_t)b * sP;
+  double* part = part_all + ((size_t)b * (P / CT) + blockIdx.y) * ld;
+  double r2[4][4];
+  tile_r2_ab(r2, xi, xj, Xp, Xss, D, i0, j0, t, tx, ty);
+  const double sf2 = sp[SP_SF2], rqa = sp[SP_RQA];
+  ExpC ex;
+  ex.load();
+  if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0) f0_all[b] = pair_eval_t<KIND, DEG>(0.0, sf2, rqa, ex).F;
+  // column sums of one slot over the rows the tile wrote: the 4 row groups of a wave by two exchanges, the 4 waves
+  // through LDS (two buffers in turn: one barrier per slot), as grad_operand_tile_kernel
+  auto column_sums = [&](const double (&sc)[4], int slot) {
+    double (*rb)[CT] = red[slot & 1];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      double v = sc[c];
+      v += __shfl_xor(v, 16, 64);
+      v += __shfl_xor(v, 32, 64);
+      if ((lane >> 4) == 0) rb[w][tx + 16 * c] = v;
+    }
+    __syncthreads();
+    if (t < CT) part[(size_t)slot * mb + j0 + t] = rb[0][t] + rb[1][t] + rb[2][t] + rb[3][t];
+  };
+  double fw[4][4];
+
+  if (!gi) {  // value points: rows i < N
+    double al[4], s[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int a = 0; a < 4; ++a) al[a] = (i0 + ty + 16 * a) < ni ? alpha[i0 + ty + 16 * a] : 0.0;
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int i = i0 + ty + 16 * a, j = j0 + tx + 16 * c;
+        double v = 0.0;
+        fw[a][c] = 0.0;
+        if (i < ni && j < m) {
+          const PairVal pv = pair_eval_t<KIND, DEG>(r2[a][c], sf2, rqa, ex);
+          v = pv.K;
+          if (r2[a][c] > 0.0) fw[a][c] = pv.F;
+        }
+        const T vt = (T)v;
+        if (i < ni) Pn[(size_t)i * ld + j] = vt;
+        s[c] = fma((double)vt, al[a], s[c]);
+      }
+    column_sums(s, 0);
+    for (int h0 = 0; h0 < D; h0 += DCH) {
+      const int dc = min(DCH, D - h0);
+      __syncthreads();
+      stage_x(xi, Xp, D, i0, h0, dc, t);
+      stage_x(xj, Xss, D, j0, h0, dc, t);
+      __syncthreads();
+      for (int h = 0; h < dc; ++h) {
+        const int slot = 1 + h0 + h;
+        const double cl = mul[h0 + h] / dv[h0 + h];
+        double vi[4], vj[4], sd[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int a = 0; a < 4; ++a) vi[a] = xi[ty + 16 * a][h];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) vj[c] = xj[tx + 16 * c][h];
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const int i = i0 + ty + 16 * a, j = j0 + tx + 16 * c;
+            const T vt = (T)(-cl * fw[a][c] * (vj[c] - vi[a]));
+            if (i < ni) Pn[(size_t)i * ld + (size_t)slot * mb + j] = vt;
+            sd[c] = fma((double)vt, al[a], sd[c]);
+          }
+        column_sums(sd, slot);
+      }
+    }
+    return;
+  }
+
+  // gradient points: rows N + a Ng + g.  ok: the pair exists (bit 4 a + c); nz: r2 > 0
+  double gw[4][4];
+  unsigned ok = 0, nz = 0;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const bool e = (pi0 + ty + 16 * a) < ni && (j0 + tx + 16 * c) < m, p = r2[a][c] > 0.0;
+      const PairFG fg = pair_eval_fg_t<KIND, DEG>(r2[a][c], sf2, rqa, ex);
+      fw[a][c] = e ? fg.F : 0.0;
+      gw[a][c] = e && p ? fg.G : 0.0;  // the G term is dropped at coincident points (Matern 3: G = inf there)
+      ok |= (unsigned)e << (4 * a + c);
+      nz |= (unsigned)p << (4 * a + c);
+    }
+  const bool one = D <= DCH;  // one chunk of a-dimensions: staged once for all slots
+  if (one) {
+    __syncthreads();
+    stage_x(xi, Xp, D, i0, 0, D, t);
+    stage_x(xj, Xss, D, j0, 0, D, t);
+  }
+  // one slot: the a-dimensions in ascending order.  entry(a, c, d_a, la, c_a) is the pair's value in row dimension la
+  auto slot_pass = [&](int slot, auto&& entry) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int h0 = 0; h0 < D; h0 += DCH) {
+      const int dc = min(DCH, D - h0);
+      if (!one) {
+        __syncthreads();
+        stage_x(xi, Xp, D, i0, h0, dc, t);
+        stage_x(xj, Xss, D, j0, h0, dc, t);
+        __syncthreads();
+      }
+#pragma unroll 1
+      for (int h = 0; h < dc; ++h) {
+        const int la = h0 + h;
+        const double ca = mul[la] / dv[la];
+        double vj[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) vj[c] = xj[tx + 16 * c][h];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+          const int p = pi0 + ty + 16 * a;
+          if (p >= ni) continue;
+          const size_t row = (size_t)N + (size_t)la * Ng + p;
+          const double al = alpha[row], va = xi[ty + 16 * a][h];
+          T* pr = Pn + row * ld + (size_t)slot * mb + j0 + tx;
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            const double v = entry(a, c, va - vj[c], la, ca);
+            const T vt = (T)((ok & (1u << (4 * a + c))) ? v : 0.0);
+            pr[16 * c] = vt;
+            s[c] = fma((double)vt, al, s[c]);
+          }
+        }
+      }
+    }
+    column_sums(s, slot);
+  };
+  __syncthreads();  // (the chunk above is staged)
+  slot_pass(0, [&](int a, int c, double d, int, double ca) {  // -c_a F d_a; exactly 0 at r2 = 0
+    const double f = (nz & (1u << (4 * a + c))) ? fw[a][c] : 0.0;
+    const double wv = (ca * f) * d;
+    return f != 0.0 ? -wv : 0.0;
+  });
+  for (int l = 0; l < D; ++l) {
+    __syncthreads();  // (the previous slot's readers of bi, bj, xi and xj are done)
+    if (t < CT)
+      bi[t] = Xp[(size_t)(i0 + t) * D + l];
+    else if (t < 2 * CT)
+      bj[t - CT] = Xss[(size_t)(j0 + t - CT) * D + l];
+    __syncthreads();
+    const double cl = mul[l] / dv[l];
+    double bv[4], bq[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) bv[a] = bi[ty + 16 * a];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) bq[c] = bj[tx + 16 * c];
+    slot_pass(1 + l, [&](int a, int c, double d, int la, double ca) {  // c_a c_l (F delta_al - G d_a d_l)
+      return (ca * cl) * fma(-gw[a][c], d * (bv[a] - bq[c]), la == l ? fw[a][c] : 0.0);
+    });
+  }
+}
+
 // The scaled point lists of `batch` samples from the raw list `pts` (P x D, zero rows between the kinds)
 inline void launch_gobs_scale(hipStream_t st, const GobsDims& gd, const double* pts, const double* mul, const double* dv,
                               int batch, double* xs) {
@@ -623,6 +826,27 @@ inline hipError_t launch_gobs_cross(hipStream_t st, const CovDesc& cd, const Gob
                    dv, alpha, astride, m, mb, Ks, sKs, part);
   hipLaunchKernelGGL(colpart_reduce_kernel, dim3((mb + 255) / 256, batch), dim3(256), 0, st, (const double*)part,
                      gd.P() / CT, mb, mu);
+  return hipGetLastError();
+}
+
+// The derivative operands of `batch` samples for one block of mb = GQB queries (panels sP apart, npad x (D + 1) mb) with
+// their mean products: part: batch x P/64 x (D + 1) mb partials, mean: batch x (D + 1) mb, f0: batch.  The rows
+// [n, npad) of every panel are zeroed here.
+template <typename T>
+inline hipError_t launch_gobs_grad_operand(hipStream_t st, const CovDesc& cd, const GobsDims& gd, const double* xp,
+                                           const double* xsq, const double* sp, const double* mul, const double* dv,
+                                           const double* alpha, int astride, int npad, int m, int batch, T* P,
+                                           long long sP, double* part, double* mean, double* f0) {
+  const int mb = GQB, ld = (gd.D + 1) * mb;
+  const size_t n = (size_t)gd.n();
+  if ((size_t)npad > n) {
+    hipError_t e = hipMemset2DAsync(P + n * ld, (size_t)sP * sizeof(T), 0, ((size_t)npad - n) * ld * sizeof(T), batch, st);
+    if (e != hipSuccess) return e;
+  }
+  GPC_COV_DISPATCH(gobs_grad_operand_tile_kernel, T, cd, dim3(mb / CT, gd.P() / CT, batch), dim3(256), 0, st, gd, xp, xsq,
+                   sp, mul, dv, alpha, astride, m, mb, P, sP, part, f0);
+  hipLaunchKernelGGL(colpart_reduce_kernel, dim3((ld + 255) / 256, batch), dim3(256), 0, st, (const double*)part,
+                     gd.P() / CT, ld, mean);
   return hipGetLastError();
 }
 

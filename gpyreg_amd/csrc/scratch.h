@@ -172,14 +172,18 @@ struct BlockScratch {
   T *P, *V, *Q;
   double *part, *colsq, *hpart, *hsum, *gpart, *gram, *mean, *xsq, *f0;
   // vprod: V = W panel is formed; qprod: Q = W^T V[slot 0] too; gram_w: width of a query's Gram result (0: none);
-  // colsq: the diagonal form's column sums of squares; hper: doubles of a sample's reduced Hessian sums (0: none)
-  void layout(ScratchCarver& sc, int cnt, int npad, int D, bool vprod, bool qprod, int gram_w, bool colsq_, size_t hper) {
+  // colsq: the diagonal form's column sums of squares; hper: doubles of a sample's reduced Hessian sums (0: none);
+  // prow: tile rows of the operand kernel's fused mean product (0: npad / 64; gpc_grad_post_gobs: the rows of its point
+  // list / 64, which can exceed npad / 64 -- N = 65, Ng = 1, D = 1 has 3 against 2)
+  void layout(ScratchCarver& sc, int cnt, int npad, int D, bool vprod, bool qprod, int gram_w, bool colsq_, size_t hper,
+              int prow = 0) {
     const size_t c = cnt, mb = GQB, ld = (size_t)(D + 1) * mb, sP = (size_t)npad * ld, nt64 = npad / CT;
+    const size_t pt = prow > 0 ? (size_t)prow : nt64;
     const size_t gper = mb * (D + 1) * gram_w, nseg = gram_segments(npad);
     P = sc.take<T>(c * sP, 16);                           // [ k | dk/dx*_1 .. dk/dx*_D ]
     V = sc.take<T>(vprod ? c * sP : 0, 16);               // V = W panel | Z = L panel
     Q = sc.take<T>(qprod ? c * npad * mb : 0, 16);
-    part = sc.take(c * nt64 * ld, 16);                    // the operand kernel's fused mean product, per tile row
+    part = sc.take(c * pt * ld, 16);                      // the operand kernel's fused mean product, per tile row
     colsq = sc.take(colsq_ ? c * (npad / TILE) * ld : 0, 16);
     hpart = sc.take(c * nt64 * hper, 16);                 // the contraction's per-tile partials and their sums
     hsum = sc.take(c * hper, 16);
@@ -485,6 +489,17 @@ int scratch_bytes_of(const std::string& name, const int* d, int n, unsigned long
           else BlockScratch<T>().layout(sc, cnt, npad, D, true, false, f ? 1 : D + 1, f, hper);
         },
         [&](ScratchCarver& sc) { sc.take((size_t)d[1] * D); }, 0, per, shared, mis);
+  }
+  if (name == "grad_post_gobs" && n == 4) {  // N, Ng, D, diag: one block of queries (the raw queries are the caller's M x D)
+    GobsDims gd;
+    gd.N = d[0], gd.Ng = d[1], gd.D = d[2];
+    const bool f = d[3] != 0;
+    const int jpad = pad_tile((int)gd.n());
+    return scratch_report(
+        [&](ScratchCarver& sc, int cnt) {
+          BlockScratch<T>().layout(sc, cnt, jpad, gd.D, true, false, f ? 1 : gd.D + 1, f, (size_t)0, gd.P() / CT);
+        },
+        none, 0, per, shared, mis);
   }
   if (name == "append_block" && n == 3) {  // N + k, k, engine
     const int k = d[1], kq = ((k + BA_R - 1) / BA_R) * BA_R;

@@ -317,8 +317,9 @@ class GradientConditionedPosterior:
     when it was made and stays valid after the GP changes.  ``nlZ`` (S,) is the joint negative log marginal likelihood
     (the number ``GP.nll_batch_grad_obs`` returns for the same hyperparameters), ``sn2_mult`` (S,) and ``L_chol`` (S,)
     the jitter multiplier and the branch of each sample's joint factorization, ``alpha`` a list of (values (N,),
-    gradients (Ng, D)) pairs in the user's order.  ``close()`` (or leaving a ``with`` block, or garbage collection)
-    frees the device memory."""
+    gradients (Ng, D)) pairs in the user's order.  ``predict`` gives the mean and variance, ``gradient_posterior`` the
+    joint posterior of the gradient (and the value), ``predict_grad`` the gradients of ``predict``'s two moments.
+    ``close()`` (or leaving a ``with`` block, or garbage collection) frees the device memory."""
 
     def __init__(self, handle, mean, noise, counts, hyps, dims, nlZ, sn2_mult, L_chol):
         self._handle, self._mean, self._noise, self._counts, self._hyps = handle, mean, noise, counts, hyps
@@ -364,6 +365,96 @@ class GradientConditionedPosterior:
         if not separate_samples and S >= 1:
             mu, s2, _ = _mix_samples(mu, s2)
         return mu, s2
+
+    def _queries(self, x_star):
+        x_star = np.atleast_2d(np.asarray(x_star, dtype=float))
+        if x_star.ndim != 2 or x_star.shape[1] != self.D or x_star.shape[0] < 1:
+            raise ValueError(f"x_star must be (M, {self.D}), got {x_star.shape}")
+        if not np.all(np.isfinite(x_star)):
+            raise ValueError("x_star must be finite")
+        return x_star
+
+    def _joint_rows(self, x_star, diag, who):
+        """(mean (M, D + 1, S), C (M, D + 1[, D + 1], S)) of (f, grad f) per sample: one gpc_grad_post_gobs call plus the
+        mean function's value and x-gradient (stock means only)."""
+        handle = self._live()
+        M, P, S = x_star.shape[0], self.D + 1, len(self._hyps)
+        mean = np.empty((M, P, S))
+        for s, h in enumerate(self._hyps):
+            hm = _mean_hyp(h, self._counts)
+            mean[:, 1:, s] = _mean_grad_x(self._mean, hm, x_star, who)
+            mean[:, 0, s] = np.reshape(self._mean.compute(hm, x_star), (-1,))
+        fmu, dfmu, C = handle.grad_post_gobs(x_star, diag)
+        mean[:, 0, :] += fmu
+        mean[:, 1:, :] += dfmu
+        return mean, C
+
+    def gradient_posterior(self, x_star, cov: str = "full", with_value: bool = False,
+                           separate_samples: bool = False):
+        """The posterior distribution of the gradient of the latent function at ``x_star`` given the values AND the
+        gradient observations: (dmu, dcov), with ``GP.gradient_posterior``'s contract.
+
+        dmu (M, D) is the posterior mean of grad f (the stock mean functions' gradient included); dcov (M, D, D) its
+        posterior covariance, entry [j, l, k] = Cov(df/dx_l, df/dx_k) at x_star[j], or with ``cov="diag"`` the
+        variances (M, D) alone (cheaper: no Gram matrix is formed).  With ``with_value`` f itself is prepended as slot
+        0: shapes (M, D + 1) and (M, D + 1, D + 1) (or (M, D + 1)), slot 0 holding ``predict``'s latent mean and variance
+        before its clamp and [j, 0, 1 + l] = Cov(f, df/dx_l) = half of ``predict_grad``'s variance gradient.  Nothing is
+        clamped or projected: each per-sample matrix is returned as computed (symmetric to the bit; its smallest
+        eigenvalue may be a rounding error below 0 where the posterior is nearly certain -- at a gradient point
+        observed without noise, for one).  With ``separate_samples`` a trailing axis S holds the hyperparameter
+        samples; otherwise the moments of their equal-weight mixture are returned: the mean of the means, and the mean
+        of the covariances plus the between-sample covariance of the mean vectors (divisor S - 1; one sample is
+        returned as it is).
+
+        The operand of the joint system, the solves and the per-query Gram matrices run on the device
+        (gpc_grad_post_gobs; ``_gradobs`` has the formulas).  Stock mean functions only (NotImplementedError
+        otherwise).  Not sharded: the calling rank computes every sample."""
+        from . import _gradpost as _gpm
+
+        if cov not in ("full", "diag"):
+            raise ValueError(f"gradient_posterior: cov must be 'full' or 'diag', got {cov!r}")
+        diag = cov == "diag"
+        self._live()
+        x_star = self._queries(x_star)
+        mean, C = self._joint_rows(x_star, diag, "gradient_posterior")
+        if not with_value:
+            mean = mean[:, 1:]
+            C = C[:, 1:] if diag else C[:, 1:, 1:]
+        if separate_samples:
+            return mean, C
+        return _gpm.mix_diag(mean, C) if diag else _gpm.mix(mean, C)
+
+    def predict_grad(self, x_star, add_noise: bool = False, s2_star=None, separate_samples: bool = False):
+        """``predict``'s mean and variance at ``x_star`` and their gradients with respect to ``x_star``:
+        (mu, s2, dmu, ds2), with ``GP.predict_grad``'s conventions.  mu and s2 are what ``predict`` returns for the same
+        arguments (within rounding); dmu and ds2 are (M, D), or (M, D, S) with ``separate_samples``, entry [j, l] the
+        derivative with respect to x_star[j, l].  All four come from ONE gpc_grad_post_gobs call: mu and s2 are slot 0
+        of the joint posterior of (f, grad f), dmu its gradient slots and ds2_l = 2 Cov(f, df/dx_l).  The variance is
+        clamped at 0 and its gradient is 0 where the clamp holds; ``add_noise`` adds the noise function's value (with
+        ``s2_star``) times the joint factorization's multiplier, as ``predict`` does, and leaves ds2 unchanged (stock
+        ``GaussianNoise`` only: the noise must not depend on x_star).  Stock mean functions only.  Not sharded."""
+        from .noise_functions import GaussianNoise
+
+        self._live()
+        x_star = self._queries(x_star)
+        if add_noise and type(self._noise) is not GaussianNoise:
+            raise NotImplementedError(f"predict_grad: the noise function {self._noise!r} is user-defined; add_noise "
+                                      "needs noise that does not depend on x_star")
+        cov_N, noise_N, _ = self._counts
+        mean, C = self._joint_rows(x_star, False, "predict_grad")
+        mu, dmu = mean[:, 0, :], mean[:, 1:, :]
+        fs2 = C[:, 0, 0, :]
+        # the clamp of predict, s2 = max(s2, 0): no variance gradient where it holds s2 at 0
+        ds2 = np.where((fs2 <= 0)[:, None, :], 0.0, 2 * C[:, 0, 1:, :])
+        s2 = np.maximum(fs2, 0)
+        if add_noise:
+            for s, hyp in enumerate(self._hyps):
+                sn2 = self._noise.compute(hyp[cov_N:cov_N + noise_N], x_star, None, s2_star) * self.sn2_mult[s]
+                s2[:, s] += np.reshape(np.broadcast_to(sn2, (x_star.shape[0], 1)), (-1,))
+        if not separate_samples:
+            dmu, ds2 = _mix_sample_grads(mu, dmu, ds2)
+            mu, s2, _ = _mix_samples(mu, s2)
+        return mu, s2, dmu, ds2
 
     def close(self):
         if self._handle is not None:

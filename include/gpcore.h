@@ -945,9 +945,9 @@ int gpc_set_data_gobs(gpc_ctx* ctx, const double* X, const double* y, int N, int
  * above).  nlz (S; may be NULL): the joint negative log marginal likelihood as this pipeline rounds it --
  * gpc_nll_batch_gobs factors without the inverse and agrees with it to rounding, not to the bit.  sn2_mult, L_chol,
  * info as gpc_posterior_batch.  The handle is a GRADIENT-OBSERVATION posterior: it owns a copy of the points,
- * gpc_predict_gobs, gpc_post_fetch (alpha: n, L: n x n) and gpc_post_free work on it, and every other consumer
- * (gpc_predict, gpc_predict_grad, gpc_post_append*, gpc_post_remove, gpc_draw, gpc_paths_create, gpc_cv, gpc_quad*,
- * gpc_predict_K, ...) returns an error that says so.                                                                 */
+ * gpc_predict_gobs, gpc_grad_post_gobs, gpc_post_fetch (alpha: n, L: n x n) and gpc_post_free work on it, and every
+ * other consumer (gpc_predict, gpc_predict_grad, gpc_grad_post, gpc_post_append*, gpc_post_remove, gpc_draw,
+ * gpc_paths_create, gpc_cv, gpc_quad*, gpc_predict_K, ...) returns an error that says so.                             */
 int gpc_posterior_batch_gobs(gpc_ctx* ctx, int kernel_id, int degree, int dtype, int S, const double* hyp_cov,
                              const double* m, const double* sn2, gpc_post** post, double* nlz, double* sn2_mult,
                              int* L_chol, int* info);
@@ -969,16 +969,33 @@ int gpc_nll_batch_gobs_grad(gpc_ctx* ctx, int kernel_id, int degree, int dtype, 
 /* gpc_predict for a gradient-observation posterior: the n x M operand [k(X, x*) ; -c_l F (xs_g - xs*)_l] is built on
  * the device with the mean product fused in; fmu (caller adds m*) and fs2 (unclamped) as gpc_predict, [j*S + s].    */
 int gpc_predict_gobs(gpc_post* post, const double* xstar, int M, double* fmu, double* fs2);
+/* gpc_grad_post for a gradient-observation posterior: the joint posterior of (f(x*), grad f(x*)) given values AND
+ * gradients.  Arguments, layouts and semantics are gpc_grad_post's (fmu [j*S + s], dfmu [(j*D + l)*S + s], cov
+ * [((j*(D+1) + a)*(D+1) + b)*S + s] or, with diag_only, [(j*(D+1) + a)*S + s]; slot 0 = f, slot 1 + l = d/dx_l; no
+ * clamp, no noise, no mean function; symmetric to the bit).  The operand is the npad x (D + 1) 128 panel of the JOINT
+ * system per block of 128 queries (gradobs.h: gobs_grad_operand_tile_kernel -- value rows [k | -c_l F (xs* - xs_i)_l],
+ * gradient rows N + a Ng + g [-c_a F d_a | c_a c_l (F delta_al - G d_a d_l)], d = xs_g - xs*), with the mean product
+ * fused in; the products with the factor, the per-query Gram matrices and the diagonal form are gpc_grad_post's own.
+ * A handle without gradient observations, or one that is not factorized, is an error.  Counter
+ * "gobs_grad_operand_us": the device time of the operand builds of a timed call.                                     */
+int gpc_grad_post_gobs(gpc_post* post, const double* xstar, int M, int diag_only, double* fmu, double* dfmu, double* cov);
 /* Test hooks: the kernels of gradobs.h on their own, fp64, one hyperparameter row.
  * gpc_debug_gobs_cov: out = the dense n x n joint covariance (preset to NaN, so an entry nobody wrote shows).
  * gpc_debug_gobs_cross: out = the WHOLE panel, pad128(n) x pad128(M) row-major (preset to NaN; rows >= n and columns
  * >= M must come back as zeros); colsum (pad128(M); may be NULL) = the fused products out^T alpha with alpha (n; NULL:
- * zeros) in joint order.                                                                                            */
+ * zeros) in joint order.
+ * gpc_debug_gobs_grad_operand: gobs_grad_operand_tile_kernel as gpc_grad_post_gobs launches it for ONE block of queries
+ * (M <= 128): out = the WHOLE panel, pad128(n) x (D + 1) 128 row-major, column a 128 + j = slot a of query j (preset to
+ * NaN; rows >= n and queries >= M must come back as zeros); colsum ((D + 1) 128; may be NULL) = the fused products
+ * out^T alpha.  Counter "gobs_grad_operand_us": the device time of the build.                                         */
 int gpc_debug_gobs_cov(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
                        const double* Xg, int Ng, double* out);
 int gpc_debug_gobs_cross(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N, int D,
                          const double* Xg, int Ng, const double* xstar, int M, const double* alpha, double* out,
                          double* colsum);
+int gpc_debug_gobs_grad_operand(gpc_ctx* ctx, int kernel_id, int degree, const double* hyp_cov, const double* X, int N,
+                                int D, const double* Xg, int Ng, const double* xstar, int M, const double* alpha,
+                                double* out, double* colsum);
 /* gpc_debug_gobs_trace: gobs_trace_kernel and its reduction alone.  Ainv: n x n row-major, of which only the LOWER
  * triangle is read (the weight is Ainv / sl - alpha alpha^T, taken symmetric); alpha: n; sl > 0.  out (cov_N) =
  * sum_IJ weight_IJ dK_IJ / d theta_p.  Counter "gobs_trace_us": the device time of the contraction.                   */
